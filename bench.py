@@ -30,7 +30,9 @@ ECSIMD_BENCH_REHEARSE_ONE_GPU=1 (a one-GPU box): N ranks share cuda:0 and gather
 group leg puts N members on the one device -- an N > 1 run's control flow on hardware, RCCL excepted (it refuses two ranks
 per device); the line says `rehearsal` and its value is no scaling result.
 
-Rank 0 prints ONE JSON line.  Besides the contract fields it carries
+Rank 0 prints ONE JSON line.  A plain run does only what that line's headline needs: set-up, warm-up, the timed steps
+(their outputs written with --dump-outputs DIR) and the contract fields (`metric ... config`, `ms_per_step` among them).
+With --full the line also carries what takes work of its own:
   roofline     : integer-VALU bound.  achieved = scalar-mults/s x 555 968 mad32 (SURVEY.md 8(d):
                  (2299 M + 1789 S) x 136), kernel time from HIP events on the launch stream;
                  peak = the dependency-free v_mad_u64_u32 stream measured live on the same GPU.
@@ -41,6 +43,9 @@ Rank 0 prints ONE JSON line.  Besides the contract fields it carries
                  Its sub-object competitor_openssl is the reference's competitor benchmark
                  (benchs/p256_ref.cpp:55-91, libcrypto's EC_POINT_mul) on the same cores, with 8 192 of
                  the GPU's results checked against libcrypto at the affine level.
+  ref_compat   : (default workload) the same batch through ECSIMD_HIP_REF_SQUARE_COMPAT, timed and compared with the CPU leg's lanes.
+  N > 1        : the compute-only loop, rank 0's check of the gathered shards and the device-group leg; --multi group: its
+                 compute-only loop and the check of the gathered result against every member's own ladder.
 The process exits NON-ZERO (after printing the line) when a checker disagrees with the GPU in a way the
 reference's documented defect does not explain, and on any rank's failure.
 """
@@ -62,6 +67,7 @@ A_PRIORI_PEAK_TMAD32 = 256 * 4 * 16 * 2.4e9 / 1e12
 SEED = 0x5EEDEC51D0000001
 EXIT_PARITY = 3                         # a checker contradicts the GPU result
 LADDER_WORKLOADS = ("ladder", "ladder-ref-compat", "ladder-radix32")
+DUMP_LANES = 1 << 16                    # --dump-outputs: lanes sampled per coordinate (3 x 2^16 x 128 B = 24 MiB at most)
 
 
 class CheckerUnavailable(Exception):
@@ -97,9 +103,21 @@ def parse_args(argv=None):
                          "started without it, --gpus N > 1 launches it); group: ONE process driving N GPUs through the C ABI's device "
                          "group (ecsimd_hip_group_*), the gather by grouped ncclSend / ncclRecv")
     ap.add_argument("--no-group-check", action="store_true", help="N > 1, --multi procs: do not run the --multi group leg in a child process")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure and check what the headline does not need: roofline (live multiply-peak probe), cpu_baseline with its parity "
+                         "checks, ref_compat, and at N > 1 the compute-only loop, the gathered-shard check and the device-group leg")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full without the cpu_baseline and ref_compat legs")
     ap.add_argument("--cpu-seconds", type=float, default=12.0, help="target wall time of the CPU baseline sample")
-    return ap.parse_args(argv)
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last one computed to DIR/<coordinate>.npy: a fixed, seeded sample of "
+                         f"{DUMP_LANES} lanes (every lane of a smaller batch), each 256-bit word as its 32 little-endian bytes in float32, "
+                         "and DIR/lanes.npy, the sampled lanes' global indices in float64")
+    args = ap.parse_args(argv)
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    if args.warmup < 0:
+        ap.error("--warmup must not be negative")
+    return args
 
 
 def claim_stdout():
@@ -192,7 +210,7 @@ def main():
             dist.init_process_group("gloo")
         else:
             dist.init_process_group("nccl", device_id=torch.device("cuda", local_rank))
-        if world > 1 and not args.no_group_check:
+        if world > 1 and args.full and not args.no_group_check:
             # while rank 0's child process drives all N GPUs through the C ABI's device group (group_leg), the other ranks must
             # wait on the HOST: an RCCL barrier would keep a spinning kernel on every GPU the child is measuring
             host_group = dist.new_group(backend="gloo")
@@ -275,8 +293,15 @@ def main():
         runner.step(compute)
     elapsed, kernel_ms = timed(args.steps, True)                     # THE measurement: gathers (N > 1) inside
     gather_ms = runner.gather_ms(args.steps) if distributed else []
+    if args.dump_outputs and rank == 0:                               # the last timed step's result, every rank's shard
+        names = ("x",) if args.workload == "ladder-x" else ("x", "y", "z") if args.workload in LADDER_WORKLOADS else ("x", "y")
+        if world > 1:
+            shards = [plan(args.scaling, units, r, world)[:2] + (runner.gathered[r],) for r in range(world)]
+        else:
+            shards = [(first, n, runner.last_result())]
+        dump_outputs(args.dump_outputs, names, total_units, [(f, c, list(o[:len(names)])) for f, c, o in shards])
     compute_only = None
-    if distributed:                                                   # the same steps without the gather
+    if distributed and args.full:                                     # the same steps without the gather
         runner.gather = False
         compute_only, _ = timed(args.steps, False)
         runner.gather = True
@@ -293,11 +318,12 @@ def main():
             "what": ("one gloo gather of every rank's result shard, staged through pinned host memory (rehearsal)" if rehearse else
                      "one RCCL gather of every rank's result shard to rank 0 per step, on a side stream, into one pre-sized receive buffer"),
             "bytes_per_rank_per_step": 3 * rows * 32, "ms_avg_on_the_side_stream_rank0": (float(np.mean(gather_ms)) if gather_ms else None),
-            "ms_per_step_with_gather": 1e3 * elapsed / args.steps, "ms_per_step_compute_only": 1e3 * compute_only / args.steps,
-            "value_compute_only": total / compute_only}
+            "ms_per_step_with_gather": 1e3 * elapsed / args.steps}
+        if compute_only is not None:
+            result["config"]["gather"].update({"ms_per_step_compute_only": 1e3 * compute_only / args.steps, "value_compute_only": total / compute_only})
 
     failures = []
-    if rank == 0:
+    if rank == 0 and args.full:
         result["roofline"] = roofline_object(args, eng, n, float(np.mean(kernel_ms)))
         if world == 1 and not args.no_cpu_baseline:
             try:
@@ -333,6 +359,7 @@ def main():
                 failures.append(f"the shards gathered from ranks {bad_ranks} differ from rank 0's own ladder on the same inputs")
         if world > 1 and not args.no_group_check:
             result["multi_group"] = group_leg(args, world)          # the other ranks wait at the barrier below
+    if rank == 0:
         if failures:
             result["parity_failures"] = failures
         emit(json.dumps(result))
@@ -342,6 +369,30 @@ def main():
         dist.barrier()
         dist.destroy_process_group()
     return EXIT_PARITY if failures else 0
+
+
+def dump_outputs(path, names, total, shards):
+    """--dump-outputs: what the last timed step computed, for comparing two builds output for output.  `shards` = [(first global
+    index, count, [one (rows, 4) int64 tensor per name])]; the lanes are a fixed sample of the global index space (every lane
+    when there are at most DUMP_LANES), the same for every run with the same arguments.  A 256-bit word is written as its 32
+    little-endian bytes in float32 (exact, and a one-bit difference is a difference of at least 1 in a value below 256)."""
+    import numpy as np
+    import torch
+    os.makedirs(path, exist_ok=True)
+    m = min(total, DUMP_LANES)
+    lanes = np.sort(np.random.default_rng(SEED).choice(total, size=m, replace=False)) if m < total else np.arange(total)
+    cols = {name: np.empty((m, 32), dtype=np.float32) for name in names}
+    for first, count, tensors in shards:
+        sel = np.nonzero((lanes >= first) & (lanes < first + count))[0]
+        if not len(sel):
+            continue
+        for name, t in zip(names, tensors):
+            rows = torch.from_numpy(lanes[sel] - first).to(t.device)
+            words = np.ascontiguousarray(t.index_select(0, rows).cpu().numpy().astype("<i8"))
+            cols[name][sel] = words.view(np.uint8).reshape(len(sel), 32)
+    for name, a in cols.items():
+        np.save(os.path.join(path, name + ".npy"), a)
+    np.save(os.path.join(path, "lanes.npy"), lanes.astype(np.float64))
 
 
 def base_line(args, world, total_units, n, value, elapsed):
@@ -526,7 +577,7 @@ def group_leg(args, world, timeout_s=120):
     import subprocess
     cmd = [sys.executable, os.path.abspath(__file__), "--multi", "group", "--gpus", str(world), "--steps", str(min(args.steps, 5)), "--warmup", "1",
            "--scaling", args.scaling, "--global-log2-batch", str(args.global_log2_batch), "--log2-batch", str(args.log2_batch),
-           "--curve", args.curve, "--workload", args.workload, "--no-cpu-baseline"]
+           "--curve", args.curve, "--workload", args.workload, "--full", "--no-cpu-baseline"]
     # the child is NOT a rank: it must not inherit torch.distributed.run's environment
     env = {k: v for k, v in os.environ.items()
            if k not in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "LOCAL_WORLD_SIZE", "GROUP_RANK", "GROUP_WORLD_SIZE", "ROLE_RANK", "ROLE_WORLD_SIZE", "ROLE_NAME",
@@ -603,8 +654,9 @@ def main_group(args):
     loop(max(1, args.warmup), flags)                      # sizes staging and workspaces, creates RCCL's channels
     elapsed, gather_ms = loop(args.steps, flags)
     member_ms = [grp.member_ms(m) for m in range(N)]
-    compute_only, _ = loop(args.steps, flags | GROUP_NO_GATHER)
-    loop(1, flags)                                        # the arrays hold a gathered result again
+    if args.dump_outputs:                                 # the last timed step's gathered result, on device 0
+        names = ("x",) if x_only else ("x", "y", "z")
+        dump_outputs(args.dump_outputs, names, total_units, [(0, total_units, outs[(args.steps - 1) & 1])])
     total = float(total_units) * args.steps
     n0 = spans[0][1]
     result = base_line(args, N, total_units, n0, total / elapsed, elapsed)
@@ -617,8 +669,14 @@ def main_group(args):
     result["config"]["gather"] = {
         "what": "every other member's result shard into device 0's arrays by one grouped ncclSend / ncclRecv exchange per step, on device 0's gather stream",
         "bytes_per_member_per_step": (1 if x_only else 3) * spans[0][3] * 32, "ms_last_on_the_gather_stream": (gather_ms if gather_ms >= 0 else None),
-        "ms_per_step_with_gather": 1e3 * elapsed / args.steps, "ms_per_step_compute_only": 1e3 * compute_only / args.steps,
-        "value_compute_only": total / compute_only}
+        "ms_per_step_with_gather": 1e3 * elapsed / args.steps}
+    if not args.full:
+        emit(json.dumps(result))
+        grp.close()
+        return 0
+    compute_only, _ = loop(args.steps, flags | GROUP_NO_GATHER)
+    loop(1, flags)                                        # the arrays hold a gathered result again
+    result["config"]["gather"].update({"ms_per_step_compute_only": 1e3 * compute_only / args.steps, "value_compute_only": total / compute_only})
     failures = []
     # every member's shard of the gathered result against that member's own single-device ladder (bit for bit, on the devices)
     last = outs[0]

@@ -344,3 +344,51 @@ def test_ref_compat_is_part_of_the_documented_contract():
         for key in ("value", "unit", "kernel_ms", "steps", "frac", "frac_of_a_priori_peak", "lanes_compared", "lanes_differing", "compared_with"):
             assert key in rc, (p, key)
         assert rc["lanes_differing"] == 0 and rc["lanes_compared"] > 10 ** 6 and rc["unit"] == "scalar_mults/s"
+
+
+# ---------------------------------------------------------------- a plain run does what the headline needs; --full the rest; --dump-outputs
+def _bench_module(name):
+    import importlib.util
+    spec = importlib.util.spec_from_file_location(name, os.path.join(ROOT, "bench.py"))
+    bench = importlib.util.module_from_spec(spec); spec.loader.exec_module(bench)
+    return bench
+
+
+def test_full_is_off_by_default_and_steps_are_what_was_asked():
+    bench = _bench_module("bench_for_test5")
+    a = bench.parse_args(["--steps", "7", "--warmup", "0"])
+    assert a.full is False and a.dump_outputs is None and a.steps == 7 and a.warmup == 0
+    a = bench.parse_args(["--full", "--dump-outputs", "out"])
+    assert a.full is True and a.dump_outputs == "out"
+    for bad in (["--steps", "0"], ["--warmup", "-1"]):
+        with pytest.raises(SystemExit):
+            bench.parse_args(bad)
+
+
+def test_dump_outputs_is_a_fixed_sample_of_every_shard(tmp_path):
+    """Two ranks' shards of a 3-coordinate result: the same lanes on every call, each lane's words from the shard that owns it, each 256-bit word as
+    its 32 little-endian bytes in float32, at most 64 MB for the largest output; a batch below the sample size is dumped whole."""
+    import numpy as np
+    import torch
+    bench = _bench_module("bench_for_test6")
+    total = bench.DUMP_LANES * 4
+    assert 3 * bench.DUMP_LANES * 32 * 4 + bench.DUMP_LANES * 8 <= 64 << 20
+    g = torch.Generator().manual_seed(7)
+    full = torch.randint(-2 ** 63, 2 ** 63 - 1, (3, total, 4), dtype=torch.int64, generator=g)
+    cut = total // 3
+    shards = [(0, cut, list(full[:, :cut])), (cut, total - cut, list(full[:, cut:]))]
+    bench.dump_outputs(str(tmp_path / "a"), ("x", "y", "z"), total, shards)
+    bench.dump_outputs(str(tmp_path / "b"), ("x", "y", "z"), total, shards)
+    lanes = np.load(tmp_path / "a" / "lanes.npy")
+    assert lanes.dtype == np.float64 and len(lanes) == bench.DUMP_LANES and np.all(np.diff(lanes) > 0) and lanes[-1] < total
+    assert (lanes < cut).any() and (lanes >= cut).any()
+    for j, name in enumerate("xyz"):
+        a, b = np.load(tmp_path / "a" / f"{name}.npy"), np.load(tmp_path / "b" / f"{name}.npy")
+        assert a.dtype == np.float32 and a.shape == (len(lanes), 32) and np.array_equal(a, b)
+        for i in (0, len(lanes) // 2, len(lanes) - 1):
+            lane = int(lanes[i])
+            want = sum((int(w) & (2 ** 64 - 1)) << (64 * q) for q, w in enumerate(full[j, lane].tolist()))
+            assert int.from_bytes(bytes(a[i].astype(np.uint8)), "little") == want
+    bench.dump_outputs(str(tmp_path / "c"), ("x",), 1000, [(0, 1000, [full[0, :1000]])])
+    assert np.array_equal(np.load(tmp_path / "c" / "lanes.npy"), np.arange(1000.0))
+    assert np.array_equal(np.load(tmp_path / "c" / "x.npy"), full[0, :1000].numpy().view(np.uint8).reshape(1000, 32).astype(np.float32))

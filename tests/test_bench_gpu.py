@@ -1,4 +1,4 @@
-"""GPU suite: bench.py itself, as the driver runs it (`--multi group` at N = 1 must cost nothing)."""
+"""GPU suite: bench.py itself, as the driver runs it (`--multi group` at N = 1 must cost nothing).  The tests that read\nroofline, group_parity or the N > 1 checks run it with --full; a plain run prints the headline and writes its outputs."""
 import json
 import os
 import subprocess
@@ -12,7 +12,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 def run_bench(*args):
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "WORLD_SIZE", "LOCAL_RANK")}
-    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--no-cpu-baseline", "--global-log2-batch", "23", "--steps", "8", "--warmup", "2"] + list(args),
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--no-cpu-baseline", "--global-log2-batch", "23", "--steps", "8", "--warmup", "2"] + list(args),
                        capture_output=True, text=True, env=env, timeout=600)
     assert r.returncode == 0, r.stderr[-800:]
     lines = r.stdout.splitlines()
@@ -65,7 +65,7 @@ def test_two_ranks_rehearsed_on_one_gpu():
     members on one device) while the ranks wait on the host group, one JSON line, exit code 0."""
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "WORLD_SIZE", "LOCAL_RANK")}
     env["ECSIMD_BENCH_REHEARSE_ONE_GPU"] = "1"
-    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--no-cpu-baseline", "--global-log2-batch", "21", "--steps", "3", "--warmup", "1"],
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--full", "--no-cpu-baseline", "--global-log2-batch", "21", "--steps", "3", "--warmup", "1"],
                        capture_output=True, text=True, env=env, timeout=900)
     assert r.returncode == 0, r.stderr[-1500:]
     lines = r.stdout.splitlines()
@@ -80,3 +80,40 @@ def test_two_ranks_rehearsed_on_one_gpu():
     assert mg["ok"] is True, mg
     assert mg["parity"] == {"gathered_equals_each_members_own_ladder": True, "members": 2}
     assert d["roofline"]["frac"] > 0.2            # two ranks share the card: each ladder runs at about half rate
+
+
+def test_a_plain_run_is_lean_and_dumps_what_its_last_step_computed(tmp_path, engine):
+    """`bench.py --steps K --warmup W` without --full: the contract fields only (no roofline probe, no CPU leg, no ref_compat), K timed steps, and with
+    --dump-outputs the last step's Jacobian (X, Y, Z) on a fixed sample of lanes -- the very words the ladder returns for those lanes' inputs."""
+    import importlib.util
+    import numpy as np
+    from ecsimd_amd import BASE_MGRY, OUT_JACOBIAN, OUT_AFFINE
+    from ecsimd_amd.curves import curve_id
+    spec = importlib.util.spec_from_file_location("bench_for_dump_test", os.path.join(ROOT, "bench.py"))
+    bench = importlib.util.module_from_spec(spec); spec.loader.exec_module(bench)
+    env = {k: v for k, v in os.environ.items() if k not in ("RANK", "WORLD_SIZE", "LOCAL_RANK")}
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--global-log2-batch", "20", "--steps", "3", "--warmup", "1",
+                        "--dump-outputs", str(tmp_path)], capture_output=True, text=True, env=env, timeout=600)
+    assert r.returncode == 0, r.stderr[-800:]
+    lines = r.stdout.splitlines()
+    assert len(lines) == 1, lines
+    d = json.loads(lines[0])
+    for key in ("metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step"):
+        assert key in d, key
+    assert d["steps"] == 3 and d["warmup"] == 1 and d["unit"] == "scalar_mults/s" and d["dtype"] == "u32"
+    assert abs(d["value"] - (1 << 20) / (d["ms_per_step"] * 1e-3)) / d["value"] < 1e-6
+    for key in ("roofline", "cpu_baseline", "ref_compat", "parity_failures"):
+        assert key not in d, key
+    lanes = np.load(tmp_path / "lanes.npy")
+    assert lanes.dtype == np.float64 and len(lanes) == bench.DUMP_LANES and np.all(np.diff(lanes) > 0) and lanes[-1] < 1 << 20
+    n, curve = 1 << 20, curve_id("p256")               # the inputs bench.py makes: (seed, stream, global index), base points from the ladder
+    k = engine.fill_random(n, bench.SEED, 1); s = engine.fill_random(n, bench.SEED, 2)
+    bx, by = engine.scalar_mult_base(curve, s, flags=OUT_AFFINE)
+    P = engine.from_affine(curve, bx, by)
+    exp = engine.scalar_mult(curve, k, P[0], P[1], flags=BASE_MGRY | OUT_JACOBIAN)
+    rows = lanes.astype(np.int64)
+    for name, t in zip("xyz", exp):
+        got = np.load(tmp_path / f"{name}.npy")
+        assert got.dtype == np.float32 and got.shape == (len(lanes), 32)
+        want = np.ascontiguousarray(engine.to_numpy(t)[rows]).view(np.uint8).reshape(-1, 32)
+        assert np.array_equal(got, want.astype(np.float32)), name

@@ -18,7 +18,7 @@ for spec in sys.argv[2:]:
         env["ECSIMD_HIP_LIBRARY"] = os.path.join(ROOT, path)
     vals = []
     for rep in range(2):
-        r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--no-cpu-baseline"] + args, capture_output=True, text=True, env=env)
+        r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--no-cpu-baseline"] + args, capture_output=True, text=True, env=env)
         try:
             d = json.loads([ln for ln in r.stdout.splitlines() if ln.startswith("{")][-1])
             vals.append((d["value"] / 1e6, d["roofline"]["kernel_ms"]))

@@ -9,7 +9,7 @@ mkdir -p "$OUT"
 cd "$REPO"
 run() {   # run <file> <bench args...>
   local f="$1"; shift
-  python3 bench.py "$@" > "$OUT/$f.json" 2> "$OUT/$f.err"; local rc=$?
+  python3 bench.py --full "$@" > "$OUT/$f.json" 2> "$OUT/$f.err"; local rc=$?
   echo "$f rc=$rc $(python3 -c "import json,sys; d=json.load(open('$OUT/$f.json')); print('%.3f M/s  frac %.3f' % (d['value']/1e6, d['roofline']['frac']))" 2>/dev/null)"
 }
 run bench_n1_ladder --steps 10 --warmup 2
@@ -47,6 +47,6 @@ run bench_n1_ladder_radix32_p256 --steps 10 --warmup 2 --workload ladder-radix32
 run bench_n1_group_mode --steps 10 --warmup 2 --multi group
 # the whole N > 1 code path of the one-process-per-GPU mode on the one GPU a builder's box has: RCCL init, side stream, dist.gather
 f=bench_n1_nccl_single_rank_rehearsal
-ECSIMD_BENCH_FORCE_DIST=1 python3 -m torch.distributed.run --nnodes=1 --nproc-per-node 1 --master-addr 127.0.0.1 --master-port 29611 bench.py --gpus 1 --steps 10 --warmup 2 --no-cpu-baseline > "$OUT/$f.json" 2> "$OUT/$f.err"
+ECSIMD_BENCH_FORCE_DIST=1 python3 -m torch.distributed.run --nnodes=1 --nproc-per-node 1 --master-addr 127.0.0.1 --master-port 29611 bench.py --gpus 1 --steps 10 --warmup 2 --full --no-cpu-baseline > "$OUT/$f.json" 2> "$OUT/$f.err"
 echo "$f rc=$? $(python3 -c "import json; d=json.load(open('$OUT/$f.json')); print('%.3f M/s, compute only %.3f' % (d['value']/1e6, d['config']['gather']['value_compute_only']/1e6))" 2>/dev/null)"
 ls -la "$OUT"

@@ -28,7 +28,7 @@ case "$name" in
     done
     cat "$out/ab.txt"; exit 0 ;;
   bench)            # the driver's default command, timed by the shell as the driver does
-    s0=$(date +%s); timeout -k 10 600 python bench.py "$@" > "$out/bench.json" 2> "$out/bench.err"; rc=$?; s1=$(date +%s)
+    s0=$(date +%s); timeout -k 10 600 python bench.py --full "$@" > "$out/bench.json" 2> "$out/bench.err"; rc=$?; s1=$(date +%s)
     echo "rc=$rc wall=$((s1 - s0)) s"; tail -3 "$out/bench.err"; python3 -c "
 import json; d=json.load(open('$out/bench.json')); r=d['roofline']; print('value %.3f M/s  ms/step %.2f  frac %.3f (a priori %.3f)' % (d['value']/1e6, d['ms_per_step'], r['frac'], r['frac_of_a_priori_peak'])); print('ref_compat', {k: v for k, v in d.get('ref_compat', {}).items() if k != 'what'}); print('cpu', {k: d['cpu_baseline'][k] for k in ('value','cores','kind','lanes_compared','lanes_differing_from_gpu','lanes_differing_confirmed_by_openssl')})"
     exit $rc ;;
@@ -86,7 +86,7 @@ import json; d=json.load(open('$out/bench.json')); r=d['roofline']; print('value
       -k "adapter or ecdsa or prime_flagged or small_base or to_affine or inversion or runtime_modulus or random_odd" > "$out/pytest.txt" 2>&1; rc=$?
     tail -8 "$out/pytest.txt"; [ $rc -ne 0 ] && exit $rc
     ./oracle/_ref/adapter_driver 512 65536 > "$out/adapter_driver.txt" 2>&1; cat "$out/adapter_driver.txt"
-    timeout -k 10 600 python bench.py > "$out/bench.json" 2> "$out/bench.err"; rc=$?; tail -3 "$out/bench.err"; head -c 1500 "$out/bench.json"; exit $rc ;;
+    timeout -k 10 600 python bench.py --full > "$out/bench.json" 2> "$out/bench.err"; rc=$?; tail -3 "$out/bench.err"; head -c 1500 "$out/bench.json"; exit $rc ;;
   r5_curves)        # round 5: curves registered at run time -- the parity tests, then the three loops' rates on brainpoolP256r1 beside P-256's
     timeout -k 10 900 python -m pytest tests/test_gpu_curves.py -x -q -m gpu > "$out/pytest.txt" 2>&1; rc=$?
     tail -12 "$out/pytest.txt"; [ $rc -ne 0 ] && exit $rc
@@ -94,7 +94,7 @@ import json; d=json.load(open('$out/bench.json')); r=d['roofline']; print('value
   r5_suite)         # round 5: the whole GPU suite, then the bench lines of a registered curve (default loop, canonical words, reference squaring)
     timeout -k 10 1000 python -m pytest tests -x -q -m gpu > "$out/pytest.txt" 2>&1; rc=$?; tail -6 "$out/pytest.txt"; [ $rc -ne 0 ] && exit $rc
     for w in ladder ladder-radix32 ladder-ref-compat; do
-      timeout -k 10 300 python bench.py --curve brainpoolP256r1 --workload $w --global-log2-batch 22 --steps 5 --warmup 1 > "$out/bench_brainpool_$w.json" 2> "$out/bench_brainpool_$w.err" || { rc=$?; tail -5 "$out/bench_brainpool_$w.err"; exit $rc; }
+      timeout -k 10 300 python bench.py --full --curve brainpoolP256r1 --workload $w --global-log2-batch 22 --steps 5 --warmup 1 > "$out/bench_brainpool_$w.json" 2> "$out/bench_brainpool_$w.err" || { rc=$?; tail -5 "$out/bench_brainpool_$w.err"; exit $rc; }
       python3 -c "
 import json; d=json.load(open('$out/bench_brainpool_$w.json')); r=d['roofline']; c=d['cpu_baseline']; print('$w: %.2f M/s, frac %.3f; cpu %s %.1f k/s on %d cores, %d lanes compared, %d differing' % (d['value']/1e6, r['frac'], c['kind'], c['value']/1e3, c['cores'], c['lanes_compared'], c['lanes_differing_from_gpu']))"
     done; exit 0 ;;
@@ -153,7 +153,7 @@ import json; d=json.load(open('$out/bench_brainpool_$w.json')); r=d['roofline'];
   r5_gvw_lines)     # round 5: the window loop of a registered curve -- its bench lines (CPU leg: the reference instantiated for the curve + to_affine), rocprofv3 stats + --pmc passes, the soak against the ladder
     rc=0; mkdir -p "$out/lines"
     for c in brainpoolP256r1 sm2 frp256v1; do
-      timeout -k 10 400 python3 bench.py --steps 10 --warmup 2 --curve $c --workload windowed > "$out/lines/bench_n1_windowed_variable_base_$c.json" 2> "$out/lines/bench_n1_windowed_variable_base_$c.err" || rc=$?
+      timeout -k 10 400 python3 bench.py --full --steps 10 --warmup 2 --curve $c --workload windowed > "$out/lines/bench_n1_windowed_variable_base_$c.json" 2> "$out/lines/bench_n1_windowed_variable_base_$c.err" || rc=$?
       python3 -c "import json; d=json.load(open('$out/lines/bench_n1_windowed_variable_base_$c.json')); print('$c %.3f M/s  frac %.3f' % (d['value']/1e6, d['roofline']['frac']), {k: v for k, v in d['cpu_baseline'].items() if k.startswith('lanes') or k in ('value', 'kind')})" || { tail -5 "$out/lines/bench_n1_windowed_variable_base_$c.err"; rc=1; }
     done
     [ $rc -ne 0 ] && exit $rc
@@ -177,7 +177,7 @@ import json; d=json.load(open('$out/bench_brainpool_$w.json')); r=d['roofline'];
     exit $rc ;;
   r5_gvw_relines)   # round 5: the window loop's bench lines again, with the committed counter traffic in them
     rc=0; mkdir -p "$out/lines"
-    line() { f=$1; shift; timeout -k 10 400 python3 bench.py --steps 10 --warmup 2 "$@" > "$out/lines/$f.json" 2> "$out/lines/$f.err" || rc=$?
+    line() { f=$1; shift; timeout -k 10 400 python3 bench.py --full --steps 10 --warmup 2 "$@" > "$out/lines/$f.json" 2> "$out/lines/$f.err" || rc=$?
       python3 -c "import json; d=json.load(open('$out/lines/$f.json')); print('$f %.3f M/s  frac %.3f traffic %s' % (d['value']/1e6, d['roofline']['frac'], d['roofline']['traffic']))" || { tail -5 "$out/lines/$f.err"; rc=1; }; }
     for c in brainpoolP256r1 sm2 frp256v1; do line bench_n1_windowed_variable_base_$c --curve $c --workload windowed; done
     line bench_n1_windowed_constant_time_brainpoolP256r1 --curve brainpoolP256r1 --workload windowed-ct
