@@ -53,7 +53,7 @@ void zdau_repeat(hipStream_t s, int curve, const uint64_t* px, const uint64_t* p
 void to_affine_batched(hipStream_t s, int curve, const uint64_t* jx, const uint64_t* jy, const uint64_t* jz, uint64_t* x, uint64_t* y, size_t n, bool in_fast) { DISPATCH2(to_affine_batched, s, jx, jy, jz, x, y, n, in_fast); }
 void pack_table(hipStream_t s, int curve, const uint64_t* tx, const uint64_t* ty, uint32_t* table) { DISPATCH2(pack_table, s, tx, ty, table); }
 void pack_table_signed(hipStream_t s, int curve, int wbits, const uint64_t* tx, const uint64_t* ty, uint32_t* table) { DISPATCH2(pack_table_signed, s, wbits, tx, ty, table); }
-void base_windowed_signed(hipStream_t s, int curve, int wbits, const uint64_t* k, const uint32_t* table, uint64_t* ox, uint64_t* oy, uint64_t* oz, size_t n, bool constant_time) { DISPATCH2(base_windowed_signed, s, wbits, k, table, ox, oy, oz, n, constant_time); }
+void base_windowed_signed(hipStream_t s, int curve, const uint64_t* k, const uint32_t* table, uint64_t* ox, uint64_t* oy, uint64_t* oz, size_t n, bool constant_time) { DISPATCH2(base_windowed_signed, s, k, table, ox, oy, oz, n, constant_time); }
 void inverse_batched(hipStream_t s, int curve, const uint64_t* a, uint64_t* out, size_t n) { DISPATCH2(inverse_batched, s, a, out, n); }
 void x_mod_n_equals(hipStream_t s, int curve, const uint64_t* x, const uint8_t* finite, const uint64_t* r, uint8_t* ok, size_t n) { DISPATCH2(x_mod_n_equals, s, x, finite, r, ok, n); }
 void affine_add_batched(hipStream_t s, int curve, const uint64_t* ax, const uint64_t* ay, const uint64_t* bx, const uint64_t* by, uint64_t* rx, uint64_t* ry, uint8_t* finite, size_t n) { DISPATCH2(affine_add_batched, s, ax, ay, bx, by, rx, ry, finite, n); }
@@ -74,9 +74,9 @@ struct ecsimd_hip_ctx {
   hipEvent_t handoff;  // orders a newly selected stream after the work already enqueued on the previous one
   int cus;
   uint32_t* sink;      // 4 KiB scratch: peak-probe sink [0, 1024) and the shared scalar at word 1024-8
-  uint32_t* window_table[2];   // per curve: 64 x 16 affine multiples d*16^w*G (built on first use)
-  uint32_t* windowct_table[2]; // per curve: the 5- / 6-bit odd-digit table of the constant-time comb (CT_WBITS, CT_WBITS_SECP)
-  uint32_t* window6_table[2];  // per curve: signed-window table (SIGNED_WBITS bits): m * 2^(WB i) * G, m = 1..2^(WB-1)
+  uint32_t* window_table[2];   // per curve: 64 x 8 affine odd multiples (2d + 1) 16^w G (built on first use)
+  uint32_t* windowct_table[2]; // per curve: the 5-bit odd-digit table of the constant-time comb (CT_WBITS)
+  uint32_t* window6_table[2];  // per curve: signed-window table (SIGNED_WBITS bits): (2d + 1) 2^(WB i) G, d = 0..2^(WB-1) - 1
   uint32_t* window16_table[2]; // per curve: signed BIG_WINDOW_BITS-bit windows in device memory (20 bits: 13 x 524 288 entries, 436 MB)
   uint64_t* workspace;         // grow-only scratch for the windowed path's Jacobian intermediates
   size_t workspace_bytes;
@@ -126,6 +126,18 @@ void words_to_limbs(const uint32_t (&w)[8], uint64_t out[4]) {
   for (int i = 0; i < 4; ++i) out[i] = (uint64_t)w[2 * i] | ((uint64_t)w[2 * i + 1] << 32);
 }
 
+// 256-bit host arithmetic (table plans, run-time moduli and curves): four 64-bit limbs, least significant first
+struct u256 { uint64_t l[4]; };
+bool u_geq(const u256& a, const u256& b) { for (int i = 3; i >= 0; --i) if (a.l[i] != b.l[i]) return a.l[i] > b.l[i]; return true; }
+uint64_t u_sub(u256& r, const u256& a, const u256& b) {
+  uint64_t bw = 0;
+  for (int i = 0; i < 4; ++i) { const unsigned __int128 d = (unsigned __int128)a.l[i] - b.l[i] - bw; r.l[i] = (uint64_t)d; bw = (uint64_t)(d >> 64) & 1u; }
+  return bw;
+}
+bool u_is_zero(const u256& a) { return !(a.l[0] | a.l[1] | a.l[2] | a.l[3]); }
+bool u_eq(const u256& a, const u256& b) { return !memcmp(a.l, b.l, 32); }
+u256 u_from(const uint64_t v[4]) { u256 r; memcpy(r.l, v, 32); return r; }
+
 // Grow-only device scratch, ordered by the context's stream (synchronise before switching streams with
 // ecsimd_hip_set_stream while a scratch-using call is in flight).  hipMalloc synchronises: callers that
 // capture graphs warm the path up once.
@@ -160,136 +172,107 @@ int ensure_valid(ecsimd_hip_ctx* ctx, size_t bytes) {
   return ECSIMD_HIP_OK;
 }
 
-// Window tables, produced with the (parity-checked) ladder kernel itself.
-//   bits = 4: 64 x 8 entries (2d + 1) * 16^w * G (odd digits; 64 x 16 entries d * 16^w * G with -DECS_FIXED4_ODD=0);  bits = 6 / 7 (signed windows): 43 x 32 / 37 x 64
-//   entries m * 2^(bits i) * G, m = slot + 1.
+// Window tables, produced with the (parity-checked) ladder kernel itself: odd multiples (2d + 1) 2^(bits w) G, 4 bits (64 x 8 entries), the
+// constant-time comb's 5 bits (52 x 16), the signed comb's 7 bits (37 x 64) and the device-memory comb's BIG_WINDOW_BITS.
 // ALG_CONSTANT_TIME reads EVERY entry of a window, so the best window is narrower than without it (profiles/r03/ab_constant_time_window_width.txt):
 // 5 bits on both curves -- 52 windows x 16 entries, 51 additions, a 53 KB table, THREE 256-thread workgroups per CU (3 waves per SIMD, 146 VGPRs at most,
 // no spill): P-256 326.0 M/s, secp256k1 323.0.  Measured against it: 4 bits (k_base_windowed<true>: 64 x 8, 63 additions) 280.7 / 278.1; 6 bits (43 x 32,
 // one 1024-thread workgroup per CU) 324.2 / 279.5 (19 spills on secp256k1; at 768 threads 310.8 / 268.4); 7 bits (36 additions, 64 entries to read) 294.1 / 235.2.
-#ifndef ECS_CT_P256_BITS
-#define ECS_CT_P256_BITS 5          // 4: k_base_windowed<true>; 5 / 6: the signed kernel's template
-#endif
-#ifndef ECS_CT_SECP_BITS
-#define ECS_CT_SECP_BITS 5
-#endif
-constexpr int CT_WBITS = (ECS_CT_P256_BITS == 5 || ECS_CT_P256_BITS == 6) ? ECS_CT_P256_BITS : 0;
-constexpr int CT_WBITS_SECP = (ECS_CT_SECP_BITS == 5 || ECS_CT_SECP_BITS == 6) ? ECS_CT_SECP_BITS : 0;
+// The other widths were removed.
+constexpr int CT_WBITS = 5;
 constexpr int SIGNED_WBITS = 7;     // 37 additions, 151 552 B of LDS (6 -> 43 additions, 88 064 B): measured faster
 // The reference ladder's degenerate scalars (curve_group.h:189-218 as written: k forced odd, R0 + R1 = 2^i P): 0 and n end at Z = 0, n - 1,
-// 2^256 - n - 1 and 2^256 - n meet n P = infinity inside a formula and return a wrong point.  k < 2^256; nn = the group order.
-bool ladder_degenerate(const uint64_t nn[4], const uint64_t k[4]) {
-  uint64_t c[4], b = 0;                                        // c = 2^256 - n
-  for (int l = 0; l < 4; ++l) { const unsigned __int128 d = (unsigned __int128)0 - nn[l] - b; c[l] = (uint64_t)d; b = (uint64_t)(d >> 64) & 1u; }
-  auto eq = [](const uint64_t* a, const uint64_t* v, uint64_t plus) {          // a == v - plus
-    uint64_t t[4], bb = plus;
-    for (int l = 0; l < 4; ++l) { const unsigned __int128 d = (unsigned __int128)v[l] - bb; t[l] = (uint64_t)d; bb = (uint64_t)(d >> 64) & 1u; }
-    return a[0] == t[0] && a[1] == t[1] && a[2] == t[2] && a[3] == t[3];
-  };
-  const bool zero = (k[0] | k[1] | k[2] | k[3]) == 0;
-  return zero || eq(k, nn, 0) || eq(k, nn, 1) || eq(k, c, 0) || eq(k, c, 1);
+// 2^256 - n - 1 and 2^256 - n meet n P = infinity inside a formula and return a wrong point.  k < 2^256; n = the group order.
+// s = the three that return a point: {n - 1, 2^256 - n - 1, 2^256 - n}.
+void ladder_degenerate_points(const u256& n, u256 (&s)[3]) {
+  const u256 one = {{1, 0, 0, 0}}, zero = {{0, 0, 0, 0}};
+  (void)u_sub(s[0], n, one); (void)u_sub(s[2], zero, n); (void)u_sub(s[1], s[2], one);
 }
-int ensure_window_table(ecsimd_hip_ctx* ctx, int curve, int bits = 4) {
-  uint32_t** slot = (bits == 4) ? &ctx->window_table[curve] : (bits == launch::BIG_WINDOW_BITS) ? &ctx->window16_table[curve] : (bits == 5 || bits == 6) ? &ctx->windowct_table[curve] : &ctx->window6_table[curve];
-  if (*slot) return ECSIMD_HIP_OK;
-  const bool big = (bits == launch::BIG_WINDOW_BITS);        // odd multiples (2d + 1) * 2^(bits w) * G, ceil(256 / bits) windows, no carry window
-  const bool odd4 = (bits == 4) && (launch::FIXED4_ENTRIES == 8);        // the 4-bit LDS table with odd digits (kernels.h ECS_FIXED4_ODD)
-  const bool odds = !big && bits != 4 && ECS_SIGNED_ODD;                  // the 6- / 7-bit LDS table with odd digits (kernels.h ECS_SIGNED_ODD)
-  const int windows = (bits == 4) ? 64 : big ? (256 + bits - 1) / bits : launch::signed_windows(bits), per = (bits == 4) ? launch::FIXED4_ENTRIES : 1 << (bits - 1);
-  const size_t table_entries = (size_t)windows * per;
-  // odd-digit combs: one more scalar, k*, whose point the kernel substitutes for its own sum (k_affine.inc comb_special: the one
-  // odd scalar at which the comb's last mixed addition meets R = T), and a 64-byte record holding k* itself behind it
-  const bool odd = big || odd4 || odds;
-  const size_t entries = table_entries + (odd ? 1 : 0);
-  std::vector<uint64_t> host_k;
-  try { host_k.assign(entries * 4, 0); }                       // up to 218 MB of host memory (20-bit windows): nothing may throw across the C ABI
+bool ladder_degenerate(const u256& n, const u256& k) {
+  u256 s[3]; ladder_degenerate_points(n, s);
+  return u_is_zero(k) || u_eq(k, n) || u_eq(k, s[0]) || u_eq(k, s[1]) || u_eq(k, s[2]);
+}
+// What an odd-digit comb with `bits`-bit windows asks of the ladder, for a built-in or a registered curve of order n >= 2^255 (ensure_window_table,
+// ensure_gc_comb): ceil(256 / bits) windows x 2^(bits - 1) multipliers (2d + 1) 2^(bits w), then one more scalar, k*, whose point the kernel
+// substitutes for its own sum (k_affine.inc comb_special: the one odd scalar at which the comb's last mixed addition meets R = T), and the 64-byte
+// record {k*, 0} that goes behind the table.  Summed from the top (4 bits): k* = n - 2 (n mod 2^bits), and only if bit `bits` of k* is 0 (then its
+// lowest digit is -(n mod 2^bits)); summed from the bottom (the others): k* = n - 2 (n mod 2^(bits (windows - 1))).
+struct comb_plan {
+  size_t table_entries, entries;        // entries = table_entries + 1: the point of k*
+  std::vector<uint64_t> k;              // entries x 4 limbs: the ladder's scalars
+  uint64_t kstar[8];                    // {k* (0: this kernel has no such scalar), 0}: read by comb_special
+  bool negate_special;                  // the k* entry was computed as (n - k*) G: y -> p - y
+};
+int plan_comb(ecsimd_hip_ctx* ctx, const u256& n, int bits, comb_plan& P) {
+  const int windows = (256 + bits - 1) / bits, per = 1 << (bits - 1);
+  P.table_entries = (size_t)windows * per; P.entries = P.table_entries + 1;
+  try { P.k.assign(P.entries * 4, 0); }                        // up to 218 MB of host memory (20-bit windows): nothing may throw across the C ABI
   catch (...) { return bad(ctx, "window table: out of host memory"); }
-  uint64_t kstar[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-  bool negate_special = false;                                 // the table's k* entry was computed as (n - k*) G: y -> p - y
-  if (odd) {
-    // high-to-low accumulation (the 4-bit LDS kernel): k* = n - 2 (n mod 2^bits), and only if bit `bits` of k* is 0 (then its lowest digit
-    // is -(n mod 2^bits)); low-to-high (the device-memory table): k* = n - 2 (n mod 2^(bits (windows - 1)))
-    uint64_t nn[4], m[4] = {0, 0, 0, 0};
-    words_to_limbs(curve == ECSIMD_HIP_P256 ? curve_order<CURVE_P256>::N : curve_order<CURVE_SECP256K1>::N, nn);
-    const int low_bits = (big || odds) ? bits * (windows - 1) : bits;       // summed from the bottom (20-bit table, 6- / 7-bit LDS tables) or from the top (4 bits)
-    for (int l = 0; l < 4; ++l) {
-      const int lo = 64 * l;
-      if (low_bits >= lo + 64) m[l] = nn[l];
-      else if (low_bits > lo) m[l] = nn[l] & ((1ull << (low_bits - lo)) - 1ull);
-    }
-    unsigned __int128 acc = 0; uint64_t m2[4];                                 // 2m (m < 2^255)
-    for (int l = 0; l < 4; ++l) { acc += (unsigned __int128)m[l] * 2u; m2[l] = (uint64_t)acc; acc >>= 64; }
-    uint64_t borrow = 0;
-    for (int l = 0; l < 4; ++l) {
-      const unsigned __int128 d = (unsigned __int128)nn[l] - m2[l] - borrow;
-      kstar[l] = (uint64_t)d; borrow = (uint64_t)(d >> 64) & 1u;
-    }
-    if (borrow || (odd4 && ((kstar[bits / 64] >> (bits % 64)) & 1u))) { for (int l = 0; l < 4; ++l) kstar[l] = 0; }   // no such scalar for this kernel
-    const bool have = (kstar[0] | kstar[1] | kstar[2] | kstar[3]) != 0;
-    for (int l = 0; l < 4; ++l) host_k[table_entries * 4 + l] = have ? kstar[l] : (l == 0 ? 1u : 0u);        // without a k*: any scalar, the point is never used
-    // k* G comes from the reference ladder below, and the ladder has degenerate scalars of its own (0, n, n - 1, 2^256 - n - 1, 2^256 - n:
-    // DESIGN.md section 5).  The 5-bit comb summed from the bottom has k* = n - 2 (n mod 2^255) = 2^256 - n -- one of them:
-    // there the ladder multiplies by n - k* instead (never degenerate when k* is: checked) and the entry's y is negated after the conversion.
-    if (have && ladder_degenerate(nn, kstar)) {
-      uint64_t alt[4], b2 = 0;
-      for (int l = 0; l < 4; ++l) { const unsigned __int128 d = (unsigned __int128)nn[l] - kstar[l] - b2; alt[l] = (uint64_t)d; b2 = (uint64_t)(d >> 64) & 1u; }
-      if (b2 || ladder_degenerate(nn, alt)) return bad(ctx, "window table: neither k* nor n - k* is a scalar the ladder multiplies correctly");
-      for (int l = 0; l < 4; ++l) host_k[table_entries * 4 + l] = alt[l];
-      negate_special = true;
-    }
-  }
+  u256 dg[3]; ladder_degenerate_points(n, dg);
   for (int w = 0; w < windows; ++w)
     for (int d = 0; d < per; ++d) {
-      const unsigned mult = odd ? 2u * (unsigned)d + 1u : (bits == 4) ? (unsigned)d : (unsigned)d + 1u;   // multiplier m
-      const int pos = bits * w;                                                         // entry = m * 2^pos * G
-      uint64_t* e = &host_k[((size_t)w * per + d) * 4];
-      const int limb = pos / 64, off = pos % 64;
-      if (limb >= 4) continue;                                                          // 16-bit windows: the carry window, m * 2^256 (filled below)
-      const unsigned __int128 v = (unsigned __int128)mult << off;
+      uint64_t* e = &P.k[((size_t)w * per + d) * 4];
+      const int pos = bits * w, limb = pos / 64, off = pos % 64;
+      const unsigned __int128 v = (unsigned __int128)(2u * (unsigned)d + 1u) << off;
+      if (limb + 1 >= 4 && (uint64_t)(v >> 64) != 0) { e[0] = 1; continue; }        // (2d + 1) 2^pos >= 2^256: beyond the top digit's range, never read
       e[limb] = (uint64_t)v;
       if (limb + 1 < 4) e[limb + 1] = (uint64_t)(v >> 64);
-      else if ((uint64_t)(v >> 64) != 0) {
-        // m * 2^pos >= 2^256: only the top signed window, where the top digit + carry asks for 2^256 * G.  That
-        // point cannot come from the ladder: k = 2^256 mod n is one of its degenerate scalars (the Joye
-        // ladder keeps R0 + R1 = 2^i * P, so at i = 256 it meets n * P = infinity; the reference's ladder
-        // fails there too).  The slot is filled below by doubling 2^255 * G with the affine-addition kernel.
-        for (int l = 0; l < 4; ++l) e[l] = 0;
-      }
+      const u256 m = u_from(e);                                                    // (odd times a power of two: never 0 or n)
+      if (u_eq(m, dg[0]) || u_eq(m, dg[1]) || u_eq(m, dg[2])) return bad(ctx, "window table: a table multiplier is one of the ladder's degenerate scalars on this curve");
     }
+  const int low = bits == 4 ? bits : bits * (windows - 1);
+  u256 m = n, m2, ks;
+  for (int l = 0; l < 4; ++l) { const int lo = 64 * l; if (low <= lo) m.l[l] = 0; else if (low < lo + 64) m.l[l] &= (1ull << (low - lo)) - 1ull; }
+  for (int l = 3; l > 0; --l) m2.l[l] = (m.l[l] << 1) | (m.l[l - 1] >> 63);
+  m2.l[0] = m.l[0] << 1;                                                           // 2 m (m < 2^255)
+  const bool have = !u_sub(ks, n, m2) && !u_is_zero(ks) && (bits != 4 || ((ks.l[0] >> bits) & 1u) == 0);
+  for (int l = 0; l < 8; ++l) P.kstar[l] = (have && l < 4) ? ks.l[l] : 0;
+  u256 mult = have ? ks : u256{{1, 0, 0, 0}};                                      // without a k*: any scalar, the point is never used
+  P.negate_special = false;
+  // k* G comes from the reference ladder, and the ladder has degenerate scalars of its own.  The 5-bit comb summed from the
+  // bottom has k* = n - 2 (n mod 2^255) = 2^256 - n -- one of them: there the ladder multiplies by n - k* instead (never degenerate when
+  // k* is: checked) and the entry's y is negated after the conversion.
+  if (have && ladder_degenerate(n, ks)) {
+    (void)u_sub(mult, n, ks);
+    if (ladder_degenerate(n, mult)) return bad(ctx, "window table: neither k* nor n - k* is a scalar the ladder multiplies correctly");
+    P.negate_special = true;
+  }
+  for (int l = 0; l < 4; ++l) P.k[P.table_entries * 4 + l] = mult.l[l];
+  return ECSIMD_HIP_OK;
+}
+u256 order_of(int curve) {
+  uint64_t l[4];
+  words_to_limbs(curve == ECSIMD_HIP_P256 ? curve_order<CURVE_P256>::N : curve_order<CURVE_SECP256K1>::N, l);
+  return u_from(l);
+}
+static_assert(launch::FIXED4_ENTRIES == 8, "plan_comb: the 4-bit comb's table is 64 x 8");
+int ensure_window_table(ecsimd_hip_ctx* ctx, int curve, int bits) {
+  uint32_t** slot = (bits == 4) ? &ctx->window_table[curve] : (bits == launch::BIG_WINDOW_BITS) ? &ctx->window16_table[curve] : (bits == CT_WBITS) ? &ctx->windowct_table[curve] : &ctx->window6_table[curve];
+  if (*slot) return ECSIMD_HIP_OK;
+  comb_plan P;
+  int rc = plan_comb(ctx, order_of(curve), bits, P);
+  if (rc != ECSIMD_HIP_OK) return rc;
+  const size_t entries = P.entries;
   // The build needs 6 x entries x 32 B of scratch (1.3 GB for the 20-bit table): a TEMPORARY block freed below, not the
   // context's grow-only workspace -- a caller that verifies one signature must not keep 1.3 GB pinned for it.
   if (capturing(ctx)) return bad(ctx, "a window table would have to be built during stream capture: run this call once before capturing");
   uint64_t* kd = nullptr;
   uint32_t* table = nullptr;
   hipError_t e = hipMalloc(&kd, 6 * entries * 32);
-  if (e == hipSuccess) e = hipMalloc(&table, (entries + (odd ? 1 : 0)) * 64);      // odd-digit combs: + the record that holds k*
+  if (e == hipSuccess) e = hipMalloc(&table, (entries + 1) * 64);      // + the record that holds k*
   uint64_t* tx = kd + entries * 4; uint64_t* ty = tx + entries * 4;
-  if (e == hipSuccess) e = hipMemcpyAsync(kd, host_k.data(), entries * 32, hipMemcpyHostToDevice, ctx->stream);
-  if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);          // host_k must outlive the copy
+  if (e == hipSuccess) e = hipMemcpyAsync(kd, P.k.data(), entries * 32, hipMemcpyHostToDevice, ctx->stream);
+  if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);          // P.k must outlive the copy
   if (e == hipSuccess) {   // ladder (Jacobian, fast domain) into scratch, then affine classical (x, y)
     uint64_t* jx = ty + entries * 4; uint64_t* jy = jx + entries * 4; uint64_t* jz = jy + entries * 4;
     launch::scalar_mult(ctx->stream, curve, kd, 4, nullptr, nullptr, jx, jy, jz, entries, ECSIMD_HIP_OUT_AFFINE);
     launch::to_affine_batched(ctx->stream, curve, jx, jy, jz, tx, ty, entries, true);
-    if (negate_special) launch::field_unop(ctx->stream, curve, launch::F_OPPOSITE, ty + table_entries * 4, ty + table_entries * 4, 1);   // -(x, y) = (x, p - y)
-    if (big) {
-      launch::pack_table_big(ctx->stream, curve, tx, ty, table);           // odd digits: no carry, no 2^256 * G entry
-    } else if (odds) {
-      launch::pack_table_signed(ctx->stream, curve, bits, tx, ty, table);  // odd digits: no carry, no 2^256 * G entry
-    } else if (bits != 4) {
-      // The one reachable entry with m * 2^pos = 2^256 (top digit + carry): the ladder cannot produce 2^256 * G (a degenerate
-      // scalar, see above), so it is the entry holding 2^255 * G doubled by the affine-addition kernel.
-      uint64_t* sx = ty + entries * 4; uint64_t* sy = sx + 4;                                  // scratch (the Jacobian area is free again)
-      const size_t src = ((size_t)(255 / bits) * per + ((size_t)1 << (255 % bits)) - 1) * 4;
-      const size_t dst = ((size_t)(256 / bits) * per + ((size_t)1 << (256 % bits)) - 1) * 4;
-      launch::affine_add_batched(ctx->stream, curve, tx + src, ty + src, tx + src, ty + src, sx, sy, nullptr, 1);
-      e = hipMemcpyAsync(tx + dst, sx, 32, hipMemcpyDeviceToDevice, ctx->stream);
-      if (e == hipSuccess) e = hipMemcpyAsync(ty + dst, sy, 32, hipMemcpyDeviceToDevice, ctx->stream);
-      if (e == hipSuccess) launch::pack_table_signed(ctx->stream, curve, bits, tx, ty, table);
-    } else {
-      launch::pack_table(ctx->stream, curve, tx, ty, table);
-    }
+    if (P.negate_special) launch::field_unop(ctx->stream, curve, launch::F_OPPOSITE, ty + P.table_entries * 4, ty + P.table_entries * 4, 1);   // -(x, y) = (x, p - y)
+    if (bits == launch::BIG_WINDOW_BITS) launch::pack_table_big(ctx->stream, curve, tx, ty, table);
+    else if (bits == 4) launch::pack_table(ctx->stream, curve, tx, ty, table);
+    else launch::pack_table_signed(ctx->stream, curve, bits, tx, ty, table);
+    e = hipMemcpyAsync(table + entries * 16, P.kstar, 64, hipMemcpyHostToDevice, ctx->stream);
   }
-  if (e == hipSuccess && odd) e = hipMemcpyAsync(table + entries * 16, kstar, 64, hipMemcpyHostToDevice, ctx->stream);   // {k*, 0}: read by comb_special
   if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
   if (e == hipSuccess) e = hipGetLastError();
   (void)hipFree(kd);
@@ -409,15 +392,9 @@ bool capturing_needs_build(ecsimd_hip_ctx* ctx, int curve) {
 }
 int ensure_base_special(ecsimd_hip_ctx* ctx, int curve) {
   if (ctx->base_special[curve]) return ECSIMD_HIP_OK;
-  uint64_t nn[4], host[12];
-  words_to_limbs(curve == ECSIMD_HIP_P256 ? curve_order<CURVE_P256>::N : curve_order<CURVE_SECP256K1>::N, nn);
-  uint64_t b = 1;                                                // n - 1
-  for (int l = 0; l < 4; ++l) { const unsigned __int128 d = (unsigned __int128)nn[l] - b; host[l] = (uint64_t)d; b = (uint64_t)(d >> 64) & 1u; }
-  b = 0;                                                         // 2^256 - n
-  for (int l = 0; l < 4; ++l) { const unsigned __int128 d = (unsigned __int128)0 - nn[l] - b; host[8 + l] = (uint64_t)d; b = (uint64_t)(d >> 64) & 1u; }
-  b = 1;                                                         // 2^256 - n - 1
-  for (int l = 0; l < 4; ++l) { const unsigned __int128 d = (unsigned __int128)host[8 + l] - b; host[4 + l] = (uint64_t)d; b = (uint64_t)(d >> 64) & 1u; }
-  for (int j = 0; j < 3; ++j) if (!ladder_degenerate(nn, host + 4 * j)) return bad(ctx, "base_special: not a degenerate scalar");
+  u256 s3[3]; ladder_degenerate_points(order_of(curve), s3);
+  uint64_t host[12];
+  for (int j = 0; j < 3; ++j) for (int l = 0; l < 4; ++l) host[4 * j + l] = s3[j].l[l];
   uint64_t* rec = nullptr; uint64_t* tmp = nullptr;
   hipError_t e = hipMalloc(&rec, 9 * 32);
   if (e == hipSuccess) e = hipMalloc(&tmp, 9 * 32);               // Jacobian scratch of the three ladders
@@ -444,13 +421,6 @@ int ensure_base_special(ecsimd_hip_ctx* ctx, int curve) {
 // special-form kernels, field.cuh); 2, 3 the two group orders; 4... whatever ecsimd_hip_register_modulus was given.  Process-wide,
 // append-only, guarded by one mutex (registration is rare; lookups copy 236 bytes).
 namespace {
-struct u256 { uint64_t l[4]; };
-bool u_geq(const u256& a, const u256& b) { for (int i = 3; i >= 0; --i) if (a.l[i] != b.l[i]) return a.l[i] > b.l[i]; return true; }
-uint64_t u_sub(u256& r, const u256& a, const u256& b) {
-  uint64_t bw = 0;
-  for (int i = 0; i < 4; ++i) { const unsigned __int128 d = (unsigned __int128)a.l[i] - b.l[i] - bw; r.l[i] = (uint64_t)d; bw = (uint64_t)(d >> 64) & 1u; }
-  return bw;
-}
 void u_dbl_mod(u256& a, const u256& p) {                       // a < p  ->  2a mod p
   const uint64_t top = a.l[3] >> 63;
   for (int i = 3; i > 0; --i) a.l[i] = (a.l[i] << 1) | (a.l[i - 1] >> 63);
@@ -513,9 +483,6 @@ bool lookup_modulus(int id, gmod* out) {
 // the host derives what the templates derive (the field's constants as for a modulus, Am = a R, Bm = b R: curve_group.h:31-32) plus the 29-bit-limb
 // constants of the ladder's loop, and the generic kernels (k_gcurve.hip, k_gladder.hip) take the 512-byte record as a kernel argument.
 constexpr int FIRST_CURVE_ID = ECSIMD_HIP_FIRST_REGISTERED_CURVE, MAX_CURVES = 4096;
-bool u_is_zero(const u256& a) { return !(a.l[0] | a.l[1] | a.l[2] | a.l[3]); }
-bool u_eq(const u256& a, const u256& b) { return !memcmp(a.l, b.l, 32); }
-u256 u_from(const uint64_t v[4]) { u256 r; memcpy(r.l, v, 32); return r; }
 u256 u_add_mod(const u256& a, const u256& b, const u256& p) {          // a, b < p
   u256 s; unsigned __int128 c = 0;
   for (int i = 0; i < 4; ++i) { c += (unsigned __int128)a.l[i] + b.l[i]; s.l[i] = (uint64_t)c; c >>= 64; }
@@ -578,8 +545,6 @@ bool u_probable_prime(const u256& n) {
   }
   return true;
 }
-// the reference ladder's degenerate scalars for a group of order nn (ladder_degenerate above works on uint64_t[4])
-bool u_ladder_degenerate(const u256& nn, const u256& k) { return ladder_degenerate(nn.l, k.l); }
 struct curve_registry { std::mutex mu; std::vector<curve_record> curves; };
 curve_registry& curves() { static curve_registry r; return r; }
 bool lookup_curve(int id, gcurve* out) {
@@ -750,10 +715,10 @@ int ecsimd_hip_register_curve(const uint64_t p[4], const uint64_t a[4], const ui
       // ECDSA on this curve multiplies through the reference's ladder, which is wrong at n - 1, 2^256 - n - 1 and 2^256 - n: such a scalar u is replaced by n - u
       // (k_gc_ladder_safe_scalars).  That needs n - u to be a good scalar in turn; and x mod n by ONE conditional subtraction needs p < 2n.
       rec.N = make_gmod(n, GMOD_PRIME);
-      u256 one = {{1, 0, 0, 0}}, zero = {{0, 0, 0, 0}}, nm1, c, cm1, alt, twice;
-      (void)u_sub(nm1, N, one); (void)u_sub(c, zero, N); (void)u_sub(cm1, c, one);
+      u256 s3[3], alt, twice;
+      ladder_degenerate_points(N, s3);
       bool safe = true;
-      for (const u256* d : {&nm1, &c, &cm1}) if (!u_geq(*d, N)) { (void)u_sub(alt, N, *d); if (u_is_zero(alt) || u_ladder_degenerate(N, alt)) safe = false; }
+      for (const u256& d : s3) if (!u_geq(d, N)) { (void)u_sub(alt, N, d); if (ladder_degenerate(N, alt)) safe = false; }
       const uint64_t top = N.l[3] >> 63;
       for (int i = 3; i > 0; --i) twice.l[i] = (N.l[i] << 1) | (N.l[i - 1] >> 63);
       twice.l[0] = N.l[0] << 1;
@@ -1145,21 +1110,18 @@ int ecsimd_hip_scalar_mult_base(ecsimd_hip_ctx* ctx, int curve, const uint64_t* 
     // (the Jacobian representative differs from the reference ladder's -- SURVEY.md 8(a) level A).
     if (!(flags & ECSIMD_HIP_OUT_AFFINE)) return bad(ctx, "ALG_WINDOWED needs OUT_AFFINE");
     const bool ct = (flags & ECSIMD_HIP_ALG_CONSTANT_TIME) != 0;
-    if (ct && !(ECS_FIXED4_ODD && ECS_SIGNED_ODD)) return bad(ctx, "this build (-DECS_FIXED4_ODD=0 / -DECS_SIGNED_ODD=0) has no constant-time comb");
     if (ct && (big || six)) return bad(ctx, "ALG_CONSTANT_TIME modifies ALG_WINDOWED only (its own 5-bit comb in LDS), not ALG_WINDOWED_SIGNED / ALG_WINDOWED_BIG");
     NO_COMPAT("ALG_WINDOWED");
     if (n == 0) return ECSIMD_HIP_OK;
     (void)hipSetDevice(ctx->device);
-    const int ctbits = (ct && !six) ? (curve == ECSIMD_HIP_P256 ? CT_WBITS : CT_WBITS_SECP) : 0;   // the constant-time comb's own table (0: the 4-bit kernel)
-    const bool ct6 = ctbits != 0;
-    int rc = ensure_window_table(ctx, curve, big ? launch::BIG_WINDOW_BITS : six ? SIGNED_WBITS : ct6 ? ctbits : 4);
+    int rc = ensure_window_table(ctx, curve, big ? launch::BIG_WINDOW_BITS : six ? SIGNED_WBITS : ct ? CT_WBITS : 4);    // ALG_CONSTANT_TIME: its own 5-bit comb
     if (rc == ECSIMD_HIP_OK) rc = ensure_workspace(ctx, 3 * n * 32);
     if (rc != ECSIMD_HIP_OK) return rc;
     uint64_t* jx = ctx->workspace; uint64_t* jy = jx + 4 * n; uint64_t* jz = jy + 4 * n;
     RUN(((big ? launch::base_windowed_big(s, curve, k, ctx->window16_table[curve], jx, jy, jz, n)
-          : six ? launch::base_windowed_signed(s, curve, SIGNED_WBITS, k, ctx->window6_table[curve], jx, jy, jz, n, false)
-          : ct6 ? launch::base_windowed_signed(s, curve, ctbits, k, ctx->windowct_table[curve], jx, jy, jz, n, true)
-                : launch::base_windowed(s, curve, k, ctx->window_table[curve], jx, jy, jz, n, ct)),
+          : six ? launch::base_windowed_signed(s, curve, k, ctx->window6_table[curve], jx, jy, jz, n, false)
+          : ct ? launch::base_windowed_signed(s, curve, k, ctx->windowct_table[curve], jx, jy, jz, n, true)
+               : launch::base_windowed(s, curve, k, ctx->window_table[curve], jx, jy, jz, n, false)),
          launch::to_affine_batched(s, curve, jx, jy, jz, ox, oy, n, true)));
   }
   if (flags & ECSIMD_HIP_ALG_CONSTANT_TIME) return bad(ctx, "ALG_CONSTANT_TIME modifies ALG_WINDOWED (the ladder is constant-time as it is)");
@@ -1168,24 +1130,21 @@ int ecsimd_hip_scalar_mult_base(ecsimd_hip_ctx* ctx, int curve, const uint64_t* 
   // safe for secret scalars as the ladder; its affine result is the true k*G, which is the ladder's everywhere but at the ladder's three degenerate
   // scalars, and there the lanes take the ladder's own (meaningless, but the reference's) coordinates from a 288-byte record: the same bits out.
   if ((flags & ECSIMD_HIP_OUT_AFFINE) && n <= SMALL_BASE_MAX && !(flags & (ECSIMD_HIP_REF_SQUARE_COMPAT | ECSIMD_HIP_LADDER_RADIX32)) && !ctx->ref_square &&
-      ECS_FIXED4_ODD && ECS_SIGNED_ODD && !capturing_needs_build(ctx, curve)) {
+      !capturing_needs_build(ctx, curve)) {
     if (n == 0) return ECSIMD_HIP_OK;
     (void)hipSetDevice(ctx->device);
-    const int ctbits = curve == ECSIMD_HIP_P256 ? CT_WBITS : CT_WBITS_SECP;
-    if (ctbits) {
-      int rc = ensure_window_table(ctx, curve, ctbits);
-      const bool x_is_exact = (oy == nullptr && curve == ECSIMD_HIP_P256);    // the P-256 x-only ladder returns the true x for every k already
-      if (rc == ECSIMD_HIP_OK && !x_is_exact) rc = ensure_base_special(ctx, curve);
-      if (rc == ECSIMD_HIP_OK) rc = ensure_workspace(ctx, 3 * n * 32);
-      if (rc != ECSIMD_HIP_OK) return rc;
-      uint64_t* jx = ctx->workspace; uint64_t* jy = jx + 4 * n; uint64_t* jz = jy + 4 * n;
-      hipStream_t s = ctx->stream;
-      launch::base_windowed_signed(s, curve, ctbits, k, ctx->windowct_table[curve], jx, jy, jz, n, true);
-      launch::to_affine_batched(s, curve, jx, jy, jz, ox, oy, n, true);
-      if (!x_is_exact) launch::patch_special(s, k, ctx->base_special[curve], ox, oy, n);
-      hipError_t e = hipGetLastError();
-      return e == hipSuccess ? ECSIMD_HIP_OK : fail(ctx, e, "scalar_mult_base (small batch) launch");
-    }
+    int rc = ensure_window_table(ctx, curve, CT_WBITS);
+    const bool x_is_exact = (oy == nullptr && curve == ECSIMD_HIP_P256);    // the P-256 x-only ladder returns the true x for every k already
+    if (rc == ECSIMD_HIP_OK && !x_is_exact) rc = ensure_base_special(ctx, curve);
+    if (rc == ECSIMD_HIP_OK) rc = ensure_workspace(ctx, 3 * n * 32);
+    if (rc != ECSIMD_HIP_OK) return rc;
+    uint64_t* jx = ctx->workspace; uint64_t* jy = jx + 4 * n; uint64_t* jz = jy + 4 * n;
+    hipStream_t s = ctx->stream;
+    launch::base_windowed_signed(s, curve, k, ctx->windowct_table[curve], jx, jy, jz, n, true);
+    launch::to_affine_batched(s, curve, jx, jy, jz, ox, oy, n, true);
+    if (!x_is_exact) launch::patch_special(s, k, ctx->base_special[curve], ox, oy, n);
+    hipError_t e = hipGetLastError();
+    return e == hipSuccess ? ECSIMD_HIP_OK : fail(ctx, e, "scalar_mult_base (small batch) launch");
   }
   return run_ladder(ctx, curve, k, 4, nullptr, nullptr, ox, oy, oz, n, flags); }
 int ecsimd_hip_affine_add(ecsimd_hip_ctx* ctx, int curve, const uint64_t* ax, const uint64_t* ay, const uint64_t* bx, const uint64_t* by,
@@ -1221,7 +1180,7 @@ int double_scalar_mult_impl(ecsimd_hip_ctx* ctx, int curve, const uint64_t* u1, 
   for (size_t first = 0; first < n; first += chunk) {
     const size_t m = (n - first) < chunk ? (n - first) : chunk;
     if (big) launch::base_windowed_big(s, curve, u1 + 4 * first, ctx->window16_table[curve], jx, jy, jz, m);   // u1*G
-    else launch::base_windowed_signed(s, curve, SIGNED_WBITS, u1 + 4 * first, ctx->window6_table[curve], jx, jy, jz, m, false);
+    else launch::base_windowed_signed(s, curve, u1 + 4 * first, ctx->window6_table[curve], jx, jy, jz, m, false);
     launch::to_affine_batched(s, curve, jx, jy, jz, gx, gy, m, true);
     launch::varwin_scalar_mult(s, curve, u2 + 4 * first, 4, qx + 4 * first, qy + 4 * first, ECSIMD_HIP_BASE_CLASSICAL, scratch, px, py, m);   // u2*Q
     launch::affine_add_batched(s, curve, gx, gy, px, py, rx + 4 * first, ry ? ry + 4 * first : nullptr, finite ? finite + first : nullptr, m);
@@ -1264,47 +1223,13 @@ int ensure_gc_comb(ecsimd_hip_ctx* ctx, int curve, const curve_record& rec, cons
   for (auto& t : ctx->gcomb) if (t.curve == curve && slot(t)) { *out = slot(t); return ECSIMD_HIP_OK; }
   if (!gc_comb_possible(rec)) return bad(ctx, "the windowed algorithms on a registered curve need its group order n, n >= 2^255");
   if (capturing(ctx)) return bad(ctx, "a window table would have to be built during stream capture: run this call once before capturing");
-  const int W = bits == 4 ? launch::GCOMB_WINDOWS : bits == 7 ? launch::GCOMB7_WINDOWS : bits == 20 ? launch::GCOMB20_WINDOWS : launch::GCOMB5_WINDOWS;
-  const int PER = bits == 4 ? launch::GCOMB_ENTRIES : bits == 7 ? launch::GCOMB7_ENTRIES : bits == 20 ? launch::GCOMB20_ENTRIES : launch::GCOMB5_ENTRIES;
-  const size_t table_entries = (size_t)W * PER, entries = table_entries + 1;
-  std::vector<uint64_t> host_k;
-  try { host_k.assign(entries * 4, 0); ctx->gcomb.reserve(ctx->gcomb.size() + 1); } catch (...) { return bad(ctx, "window table: out of host memory"); }
-  for (int w = 0; w < W; ++w)
-    for (int d = 0; d < PER; ++d) {
-      uint64_t* e = &host_k[((size_t)w * PER + d) * 4];
-      const int pos = bits * w, limb = pos / 64, off = pos % 64;
-      const unsigned __int128 v = (unsigned __int128)(2u * (unsigned)d + 1u) << off;
-      if (limb + 1 >= 4 && (uint64_t)(v >> 64) != 0) { e[0] = 1; continue; }        // (2d + 1) 2^pos >= 2^256: beyond the top digit's range, never read
-      e[limb] = (uint64_t)v;
-      if (limb + 1 < 4) e[limb + 1] = (uint64_t)(v >> 64);
-      u256 m; for (int l = 0; l < 4; ++l) m.l[l] = e[l];
-      if (u_ladder_degenerate(rec.n, m)) return bad(ctx, "window table: a table multiplier is one of the ladder's degenerate scalars on this curve");
-    }
-  // 4 bits, summed from the top: k* = n - 2 (n mod 16), and only if bit 4 of it is clear (k_affine.inc comb_special); 7 / 5 bits, summed from the bottom:
-  // k* = n - 2 (n mod 2^(bits (W - 1))) (5 bits: 2^256 - n, one of the ladder's degenerate scalars).  Its point by way of n - k* if the ladder cannot do k*
-  uint64_t kstar[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-  bool negate_special = false;
-  {
-    u256 m2, ks;
-    if (bits == 4) m2 = u256{{2 * (rec.n.l[0] & 15u), 0, 0, 0}};
-    else {
-      const int low = bits * (W - 1);                                            // 252 / 255
-      u256 m = rec.n;
-      for (int l = 0; l < 4; ++l) { const int lo = 64 * l; if (low <= lo) m.l[l] = 0; else if (low < lo + 64) m.l[l] &= (1ull << (low - lo)) - 1ull; }
-      for (int l = 3; l > 0; --l) m2.l[l] = (m.l[l] << 1) | (m.l[l - 1] >> 63);
-      m2.l[0] = m.l[0] << 1;                                                     // 2 m < n (m = n mod 2^252 < 2^252; m = n - 2^255 < n / 2)
-    }
-    (void)u_sub(ks, rec.n, m2);
-    const bool have = bits == 4 ? ((ks.l[0] >> 4) & 1u) == 0 : !u_is_zero(ks);
-    if (have) for (int l = 0; l < 4; ++l) kstar[l] = ks.l[l];
-    u256 mult = have ? ks : u256{{1, 0, 0, 0}};                  // without a k*: any scalar, the point is never used
-    if (have && u_ladder_degenerate(rec.n, ks)) {
-      u256 alt; (void)u_sub(alt, rec.n, ks);
-      if (u_is_zero(alt) || u_ladder_degenerate(rec.n, alt)) return bad(ctx, "window table: neither k* nor n - k* is a scalar the ladder multiplies correctly");
-      mult = alt; negate_special = true;
-    }
-    for (int l = 0; l < 4; ++l) host_k[table_entries * 4 + l] = mult.l[l];
-  }
+  static_assert(launch::GCOMB_WINDOWS == 64 && launch::GCOMB_ENTRIES == 8 && launch::GCOMB7_WINDOWS == 37 && launch::GCOMB7_ENTRIES == 64 && launch::GCOMB5_WINDOWS == 52 &&
+                launch::GCOMB5_ENTRIES == 16 && launch::GCOMB20_WINDOWS == 13 && launch::GCOMB20_ENTRIES == 1 << 19, "plan_comb: ceil(256 / bits) windows x 2^(bits - 1) entries");
+  comb_plan P;
+  int rc = plan_comb(ctx, rec.n, bits, P);
+  if (rc != ECSIMD_HIP_OK) return rc;
+  try { ctx->gcomb.reserve(ctx->gcomb.size() + 1); } catch (...) { return bad(ctx, "window table: out of host memory"); }
+  const size_t table_entries = P.table_entries, entries = P.entries;
   (void)hipSetDevice(ctx->device);
   uint64_t* kd = nullptr;
   uint32_t* table = nullptr;
@@ -1313,15 +1238,15 @@ int ensure_gc_comb(ecsimd_hip_ctx* ctx, int curve, const curve_record& rec, cons
   uint64_t* tx = kd + entries * 4; uint64_t* ty = tx + entries * 4;
   uint64_t* jx = ty + entries * 4; uint64_t* jy = jx + entries * 4; uint64_t* jz = jy + entries * 4;
   uint8_t* flag = reinterpret_cast<uint8_t*>(jz + entries * 4);
-  if (e == hipSuccess) e = hipMemcpyAsync(kd, host_k.data(), entries * 32, hipMemcpyHostToDevice, ctx->stream);
+  if (e == hipSuccess) e = hipMemcpyAsync(kd, P.k.data(), entries * 32, hipMemcpyHostToDevice, ctx->stream);
   if (e == hipSuccess) e = hipMemsetAsync(flag, 1, 16, ctx->stream);
-  if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);          // host_k must outlive the copy
+  if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);          // P.k must outlive the copy
   if (e == hipSuccess) {
     launch::gc_scalar_mult(ctx->stream, rec.G, kd, 4, nullptr, nullptr, jx, jy, jz, entries, 0);
     launch::gc_to_affine_batched(ctx->stream, rec.G, jx, jy, jz, tx, ty, entries);
-    if (negate_special) launch::gc_negate_where(ctx->stream, rec.G, flag, ty + table_entries * 4, 1);
+    if (P.negate_special) launch::gc_negate_where(ctx->stream, rec.G, flag, ty + table_entries * 4, 1);
     launch::gc_pack_table(ctx->stream, rec.G, tx, ty, table, (int)entries);
-    e = hipMemcpyAsync(table + entries * 16, kstar, 64, hipMemcpyHostToDevice, ctx->stream);
+    e = hipMemcpyAsync(table + entries * 16, P.kstar, 64, hipMemcpyHostToDevice, ctx->stream);
   }
   if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
   if (e == hipSuccess) e = hipGetLastError();
@@ -1338,10 +1263,9 @@ int ensure_gc_comb(ecsimd_hip_ctx* ctx, int curve, const curve_record& rec, cons
 int ensure_gc_base_special(ecsimd_hip_ctx* ctx, int curve, const curve_record& rec, const uint64_t** out) {
   for (auto& t : ctx->gcomb) if (t.curve == curve && t.special) { *out = t.special; return ECSIMD_HIP_OK; }
   if (capturing(ctx)) return bad(ctx, "a record would have to be built during stream capture: run this call once before capturing");
-  u256 one = {{1, 0, 0, 0}}, zero = {{0, 0, 0, 0}}, s3[3];
-  (void)u_sub(s3[0], rec.n, one); (void)u_sub(s3[2], zero, rec.n); (void)u_sub(s3[1], s3[2], one);
+  u256 s3[3]; ladder_degenerate_points(rec.n, s3);
   uint64_t host[12];
-  for (int j = 0; j < 3; ++j) { if (!u_ladder_degenerate(rec.n, s3[j])) return bad(ctx, "base_special: not a degenerate scalar"); for (int l = 0; l < 4; ++l) host[4 * j + l] = s3[j].l[l]; }
+  for (int j = 0; j < 3; ++j) for (int l = 0; l < 4; ++l) host[4 * j + l] = s3[j].l[l];
   uint64_t* r = nullptr; uint64_t* tmp = nullptr;
   hipError_t e = hipMalloc(&r, 9 * 32);
   if (e == hipSuccess) e = hipMalloc(&tmp, 9 * 32);
@@ -1641,20 +1565,17 @@ int ecsimd_hip_ecdsa_sign(ecsimd_hip_ctx* ctx, int curve, const uint64_t* e, con
   }
   REQUIRE_CURVE();
   if (ctx->ref_square) return bad(ctx, "ecdsa_sign is not the reference's algorithm: no ECSIMD_HIP_REF_SQUARE_COMPAT form");
-  if (!(ECS_FIXED4_ODD && ECS_SIGNED_ODD)) return bad(ctx, "this build (-DECS_FIXED4_ODD=0 / -DECS_SIGNED_ODD=0) has no constant-time comb");
   if (overlaps(r, e) || overlaps(r, d) || overlaps(r, k) || overlaps(s_, e) || overlaps(s_, d) || overlaps(s_, k) || overlaps(r, s_)) return bad(ctx, "r and s must not alias an input or each other");
   if (n == 0) return ECSIMD_HIP_OK;
   if (n > (size_t)0x7fffffff * BLOCK) return bad(ctx, "batch too large");
   (void)hipSetDevice(ctx->device);
   gmod N; if (!lookup_modulus(curve == ECSIMD_HIP_P256 ? ECSIMD_HIP_FIELD_P256_ORDER : ECSIMD_HIP_FIELD_SECP256K1_ORDER, &N)) return bad(ctx, "group order missing from the registry");
-  const int ctbits = curve == ECSIMD_HIP_P256 ? CT_WBITS : CT_WBITS_SECP;
-  if (!ctbits) return bad(ctx, "this build has no 5- / 6-bit constant-time comb");
-  int rc = ensure_window_table(ctx, curve, ctbits);
+  int rc = ensure_window_table(ctx, curve, CT_WBITS);
   if (rc == ECSIMD_HIP_OK) rc = ensure_workspace(ctx, 4 * n * 32);
   if (rc != ECSIMD_HIP_OK) return rc;
   uint64_t* jx = ctx->workspace; uint64_t* jy = jx + 4 * n; uint64_t* jz = jy + 4 * n; uint64_t* rx = jz + 4 * n;
   hipStream_t st = ctx->stream;
-  launch::base_windowed_signed(st, curve, ctbits, k, ctx->windowct_table[curve], jx, jy, jz, n, true);      // k >= n is reduced by the comb; the lane is refused below
+  launch::base_windowed_signed(st, curve, k, ctx->windowct_table[curve], jx, jy, jz, n, true);      // k >= n is reduced by the comb; the lane is refused below
   launch::to_affine_batched(st, curve, jx, jy, jz, rx, nullptr, n, true);
   launch::ecdsa_sign_scalars(st, N, e, d, k, rx, r, s_, ok, n);
   hipError_t err = hipGetLastError();

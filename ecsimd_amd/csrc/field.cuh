@@ -358,45 +358,7 @@ template <int CURVE> ECS_DEV fe fe_add(const fe& x, const fe& b) {
 }
 // (a - b) mod p: subtract, then add p where the subtraction borrowed.        modular.h:24-41
 // The add-back runs under EXEC = the borrow mask with p's words as inline constants: no mask word is ever built
-// (16 VALU instructions + 2 scalar ones; the masked-operand form took 18).
-#ifndef ECS_SUB_EXEC
-#define ECS_SUB_EXEC 1
-#endif
-#if !ECS_SUB_EXEC
-// the masked-operand form (round 1): borrow word, p & mask, one more chain.  Kept for the A/B: 47.8-47.9 M scalar mults/s against
-// 48.5-48.6 with the EXEC form (-DECS_SUB_EXEC=0, same box, two runs each).
-template <int CURVE> ECS_DEV fe fe_sub(const fe& x, const fe& b) {
-  fe a;
-  uint32_t m = sub8_3(a, x, b);
-  if constexpr (curve_prime<CURVE>::is_p256) {
-    uint32_t m1 = m & 1u;
-    asm("v_add_co_u32 %0, vcc, %0, %8\n\t"
-        "v_addc_co_u32 %1, vcc, %1, %8, vcc\n\t"
-        "v_addc_co_u32 %2, vcc, %2, %8, vcc\n\t"
-        "v_addc_co_u32 %3, vcc, 0, %3, vcc\n\t"
-        "v_addc_co_u32 %4, vcc, 0, %4, vcc\n\t"
-        "v_addc_co_u32 %5, vcc, 0, %5, vcc\n\t"
-        "v_addc_co_u32 %6, vcc, %6, %9, vcc\n\t"
-        "v_addc_co_u32 %7, vcc, %7, %8, vcc"
-        : "+v"(a.w[0]), "+v"(a.w[1]), "+v"(a.w[2]), "+v"(a.w[3]), "+v"(a.w[4]), "+v"(a.w[5]), "+v"(a.w[6]), "+v"(a.w[7])
-        : "v"(m), "v"(m1) : "vcc");
-  } else {
-    using K = curve_consts<CURVE>;
-    uint32_t m0 = m & K::P[0], m1 = m & K::P[1];
-    asm("v_add_co_u32 %0, vcc, %0, %9\n\t"
-        "v_addc_co_u32 %1, vcc, %1, %10, vcc\n\t"
-        "v_addc_co_u32 %2, vcc, %2, %8, vcc\n\t"
-        "v_addc_co_u32 %3, vcc, %3, %8, vcc\n\t"
-        "v_addc_co_u32 %4, vcc, %4, %8, vcc\n\t"
-        "v_addc_co_u32 %5, vcc, %5, %8, vcc\n\t"
-        "v_addc_co_u32 %6, vcc, %6, %8, vcc\n\t"
-        "v_addc_co_u32 %7, vcc, %7, %8, vcc"
-        : "+v"(a.w[0]), "+v"(a.w[1]), "+v"(a.w[2]), "+v"(a.w[3]), "+v"(a.w[4]), "+v"(a.w[5]), "+v"(a.w[6]), "+v"(a.w[7])
-        : "v"(m), "v"(m0), "v"(m1) : "vcc");
-  }
-  return a;
-}
-#else
+// (16 VALU instructions + 2 scalar ones; round 1's masked-operand form took 18 and ran 47.8-47.9 M scalar mults/s against 48.5-48.6: removed).
 template <int CURVE> ECS_DEV fe fe_sub(const fe& x, const fe& b) {
   fe a;
   lane_mask save;
@@ -445,7 +407,6 @@ template <int CURVE> ECS_DEV fe fe_sub(const fe& x, const fe& b) {
 #undef ECS_SUB_OPS
   return a;
 }
-#endif
 // 2a mod p                                                                 modular.h:17-22
 template <int CURVE> ECS_DEV fe fe_dbl(const fe& a) {
   fe s;
@@ -681,9 +642,9 @@ ECS_DEV fe2 sqr8(const fe& a) {
 // including the ones where they are not a^2.  Only the ECSIMD_HIP_REF_SQUARE_COMPAT instances use it
 // (curve_prime<C>::ref_square).
 //
-// sqr8_ref_c is the restatement in wrapping uint64_t C (round 2; proven equal to the compiled reference on 200 000
-// carry-heavy operands): ~230 instructions as the compiler lowers it.  sqr8_ref is the same function of a, hand-laid for
-// gfx950 (round 3, ~150 instructions), one "node" (i, j) = one doubled cross product:
+// Round 2 restated it in wrapping uint64_t C (proven equal to the compiled reference on 200 000 carry-heavy operands; ~230
+// instructions as the compiler lowers it; since removed).  sqr8_ref is the same function of a, hand-laid for gfx950 (round 3,
+// ~150 instructions), one "node" (i, j) = one doubled cross product:
 //   * c = bit 63 of a_i*a_j (mul.h:184 `carry`) is the CARRY-OUT of the multiply itself when 2^63 is the accumulator
 //     input -- v_mad_u64_u32 writes it to an SGPR pair as a lane mask -- and the result's flipped bit 63 is the bit the
 //     doubling shifts out anyway;
@@ -693,37 +654,6 @@ ECS_DEV fe2 sqr8(const fe& a) {
 //     two-word carry chain whose carry-IN is the lane mask of the node before.
 // The digit a row leaves unnormalised (mul.h:207 `ret[i+nlimbs] += prevs[0]`) stays a 64-bit value until the next row's
 // last node (or the last diagonal) consumes it, as in the reference.
-ECS_DEV fe2 sqr8_ref_c(const fe& a) {
-  uint64_t ret[16];
-#pragma unroll
-  for (int i = 0; i < 16; ++i) ret[i] = 0;
-#pragma unroll
-  for (int i = 0; i < 8; ++i) {
-    uint64_t t = (uint64_t)a.w[i] * a.w[i];
-    t += ret[2 * i];
-    ret[2 * i] = t & 0xffffffffu;
-    uint64_t prevs0 = t >> 32, prevs1 = 0;
-#pragma unroll
-    for (int j = i + 1; j < 8; ++j) {
-      uint64_t u = (uint64_t)a.w[i] * a.w[j];
-      const uint64_t carry = u >> 63;
-      u <<= 1;
-      u += ret[i + j];
-      u += prevs0;                         // may wrap: the reference's dropped carry
-      ret[i + j] = u & 0xffffffffu;
-      prevs0 = prevs1;
-      prevs0 += u >> 32;
-      prevs1 = carry;
-    }
-    ret[i + 8] += prevs0;                  // mul.h:207
-    if (i + 9 < 16) ret[i + 9] = prevs1;
-  }
-  fe2 r;
-#pragma unroll
-  for (int i = 0; i < 16; ++i) r.w[i] = (uint32_t)ret[i];
-  return r;
-}
-
 // One node: u = (2*a*b + S) mod 2^64 and c = the lanes where a*b >= 2^63.  The multiply accumulates onto 2^63: its carry-out
 // IS c, and the bit it flips is the one the doubling shifts out.  (One statement: a compiler-scheduled instruction that
 // reads the result of an asm statement is held back by an s_nop -- the gfx950 trans-forwarding hazard it cannot rule out.)
@@ -938,9 +868,6 @@ template <int CURVE> ECS_DEV fe mgry_reduce_generic(fe2& t) {
   return res;
 }
 
-#ifndef ECS_K1_REDUCE_MAD64
-#define ECS_K1_REDUCE_MAD64 1          // 0: round 1-4's borrow-tracking rounds (the A/B build)
-#endif
 // secp256k1, Montgomery domain: T * 2^-256 mod p with the prime's special form.  The reference's eight 32-bit rounds
 // (mgry_mul.h:110-116) add q_i * p * W^i, W = 2^32; with p = W^8 - c, c = W + 977, that is  + q_i W^(8+i)  - q_i c W^i:
 //     (T + Q p) / W^8  =  T_hi + Q - E,      Q = sum q_i W^i,   E = (Q c - T_lo) / W^8   (exact: Q c = T_lo mod W^8).
@@ -953,7 +880,6 @@ template <int CURVE> ECS_DEV fe mgry_reduce_generic(fe2& t) {
 ECS_DEV fe mgry_reduce_secp256k1(fe2& t) {
   const uint32_t MP = curve_consts<CURVE_SECP256K1>::MPRIME, K = 977u;
   fe q; uint32_t dl, dh;
-#if ECS_K1_REDUCE_MAD64
   // Round 5 (the reference-square ladder of secp256k1 ran 8 % behind P-256's, and this reduction -- which those instances cannot trade
   // for the classical domain's fold, the dropped carry being a function of the MONTGOMERY digits -- is where: 64 instructions against P-256's 46, sixteen
   // times per iteration).  The same recurrence with the 64-bit D kept whole:  A = D_i + 977 q_i  is ONE v_mad_u64_u32; its low word IS t_i (that is what
@@ -971,25 +897,6 @@ ECS_DEV fe mgry_reduce_secp256k1(fe2& t) {
     D = ((uint64_t)hi << 32) | lo;
   }
   dl = (uint32_t)D; dh = (uint32_t)(D >> 32);
-#else
-  uint32_t sw, xh;
-  // %0..%7 = q_0..q_7, %8 = lo(D), %9 = hi(D), %10 = s, %11 = hi(977 q), %12..%19 = t_0..t_7, %20 = m', %21 = 977
-#define ECS_K1_ROUND(QI, TI) \
-      "v_sub_co_u32 %10, vcc, " TI ", %8\n\t"        /* s = t_i - lo(D), borrow in VCC */ \
-      "v_mul_lo_u32 " QI ", %10, %20\n\t"             /* q_i = s * m' */ \
-      "v_mul_hi_u32 %11, " QI ", %21\n\t"             /* hi(977 q_i) */ \
-      "v_addc_co_u32 %11, vcc, %9, %11, vcc\n\t"      /* + hi(D) + b   (< 2^11: no carry) */ \
-      "v_add_co_u32 %8, vcc, %11, " QI "\n\t"         /* lo(D') = ... + q_i */ \
-      "v_addc_co_u32 %9, vcc, 0, 0, vcc\n\t"          /* hi(D') */
-  asm("v_mov_b32 %8, 0\n\tv_mov_b32 %9, 0\n\t"
-      ECS_K1_ROUND("%0", "%12") ECS_K1_ROUND("%1", "%13") ECS_K1_ROUND("%2", "%14") ECS_K1_ROUND("%3", "%15")
-      ECS_K1_ROUND("%4", "%16") ECS_K1_ROUND("%5", "%17") ECS_K1_ROUND("%6", "%18") ECS_K1_ROUND("%7", "%19")
-      : "=&v"(q.w[0]), "=&v"(q.w[1]), "=&v"(q.w[2]), "=&v"(q.w[3]), "=&v"(q.w[4]), "=&v"(q.w[5]), "=&v"(q.w[6]), "=&v"(q.w[7]),
-        "=&v"(dl), "=&v"(dh), "=&v"(sw), "=&v"(xh)
-      : "v"(t.w[0]), "v"(t.w[1]), "v"(t.w[2]), "v"(t.w[3]), "v"(t.w[4]), "v"(t.w[5]), "v"(t.w[6]), "v"(t.w[7]), "s"(MP), "s"(K)
-      : "vcc");
-#undef ECS_K1_ROUND
-#endif
   // res = T_hi + Q - E; carry of the addition and borrow of the subtraction net out to the 257th bit (the value is in [0, 2p))
   fe res;
   lane_mask top;
@@ -1086,11 +993,7 @@ template <int CURVE> ECS_DEV fe fe_mul(const fe& a, const fe& b) {
 // a*a*R^-1 mod p                                                           mgry_ops.h:37-42
 template <int CURVE> ECS_DEV fe fe_sqr(const fe& a) {
   fe2 t;
-#if defined(ECS_SQR8_REF_C) && ECS_SQR8_REF_C
-  if constexpr (curve_prime<CURVE>::ref_square) t = sqr8_ref_c(a); else t = sqr8(a);     // A/B build: round 2's restatement in C
-#else
   if constexpr (curve_prime<CURVE>::ref_square) t = sqr8_ref(a); else t = sqr8(a);
-#endif
   return mgry_reduce<CURVE>(t);
 }
 // (a*b - T) * R^-1 mod p for an UNREDUCED 512-bit product T < p^2: one reduction for a difference of two products.
@@ -1154,24 +1057,11 @@ template <int CURVE> ECS_DEV fe fe_to_classical(const fe& n) {
 
 // ---------------------------------------------------------------- masked select / swap
 // m is an all-ones / all-zeros word per lane (the reference's lane mask, utility.h:45-51).
-#ifndef ECS_CSWAP_CNDMASK
-#define ECS_CSWAP_CNDMASK 0       // 1: one v_cmp + 16 v_cndmask by an SGPR mask instead of the XOR / AND form (the compiler lowers that to 9 v_xor +
-                                  // 16 v_bitop3 per ladder iteration).  Measured (profiles/r03/ab_cswap_cndmask.txt): see DESIGN.md section 9
-#endif
+// (Round 3 measured one v_cmp + 16 v_cndmask by an SGPR mask against this XOR / AND form and removed it: profiles/r03/ab_cswap_cndmask.txt,
+// DESIGN.md section 9.)
 ECS_DEV void fe_cswap(uint32_t m, fe& a, fe& b) {                            // swap.h:15-22
-#if ECS_CSWAP_CNDMASK
-  lane_mask k;
-  asm("v_cmp_ne_u32_e64 %0, %1, 0" : "=s"(k) : "v"(m));
-#pragma unroll
-  for (int i = 0; i < 8; ++i) {
-    uint32_t na, nb;
-    asm("v_cndmask_b32_e64 %0, %2, %3, %4\n\tv_cndmask_b32_e64 %1, %3, %2, %4" : "=&v"(na), "=&v"(nb) : "v"(a.w[i]), "v"(b.w[i]), "s"(k));
-    a.w[i] = na; b.w[i] = nb;
-  }
-#else
 #pragma unroll
   for (int i = 0; i < 8; ++i) { uint32_t t = (a.w[i] ^ b.w[i]) & m; a.w[i] ^= t; b.w[i] ^= t; }
-#endif
 }
 ECS_DEV fe fe_select(uint32_t m, const fe& a, const fe& b) {                 // ifelse.h:15-22 (m ? a : b)
   fe r;

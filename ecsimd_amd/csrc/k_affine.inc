@@ -42,18 +42,11 @@ ECS_DEV fe fe_and_not(const fe& a, uint32_t m) { fe r;
 
 // ---------------------------------------------------------------- the combs' accumulator (round 4)
 // Every fixed-base comb (k_base_windowed, k_base_windowed_s, k_base_windowed_g) is "start from one table entry, add the others, hand the Jacobian
-// sum to k_to_affine_batched".  ECS_COMB_RADIX picks the representation the additions run in: 29 (default) = fe29.cuh's nine signed 29-bit limbs
-// (madd29: carry-free columns, lazy limbs, three carry passes per addition; bounds proven by tools/radix29_model.py prove_comb_invariant), 32 =
-// field.cuh's canonical words (madd_hmv, rounds 1-3).  The table keeps 64-byte entries either way: with radix 29 a coordinate is stored as the
-// canonical residue of x * 2^261 (pack29 at build time) and unpacked to tight limbs by shifts and masks at the read (to29).  The sums are the
-// same points; the Jacobian representative is free at the affine level (SURVEY.md 8(a) level A).
-#ifndef ECS_COMB_RADIX
-#define ECS_COMB_RADIX 29
-#endif
-#if !(ECS_FIXED4_ODD && ECS_SIGNED_ODD)
-#undef ECS_COMB_RADIX
-#define ECS_COMB_RADIX 32            // the old unsigned / carry-recoded digit forms (A/B builds only) sum canonical words
-#endif
+// sum to k_to_affine_batched".  comb_acc<RADIX> is the representation the additions run in: 29 = fe29.cuh's nine signed 29-bit limbs (madd29:
+// carry-free columns, lazy limbs, three carry passes per addition; bounds proven by tools/radix29_model.py prove_comb_invariant), 32 = field.cuh's
+// canonical words (madd_hmv, rounds 1-3).  The table keeps 64-byte entries either way: with radix 29 a coordinate is stored as the canonical residue
+// of x * 2^261 (pack29 at build time) and unpacked to tight limbs by shifts and masks at the read (to29).  The sums are the same points; the Jacobian
+// representative is free at the affine level (SURVEY.md 8(a) level A).  The LDS combs sum on 29-bit limbs (round 4; canonical words removed).
 template <int RADIX> struct comb_acc;
 template <> struct comb_acc<32> {
   jpoint A;
@@ -72,14 +65,11 @@ template <> struct comb_acc<29> {
     A.x = select29(m, to29(tx), A.x); A.y = select29(m, to29(ty), A.y); A.z = select29(m, fe29_const<r29_consts<CI>::ONE>(), A.z); }
   ECS_DEV jpoint finish() const { jpoint R; R.x = leave29<CI>(A.x); R.y = leave29<CI>(A.y); R.z = leave29<CI>(A.z); return R; }
 };
-using comb = comb_acc<ECS_COMB_RADIX>;
+using comb = comb_acc<29>;
 // The 20-bit comb in device memory is 12 additions behind 13 random table reads: the radix-29 form's boundary work (three leave29 products and
 // the unpacking) costs what its cheaper additions save at 2^22 lanes and loses 6 % at 2^24 (1 313 against 1 405 M/s, profiles/r04/README.md):
 // that kernel and its table keep the canonical words.
-#ifndef ECS_COMB_BIG_RADIX
-#define ECS_COMB_BIG_RADIX 32
-#endif
-using comb_big = comb_acc<ECS_COMB_BIG_RADIX>;
+using comb_big = comb_acc<32>;
 
 // IN_FAST: the Jacobian input is already in the fast domain (internal callers); otherwise it is in
 // the API's Montgomery form.  x[] doubles as scratch for the prefix products, so x/y must not alias
@@ -233,12 +223,11 @@ __global__ void __launch_bounds__(256) k_affine_add_batched(const uint64_t* __re
   }
 }
 
-// Table entry (w, d), affine, fast domain: 16 words {x[8], y[8]} at T[(w*E + d)*16], E = launch::FIXED4_ENTRIES:
-//   ECS_FIXED4_ODD (default): (2d + 1) * 16^w * G, d = 0..7;   otherwise d * 16^w * G, d = 0..15.
-constexpr int WINDOWS = 64, W4E = launch::FIXED4_ENTRIES, TABLE_WORDS = WINDOWS * W4E * 16;          // 32 768 B (odd digits) / 65 536 B
+// Table entry (w, d), affine, fast domain: 16 words {x[8], y[8]} at T[(w*E + d)*16], E = launch::FIXED4_ENTRIES: (2d + 1) * 16^w * G, d = 0..7.
+constexpr int WINDOWS = 64, W4E = launch::FIXED4_ENTRIES, TABLE_WORDS = WINDOWS * W4E * 16;          // 32 768 B
 __global__ void __launch_bounds__(256) k_pack_table(const uint64_t* __restrict__ tx, const uint64_t* __restrict__ ty, uint32_t* __restrict__ table) {
   const int e = blockIdx.x * 256 + threadIdx.x;
-  if (e >= WINDOWS * W4E + (ECS_FIXED4_ODD ? 1 : 0)) return;      // odd digits: + the point of k* (comb_special)
+  if (e >= WINDOWS * W4E + 1) return;                             // + the point of k* (comb_special)
   fe x = fe_load(tx, e), y = fe_load(ty, e);           // classical affine from the ladder kernel
   x = comb::pack(classical_to_fast<C>(x)); y = comb::pack(classical_to_fast<C>(y));
 #pragma unroll
@@ -300,7 +289,6 @@ template <bool CT> __global__ void __launch_bounds__(WBLOCK) k_base_windowed(con
   __syncthreads();
   const size_t i = (size_t)blockIdx.x * WBLOCK + threadIdx.x;
   if (i >= n) return;
-#if ECS_FIXED4_ODD
   // Regular recoding with odd digits (Joye-Tunstall), the scheme of k_base_windowed_g and k_varwin_mult_odd at 4 bits: k mod n is replaced
   // by the odd one of k, n - k (the sign goes to the result); digit w = (nibble w | 1) - 16 where nibble w + 1 is even (its forced low bit is
   // what the 16 pays for), the top digit = nibble 63 | 1: sixty-four odd digits in [-15, 15].  The accumulator starts from the top entry
@@ -357,44 +345,14 @@ template <bool CT> __global__ void __launch_bounds__(WBLOCK) k_base_windowed(con
 #pragma unroll
   for (int j = 0; j < 8; ++j) { A.x.w[j] &= ~zmask; A.y.w[j] &= ~zmask; A.z.w[j] &= ~zmask; }      // k = 0 mod n: infinity
   fe_store(ox, i, A.x); fe_store(oy, i, A.y); fe_store(oz, i, A.z);
-#else
-  static_assert(!CT, "ALG_CONSTANT_TIME is built on the odd-digit recoding");
-  const uint32_t* kw = reinterpret_cast<const uint32_t*>(k + 4 * i);
-  const fe one = FE_CONST(CI, R_P);
-  fe ax, ay, az;
-#pragma unroll
-  for (int j = 0; j < 8; ++j) { ax.w[j] = 0; ay.w[j] = 0; az.w[j] = 0; }
-  uint32_t inf = ~0u;                                  // accumulator is the point at infinity
-  for (int w8 = 0; w8 < 8; ++w8) {
-    const uint32_t word = kw[w8];
-    for (int s = 0; s < 8; ++s) {
-      const uint32_t d = (word >> (4 * s)) & 15u;
-      fe tx, ty;
-      lds_entry(&lds[((w8 * 8 + s) * 16 + d) * 4], tx, ty);
-      const jpoint R = madd_hmv<CI>(ax, ay, az, tx, ty);
-      const uint32_t skip = 0u - (uint32_t)(d == 0u);                // digit 0: keep the accumulator
-      // first non-zero digit: accumulator := table entry (Z = 1)
-      const fe nx = fe_select(inf, tx, R.x), ny = fe_select(inf, ty, R.y), nz = fe_select(inf, one, R.z);
-      ax = fe_select(skip, ax, nx); ay = fe_select(skip, ay, ny); az = fe_select(skip, az, nz);
-      inf &= skip;
-    }
-  }
-  fe_store(ox, i, ax); fe_store(oy, i, ay); fe_store(oz, i, az);     // k = 0 leaves Z = 0
-#endif
 }
 
-// ---- signed WB-bit windows (WB = 6: 43 mixed additions, WB = 7: 37, instead of 64) ---------------
-// k = sum_i d_i (2^WB)^i with d_i in [-(2^(WB-1) - 1), 2^(WB-1)] (carry recoding of the unsigned digits; the
-// windows cover more than 257 bits, so the last carry is absorbed).  Table entry (i, m) = m * 2^(WB i) * G for
-// m = 1..2^(WB-1): 43 x 32 x 64 B = 88 064 B (WB = 6) or 37 x 64 x 64 B = 151 552 B (WB = 7) of LDS, one
-// workgroup per CU.  A negative digit negates the table point's y.  Same affine results as the 4-bit kernel and the ladder.
-// (That is round 2's recoding, kept under ECS_SIGNED_ODD=0; the default since round 3 is the odd-digit form described in the kernel.)
+// ---- signed WB-bit windows (WB = 5: 51 mixed additions, WB = 7: 36, instead of 63) ---------------
+// Odd digits (the kernel below): table entry (i, d) = (2d + 1) * 2^(WB i) * G for d = 0..2^(WB-1) - 1 -- 52 x 16 x 64 B = 53 248 B (WB = 5) or
+// 37 x 64 x 64 B = 151 552 B (WB = 7) of LDS.  A negative digit negates the table point's y.  Same affine results as the 4-bit kernel and the ladder.
+// (Round 2's carry recoding of unsigned digits was measured against it and removed.)
 template <int WB> struct swin {
-#if ECS_SIGNED_ODD
-  static constexpr int WINDOWS = (256 + WB - 1) / WB;        // 43 / 37 odd digits cover 256 bits: no carry window
-#else
-  static constexpr int WINDOWS = (256 + WB) / WB;            // 43 / 37: enough for 256 bits + the carry
-#endif
+  static constexpr int WINDOWS = (256 + WB - 1) / WB;        // 52 / 37 odd digits cover 256 bits: no carry window
   static constexpr int ENTRIES = 1 << (WB - 1);
   static constexpr int TABLE_WORDS = WINDOWS * ENTRIES * 16;
 };
@@ -409,7 +367,7 @@ template <int WB> struct swin {
 constexpr int SW_BLOCK = ECS_SW_BLOCK;
 template <int WB> __global__ void __launch_bounds__(256) k_pack_table_s(const uint64_t* __restrict__ tx, const uint64_t* __restrict__ ty, uint32_t* __restrict__ table) {
   const int e = blockIdx.x * 256 + threadIdx.x;
-  if (e >= swin<WB>::WINDOWS * swin<WB>::ENTRIES + (ECS_SIGNED_ODD ? 1 : 0)) return;      // odd digits: + the point of k* (comb_special)
+  if (e >= swin<WB>::WINDOWS * swin<WB>::ENTRIES + 1) return;      // + the point of k* (comb_special)
   const fe x = comb::pack(classical_to_fast<C>(fe_load(tx, e))), y = comb::pack(classical_to_fast<C>(fe_load(ty, e)));
 #pragma unroll
   for (int i = 0; i < 8; ++i) { table[e * 16 + i] = x.w[i]; table[e * 16 + 8 + i] = y.w[i]; }
@@ -424,7 +382,6 @@ template <int WB, bool CT, int BLK = SW_BLOCK> __global__ void __launch_bounds__
   __syncthreads();
   const size_t i = (size_t)blockIdx.x * BLK + threadIdx.x;
   if (i >= n) return;
-#if ECS_SIGNED_ODD
   // Odd digits (round 3), the scheme of k_base_windowed_g with the table in LDS: the odd one of k mod n, n - k; digit w = ((k >> WB w) mod
   // 2^(WB + 1) | 1) - 2^WB for every window but the top one, whose digit is what remains | 1; the table holds (2d + 1) 2^(WB w) G.  No zero
   // digit: the first entry starts the sum, WINDOWS - 1 mixed additions follow, nothing to skip.  Summed from the bottom: the one scalar whose
@@ -494,37 +451,6 @@ template <int WB, bool CT, int BLK = SW_BLOCK> __global__ void __launch_bounds__
     for (int j = 0; j < 8; ++j) { A.x.w[j] = 0; A.y.w[j] = 0; A.z.w[j] = 0; }
   }
   fe_store(ox, i, A.x); fe_store(oy, i, A.y); fe_store(oz, i, A.z);
-  return;
-#else
-  static_assert(!CT, "ALG_CONSTANT_TIME is built on the odd-digit recoding");
-  const uint32_t* kw = reinterpret_cast<const uint32_t*>(k + 4 * i);
-  const fe one = FE_CONST(CI, R_P);
-  constexpr uint32_t HALF = 1u << (WB - 1), FULL = 1u << WB;
-  fe ax, ay, az;
-#pragma unroll
-  for (int j = 0; j < 8; ++j) { ax.w[j] = 0; ay.w[j] = 0; az.w[j] = 0; }
-  uint32_t inf = ~0u, carry = 0;
-  for (int w = 0; w < swin<WB>::WINDOWS; ++w) {
-    const int bit = WB * w, wi = bit >> 5, sh = bit & 31;            // wave-uniform
-    const uint64_t two = (wi < 8 ? (uint64_t)kw[wi] : 0ull) | ((wi + 1 < 8) ? ((uint64_t)kw[wi + 1] << 32) : 0ull);
-    const uint32_t u = ((uint32_t)(two >> sh) & (FULL - 1u)) + carry;   // unsigned digit + carry: 0..2^WB
-    carry = (u > HALF) ? 1u : 0u;
-    const uint32_t neg = 0u - carry;                                 // digit = u - 2^WB when u > 2^(WB-1)
-    const uint32_t mag = carry ? (FULL - u) : u;                     // |digit| in 0..2^(WB-1)
-    const uint4* e = &lds_s[((size_t)w * swin<WB>::ENTRIES + (mag == 0u ? 0u : mag - 1u)) * 4];
-    const uint4 q0 = e[0], q1 = e[1], q2 = e[2], q3 = e[3];
-    fe tx, ty;
-    tx.w[0] = q0.x; tx.w[1] = q0.y; tx.w[2] = q0.z; tx.w[3] = q0.w; tx.w[4] = q1.x; tx.w[5] = q1.y; tx.w[6] = q1.z; tx.w[7] = q1.w;
-    ty.w[0] = q2.x; ty.w[1] = q2.y; ty.w[2] = q2.z; ty.w[3] = q2.w; ty.w[4] = q3.x; ty.w[5] = q3.y; ty.w[6] = q3.z; ty.w[7] = q3.w;
-    ty = fe_select(neg, fe_neg<CI>(ty), ty);
-    const jpoint R = madd_hmv<CI>(ax, ay, az, tx, ty);
-    const uint32_t skip = 0u - (uint32_t)(mag == 0u);
-    const fe nx = fe_select(inf, tx, R.x), ny = fe_select(inf, ty, R.y), nz = fe_select(inf, one, R.z);
-    ax = fe_select(skip, ax, nx); ay = fe_select(skip, ay, ny); az = fe_select(skip, az, nz);
-    inf &= skip;
-  }
-  fe_store(ox, i, ax); fe_store(oy, i, ay); fe_store(oz, i, az);
-#endif
 }
 
 // GW_BITS-bit windows over a table in device memory (20 bits: 13 windows x 524 288 entries x 64 B = 436 MB per curve),
@@ -658,17 +584,13 @@ template <int WB, bool CT, int BLK = SW_BLOCK> static void launch_swin(hipStream
 }
 template <> void point_launch<C>::pack_table_signed(hipStream_t s, int wbits, const uint64_t* tx, const uint64_t* ty, uint32_t* table) {
   if (wbits == 5) hipLaunchKernelGGL(k_pack_table_s<5>, dim3((swin<5>::WINDOWS * swin<5>::ENTRIES + 256) / 256), dim3(256), 0, s, tx, ty, table);
-  else if (wbits == 6) hipLaunchKernelGGL(k_pack_table_s<6>, dim3((swin<6>::WINDOWS * swin<6>::ENTRIES + 255) / 256), dim3(256), 0, s, tx, ty, table);
   else hipLaunchKernelGGL(k_pack_table_s<7>, dim3((swin<7>::WINDOWS * swin<7>::ENTRIES + 255) / 256), dim3(256), 0, s, tx, ty, table);
 }
-template <> void point_launch<C>::base_windowed_signed(hipStream_t s, int wbits, const uint64_t* k, const uint32_t* table, uint64_t* ox, uint64_t* oy, uint64_t* oz, size_t n, bool constant_time) {
-#if ECS_SIGNED_ODD
-  // the constant-time combs (every entry of a window read): 6-bit windows, one 1024-thread workgroup per CU; 5-bit windows (53 KB), three 256-thread workgroups per CU
-  if (wbits == 6 && constant_time) { launch_swin<6, true>(s, k, table, ox, oy, oz, n); return; }
-  if (wbits == 5 && constant_time) { launch_swin<5, true, 256>(s, k, table, ox, oy, oz, n); return; }
-#endif
-  if (wbits == 6) launch_swin<6, false>(s, k, table, ox, oy, oz, n);   // (an -DECS_SIGNED_ODD=0 build has no constant-time form: capi.hip refuses the flag)
-  else launch_swin<7, false>(s, k, table, ox, oy, oz, n);          // constant time at 7 bits lost (64 entries to read per window): not built
+template <> void point_launch<C>::base_windowed_signed(hipStream_t s, const uint64_t* k, const uint32_t* table, uint64_t* ox, uint64_t* oy, uint64_t* oz, size_t n, bool constant_time) {
+  // the constant-time comb (every entry of a window read): 5-bit windows (53 KB), three 256-thread workgroups per CU; public scalars: 7-bit windows.
+  // (6-bit windows, and constant time at 7 bits with its 64 entries to read per window, were measured and removed: capi.hip CT_WBITS.)
+  if (constant_time) launch_swin<5, true, 256>(s, k, table, ox, oy, oz, n);
+  else launch_swin<7, false>(s, k, table, ox, oy, oz, n);
 }
 template <> void point_launch<C>::pack_table_big(hipStream_t s, const uint64_t* tx, const uint64_t* ty, uint32_t* table) {
   const size_t count = (size_t)GW_WINDOWS * GW_ENTRIES + 1;        // + the point of k* (comb_special)
@@ -679,9 +601,8 @@ template <> void point_launch<C>::base_windowed_big(hipStream_t s, const uint64_
 }
 template <> void point_launch<C>::base_windowed(hipStream_t s, const uint64_t* k, const uint32_t* table, uint64_t* ox, uint64_t* oy, uint64_t* oz, size_t n, bool constant_time) {
   const dim3 grid((unsigned)((n + WBLOCK - 1) / WBLOCK));
-#if ECS_FIXED4_ODD
+  // (no entry point asks for constant_time since the 5-bit comb replaced this one there; tests/test_constant_time_isa.py still holds k_base_windowed<true> to the ISA)
   if (constant_time) { hipLaunchKernelGGL(k_base_windowed<true>, grid, dim3(WBLOCK), 0, s, k, table, ox, oy, oz, n); return; }
-#endif
   hipLaunchKernelGGL(k_base_windowed<false>, grid, dim3(WBLOCK), 0, s, k, table, ox, oy, oz, n);
 }
 }  // namespace launch

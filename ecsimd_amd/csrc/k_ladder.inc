@@ -19,13 +19,10 @@ constexpr int C = ECS_CURVE;
                                   // scalar pointer's reload outside the bit loop: 48.41 against 48.33 M/s, nothing to gain either way)
 #endif
 
-// RADIX: the representation the 254-iteration loop runs in -- 32: field.cuh's canonical 8 x 32-bit words (rounds 1-3, and what the
-// reference-square instances need); 29: fe29.cuh's nine signed 29-bit limbs (round 4; the default where it exists).  Same results.
-#ifndef ECS_LADDER_RADIX
-#define ECS_LADDER_RADIX 29
-#endif
+// RADIX: the representation the 254-iteration loop runs in -- 32: field.cuh's canonical 8 x 32-bit words (rounds 1-3, what the
+// reference-square instances need, and ECSIMD_HIP_LADDER_RADIX32); 29: fe29.cuh's nine signed 29-bit limbs (round 4; the default where
+// it exists).  Same results.
 constexpr bool HAS_R29 = ladder_has_radix29<curve_domain<C>::fast>::value;
-constexpr int DEFAULT_RADIX = (HAS_R29 && ECS_LADDER_RADIX == 29) ? 29 : 32;
 template <int RADIX> __global__ void __launch_bounds__(BLOCK, LADDER_WAVES_PER_SIMD)
 k_scalar_mult(const uint64_t* __restrict__ k, int k_stride, const uint64_t* __restrict__ x, const uint64_t* __restrict__ y,
               uint64_t* __restrict__ ox, uint64_t* __restrict__ oy, uint64_t* __restrict__ oz, size_t n, int flags) {
@@ -182,7 +179,7 @@ template <> void point_launch<C>::scalar_mult_x(hipStream_t s, const uint64_t* k
 template <> void point_launch<C>::scalar_mult(hipStream_t s, const uint64_t* k, int k_stride, const uint64_t* x, const uint64_t* y,
                                               uint64_t* ox, uint64_t* oy, uint64_t* oz, size_t n, int flags) {
   if constexpr (HAS_R29) {
-    if (DEFAULT_RADIX == 29 && !(flags & ECSIMD_HIP_LADDER_RADIX32)) { hipLaunchKernelGGL(k_scalar_mult<29>, grid_for(n), dim3(BLOCK), 0, s, k, k_stride, x, y, ox, oy, oz, n, flags); return; }
+    if (!(flags & ECSIMD_HIP_LADDER_RADIX32)) { hipLaunchKernelGGL(k_scalar_mult<29>, grid_for(n), dim3(BLOCK), 0, s, k, k_stride, x, y, ox, oy, oz, n, flags); return; }
   }
   hipLaunchKernelGGL(k_scalar_mult<32>, grid_for(n), dim3(BLOCK), 0, s, k, k_stride, x, y, ox, oy, oz, n, flags);
 }

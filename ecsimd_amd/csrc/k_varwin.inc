@@ -9,20 +9,19 @@
 //   secp256k1: the GLV split k = k1 + k2*lambda -- {1..8}P, 32 x (4 doublings + 2 checked additions) (k_varwin_mult_glv).
 //
 // Kernels:
-//   k_varwin_odd_multiples<CHAIN> / k_varwin_multiples_chain   the table's multiples in Jacobian form -> scratch (SoA, entry-major), each Z the one before
+//   k_varwin_odd_multiples / k_varwin_multiples_chain   the table's multiples in Jacobian form -> scratch (SoA, entry-major), each Z the one before
 //                        times a stored ratio, the last Z on its own; 1P -> slot 0
 //   k_varwin_invert_last + k_varwin_chain_to_table   ONE shared inversion per lane (the chain's last Z), the walk back through the ratios -> table slots 1..7
 //   k_varwin_table_iso   secp256k1's default loop: all eight multiples over one Z, no inversion (the loop runs on the isomorphic curve)
-//   k_varwin_multiples + k_varwin_to_table   rounds 1-3's form (-DECS_VARWIN_CHAIN=0): Montgomery's simultaneous inversion over all 7n Jacobian points
-//   k_varwin_mult_odd / k_varwin_mult_glv / k_varwin_mult_glv_ct   the window loop; Jacobian result (fast domain) -> scratch, then the caller
-//                        runs k_to_affine_batched (k_affine.inc)
+//   k_varwin_mult_odd / k_varwin_mult_glv / k_varwin_mult_glv_ct   the window loop, on fe29.cuh's 29-bit limbs; Jacobian result (fast domain) -> scratch,
+//                        then the caller runs k_to_affine_batched (k_affine.inc)
+// (Rounds 1-3's canonical-word loops and their simultaneous inversion over all 7n Jacobian multiples were measured against these and removed.)
 //
 // k is reduced mod n first, so the paths are correct for every 256-bit scalar; k = 0 mod n gives Z = 0, which the affine
 // conversion turns into (0, 0) like everywhere else in this library.
 #include "kernels.h"
 #include "point.cuh"
 #include "../../include/ecsimd_hip.h"
-#include <type_traits>
 
 namespace ecsimd_hip {
 namespace {
@@ -37,54 +36,9 @@ ECS_DEV bool vw_is_zero(const fe& a) {
   return d == 0;
 }
 
-// The odd-digit window loop (k_varwin_mult_odd, plain and constant-time) runs on fe29.cuh's nine signed 29-bit limbs since round 4
-// (ECS_VARWIN_RADIX=29; 32 = rounds 1-3's canonical words): jdbl29 / dbl_add29 with lazy limbs, carry passes where a square or a wide product needs
-// them and vred29 after every point operation (tools/radix29_model.py prove_window_invariant).  Its table then holds x * 2^261 (pack29) like the
-// combs'.  (The GLV loops of secp256k1 moved later in the round: ECS_GLVCT_RADIX, ECS_GLV_RADIX below.)
-#ifndef ECS_VARWIN_RADIX
-#define ECS_VARWIN_RADIX 29
-#endif
-constexpr bool VW29 = (ECS_VARWIN_RADIX == 29);
-
-// a / 2 mod p: (a + (a odd ? p : 0)) >> 1 over 257 bits
-template <int CF> ECS_DEV fe fe_half(const fe& a) {
-  using K = curve_consts<CF>;
-  const uint32_t m = 0u - (a.w[0] & 1u);
-  fe pm, s;
-#pragma unroll
-  for (int i = 0; i < 8; ++i) pm.w[i] = K::P[i] & m;
-  const lane_mask c = add8m3(s, a, pm);
-  uint32_t top;
-  asm("v_cndmask_b32_e64 %0, 0, 1, %1" : "=v"(top) : "s"(c));
-  fe r;
-#pragma unroll
-  for (int i = 0; i < 7; ++i) r.w[i] = __builtin_amdgcn_alignbit(s.w[i + 1], s.w[i], 1);
-  r.w[7] = __builtin_amdgcn_alignbit(top, s.w[7], 1);
-  return r;
-}
-
-// Jacobian doubling, 4M + 4S (a = -3) / 3M + 4S (a = 0), 8 linear operations:
-//   Y2 = 2Y, G = Y2^2 (= 4Y^2), B = X*G (= 4XY^2), alpha = 3(X - Z^2)(X + Z^2) | 3X^2,
-//   X3 = alpha^2 - 2B, Y3 = alpha (B - X3) - G^2/2 (= 8Y^4), Z3 = Y2*Z.        Z = 0 stays Z = 0.
-ECS_DEV jpoint jdbl(const jpoint& P) {
-  const fe Y2 = fe_dbl<CI>(P.y);
-  const fe G = fe_sqr<CI>(Y2);
-  const fe B = fe_mul<CI>(P.x, G);
-  fe t;
-  if constexpr (C == CURVE_P256) {
-    const fe delta = fe_sqr<CI>(P.z);
-    t = fe_mul<CI>(fe_sub<CI>(P.x, delta), fe_add<CI>(P.x, delta));
-  } else {
-    t = fe_sqr<CI>(P.x);
-  }
-  const fe alpha = fe_add<CI>(fe_dbl<CI>(t), t);
-  jpoint R;
-  R.z = fe_mul<CI>(Y2, P.z);
-  R.x = fe_sub<CI>(fe_sqr<CI>(alpha), fe_dbl<CI>(B));
-  // G^2 / 2 = (G/2) * G: a product, so Y3 = alpha (B - X3) - (G/2) G takes ONE reduction (field.cuh fe_mul_sub_product)
-  R.y = fe_mul_sub_product<CI>(alpha, fe_sub<CI>(B, R.x), mul8x8(fe_half<CI>(G), G));
-  return R;
-}
+// The window loops run on fe29.cuh's nine signed 29-bit limbs since round 4: jdbl29 / dbl_add29 with lazy limbs, carry passes where a square or
+// a wide product needs them and vred29 after every point operation (tools/radix29_model.py prove_window_invariant).  Their tables hold x * 2^261
+// (pack29) like the combs'.
 
 ECS_DEV void load_slot(const uint4* __restrict__ table, size_t slot, fe& x, fe& y) {
   const uint4* e = table + slot * 4;
@@ -106,34 +60,10 @@ ECS_DEV void store_half_slot(uint4* __restrict__ table, size_t slot, int half, c
 constexpr int VW_ENTRIES = 8;     // {1..8}P (GLV loop) or {1, 3, .., 15}P (odd-digit loop)
 constexpr int VW_JAC = 7;         // all but 1P pass through the inversion
 
-// The GLV loop's table: 2P..8P (Jacobian, fast domain) -> jx/jy/jz[(m-2)*n + i]; 1P -> table slot 8 i.  secp256k1 only.
-template <int PACK29> __global__ void __launch_bounds__(BLOCK) k_varwin_multiples(const uint64_t* __restrict__ x, const uint64_t* __restrict__ y, int flags,
-                                                            uint64_t* __restrict__ jx, uint64_t* __restrict__ jy, uint64_t* __restrict__ jz,
-                                                            uint4* __restrict__ table, size_t n) {
-  const size_t i = (size_t)blockIdx.x * BLOCK + threadIdx.x;
-  if (i >= n) return;
-  fe px = fe_load(x, i), py = fe_load(y, i);
-  const bool in_mgry = (flags & ECSIMD_HIP_BASE_MGRY) != 0;
-  if constexpr (CI == C) { if (!in_mgry) { px = fe_from_classical<C>(px); py = fe_from_classical<C>(py); } }
-  else { if (in_mgry) { px = fe_to_classical<C>(px); py = fe_to_classical<C>(py); } }
-  store_half_slot(table, i * VW_ENTRIES, 0, PACK29 ? pack29<CI>(px) : px);        // the constant-time GLV loop's table form (29-bit limbs)
-  store_half_slot(table, i * VW_ENTRIES, 1, PACK29 ? pack29<CI>(py) : py);
-  jpoint P1; P1.x = px; P1.y = py; P1.z = FE_CONST(CI, R_P);
-#define ECS_PUT(M, PT) fe_store(jx, (size_t)(M - 2) * n + i, PT.x); fe_store(jy, (size_t)(M - 2) * n + i, PT.y); fe_store(jz, (size_t)(M - 2) * n + i, PT.z);
-  const jpoint P2 = jdbl(P1);                                  ECS_PUT(2, P2)
-  const jpoint P3 = madd_hmv<CI>(P2.x, P2.y, P2.z, px, py);    ECS_PUT(3, P3)
-  const jpoint P6 = jdbl(P3);                                  ECS_PUT(6, P6)
-  const jpoint P7 = madd_hmv<CI>(P6.x, P6.y, P6.z, px, py);    ECS_PUT(7, P7)
-  const jpoint P4 = jdbl(P2);                                  ECS_PUT(4, P4)
-  const jpoint P5 = madd_hmv<CI>(P4.x, P4.y, P4.z, px, py);    ECS_PUT(5, P5)
-  const jpoint P8 = jdbl(P4);                                  ECS_PUT(8, P8)
-#undef ECS_PUT
-}
-
-// The same multiples as a CHAIN (round 4; the constant-time GLV loop's table): 2P by DBLU, then (m + 1)P = P + mP by co-Z additions, each Z the one before
+// The constant-time GLV loop's table {1..8}P as a CHAIN (round 4): 2P by DBLU, then (m + 1)P = P + mP by co-Z additions, each Z the one before
 // times that step's x-difference -- so, as for the odd multiples below, only 8P's Z is inverted (k_varwin_invert_last) and k_varwin_chain_to_table walks
-// back through the differences.  6 + 6 x 7 products against 4 x 7 + 3 x 11, and the table step costs 5 products per entry against 10, a fifth of the traffic.
-template <int PACK29> __global__ void __launch_bounds__(BLOCK) k_varwin_multiples_chain(const uint64_t* __restrict__ x, const uint64_t* __restrict__ y, int flags,
+// back through the differences.  6 + 6 x 7 products against rounds 1-3's 4 x 7 + 3 x 11, and the table step costs 5 products per entry against 10.
+__global__ void __launch_bounds__(BLOCK) k_varwin_multiples_chain(const uint64_t* __restrict__ x, const uint64_t* __restrict__ y, int flags,
                                                             uint64_t* __restrict__ jx, uint64_t* __restrict__ jy, uint64_t* __restrict__ jh, uint64_t* __restrict__ zlast,
                                                             uint4* __restrict__ table, size_t n) {
   const size_t i = (size_t)blockIdx.x * BLOCK + threadIdx.x;
@@ -142,8 +72,8 @@ template <int PACK29> __global__ void __launch_bounds__(BLOCK) k_varwin_multiple
   const bool in_mgry = (flags & ECSIMD_HIP_BASE_MGRY) != 0;
   if constexpr (CI == C) { if (!in_mgry) { px = fe_from_classical<C>(px); py = fe_from_classical<C>(py); } }
   else { if (in_mgry) { px = fe_to_classical<C>(px); py = fe_to_classical<C>(py); } }
-  store_half_slot(table, i * VW_ENTRIES, 0, PACK29 ? pack29<CI>(px) : px);
-  store_half_slot(table, i * VW_ENTRIES, 1, PACK29 ? pack29<CI>(py) : py);
+  store_half_slot(table, i * VW_ENTRIES, 0, pack29<CI>(px));
+  store_half_slot(table, i * VW_ENTRIES, 1, pack29<CI>(py));
   fe ax, ay, z;                                          // (ax, ay) = 2P; (px, py) becomes P over the same z (curve_group.h:64-87 DBLU)
   dblu<CI>(px, py, ax, ay, z);
   fe_store(jx, i, ax); fe_store(jy, i, ay);
@@ -158,84 +88,18 @@ template <int PACK29> __global__ void __launch_bounds__(BLOCK) k_varwin_multiple
   fe_store(zlast, i, z);
 }
 
-// Simultaneous inversion over the 7n Jacobian multiples (element e = (m-2)*n + lane): a GPU lane owns `per`
-// elements strided by `lanes`, multiplies their Z, inverts once, walks back.  The prefix products wait in a
-// scratch array of their own.  Everything stays in the fast domain.
-template <bool PACK29> __global__ void __launch_bounds__(256) k_varwin_to_table(const uint64_t* __restrict__ jx, const uint64_t* __restrict__ jy, const uint64_t* __restrict__ jz,
-                                                         uint64_t* __restrict__ prefix, uint4* __restrict__ table, size_t n, size_t total, size_t lanes, int per) {
-  const size_t g = (size_t)blockIdx.x * 256 + threadIdx.x;
-  if (g >= lanes) return;
-  const fe one = FE_CONST(CI, R_P);
-  auto slot_of = [n](size_t e) { return (e % n) * VW_ENTRIES + (e / n) + 1; };
-  fe acc = one;
-  for (int j = 0; j < per; ++j) {
-    const size_t e = (size_t)j * lanes + g;
-    if (e >= total) break;
-    fe z = fe_load(jz, e);
-    if (vw_is_zero(z)) z = one;                         // an invalid input point: keep the neighbours intact
-    acc = fe_mul<CI>(acc, z);
-    fe_store(prefix, e, acc);                           // coalesced scratch, not the (512-byte strided) table
-  }
-  fe inv = fe_inverse<CI>(acc);
-  int last = per - 1;
-  while (last >= 0 && (size_t)last * lanes + g >= total) --last;
-  for (int j = last; j >= 0; --j) {
-    const size_t e = (size_t)j * lanes + g;
-    fe z = fe_load(jz, e);
-    const fe X = fe_load(jx, e), Y = fe_load(jy, e);
-    if (vw_is_zero(z)) z = one;
-    const fe prev = (j > 0) ? fe_load(prefix, (size_t)(j - 1) * lanes + g) : one;
-    const fe iz = fe_mul<CI>(inv, prev);
-    inv = fe_mul<CI>(inv, z);
-    const fe iz2 = fe_sqr<CI>(iz);
-    const fe ax = fe_mul<CI>(X, iz2), ay = fe_mul<CI>(Y, fe_mul<CI>(iz2, iz));
-    store_half_slot(table, slot_of(e), 0, PACK29 ? pack29<CI>(ax) : ax);
-    store_half_slot(table, slot_of(e), 1, PACK29 ? pack29<CI>(ay) : ay);
-  }
-}
-
 // ---------------------------------------------------------------- the plain loop with odd digits only
 // Regular recoding (Joye-Tunstall): for odd k, digit i = (bits 4i..4i+4 of k, bit 4i forced to 1) - 16 for i < 63 and
 // the top digit = (k >> 252) | 1 -- sixty-four ODD digits in [-15, 15], none of them zero, the top one positive.  Exactly
 // one of k mod n and n - (k mod n) is odd (n is odd), so every k != 0 mod n has such a form up to the sign of the result.
-// No zero digit means no "skip" and no point at infinity inside the loop, and the last doubling of every window fuses
-// with the addition: 2R + T = (R + T) + R, where the mixed addition's by-products X1*H^2, Y1*H^3 are R in the
-// coordinates of R + T, so the second addition is a co-Z one (5M + 2S): 13M + 5S instead of (4M + 4S) + (8M + 3S).
-// Table: the odd multiples {1, 3, ..., 15}P from one DBLU and seven co-Z additions (6 + 7 x 7 = 55 field mults).
-// 63 x (3 x 8 + 18) + 55 + 57 + 15 = 2 773 field multiplications (P-256).
-ECS_DEV jpoint dbl_add(const jpoint& R, const fe& x2, const fe& y2) {      // 2R + T, T affine; no exceptional case for our digits
-  const fe Z1Z1 = fe_sqr<CI>(R.z);
-  const fe U2 = fe_mul<CI>(x2, Z1Z1);
-  const fe S2 = fe_mul<CI>(y2, fe_mul<CI>(Z1Z1, R.z));
-  const fe H = fe_sub<CI>(U2, R.x);
-  const fe r = fe_sub<CI>(S2, R.y);
-  const fe HH = fe_sqr<CI>(H);
-  const fe HHH = fe_mul<CI>(H, HH);
-  const fe V = fe_mul<CI>(R.x, HH);                                       // R = (V, Yh) over Z3
-  const fe Yh = fe_mul<CI>(R.y, HHH);
-  const fe X3 = fe_sub<CI>(fe_sub<CI>(fe_sqr<CI>(r), HHH), fe_dbl<CI>(V));  // R + T = (X3, Y3) over Z3 = Z1*H
-  const fe Y3 = fe_sub<CI>(fe_mul<CI>(r, fe_sub<CI>(V, X3)), Yh);
-  const fe Z3 = fe_mul<CI>(R.z, H);
-  const fe dx = fe_sub<CI>(X3, V);                                        // co-Z addition (R + T) + R
-  const fe dy = fe_sub<CI>(Y3, Yh);
-  const fe Cc = fe_sqr<CI>(dx);
-  const fe W1 = fe_mul<CI>(X3, Cc);
-  const fe W2 = fe_mul<CI>(V, Cc);
-  const fe2 A1 = mul8x8(Y3, fe_sub<CI>(W1, W2));                           // only ever subtracted from a product: stays unreduced
-  jpoint Q;
-  Q.x = fe_sub<CI>(fe_sub<CI>(fe_sqr<CI>(dy), W1), W2);
-  Q.y = fe_mul_sub_product<CI>(dy, fe_sub<CI>(W1, Q.x), A1);
-  Q.z = fe_mul<CI>(Z3, dx);
-  return Q;
-}
+// No zero digit means no "skip" and no point at infinity inside the loop, and
+// the last doubling of every window fuses with the addition (fe29.cuh dbl_add29).  Table: the odd multiples {1, 3, ..., 15}P from one DBLU and seven
+// co-Z additions (6 + 7 x 7 = 55 field mults).
 
-// 3P, 5P, ..., 15P (Jacobian, each with the Z it was born with) -> jx/jy/jz[j*n + i], j = 0..6; 1P -> table slot 8 i.
-// CHAIN (round 4, ECS_VARWIN_CHAIN): every Z of the chain is the one before times that step's x-difference, z_j = z_(j-1) dx_j -- so only the LAST one needs
-// inverting, 1 / z_(j-1) = (1 / z_j) dx_j walks back through the rest: jz[j] takes dx_j instead of z_j, zlast[i] the last Z (k_varwin_chain_to_table).
-#ifndef ECS_VARWIN_CHAIN
-#define ECS_VARWIN_CHAIN 1
-#endif
-template <bool CHAIN> __global__ void __launch_bounds__(BLOCK) k_varwin_odd_multiples(const uint64_t* __restrict__ x, const uint64_t* __restrict__ y, int flags,
+// 3P, 5P, ..., 15P (Jacobian) -> jx/jy[j*n + i], j = 0..6; 1P -> table slot 8 i.  A chain (round 4): every Z is the one before times that step's
+// x-difference, z_j = z_(j-1) dx_j -- so only the LAST one needs inverting, 1 / z_(j-1) = (1 / z_j) dx_j walks back through the rest: jz[j] takes dx_j,
+// zlast[i] the last Z (k_varwin_chain_to_table).
+__global__ void __launch_bounds__(BLOCK) k_varwin_odd_multiples(const uint64_t* __restrict__ x, const uint64_t* __restrict__ y, int flags,
                                                                 uint64_t* __restrict__ jx, uint64_t* __restrict__ jy, uint64_t* __restrict__ jz, uint64_t* __restrict__ zlast,
                                                                 uint4* __restrict__ table, size_t n) {
   const size_t i = (size_t)blockIdx.x * BLOCK + threadIdx.x;
@@ -244,23 +108,22 @@ template <bool CHAIN> __global__ void __launch_bounds__(BLOCK) k_varwin_odd_mult
   const bool in_mgry = (flags & ECSIMD_HIP_BASE_MGRY) != 0;
   if constexpr (CI == C) { if (!in_mgry) { px = fe_from_classical<C>(px); py = fe_from_classical<C>(py); } }
   else { if (in_mgry) { px = fe_to_classical<C>(px); py = fe_to_classical<C>(py); } }
-  store_half_slot(table, i * VW_ENTRIES, 0, VW29 ? pack29<CI>(px) : px);       // the odd-digit loop's table form
-  store_half_slot(table, i * VW_ENTRIES, 1, VW29 ? pack29<CI>(py) : py);
+  store_half_slot(table, i * VW_ENTRIES, 0, pack29<CI>(px));       // the odd-digit loop's table form
+  store_half_slot(table, i * VW_ENTRIES, 1, pack29<CI>(py));
   fe dx2, dy2, z;                                          // (dx2, dy2) = 2P; (px, py) becomes P over the same z
   dblu<CI>(px, py, dx2, dy2, z);
   fe ax = px, ay = py;                                     // running odd multiple, co-Z with 2P
 #pragma unroll 1
   for (int j = 0; j < VW_JAC; ++j) {                       // (2j + 3) P = (2j + 1) P + 2P; 2P is re-expressed over the new z
     fe rx, ry;
-    if constexpr (CHAIN) fe_store(jz, (size_t)j * n + i, fe_sub<CI>(dx2, ax));      // zaddu's own x1 - x2: the ratio of its Z to the one before
+    fe_store(jz, (size_t)j * n + i, fe_sub<CI>(dx2, ax));                // zaddu's own x1 - x2: the ratio of its Z to the one before
     zaddu<CI>(dx2, dy2, ax, ay, z, rx, ry);
     ax = rx; ay = ry;
     fe_store(jx, (size_t)j * n + i, ax); fe_store(jy, (size_t)j * n + i, ay);
-    if constexpr (!CHAIN) fe_store(jz, (size_t)j * n + i, z);
   }
-  if constexpr (CHAIN) fe_store(zlast, i, z);
+  fe_store(zlast, i, z);
 }
-// The last Z of every lane's chain, inverted together (Montgomery's trick over m lanes' values per GPU lane, as k_varwin_to_table over all 7n), in
+// The last Z of every lane's chain, inverted together (Montgomery's trick over m lanes' values per GPU lane), in
 // the loop's own domain; a zero (an invalid input point) counts as one and comes back as zero.  out: the prefix products on the way up, the inverses on the way down.
 __global__ void __launch_bounds__(256) k_varwin_invert_last(const uint64_t* __restrict__ zlast, uint64_t* __restrict__ out, size_t n, size_t lanes, int m) {
   const size_t g = (size_t)blockIdx.x * 256 + threadIdx.x;
@@ -293,20 +156,18 @@ __global__ void __launch_bounds__(256) k_varwin_invert_last(const uint64_t* __re
     fe_store(out, e, iv);
   }
 }
-// One lane, its own seven entries: 1/z of the last from k_varwin_invert_last, back through the x-differences.  PACK29: the 29-bit loop's table form is
+// One lane, its own seven entries: 1/z of the last from k_varwin_invert_last, back through the x-differences.  The 29-bit loops' table form is
 // x * 2^261 mod p canonical (pack29) -- folded into 1/z^2 once per entry (a product by pack29(1)) instead of a product per coordinate.
-template <bool PACK29> __global__ void __launch_bounds__(BLOCK) k_varwin_chain_to_table(const uint64_t* __restrict__ jx, const uint64_t* __restrict__ jy, const uint64_t* __restrict__ jdx,
+__global__ void __launch_bounds__(BLOCK) k_varwin_chain_to_table(const uint64_t* __restrict__ jx, const uint64_t* __restrict__ jy, const uint64_t* __restrict__ jdx,
                                                                                          const uint64_t* __restrict__ zinv, uint4* __restrict__ table, size_t n) {
   const size_t i = (size_t)blockIdx.x * BLOCK + threadIdx.x;
   if (i >= n) return;
-  fe k29 = FE_CONST(CI, R_P);
-  if constexpr (PACK29) k29 = pack29<CI>(k29);
+  const fe k29 = pack29<CI>(FE_CONST(CI, R_P));
   fe iz = fe_load(zinv, i);
 #pragma unroll 1
   for (int j = VW_JAC - 1; j >= 0; --j) {
     const fe X = fe_load(jx, (size_t)j * n + i), Y = fe_load(jy, (size_t)j * n + i);
-    fe iz2 = fe_sqr<CI>(iz);
-    if constexpr (PACK29) iz2 = fe_mul<CI>(iz2, k29);
+    const fe iz2 = fe_mul<CI>(fe_sqr<CI>(iz), k29);
     store_half_slot(table, i * VW_ENTRIES + j + 1, 0, fe_mul<CI>(X, iz2));
     store_half_slot(table, i * VW_ENTRIES + j + 1, 1, fe_mul<CI>(Y, fe_mul<CI>(iz2, iz)));
     if (j > 0) iz = fe_mul<CI>(iz, fe_load(jdx, (size_t)j * n + i));
@@ -346,18 +207,13 @@ __global__ void __launch_bounds__(BLOCK, CT ? VARWIN_CT_WAVES : VARWIN_WAVES_PER
   }
   if (zero) kk.w[0] = 1;                                // any odd value; the result is replaced by infinity below (a select)
   const size_t base = i * VW_ENTRIES;
-  // the accumulator: canonical words (jdbl / dbl_add) or lazy 29-bit limbs (jdbl29 / dbl_add29); `first` takes the top digit's entry
-  struct acc32 { jpoint R;
-    ECS_DEV void first(const fe& tx, const fe& ty) { R.x = tx; R.y = ty; R.z = FE_CONST(CI, R_P); }
-    ECS_DEV void dbl() { R = jdbl(R); }
-    ECS_DEV void dadd(const fe& tx, const fe& ty, uint32_t neg) { R = dbl_add(R, tx, fe_select(neg, fe_neg<CI>(ty), ty)); }
-    ECS_DEV jpoint finish() const { return R; } };
+  // the accumulator, lazy 29-bit limbs (jdbl29 / dbl_add29); `first` takes the top digit's entry
   struct acc29 { jpoint29 R;
     ECS_DEV void first(const fe& tx, const fe& ty) { R.x = to29(tx); R.y = to29(ty); R.z = fe29_const<r29_consts<CI>::ONE>(); }
     ECS_DEV void dbl() { R = jdbl29<CI>(R); }
     ECS_DEV void dadd(const fe& tx, const fe& ty, uint32_t neg) { R = dbl_add29<CI>(R, to29(tx), cneg29(neg, to29(ty))); }
     ECS_DEV jpoint finish() const { jpoint Q; Q.x = leave29<CI>(R.x); Q.y = leave29<CI>(R.y); Q.z = leave29<CI>(R.z); return Q; } };
-  typename std::conditional<VW29, acc29, acc32>::type A;
+  acc29 A;
   uint32_t above = kk.w[7] >> 28;                       // the nibble above the current one (its low bit is the digit's sign)
   if constexpr (CT) {
     const uint4* mine = table + base * 4;               // this lane's 8 entries: 32 x 16 bytes = four 128-byte lines
@@ -498,62 +354,23 @@ ECS_DEV uint32_t abs256(fe& v) {
   v = fe_select(neg, m, v);
   return neg;
 }
-// R (+inf flag) += +-T, every case handled: R = inf, T skipped, R = T (tangent), R = -T (infinity)
-ECS_DEV void add_checked(jpoint& R, uint32_t& inf, const fe& tx, fe ty, uint32_t neg, uint32_t skip, const fe& one) {
-  ty = fe_select(neg, fe_neg<CI>(ty), ty);
-  // madd_hmv unrolled far enough to see H and r
-  const fe Z1Z1 = fe_sqr<CI>(R.z);
-  const fe U2 = fe_mul<CI>(tx, Z1Z1);
-  const fe S2 = fe_mul<CI>(ty, fe_mul<CI>(Z1Z1, R.z));
-  const fe H = fe_sub<CI>(U2, R.x);
-  const fe r = fe_sub<CI>(S2, R.y);
-  const fe HH = fe_sqr<CI>(H);
-  const fe HHH = fe_mul<CI>(H, HH);
-  const fe V = fe_mul<CI>(R.x, HH);
-  jpoint S;
-  S.z = fe_mul<CI>(R.z, H);
-  S.x = fe_sub<CI>(fe_sub<CI>(fe_sqr<CI>(r), HHH), fe_dbl<CI>(V));
-  S.y = fe_mul_sub_product<CI>(r, fe_sub<CI>(V, S.x), mul8x8(R.y, HHH));
-  uint32_t same_x = 0u - (uint32_t)vw_is_zero(H);
-  same_x &= ~inf & ~skip;                               // only where a real addition happens
-  uint32_t to_inf = 0;
-  if (__builtin_amdgcn_ballot_w64(same_x != 0u) != 0ull) {            // wave-uniform and practically never taken
-    jpoint T1; T1.x = tx; T1.y = ty; T1.z = one;
-    const jpoint D = jdbl(T1);
-    const uint32_t same_y = 0u - (uint32_t)vw_is_zero(r);
-    const uint32_t dbl = same_x & same_y;
-    S.x = fe_select(dbl, D.x, S.x); S.y = fe_select(dbl, D.y, S.y); S.z = fe_select(dbl, D.z, S.z);
-    to_inf = same_x & ~same_y;
-  }
-  const fe nx = fe_select(inf, tx, S.x), ny = fe_select(inf, ty, S.y), nz = fe_select(inf, one, S.z);
-  R.x = fe_select(skip, R.x, nx); R.y = fe_select(skip, R.y, ny); R.z = fe_select(skip, R.z, nz);
-  inf = (inf & skip) | to_inf;
-}
 template <uint32_t HALF = 8u> ECS_DEV void digit_of(uint32_t nib, bool top, uint32_t scalar_neg, uint32_t& mag, uint32_t& neg, uint32_t& skip) {
   if (top) { mag = nib; neg = scalar_neg; }                             // unsigned top digit (0 or 1; up to 8 with 5-bit windows)
   else { mag = nib < HALF ? HALF - nib : nib - HALF; neg = (0u - (uint32_t)(nib < HALF)) ^ scalar_neg; }
   skip = 0u - (uint32_t)(mag == 0u);
 }
-// ---------------------------------------------------------------- the GLV loop's table without an inversion (round 4, ECS_GLV_ISO)
+// ---------------------------------------------------------------- the GLV loop's table without an inversion (round 4)
 // All eight multiples over ONE Z, and the loop on the isomorphic curve.  2P = jdbl29(P), (k + 1)P = P + kP by co-Z additions (zaddu29): Z_(k+1) = Z_k dx_k,
 // so every multiple's Z divides the last one's, Zg = Z_8, and kP = (X_k f_k^2, Y_k f_k^3) over Zg with f_k = dx_k dx_(k+1) .. dx_7 -- one backward
 // walk, 5 products per entry, no inversion, nothing but the lane's own scratch between the lane and its 512 bytes of table.  (x, y) -> (x Zg^2, y Zg^3) maps y^2 = x^3 + b onto
 // y^2 = x^3 + b Zg^6: the table's (X_k f_k^2, Y_k f_k^3) are AFFINE points there, the a = 0 doubling and the mixed addition never use b, negation
 // and (x, y) -> (beta x, y) commute with the map, and a result (X', Y', Z') of the loop is (X', Y', Z' Zg) on the curve itself: one product at
 // the end.  53 + 35 products per lane in one kernel against 61 + 63 in two with 2.4 KB of device-memory traffic per lane between them
-// (k_varwin_multiples + k_varwin_to_table: 3.8 of 34 ms at 2^22 lanes).  a != 0 would cost a product per doubling (a Zg^4): secp256k1's default loop only.
-#ifndef ECS_GLV_ISO
-#define ECS_GLV_ISO 1
-#endif
-// ENTRIES: 8 multiples for 4-bit windows.  (-DECS_GLV_ISO_WBITS=5: 16 multiples and 5-bit windows -- 26 x (5 doublings + 2 additions) + a 184-product
-// table against 33 x (4 + 2) + 88 is 5 % fewer products, and measured 2 % SLOWER, 127.2 against 129.8 M/s: the 1 KB table and its 1.5 KB of scratch cost the
-// table kernel more than the loop gains.  profiles/r04/README.md)
-#ifndef ECS_GLV_ISO_WBITS
-#define ECS_GLV_ISO_WBITS 4
-#endif
-constexpr int ISO_WBITS = ECS_GLV_ISO_WBITS;
-constexpr int ISO_ENTRIES = 1 << (ISO_WBITS - 1);       // {1 .. 2^(w-1)} P: digits are nibble - 2^(w-1), the top one unsigned and small
-static_assert(ISO_WBITS == 4 || ISO_WBITS == 5, "window tables of 8 or 16 entries");
+// (rounds 1-3's two kernels with a simultaneous inversion: 3.8 of 34 ms at 2^22 lanes).  a != 0 would cost a product per doubling (a Zg^4): secp256k1's
+// default loop only.  8 multiples for 4-bit windows: 16 multiples and 5-bit windows -- 26 x (5 doublings + 2 additions) + a 184-product table against
+// 33 x (4 + 2) + 88 is 5 % fewer products, and measured 2 % SLOWER, 127.2 against 129.8 M/s: the 1 KB table and its 1.5 KB of scratch cost the table kernel
+// more than the loop gains (profiles/r04/README.md); removed.
+constexpr int ISO_ENTRIES = 8;                          // {1 .. 8} P: digits are nibble - 8, the top one unsigned and small
 template <int ENTRIES> __global__ void __launch_bounds__(BLOCK, 2)
 k_varwin_table_iso(const uint64_t* __restrict__ x, const uint64_t* __restrict__ y, int flags, uint4* __restrict__ table, uint64_t* __restrict__ zg, size_t n) {
   constexpr int JAC = ENTRIES - 1;
@@ -596,13 +413,9 @@ k_varwin_table_iso(const uint64_t* __restrict__ x, const uint64_t* __restrict__ 
   }
 }
 
-// The same on fe29.cuh's lazy limbs (round 4, ECS_GLV_RADIX=29): madd29_hr hands out H and r, is_zero29 decides "= 0 mod p" on them (a value
-// reduction, one sequential carry pass, an OR: ~45 instructions against the 8-word compare's 9 -- two per window, beside ~6 500).
-#ifndef ECS_GLV_RADIX
-#define ECS_GLV_RADIX 29
-#endif
-constexpr bool GLV29 = (ECS_GLV_RADIX == 29);
-// Public scalars: the cases are plain divergent control flow -- a skipped digit or a fresh accumulator costs the lane nothing and, unlike a select
+// R (+inf flag) += T on fe29.cuh's lazy limbs (round 4), every case handled: R = inf, T skipped, R = T (tangent), R = -T (infinity).  madd29_hr hands out
+// H and r, is_zero29 decides "= 0 mod p" on them (a value reduction, one sequential carry pass, an OR: ~45 instructions against the 8-word compare's 9 --
+// two per window, beside ~6 500).  Public scalars: the cases are plain divergent control flow -- a skipped digit or a fresh accumulator costs the lane nothing and, unlike a select
 // at the end, does not keep the old accumulator alive beside the sum (a third of the loop's registers).
 ECS_DEV void add_checked29(jpoint29& R, uint32_t& inf, const fe29& x2, const fe29& y2, uint32_t skip) {
   if (skip) return;
@@ -619,7 +432,7 @@ ECS_DEV void add_checked29(jpoint29& R, uint32_t& inf, const fe29& x2, const fe2
 #ifndef VARWIN_GLV_WAVES
 #define VARWIN_GLV_WAVES VARWIN_WAVES_PER_SIMD    // (the 29-bit loop needs 106 registers: four waves fit whatever this says)
 #endif
-// WB: bits per window -- 4 (8-entry tables, every build) or 5 (the 16-entry table of k_varwin_table_iso)
+// WB: bits per window, 4 (8-entry tables)
 template <int WB> __global__ void __launch_bounds__(BLOCK, VARWIN_GLV_WAVES)
 k_varwin_mult_glv(const uint64_t* __restrict__ k, int k_stride, const uint4* __restrict__ table, const uint64_t* __restrict__ zg,
                   uint64_t* __restrict__ ox, uint64_t* __restrict__ oy, uint64_t* __restrict__ oz, size_t n) {
@@ -644,44 +457,21 @@ k_varwin_mult_glv(const uint64_t* __restrict__ k, int k_stride, const uint4* __r
     (void)sub8_3(k2, low_product(c1, words_fe(glv_consts::MB1)), low_product(c2, words_fe(glv_consts::A1)));
   }
   const uint32_t s1 = abs256(k1), s2 = abs256(k2);      // |k1|, |k2| < 2^128
-  // offset recoding: WINDOWS - 1 digits of WB bits, each (its bits) - 2^(WB-1) in [-2^(WB-1), 2^(WB-1)), under an unsigned top digit.
-  // WB = 4: 32 nibbles + the top one (bits 128..131, 0 or 1); WB = 5: 25 digits + the top one (bits 125..129, at most 8) -- then the whole
-  // value is moved up 3 bits so that the top digit sits at bit 128 like the nibble form's (the loop reads the low bits of word 4)
-  constexpr int HALF = 1 << (WB - 1), ENTRIES = HALF, WINDOWS = (WB == 4) ? 33 : 26;
+  // offset recoding: 32 digits of 4 bits, each (its nibble) - 8 in [-8, 8), under an unsigned top digit (bits 128..131, 0 or 1)
+  static_assert(WB == 4, "4-bit windows");
+  constexpr int HALF = 1 << (WB - 1), ENTRIES = HALF, WINDOWS = 33;
   constexpr uint32_t DMASK = (1u << WB) - 1u;
   uint32_t u1[5], u2[5];
   {
     fe off;
-    if constexpr (WB == 4) {
 #pragma unroll
-      for (int j = 0; j < 8; ++j) off.w[j] = j < 4 ? 0x88888888u : 0u;
-    } else {                                              // 16 * (32^0 + .. + 32^24): bit 5t + 4 for t = 0..24
-#pragma unroll
-      for (int j = 0; j < 8; ++j) { uint32_t wv = 0;
-#pragma unroll
-        for (int t = 0; t < 25; ++t) if ((5 * t + 4) / 32 == j) wv |= 1u << ((5 * t + 4) % 32);
-        off.w[j] = wv; }
-    }
+    for (int j = 0; j < 8; ++j) off.w[j] = j < 4 ? 0x88888888u : 0u;
     (void)add8(k1, off); (void)add8(k2, off);
 #pragma unroll
     for (int j = 0; j < 5; ++j) { u1[j] = k1.w[j]; u2[j] = k2.w[j]; }
-    if constexpr (WB == 5) {
-#pragma unroll
-      for (int j = 4; j > 0; --j) { u1[j] = __builtin_amdgcn_alignbit(u1[j], u1[j - 1], 29); u2[j] = __builtin_amdgcn_alignbit(u2[j], u2[j - 1], 29); }
-      u1[0] <<= 3; u2[0] <<= 3;
-    }
   }
   const size_t base = i * ENTRIES;
-  // the accumulator (+ its infinity flag): canonical words (rounds 1-3) or lazy 29-bit limbs
-  struct acc32 { jpoint R; fe beta, one; uint32_t inf;
-    ECS_DEV void init(const fe& b) { beta = b; one = FE_CONST(CI, R_P); inf = ~0u;
-#pragma unroll
-      for (int j = 0; j < 8; ++j) { R.x.w[j] = 0; R.y.w[j] = 0; R.z.w[j] = 0; } }
-    ECS_DEV void dbls() {
-#pragma unroll
-      for (int t = 0; t < WB; ++t) R = jdbl(R); }
-    ECS_DEV void add(const fe& tx, const fe& ty, uint32_t neg, uint32_t skip, bool lambda) { add_checked(R, inf, lambda ? fe_mul<CI>(tx, beta) : tx, ty, neg, skip, one); }
-    ECS_DEV jpoint finish(const uint64_t*, size_t) const { return R; } };
+  // the accumulator (+ its infinity flag), lazy 29-bit limbs
   struct acc29 { jpoint29 R; uint32_t inf;
     ECS_DEV void init(const fe&) { inf = ~0u;
 #pragma unroll
@@ -694,7 +484,7 @@ k_varwin_mult_glv(const uint64_t* __restrict__ k, int k_stride, const uint4* __r
     // zg: the table's common Z (k_varwin_table_iso) -- the loop ran on the isomorphic curve, (X', Y', Z') there is (X', Y', Z' Zg) here
     ECS_DEV jpoint finish(const uint64_t* zg, size_t i) const { jpoint Q; Q.x = leave29<CI>(R.x); Q.y = leave29<CI>(R.y);
       Q.z = leave29<CI>(zg ? mul29<CI>(R.z, to29(fe_load(zg, i))) : R.z); return Q; } };
-  typename std::conditional<GLV29, acc29, acc32>::type A;
+  acc29 A;
   A.init(words_fe(glv_consts::BETA));
   for (int w = WINDOWS - 1; w >= 0; --w) {
     const bool top = (w == WINDOWS - 1);
@@ -710,7 +500,7 @@ k_varwin_mult_glv(const uint64_t* __restrict__ k, int k_stride, const uint4* __r
     load_slot(table, base + (m1 == 0u ? 0u : m1 - 1u), ax, ay);         // in flight during the doublings
     if (!top) A.dbls();
     // the second entry is requested AFTER the first addition: no difference either way on 29-bit limbs (123.5 against 123.6 M/s,
-    // profiles/r04/ab_glv_default_radix29.txt; on canonical words the early request cost 21 more spilled registers); the other waves cover the latency
+    // profiles/r04/ab_glv_default_radix29.txt; on rounds 1-3's canonical words the early request cost 21 more spilled registers); the other waves cover the latency
     A.add(ax, ay, n1, z1, false);
     load_slot(table, base + (m2 == 0u ? 0u : m2 - 1u), bx, by);
     A.add(bx, by, n2, z2, true);                                        // lambda * (x, y) = (beta x, y)
@@ -723,7 +513,7 @@ k_varwin_mult_glv(const uint64_t* __restrict__ k, int k_stride, const uint4* __r
   fe_store(ox, i, R.x); fe_store(oy, i, R.y); fe_store(oz, i, R.z);
 }
 
-// Complete mixed addition R = A + B through add_checked (the API's Montgomery form in and out): A Jacobian with
+// Complete mixed addition R = A + B through add_checked29 (the API's Montgomery form in and out): A Jacobian with
 // Z = 0 meaning infinity, B affine with (0, 0) meaning infinity.  This is the only caller that drives the tangent
 // and the infinity branches of add_checked on purpose.
 __global__ void __launch_bounds__(BLOCK) k_add_mixed_complete(const uint64_t* __restrict__ ax, const uint64_t* __restrict__ ay, const uint64_t* __restrict__ az,
@@ -736,12 +526,10 @@ __global__ void __launch_bounds__(BLOCK) k_add_mixed_complete(const uint64_t* __
   const fe tx = to_fast<C>(fe_load(bx, i)), ty = to_fast<C>(fe_load(by, i));
   uint32_t inf = 0u - (uint32_t)vw_is_zero(R.z);
   const uint32_t skip = 0u - (uint32_t)(vw_is_zero(tx) && vw_is_zero(ty));
-  if constexpr (GLV29) {                                // the same branches on the 29-bit limbs (both curves: prove_glv_invariant holds for either prime)
+  {                                                     // on the 29-bit limbs (both curves: prove_glv_invariant holds for either prime)
     jpoint29 Q; Q.x = enter29<CI>(R.x); Q.y = enter29<CI>(R.y); Q.z = enter29<CI>(R.z);
     add_checked29(Q, inf, enter29<CI>(tx), enter29<CI>(ty), skip);
     R.x = leave29<CI>(Q.x); R.y = leave29<CI>(Q.y); R.z = leave29<CI>(Q.z);
-  } else {
-    add_checked(R, inf, tx, ty, 0u, skip, FE_CONST(CI, R_P));
   }
   if (inf) {
 #pragma unroll
@@ -764,52 +552,9 @@ __global__ void __launch_bounds__(BLOCK) k_add_mixed_complete(const uint64_t* __
 // whole, one 128-byte line requested right before each of the four doublings (so that nothing of the table is pending during the two
 // additions, where the registers are tightest: 29 spills instead of 53 with a read carried across windows), and BOTH halves' entries are kept from the same read under their own
 // masks; lambda (x, y) = (beta x, y).  33 windows x (4 x 8 + 2 x 11 + 1) ~= 1 800 field multiplications, the default GLV loop's count.
-struct ppoint { fe x, y, z; };
-#ifndef ECS_GLV_CT_FUSED
-#define ECS_GLV_CT_FUSED 1           // 0: every product of the complete addition reduced on its own (round 3): 84.7 against 86.0 M/s at 2^22 lanes
-#endif
-template <int UNUSED> ECS_DEV fe mul21(const fe& a) { const fe a4 = fe_shl<CI, 2>(a); return fe_add<CI>(fe_add<CI>(fe_shl<CI, 2>(a4), a4), a); }
-template <int UNUSED> ECS_DEV ppoint pdbl_complete(const ppoint& P) {
-  const fe yy = fe_sqr<CI>(P.y), zz = fe_sqr<CI>(P.z), xy = fe_mul<CI>(P.x, P.y), yz = fe_mul<CI>(P.y, P.z);
-  const fe t = mul21<UNUSED>(zz);
-  const fe m = fe_sub<CI>(yy, fe_add<CI>(fe_dbl<CI>(t), t));
-  const fe q = fe_add<CI>(yy, t);
-  ppoint R;
-  R.x = fe_dbl<CI>(fe_mul<CI>(xy, m));
-  R.y = fe_add<CI>(fe_mul<CI>(m, q), fe_shl<CI, 3>(fe_mul<CI>(yy, t)));
-  R.z = fe_shl<CI, 3>(fe_mul<CI>(yy, yz));
-  return R;
-}
-template <int UNUSED> ECS_DEV ppoint padd_mixed_complete(const ppoint& P, const fe& x2, const fe& y2) {
-  const fe t0 = fe_mul<CI>(P.x, x2), t1 = fe_mul<CI>(P.y, y2);
-  const fe t3 = fe_sub<CI>(fe_sub<CI>(fe_mul<CI>(fe_add<CI>(P.x, P.y), fe_add<CI>(x2, y2)), t0), t1);
-  const fe t4 = fe_add<CI>(fe_mul<CI>(y2, P.z), P.y), t5 = fe_add<CI>(fe_mul<CI>(x2, P.z), P.x);
-  const fe z3b = mul21<UNUSED>(P.z);
-  const fe A = fe_sub<CI>(t1, z3b), B = fe_add<CI>(t1, z3b), Cc = mul21<UNUSED>(t5);
-  const fe t03 = fe_add<CI>(fe_dbl<CI>(t0), t0);
-  ppoint R;
-#if ECS_GLV_CT_FUSED
-  // one reduction per output coordinate: u v - T for an unreduced 512-bit product T (field.cuh fe_mul_sub_product), the sums written as
-  // differences with a negated factor -- three reductions fewer per addition for two negations (r4; profiles/r04/ab_glv_ct_fused_reductions.txt)
-  const fe nB = fe_neg<CI>(B), n03 = fe_neg<CI>(t03);
-  R.x = fe_mul_sub_product<CI>(t3, A, mul8x8(Cc, t4));
-  R.y = fe_mul_sub_product<CI>(t03, Cc, mul8x8(nB, A));
-  R.z = fe_mul_sub_product<CI>(t4, B, mul8x8(n03, t3));
-#else
-  R.x = fe_sub<CI>(fe_mul<CI>(t3, A), fe_mul<CI>(Cc, t4));
-  R.y = fe_add<CI>(fe_mul<CI>(t03, Cc), fe_mul<CI>(B, A));
-  R.z = fe_add<CI>(fe_mul<CI>(t4, B), fe_mul<CI>(t03, t3));
-#endif
-  return R;
-}
-#ifndef ECS_GLV_CT
-#define ECS_GLV_CT 1                 // 1: ALG_CONSTANT_TIME on secp256k1 takes the GLV split (complete formulas: 84.2 M/s); 0: the plain odd-digit loop (76.0);
-                                     // with ALG_NO_ENDOMORPHISM the plain loop either way (profiles/r03/ab_constant_time_variable_base.txt)
-#endif
-#ifndef ECS_GLVCT_RADIX
-#define ECS_GLVCT_RADIX 29           // the complete formulas on fe29.cuh's 29-bit limbs (pdbl29 / padd29: round 4); 32: canonical words (round 3)
-#endif
-constexpr bool GLVCT29 = (ECS_GLVCT_RADIX == 29);
+// (Round 3 ran these formulas on canonical words, each product reduced on its own: 84.7 M/s at 2^22 lanes, then 86.0 with one reduction per output
+// coordinate -- profiles/r04/ab_glv_ct_fused_reductions.txt; ALG_CONSTANT_TIME through the GLV split ran 84.2 against the plain odd-digit loop's 76.0,
+// profiles/r03/ab_constant_time_variable_base.txt.  Round 4 moved them to fe29.cuh's 29-bit limbs, pdbl29 / padd29; the other forms were removed.)
 #ifndef VARWIN_GLV_CT_WAVES
 #define VARWIN_GLV_CT_WAVES 3        // 233 registers wanted; 3 waves (29 spilled -- 32 with the fused reductions --, constant-addressed scratch) beat 2 without spills: 84.6 against 80.4 M/s
 #endif
@@ -846,7 +591,6 @@ k_varwin_mult_glv_ct(const uint64_t* __restrict__ k, int k_stride, const uint4* 
 #pragma unroll
     for (int j = 0; j < 5; ++j) { u1[j] = k1.w[j]; u2[j] = k2.w[j]; }
   }
-  const fe beta = words_fe(glv_consts::BETA);
   const uint4* mine = table + i * VW_ENTRIES * 4;       // this lane's 8 entries {1..8}P: four 128-byte lines
   uint4 q[8];
   auto request = [&](int pair) {
@@ -865,21 +609,9 @@ k_varwin_mult_glv_ct(const uint64_t* __restrict__ k, int k_stride, const uint4* 
       ty.w[4] = m ? d.x : ty.w[4]; ty.w[5] = m ? d.y : ty.w[5]; ty.w[6] = m ? d.z : ty.w[6]; ty.w[7] = m ? d.w : ty.w[7];
     }
   };
-  // the accumulator: canonical words (round 3) or lazy 29-bit limbs; O = (0 : 1 : 0)
-  struct acc32 { ppoint R; fe beta;
-    ECS_DEV void init(const fe& b) { beta = b;
-#pragma unroll
-      for (int j = 0; j < 8; ++j) { R.x.w[j] = 0; R.y.w[j] = 0; R.z.w[j] = 0; }
-      R.y = FE_CONST(CI, R_P); }
-    ECS_DEV void dbl() { R = pdbl_complete<UNUSED>(R); }
-    ECS_DEV void add(const fe& tx, const fe& ty, uint32_t neg, uint32_t zero, bool lambda) {
-      const ppoint S = padd_mixed_complete<UNUSED>(R, lambda ? fe_mul<CI>(tx, beta) : tx, fe_select(neg, fe_neg<CI>(ty), ty));
-      R.x = fe_select(zero, R.x, S.x); R.y = fe_select(zero, R.y, S.y); R.z = fe_select(zero, R.z, S.z); }
-    ECS_DEV void store(uint64_t* ox, uint64_t* oy, uint64_t* oz, size_t i) const {
-      const fe zz = fe_sqr<CI>(R.z);
-      fe_store(ox, i, fe_mul<CI>(R.x, R.z)); fe_store(oy, i, fe_mul<CI>(R.y, zz)); fe_store(oz, i, R.z); } };
+  // the accumulator, lazy 29-bit limbs; O = (0 : 1 : 0)
   struct acc29 { jpoint29 R;
-    ECS_DEV void init(const fe&) {
+    ECS_DEV void init() {
 #pragma unroll
       for (int j = 0; j < R29_LIMBS; ++j) { R.x.l[j] = 0; R.z.l[j] = 0; }
       R.y = fe29_const<r29_consts<CI>::ONE>(); }
@@ -891,8 +623,8 @@ k_varwin_mult_glv_ct(const uint64_t* __restrict__ k, int k_stride, const uint4* 
     ECS_DEV void store(uint64_t* ox, uint64_t* oy, uint64_t* oz, size_t i) const {
       const fe29 Zn = norm29(R.z), zz = sqr29<CI>(Zn);
       fe_store(ox, i, leave29<CI>(mul29<CI>(R.x, Zn))); fe_store(oy, i, leave29<CI>(mul29<CI>(R.y, zz))); fe_store(oz, i, leave29<CI>(Zn)); } };
-  typename std::conditional<GLVCT29, acc29, acc32>::type A;
-  A.init(beta);
+  acc29 A;
+  A.init();
 #pragma unroll 1
   for (int w = 32; w >= 0; --w) {
     asm volatile("" : "+s"(w));                         // the window counter stays a scalar register (tools/ct_check.py)
@@ -927,62 +659,42 @@ k_varwin_mult_glv_ct(const uint64_t* __restrict__ k, int k_stride, const uint4* 
 namespace launch {
 template <> void point_launch<C>::varwin_scalar_mult(hipStream_t s, const uint64_t* k, int k_stride, const uint64_t* x, const uint64_t* y, int flags,
                                                      uint64_t* scratch, uint64_t* ox, uint64_t* oy, size_t n) {
-  // scratch: 7n x 4 field elements (Jacobian multiples + prefix products; reused for the Jacobian result) + 8n x 64 B table
+  // scratch: 7n x 4 field elements (the chain's multiples, ratios and last Z; reused for the Jacobian result) + 8n x 64 B table
   uint64_t* jx = scratch; uint64_t* jy = jx + 4 * (size_t)VW_JAC * n; uint64_t* jz = jy + 4 * (size_t)VW_JAC * n;
-  uint64_t* prefix = jz + 4 * (size_t)VW_JAC * n;
-  uint4* table = reinterpret_cast<uint4*>(prefix + 4 * (size_t)VW_JAC * n);
+  uint64_t* zlast = jz + 4 * (size_t)VW_JAC * n; uint64_t* zinv = zlast + 4 * n;
+  uint4* table = reinterpret_cast<uint4*>(zlast + 4 * (size_t)VW_JAC * n);
+  uint64_t* rx = jx; uint64_t* ry = jx + 4 * n; uint64_t* rz = jx + 8 * n;            // the Jacobian result, once the multiples are dead
   const bool ct = (flags & ECSIMD_HIP_ALG_CONSTANT_TIME) != 0;           // every entry of the lane's table read in every window
-  bool glv = false;
-  if constexpr (C == CURVE_SECP256K1) glv = !(flags & ECSIMD_HIP_ALG_NO_ENDOMORPHISM) && (!ct || ECS_GLV_CT);
-  bool iso = false;                                                        // the table over one Z, the loop on the isomorphic curve: no inversion, no second table kernel
-  if constexpr (C == CURVE_SECP256K1) iso = glv && !ct && GLV29 && ECS_GLV_ISO;
-  uint64_t* zg = jx + 12 * n;                                              // behind the Jacobian result (rx, ry, rz below); the multiples' arrays are not used then
-  if constexpr (C == CURVE_SECP256K1) {
-    if (iso) {
-      // its own layout: the Jacobian result (12n words), Zg (4n), then the table of ISO_ENTRIES x 64 B per lane -- 128 + 1 024 bytes per lane of the 1 408 there are
-      static_assert(16 * 8 + ISO_ENTRIES * 64 <= 7 * 4 * 32 + 8 * 64, "kernels.h varwin_scratch_bytes");
-      uint4* itable = reinterpret_cast<uint4*>(jx + 16 * n);
-      hipLaunchKernelGGL(k_varwin_table_iso<ISO_ENTRIES>, grid_for(n), dim3(BLOCK), 0, s, x, y, flags, itable, zg, n);
-      hipLaunchKernelGGL(k_varwin_mult_glv<ISO_WBITS>, grid_for(n), dim3(BLOCK), 0, s, k, k_stride, (const uint4*)itable, (const uint64_t*)zg, jx, jx + 4 * n, jx + 8 * n, n);
-      to_affine_batched(s, jx, jx + 4 * n, jx + 8 * n, ox, oy, n, true);
-      return;
-    }
-  }
-  bool pack = !glv && VW29;                                              // the table in the 29-bit loops' form (x * 2^261 mod p, canonical)
-  if constexpr (C == CURVE_SECP256K1) pack = pack || (glv && (ct ? GLVCT29 : GLV29));
-  const bool chain = ECS_VARWIN_CHAIN;                                    // the multiples' Z form a chain: one inversion per lane's LAST Z, the rest by the walk back
-  if (chain) {
-    uint64_t* zlast = prefix; uint64_t* zinv = prefix + 4 * n;             // 2n of the 7n field elements the prefix products had
-    if (!glv) hipLaunchKernelGGL(k_varwin_odd_multiples<true>, grid_for(n), dim3(BLOCK), 0, s, x, y, flags, jx, jy, jz, zlast, table, n);            // {1,3,..,15}P
-    else if (pack) hipLaunchKernelGGL(k_varwin_multiples_chain<1>, grid_for(n), dim3(BLOCK), 0, s, x, y, flags, jx, jy, jz, zlast, table, n);       // {1..8}P
-    else hipLaunchKernelGGL(k_varwin_multiples_chain<0>, grid_for(n), dim3(BLOCK), 0, s, x, y, flags, jx, jy, jz, zlast, table, n);
+  // the multiples' Z form a chain: ONE inversion per lane's last Z, the rest by the walk back (k_varwin_chain_to_table)
+  auto chain_to_table = [&]() {
     size_t m = n >> 17; if (m < 1) m = 1; if (m > 256) m = 256;
     const size_t ilanes = (n + m - 1) / m;
     hipLaunchKernelGGL(k_varwin_invert_last, dim3((unsigned)((ilanes + 255) / 256)), dim3(256), 0, s, zlast, zinv, n, ilanes, (int)m);
-    if (pack) hipLaunchKernelGGL(k_varwin_chain_to_table<true>, grid_for(n), dim3(BLOCK), 0, s, jx, jy, jz, zinv, table, n);
-    else hipLaunchKernelGGL(k_varwin_chain_to_table<false>, grid_for(n), dim3(BLOCK), 0, s, jx, jy, jz, zinv, table, n);
-  } else if (glv) {
-    if constexpr (C == CURVE_SECP256K1) {
-      if (pack) hipLaunchKernelGGL(k_varwin_multiples<1>, grid_for(n), dim3(BLOCK), 0, s, x, y, flags, jx, jy, jz, table, n);   // {1..8}P, table form of the 29-bit loop
-      else hipLaunchKernelGGL(k_varwin_multiples<0>, grid_for(n), dim3(BLOCK), 0, s, x, y, flags, jx, jy, jz, table, n);        // {1..8}P
-    }
-  } else hipLaunchKernelGGL(k_varwin_odd_multiples<false>, grid_for(n), dim3(BLOCK), 0, s, x, y, flags, jx, jy, jz, (uint64_t*)nullptr, table, n);           // {1,3,..,15}P
-  if (!chain) {                                                            // (-DECS_VARWIN_CHAIN=0: rounds 1-3's simultaneous inversion over all 7n Jacobian multiples)
-    const size_t total = (size_t)VW_JAC * n;
-    // elements per GPU lane: as many as still leave 2^17 lanes (two waves on every SIMD); at 7 x 2^22 points that is 224,
-    // and the shared inversion (267 field mults) drops to under 2 per point
-    size_t per = total >> 17; if (per < 1) per = 1; if (per > 256) per = 256;
-    const size_t lanes = (total + per - 1) / per;
-    if (pack) hipLaunchKernelGGL(k_varwin_to_table<true>, dim3((unsigned)((lanes + 255) / 256)), dim3(256), 0, s, jx, jy, jz, prefix, table, n, total, lanes, (int)per);
-    else hipLaunchKernelGGL(k_varwin_to_table<false>, dim3((unsigned)((lanes + 255) / 256)), dim3(256), 0, s, jx, jy, jz, prefix, table, n, total, lanes, (int)per);
-  }
-  uint64_t* rx = jx; uint64_t* ry = jx + 4 * n; uint64_t* rz = jx + 8 * n;       // the multiples are dead now
+    hipLaunchKernelGGL(k_varwin_chain_to_table, grid_for(n), dim3(BLOCK), 0, s, jx, jy, jz, zinv, table, n);
+  };
   if constexpr (C == CURVE_SECP256K1) {
-    if (glv && ct) hipLaunchKernelGGL(k_varwin_mult_glv_ct<0>, grid_for(n), dim3(BLOCK), 0, s, k, k_stride, table, rx, ry, rz, n);
-    else if (glv) hipLaunchKernelGGL(k_varwin_mult_glv<4>, grid_for(n), dim3(BLOCK), 0, s, k, k_stride, table, (const uint64_t*)nullptr, rx, ry, rz, n);
+    if (!(flags & ECSIMD_HIP_ALG_NO_ENDOMORPHISM)) {                       // the GLV split
+      if (!ct) {
+        // the table over one Z, the loop on the isomorphic curve: no inversion, no second table kernel.  Its own layout: the Jacobian result (12n words),
+        // Zg (4n), then the table of ISO_ENTRIES x 64 B per lane -- 128 + 512 bytes per lane of the 1 408 there are
+        static_assert(16 * 8 + ISO_ENTRIES * 64 <= 7 * 4 * 32 + 8 * 64, "kernels.h varwin_scratch_bytes");
+        uint64_t* zg = jx + 12 * n;
+        uint4* itable = reinterpret_cast<uint4*>(jx + 16 * n);
+        hipLaunchKernelGGL(k_varwin_table_iso<ISO_ENTRIES>, grid_for(n), dim3(BLOCK), 0, s, x, y, flags, itable, zg, n);
+        hipLaunchKernelGGL(k_varwin_mult_glv<4>, grid_for(n), dim3(BLOCK), 0, s, k, k_stride, (const uint4*)itable, (const uint64_t*)zg, rx, ry, rz, n);
+      } else {
+        hipLaunchKernelGGL(k_varwin_multiples_chain, grid_for(n), dim3(BLOCK), 0, s, x, y, flags, jx, jy, jz, zlast, table, n);       // {1..8}P
+        chain_to_table();
+        hipLaunchKernelGGL(k_varwin_mult_glv_ct<0>, grid_for(n), dim3(BLOCK), 0, s, k, k_stride, table, rx, ry, rz, n);
+      }
+      to_affine_batched(s, rx, ry, rz, ox, oy, n, true);
+      return;
+    }
   }
-  if (!glv && ct) hipLaunchKernelGGL(k_varwin_mult_odd<true>, grid_for(n), dim3(BLOCK), 0, s, k, k_stride, table, rx, ry, rz, n);
-  else if (!glv) hipLaunchKernelGGL(k_varwin_mult_odd<false>, grid_for(n), dim3(BLOCK), 0, s, k, k_stride, table, rx, ry, rz, n);
+  hipLaunchKernelGGL(k_varwin_odd_multiples, grid_for(n), dim3(BLOCK), 0, s, x, y, flags, jx, jy, jz, zlast, table, n);              // {1,3,..,15}P
+  chain_to_table();
+  if (ct) hipLaunchKernelGGL(k_varwin_mult_odd<true>, grid_for(n), dim3(BLOCK), 0, s, k, k_stride, table, rx, ry, rz, n);
+  else hipLaunchKernelGGL(k_varwin_mult_odd<false>, grid_for(n), dim3(BLOCK), 0, s, k, k_stride, table, rx, ry, rz, n);
   to_affine_batched(s, rx, ry, rz, ox, oy, n, true);
 }
 template <> void point_launch<C>::add_mixed_complete(hipStream_t s, const uint64_t* ax, const uint64_t* ay, const uint64_t* az, const uint64_t* bx, const uint64_t* by,

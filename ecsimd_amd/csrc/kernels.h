@@ -135,7 +135,7 @@ void pack_table(hipStream_t, int curve, const uint64_t* tx, const uint64_t* ty, 
 void base_windowed(hipStream_t, int curve, const uint64_t* k, const uint32_t* table, uint64_t* ox, uint64_t* oy, uint64_t* oz, size_t n, bool constant_time);
 // signed windows of wbits = 6 or 7 bits
 void pack_table_signed(hipStream_t, int curve, int wbits, const uint64_t* tx, const uint64_t* ty, uint32_t* table);
-void base_windowed_signed(hipStream_t, int curve, int wbits, const uint64_t* k, const uint32_t* table, uint64_t* ox, uint64_t* oy, uint64_t* oz, size_t n, bool constant_time);
+void base_windowed_signed(hipStream_t, int curve, const uint64_t* k, const uint32_t* table, uint64_t* ox, uint64_t* oy, uint64_t* oz, size_t n, bool constant_time);
 
 // k_varwin_<curve>.hip: variable-base multiplication with per-lane window tables of 8 multiples of P (affine out, classical).
 // scratch: varwin_scratch_bytes(n) bytes, 32-byte aligned; k_stride, x, y as for scalar_mult (flags: ECSIMD_HIP_BASE_*).
@@ -178,7 +178,7 @@ template <int C> struct point_launch {
   static void pack_table(hipStream_t, const uint64_t* tx, const uint64_t* ty, uint32_t* table);
   static void base_windowed(hipStream_t, const uint64_t* k, const uint32_t* table, uint64_t* ox, uint64_t* oy, uint64_t* oz, size_t n, bool constant_time);
   static void pack_table_signed(hipStream_t, int wbits, const uint64_t* tx, const uint64_t* ty, uint32_t* table);
-  static void base_windowed_signed(hipStream_t, int wbits, const uint64_t* k, const uint32_t* table, uint64_t* ox, uint64_t* oy, uint64_t* oz, size_t n, bool constant_time);
+  static void base_windowed_signed(hipStream_t, const uint64_t* k, const uint32_t* table, uint64_t* ox, uint64_t* oy, uint64_t* oz, size_t n, bool constant_time);
   static void pack_table_big(hipStream_t, const uint64_t* tx, const uint64_t* ty, uint32_t* table);
   static void base_windowed_big(hipStream_t, const uint64_t* k, const uint32_t* table, uint64_t* ox, uint64_t* oy, uint64_t* oz, size_t n);
   // k_varwin_<curve>.hip
@@ -186,19 +186,11 @@ template <int C> struct point_launch {
   static void varwin_scalar_mult(hipStream_t, const uint64_t* k, int k_stride, const uint64_t* x, const uint64_t* y, int flags, uint64_t* scratch, uint64_t* ox, uint64_t* oy, size_t n);
 };
 inline size_t scalar_mult_x_scratch_bytes(size_t n) { return 4 * n * 32 + ((n + 31) & ~(size_t)31); }   // odd scalars, num, den, 1/den, zero flags
-// The 4-bit fixed-base table in LDS (BASELINE configs[2]).  ECS_FIXED4_ODD = 1 (round 3): odd digits only -- the regular recoding of the
-// odd one of k mod n, n - k, as in the big-window kernel: 64 windows x 8 odd multiples (2d + 1) 16^w G = 32 KiB, 63 mixed additions, no
-// zero digit and therefore no "skip" / "infinity" selects.  0: round 1's unsigned digits (64 x 16 entries d 16^w G, 64 additions).
-#ifndef ECS_FIXED4_ODD
-#define ECS_FIXED4_ODD 1
-#endif
-constexpr int FIXED4_ENTRIES = ECS_FIXED4_ODD ? 8 : 16;
-// The signed 6- / 7-bit LDS tables (ALG_WINDOWED_SIGNED).  ECS_SIGNED_ODD = 1 (round 3): odd digits as above -- 37 windows x 64 odd multiples
-// (2d + 1) 2^(7w) G for 7 bits, 36 mixed additions, no carry window and no skip / infinity selects; 0: round 1's carry recoding (digits in [-63, 64]).
-#ifndef ECS_SIGNED_ODD
-#define ECS_SIGNED_ODD 1
-#endif
-constexpr int signed_windows(int bits) { return ECS_SIGNED_ODD ? (256 + bits - 1) / bits : (256 + bits) / bits; }
+// The 4-bit fixed-base table in LDS (BASELINE configs[2]): odd digits only (round 3) -- the regular recoding of the odd one of k mod n, n - k, as in
+// the big-window kernel: 64 windows x 8 odd multiples (2d + 1) 16^w G = 32 KiB, 63 mixed additions, no zero digit and therefore no "skip" / "infinity"
+// selects.  The signed 5- / 7-bit LDS tables use the same odd digits: 52 / 37 windows x 16 / 64 odd multiples (2d + 1) 2^(bits w) G, no carry window.
+// (Round 1's unsigned 4-bit digits and carry-recoded signed digits were measured against these and removed.)
+constexpr int FIXED4_ENTRIES = 8;
 constexpr size_t WINDOW_TABLE_BYTES = 64 * FIXED4_ENTRIES * 64;   // 64 windows x entries x (x, y)
 
 }  // namespace launch

@@ -64,23 +64,18 @@ template <int C> ECS_DEV void zaddu(fe& x1, fe& y1, const fe& x2, const fe& y2, 
 // `oswap` (a per-lane all-ones / all-zeros word) exchanges the two OUTPUT points: (x1,y1) and (x2,y2) are
 // (ym^2 - W12, ym*(W1 - x) - A1) and the same with yp, so swapping the outputs is swapping (ym, yp) -- one
 // field-element swap instead of two.  The ladder folds its per-bit swaps into it; the point kernel passes 0.
-// NOZ: the Z update (1M + 1S + 3 linear operations of the 9M + 7S) is left out -- the x-only ladder below does not need it.
 // Where ZDAU updates Z (round 3).  "Early" = as soon as C = u^2 exists, so that dx and C' die before W1, W2 and the 16-word A1:
 // same instruction count (3 400 / 3 471 VALU per iteration), shorter live ranges -- the P-256 ladder allocates 138 VGPRs instead
 // of 147, the secp256k1 one 162 with NO spill instead of 168 with 14 spilled (60 B of scratch per lane, all but the scalar
 // pointer's reload outside the bit loop).  Measured on one box, 2^24 lanes (profiles/r03/ab_zdau_z_placement_*.txt): P-256 48.29
 // (early) against 48.45 M/s (late); secp256k1 48.33 against 48.41 -- registers are not what limits the ladder (the VALU is
 // saturated at 3 waves per SIMD either way), so P-256 keeps the late placement and secp256k1 takes the spill-free one.
-// -DECS_ZDAU_Z_EARLY=0 / 1 forces one placement for both curves (the A/B builds).
-#ifndef ECS_ZDAU_Z_EARLY
-#define ECS_ZDAU_Z_EARLY (-1)
-#endif
-template <int C> struct zdau_z_early { static constexpr bool value = (ECS_ZDAU_Z_EARLY < 0) ? !curve_prime<C>::is_p256 : (ECS_ZDAU_Z_EARLY != 0); };
+template <int C> struct zdau_z_early { static constexpr bool value = !curve_prime<C>::is_p256; };
 // ZE: -1 = the curve's placement above, 0 / 1 = late / early for this call site; 2 = early with the factors of z * zz exchanged, which
 // k_zdau_repeat<32> takes: with z as the FIRST factor, updated in place from registers a global load had pinned, the compiler handed
 // mac_col's early-clobber carry counter the register of the still-live z.w[7] (a compiler defect, not a source one: the constraint is
 // "=&v"; tools/asm_clobber_check.py finds it in the ISA and tests/test_isa_guards.py keeps every shipped unit checked).
-template <int C, bool NOZ = false, int ZE = -1> ECS_DEV void zdau(fe& x1, fe& y1, fe& x2, fe& y2, fe& z, uint32_t oswap = 0u) {
+template <int C, int ZE = -1> ECS_DEV void zdau(fe& x1, fe& y1, fe& x2, fe& y2, fe& z, uint32_t oswap = 0u) {
   constexpr bool z_early = (ZE < 0) ? zdau_z_early<C>::value : (ZE != 0);
   const fe dx = fe_sub<C>(x1, x2);
   const fe Cp = fe_sqr<C>(dx);
@@ -93,7 +88,7 @@ template <int C, bool NOZ = false, int ZE = -1> ECS_DEV void zdau(fe& x1, fe& y1
   const fe u = fe_sub<C>(X3pc, W1p);
   const fe Cc = fe_sqr<C>(u);
   // Z3 = Z * ((dx + X3' - W1')^2 - C' - C): as soon as C exists -- dx and C' die here instead of living across W1, W2 and A1
-  if constexpr (!NOZ && z_early) {
+  if constexpr (z_early) {
     fe zz = fe_sqr<C>(fe_add<C>(dx, u));
     zz = fe_sub<C>(fe_sub<C>(zz, Cp), Cc);
     if constexpr (ZE == 2) z = fe_mul<C>(zz, z); else z = fe_mul<C>(z, zz);      // ZE == 2: the same product with the factors exchanged
@@ -114,7 +109,7 @@ template <int C, bool NOZ = false, int ZE = -1> ECS_DEV void zdau(fe& x1, fe& y1
   const fe2 A1wide = mul8x8(Y3p, fe_sub<C>(W1, W2));
   const fe W12 = fe_add<C>(W1, W2);
   // Z3 = Z * ((dx + X3' - W1')^2 - C' - C)
-  if constexpr (!NOZ && !z_early) {
+  if constexpr (!z_early) {
     fe zz = fe_sqr<C>(fe_add<C>(dx, u));
     zz = fe_sub<C>(fe_sub<C>(zz, Cp), Cc);
     z = fe_mul<C>(z, zz);
@@ -198,9 +193,6 @@ template <int C> ECS_DEV fe fe_sqr_n(fe a, int n) {
   for (int i = 0; i < n; ++i) a = fe_sqr<C>(a);
   return a;
 }
-#ifndef ECS_INVERSE_DIVSTEPS
-#define ECS_INVERSE_DIVSTEPS 1       // 0: the a^(p-2) addition chains below (round 1)
-#endif
 // ---------------------------------------------------------------- modular inversion by divsteps ("safegcd")
 // a^-1 mod p through the Bernstein-Yang division steps (CHES 2019; the constant-time, 30-bits-at-a-time formulation that
 // libsecp256k1 documents as modinv32) instead of a^(p-2): 20 rounds of 30 division steps on the low words of (f, g) = (p, a) --
@@ -315,30 +307,15 @@ template <int C> ECS_DEV fe fe_inverse_divsteps(const fe& a) {
 // gfp.h:42-44 inverse() = a^(p-2) and gfp.h:46-54 sqrt() = a^((p+1)/4).  The reference raises to the power with
 // square-and-multiply over the exponent's bits (mgry_ops.h:44-86: 255 S + 128 M for P-256, 255 S + 249 M for
 // secp256k1); the power of a canonical residue does not depend on how the exponent is walked, so fixed addition
-// chains over the runs of ones give the same bits with 255 S + 12 M (P-256), 255 S + 15 M and 253 S + 13 M
-// (secp256k1, the chain libsecp256k1 documents).  Exponents checked against p - 2 and (p + 1)/4 symbolically.
+// chains over the runs of ones give the same bits with 255 S + 15 M and 253 S + 13 M (secp256k1, the chain libsecp256k1
+// documents; P-256's own chains were removed once divsteps and the 29-bit square root replaced them).  Exponents checked
+// against p - 2 and (p + 1)/4 symbolically.
 template <int C> ECS_DEV fe fe_inverse(const fe& x) {
   if constexpr (curve_prime<C>::ref_square) {
     // reference-compatible squaring: the squarings the reference performs, in its order (mgry_ops.h:44-86)
     return fe_pow<C>(x, curve_exps<C>::P_M2);
-#if ECS_INVERSE_DIVSTEPS
   } else if constexpr (C == CURVE_P256 || C == CURVE_SECP256K1_CLASSICAL) {
     return fe_inverse_divsteps<C>(x);
-#endif
-  } else if constexpr (C == CURVE_P256) {
-    // p - 2 = [32 ones][31 zeros][1][96 zeros][94 ones][0][1]
-    const fe x2 = fe_mul<C>(fe_sqr<C>(x), x);
-    const fe x3 = fe_mul<C>(fe_sqr<C>(x2), x);
-    const fe x6 = fe_mul<C>(fe_sqr_n<C>(x3, 3), x3);
-    const fe x12 = fe_mul<C>(fe_sqr_n<C>(x6, 6), x6);
-    const fe x15 = fe_mul<C>(fe_sqr_n<C>(x12, 3), x3);
-    const fe x30 = fe_mul<C>(fe_sqr_n<C>(x15, 15), x15);
-    const fe x32 = fe_mul<C>(fe_sqr_n<C>(x30, 2), x2);
-    fe t = fe_mul<C>(fe_sqr_n<C>(x32, 32), x);
-    t = fe_mul<C>(fe_sqr_n<C>(t, 128), x32);
-    t = fe_mul<C>(fe_sqr_n<C>(t, 32), x32);
-    t = fe_mul<C>(fe_sqr_n<C>(t, 30), x30);
-    return fe_mul<C>(fe_sqr_n<C>(t, 2), x);
   } else {
     return secp256k1_pow_chain<C, false>(x);
   }
@@ -365,11 +342,8 @@ template <int C, bool SQRT> ECS_DEV fe secp256k1_pow_chain(const fe& x) {
     return fe_mul<C>(fe_sqr_n<C>(t, 2), x);
   }
 }
-// The same two chains on fe29.cuh's 29-bit limbs (round 4, ECS_SQRT_RADIX): 253 squarings in a row are what the carry-free columns are best at; every
-// operand is a product (tight), the value is the canonical one at the end (leave29), so the bits are the chains' above.
-#ifndef ECS_SQRT_RADIX
-#define ECS_SQRT_RADIX 29
-#endif
+// The square-root chains on fe29.cuh's 29-bit limbs (round 4; the canonical-word form of P-256's was removed): 253 squarings in a row are what the
+// carry-free columns are best at; every operand is a product (tight), the value is the canonical one at the end (leave29), so the bits are the chains'.
 template <int C> ECS_DEV fe29 sqr29_n(fe29 a, int n) {
 #pragma unroll 1
   for (int i = 0; i < n; ++i) a = sqr29<C>(a);
@@ -405,18 +379,8 @@ template <int C> ECS_DEV fe fe_sqrt_candidate29(const fe& xin) {
 template <int C> ECS_DEV fe fe_sqrt_candidate(const fe& x) {        // a^((p+1)/4): a square root if there is one (p = 3 mod 4)
   if constexpr (curve_prime<C>::ref_square) {
     return fe_pow<C>(x, curve_exps<C>::P_SQRT);            // the reference's own sequence of squarings (mgry_ops.h:44-86)
-  } else if constexpr (ECS_SQRT_RADIX == 29 && (C == CURVE_P256 || C == CURVE_SECP256K1_CLASSICAL)) {
+  } else if constexpr (C == CURVE_P256 || C == CURVE_SECP256K1_CLASSICAL) {
     return fe_sqrt_candidate29<C>(x);
-  } else if constexpr (C == CURVE_P256) {
-    // (p + 1)/4 = (2^32 - 1) 2^222 + 2^190 + 2^94: 253 S + 7 M (bit by bit it is 253 S + 33 M; the power does not depend on the walk)
-    const fe x2 = fe_mul<C>(fe_sqr<C>(x), x);
-    const fe x4 = fe_mul<C>(fe_sqr_n<C>(x2, 2), x2);
-    const fe x8 = fe_mul<C>(fe_sqr_n<C>(x4, 4), x4);
-    const fe x16 = fe_mul<C>(fe_sqr_n<C>(x8, 8), x8);
-    const fe x32 = fe_mul<C>(fe_sqr_n<C>(x16, 16), x16);
-    fe t = fe_mul<C>(fe_sqr_n<C>(x32, 32), x);
-    t = fe_mul<C>(fe_sqr_n<C>(t, 96), x);
-    return fe_sqr_n<C>(t, 94);
   } else {
     return secp256k1_pow_chain<C, true>(x);
   }
@@ -455,7 +419,7 @@ template <int C> ECS_DEV void to_affine(const jpoint& P, fe& ax, fe& ay) {     /
 // words in global memory: one word is (re)read per 32 iterations so the scalar does not occupy
 // VGPRs across the ZDAU body.
 // The ladder up to (not including) the even-k correction: (px, py) = k'P with k' = k | 1, (bx, by) the other register, common z.
-template <int C, bool NOZ> ECS_DEV uint32_t ladder_core(const uint32_t* __restrict__ kwords, const fe& xm, const fe& ym, fe& px, fe& py, fe& bx, fe& by, fe& z) {
+template <int C> ECS_DEV uint32_t ladder_core(const uint32_t* __restrict__ kwords, const fe& xm, const fe& ym, fe& px, fe& py, fe& bx, fe& by, fe& z) {
   px = xm; py = ym;
   // base = TRPLU(P): DBLU then ZADDU (curve_group.h:183-186)
   {
@@ -479,7 +443,7 @@ template <int C, bool NOZ> ECS_DEV uint32_t ladder_core(const uint32_t* __restri
     const int nb = b + 1;
     if ((nb & 31) == 0) kw = (nb < 256) ? kwords[nb >> 5] : 0u;       // one word per 32 bits: the scalar is not kept in VGPRs
     const uint32_t next = 0u - ((kw >> (nb & 31)) & 1u);              // m_(b+1); 0 after the last bit: the closing swap(m_255)
-    zdau<C, NOZ>(bx, by, px, py, z, cur ^ next);                      // base = ZDAU(base, P), outputs swapped by m_b ^ m_(b+1)
+    zdau<C>(bx, by, px, py, z, cur ^ next);                           // base = ZDAU(base, P), outputs swapped by m_b ^ m_(b+1)
     cur = next;
   }
   return k0;
@@ -528,7 +492,7 @@ template <int C, int RADIX = 32> ECS_DEV jpoint scalar_mult_ladder(const uint32_
   fe px, py, bx, by, z;
   uint32_t k0;
   if constexpr (RADIX == 29) k0 = ladder_core29<C>(kwords, xm, ym, px, py, bx, by, z);
-  else k0 = ladder_core<C, false>(kwords, xm, ym, px, py, bx, by, z);
+  else k0 = ladder_core<C>(kwords, xm, ym, px, py, bx, by, z);
   // even k: subtract the original point once (curve_group.h:214-217)
   const fe oppy = fe_opposite<C>(ym);                    // jacobian_curve_point.h:48-54 via gfp.h:60-64
   const jpoint Psub = add_z2_1<C>(px, py, z, xm, oppy);
@@ -549,17 +513,10 @@ template <int C, int RADIX = 32> ECS_DEV jpoint scalar_mult_ladder(const uint32_
 // batch follows).  Only Z^2 is determined by this -- the sign of Z, hence y, is not (both are consistent with everything but the
 // input point), which is why the reference-identical Jacobian result cannot be had this way.
 // With a = 0 (secp256k1) only w^3 is determined and x keeps a cube-root ambiguity: not offered there.
-#ifndef ECS_LADDER_X_RADIX
-#define ECS_LADDER_X_RADIX 29
-#endif
 template <int C> ECS_DEV void scalar_mult_ladder_x(const uint32_t* __restrict__ kwords_odd, const fe& xm, const fe& ym, fe& num, fe& den) {
   static_assert(curve_prime<C>::is_p256, "a = -3");
   fe x0, y0, x1, y1, z;
-#if ECS_LADDER_X_RADIX == 29
   (void)ladder_core29<C, true>(kwords_odd, xm, ym, x0, y0, x1, y1, z);      // round 4: the 254 iterations on 29-bit limbs, like the reference ladder's
-#else
-  (void)ladder_core<C, true>(kwords_odd, xm, ym, x0, y0, x1, y1, z);
-#endif
   const fe e0 = fe_sub<C>(fe_sqr<C>(y0), fe_mul<C>(fe_sqr<C>(x0), x0));
   const fe e1 = fe_sub<C>(fe_sqr<C>(y1), fe_mul<C>(fe_sqr<C>(x1), x1));
   const fe D = fe_sub<C>(e0, e1);

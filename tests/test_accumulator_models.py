@@ -3,7 +3,7 @@ mixed addition ever meets R = +-T or R = infinity -- except the one addition at 
 point (k_affine.inc comb_special / comb_take_special, capi.hip ensure_window_table).  This is DESIGN.md section 5's prose argument as a
 regression test (the k* defect of rounds 1-2 lived in exactly this gap: the recodings were modelled, the sums were not).
 
-The mixed addition the kernels use (point.cuh madd_hmv / add_z2_1, k_varwin.inc dbl_add) is the chord formula: it is wrong for R = T (needs the
+The mixed addition the kernels use (point.cuh madd_hmv / add_z2_1, fe29.cuh dbl_add29) is the chord formula: it is wrong for R = T (needs the
 tangent), for R = -T (the sum is infinity) and for R = infinity.  With G of prime order n, "R = c G equals +-T = +-t G" is "c = +-t (mod n)", so
 a model over the integers c, t decides it exactly.  Shapes (both curves each):
     top4      k_base_windowed<CT>          64 x 8 entries (2d+1) 16^w G, summed from the TOP window down      (ALG_WINDOWED, BASELINE configs[2])
@@ -12,7 +12,7 @@ a model over the integers c, t decides it exactly.  Shapes (both curves each):
     bottom20  k_base_windowed_g            13 x 2^19 entries in device memory, summed from the bottom          (ALG_WINDOWED_BIG, u1 G of double_scalar_mult)
     horner4   k_varwin_mult_odd<CT>        per-lane table {1, 3, .., 15} P: three doublings + a fused double-add per window (ALG_WINDOWED, variable base)
 Scalars: the 16 797-member digit-pattern family the GPU tests use, every k* and its neighbours / images under k -> n - k and k -> k + n, the
-ladder's degenerate scalars, and 10^5 random 256-bit values per curve.  (The GLV loops: k_varwin_mult_glv handles R = +-T behind add_checked's
+ladder's degenerate scalars, and 10^5 random 256-bit values per curve.  (The GLV loops: k_varwin_mult_glv handles R = +-T behind add_checked29's
 branch and k_varwin_mult_glv_ct runs the complete addition law -- nothing to exclude; their recoding is modelled in test_recoding_models.py.)
 """
 import random
@@ -75,7 +75,7 @@ def walk_comb(a, n, bits, windows, from_top):
 
 
 def walk_horner4(a, n):
-    """k_varwin_mult_odd: R = d_63 P; per window 8 R by three doublings, then 2 (8R) + d P as ((8R + dP) + 8R) (k_varwin.inc dbl_add)."""
+    """k_varwin_mult_odd: R = d_63 P; per window 8 R by three doublings, then 2 (8R) + d P as ((8R + dP) + 8R) (fe29.cuh dbl_add29)."""
     d = digits_top4(a)
     acc = d[63]
     events = []

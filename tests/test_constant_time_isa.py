@@ -168,7 +168,7 @@ def test_constant_time_variable_base_window_loop(tmp_path_factory, unit):
 def test_constant_time_glv_loop_of_secp256k1(tmp_path_factory):
     """k_varwin_mult_glv_ct (ALG_WINDOWED | ALG_CONSTANT_TIME on secp256k1): the GLV split on the complete addition law.  Per window 32 global
     loads (the lane's 8 entries, a line at a time) addressed by loop-invariant registers; every branch hangs on the window counter (the exit
-    test and the top window's "no doublings yet"); nothing else -- and the default GLV loop (digit-addressed reads, add_checked's branch on
+    test and the top window's "no doublings yet"); nothing else -- and the default GLV loop (digit-addressed reads, add_checked29's branch on
     the operands) must be refused."""
     asm = assembly(tmp_path_factory, "k_varwin_secp256k1")
     rep = ct_check.check(asm, "k_varwin_mult_glv_ctILi0E", allow_global_loads=32)

@@ -118,7 +118,7 @@ def test_glv_split_of_secp256k1():
         k2 = signed256(((c1 * mb1) & M256) - ((c2 * a1) & M256))
         assert (k1 + k2 * lam - k) % n == 0 and abs(k1) < 1 << 128 and abs(k2) < 1 << 128
         s1, s2 = (-1 if k1 < 0 else 1), (-1 if k2 < 0 else 1)
-        # k_varwin_mult_glv<WB>: 4-bit windows (8-entry tables) and the 5-bit windows of the 16-entry table over one Z (k_varwin_table_iso)
+        # k_varwin_mult_glv<WB>: 4-bit windows (8-entry tables); 5 bits: the 16-entry table over one Z that round 4 measured and removed
         for wb, windows in ((4, 33), (5, 26)):
             half = 1 << (wb - 1)
             offw = sum(half << (wb * j) for j in range(windows - 1))
@@ -133,7 +133,7 @@ def test_glv_split_of_secp256k1():
                     us = u << 3
                     assert [((us >> (5 * j + 3)) & 31) - 16 for j in range(25)] + [(us >> 128) & 31] == digits and us < 1 << 160
                 both.append(digits)
-            # the window loop never adds a point to itself or to its opposite (add_checked's branches stay cold)
+            # the window loop never adds a point to itself or to its opposite (add_checked29's branches stay cold)
             acc = 0                                                                 # discrete log of R
             for j in range(windows - 1, -1, -1):
                 acc = ((1 << wb) * acc) % n if j != windows - 1 else 0

@@ -1,6 +1,7 @@
 #!/usr/bin/env python3
-"""A/B of kernel variants on the GPU box: every variant is another build of the SAME library (make ... EXTRA=-D...) selected
-with ECSIMD_HIP_LIBRARY; each runs `bench.py <args>` in a child process and this prints value / kernel time per variant.
+"""A/B of library builds on a GPU: every variant is another libecsimd_hip.so (another commit, or the tree with an edit or a numeric
+launch knob, built with make OBJDIR=... TARGET=...) selected with ECSIMD_HIP_LIBRARY; each runs `bench.py <args>` in a child process and this
+prints value / kernel time per variant.
 
     tools/ab_variants.py "<bench args>" name=path [name=path ...]        (path: a libecsimd_hip.so; `base` = the in-tree one)
 """

@@ -1,6 +1,7 @@
 #!/usr/bin/env python3
-"""SEC1 decompression (a square root per point: 253 squarings) at 2^22 points on both curves, M points/s -- the A/B of the square-root chains
-(ECSIMD_HIP_LIBRARY=<other build> python tools/decode_perf.py).  The decoded points are compared with the points that were encoded."""
+"""SEC1 decompression (a square root per point: 253 squarings) at 2^22 points on both curves, M points/s (round 4 measured the square-root
+chains on 29-bit limbs with it; ECSIMD_HIP_LIBRARY=<other build> runs another library).  The decoded points are compared with the points
+that were encoded."""
 import os, sys, torch
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__))); sys.path.insert(0, ROOT)
 from ecsimd_amd import Engine, P256, SECP256K1, OUT_AFFINE

@@ -47,35 +47,6 @@ import json; d=json.load(open('$out/bench.json')); r=d['roofline']; print('value
     timeout -k 10 1000 python tools/soak_windowed.py ${1:-22} ${2:-32} ${3:-} > "$out/soak_alg.txt" 2>&1; rc=$?; tail -6 "$out/soak_alg.txt"; exit $rc ;;
   bench_all)        # every bench line profiles/rNN keeps
     bash tools/bench_all.sh ${1:-r04} > "$out/bench_all.txt" 2>&1; rc=$?; cat "$out/bench_all.txt" | head -30; exit $rc ;;
-  comb29)           # round 4: the combs' additions on 29-bit limbs -- every test that runs a comb, then A/B against the radix-32 build (build/ab_comb32)
-    timeout -k 10 900 python -m pytest tests/test_gpu_parity.py tests/test_gpu_fields.py tests/test_openssl_crosscheck.py -x -q -m gpu \
-      -k "fixed_base or config3 or comb or exceptional or digit_pattern or small_base or openssl or ecdsa or double_scalar or constant_time or x_coordinate" > "$out/pytest.txt" 2>&1; rc=$?
-    tail -5 "$out/pytest.txt"; [ $rc -ne 0 ] && exit $rc
-    for w in fixed-base fixed-base-ct fixed-base-signed fixed-base-big; do for c in p256 secp256k1; do
-      echo "== $w $c" >> "$out/ab.txt"
-      timeout -k 10 300 python tools/ab_variants.py "--workload $w --curve $c --global-log2-batch 22 --steps 10 --warmup 2" radix29=base radix32=build/ab_comb32/libecsimd_hip.so >> "$out/ab.txt" 2>&1 || rc=$?
-    done; done
-    cat "$out/ab.txt"; exit $rc ;;
-  varwin29)         # round 4: the odd-digit window loop on 29-bit limbs -- every test that runs it, then A/B against the radix-32 build (build/ab_vw32)
-    timeout -k 10 900 python -m pytest tests/test_gpu_parity.py tests/test_gpu_fields.py tests/test_openssl_crosscheck.py tests/test_gpu_large.py -x -q -m gpu \
-      -k "windowed or varwin or digit_pattern or openssl or ecdsa or double_scalar or constant_time or x_coordinate or exceptional or maximum or large or invalid" > "$out/pytest.txt" 2>&1; rc=$?
-    tail -5 "$out/pytest.txt"; [ $rc -ne 0 ] && exit $rc
-    [ -f build/ab_vw32/libecsimd_hip.so ] || exit 0           # the A/B needs the radix-32 build (-DECS_VARWIN_RADIX=32) beside the tree
-    for w in windowed windowed-ct; do for c in p256; do
-      echo "== $w $c" >> "$out/ab.txt"
-      timeout -k 10 300 python tools/ab_variants.py "--workload $w --curve $c --global-log2-batch 22 --steps 5 --warmup 1" radix29=base radix32=build/ab_vw32/libecsimd_hip.so >> "$out/ab.txt" 2>&1 || rc=$?
-    done; done
-    cat "$out/ab.txt"; exit $rc ;;
-  glv29)            # round 4: the default GLV loop + the checked mixed addition on 29-bit limbs -- the tests that run them, then A/B against build/ab_glv32
-    timeout -k 10 900 python -m pytest tests/test_gpu_parity.py tests/test_gpu_fields.py tests/test_openssl_crosscheck.py tests/test_gpu_large.py tests/test_cpp_host_api.py -x -q -m gpu \
-      -k "windowed or varwin or digit_pattern or openssl or ecdsa or double_scalar or add or complete or x_coordinate or exceptional or maximum or large or invalid or cpp_api or glv or endomorphism" > "$out/pytest.txt" 2>&1; rc=$?
-    tail -5 "$out/pytest.txt"; [ $rc -ne 0 ] && exit $rc
-    [ -f build/ab_glv32/libecsimd_hip.so ] || exit 0          # (-DECS_GLV_RADIX=32)
-    for w in windowed; do
-      echo "== $w secp256k1" >> "$out/ab.txt"
-      timeout -k 10 300 python tools/ab_variants.py "--workload $w --curve secp256k1 --global-log2-batch 22 --steps 5 --warmup 1" radix29=base radix32=build/ab_glv32/libecsimd_hip.so >> "$out/ab.txt" 2>&1 || rc=$?
-    done
-    cat "$out/ab.txt"; exit $rc ;;
   profile)          # rocprofv3 --kernel-trace --stats + separate --pmc passes around bench.py: tools/profile.sh <tag> [bench args] (summaries: tools/summarize_profiles.py)
     tag=${1:-r04_ladder}; shift || true
     bash tools/profile.sh "$tag" "$@" > "$out/profile_$tag.txt" 2>&1; rc=$?; tail -8 "$out/profile_$tag.txt"; exit $rc ;;
@@ -118,19 +89,10 @@ import json; d=json.load(open('$out/bench_brainpool_$w.json')); r=d['roofline'];
     prof ladder_radix32_brainpoolP256r1 --workload ladder-radix32 --curve brainpoolP256r1
     prof ladder_ref_compat_brainpoolP256r1 --workload ladder-ref-compat --curve brainpoolP256r1
     exit $rc ;;
-  r5_small)         # round 5: the small-batch route of a registered curve (tests, latencies), then the generic canonical-word ladders at 2 against 3 waves per SIMD (build/ab_g32w3: -DGLADDER32_WAVES_PER_SIMD=3, 27 / 11 registers spilled)
+  r5_small)         # round 5: the small-batch route of a registered curve (tests, latencies)
     timeout -k 10 900 python -m pytest tests/test_gpu_curves.py -x -q -m gpu > "$out/pytest.txt" 2>&1; rc=$?
     tail -5 "$out/pytest.txt"; [ $rc -ne 0 ] && exit $rc
-    timeout -k 10 600 python tools/curve_perf.py 22 > "$out/curve_perf.txt" 2>&1 || rc=$?; cat "$out/curve_perf.txt"
-    for w in ladder-ref-compat ladder-radix32; do
-      echo "== brainpoolP256r1 $w" >> "$out/ab.txt"
-      timeout -k 10 400 python tools/ab_variants.py "--curve brainpoolP256r1 --workload $w --global-log2-batch 22 --steps 3 --warmup 1" waves2=base waves3=build/ab_g32w3/libecsimd_hip.so >> "$out/ab.txt" 2>&1 || rc=$?
-    done
-    cat "$out/ab.txt"; exit $rc ;;
-  r5_ab_k1)         # round 5: the secp256k1 Montgomery reduction's rounds on one 64-bit MAC against rounds 1-4's borrow-tracking form (build/ab_k1old, -DECS_K1_REDUCE_MAD64=0)
-    timeout -k 10 500 python tools/ab_variants.py "--workload ladder-ref-compat --curve secp256k1 --steps 5 --warmup 1" mad64=base borrow_tracking=build/ab_k1old/libecsimd_hip.so > "$out/ab.txt" 2>&1; rc=$?
-    timeout -k 10 300 python tools/ab_variants.py "--workload ladder-ref-compat --curve p256 --steps 5 --warmup 1" p256_for_scale=base >> "$out/ab.txt" 2>&1
-    cat "$out/ab.txt"; exit $rc ;;
+    timeout -k 10 600 python tools/curve_perf.py 22 > "$out/curve_perf.txt" 2>&1 || rc=$?; cat "$out/curve_perf.txt"; exit $rc ;;
   r5_adapter)       # round 5: the reference's register layout transposed on the device -- its test, the adapter beside the reference (device transposition, then the host loop: the A/B), the PCIe-inclusive rate
     timeout -k 10 600 python -m pytest tests/test_gpu_parity.py tests/test_integration_adapter.py -x -q -m gpu -k "register_layout or adapter or wire_formats" > "$out/pytest.txt" 2>&1; rc=$?
     tail -5 "$out/pytest.txt"; [ $rc -ne 0 ] && exit $rc
