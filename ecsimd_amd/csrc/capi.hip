@@ -1164,19 +1164,20 @@ int ecsimd_hip_affine_add(ecsimd_hip_ctx* ctx, int curve, const uint64_t* ax, co
 namespace {
 constexpr size_t BIG_TABLE_WORTH_IT = (size_t)1 << 16;
 int double_scalar_mult_impl(ecsimd_hip_ctx* ctx, int curve, const uint64_t* u1, const uint64_t* u2, const uint64_t* qx, const uint64_t* qy,
-                            uint64_t* rx, uint64_t* ry, uint8_t* finite, size_t n, size_t reserve_behind) {
+                            uint64_t* rx, uint64_t* ry, uint8_t* finite, size_t n, size_t reserve_behind, const uint8_t* known_valid = nullptr) {
+  // known_valid (ecdsa_recover): the caller built every Q[i] from the curve equation and says which lanes count -- no second validation pass
   (void)hipSetDevice(ctx->device);
   const size_t chunk = n < VARWIN_CHUNK ? n : VARWIN_CHUNK;
   const bool big = ctx->window16_table[curve] != nullptr || n >= BIG_TABLE_WORTH_IT;
   int rc = ensure_window_table(ctx, curve, big ? launch::BIG_WINDOW_BITS : SIGNED_WBITS);
   if (rc == ECSIMD_HIP_OK) rc = ensure_workspace(ctx, 7 * chunk * 32 + launch::varwin_scratch_bytes(chunk) + reserve_behind);   // 3 Jacobian + 2 x 2 affine + tables
-  if (rc == ECSIMD_HIP_OK) rc = ensure_valid(ctx, (n + 15) / 16 * 16);
+  if (rc == ECSIMD_HIP_OK && !known_valid) rc = ensure_valid(ctx, (n + 15) / 16 * 16);
   if (rc != ECSIMD_HIP_OK) return rc;
   uint64_t* jx = ctx->workspace; uint64_t* jy = jx + 4 * chunk; uint64_t* jz = jy + 4 * chunk;
   uint64_t* gx = jz + 4 * chunk; uint64_t* gy = gx + 4 * chunk; uint64_t* px = gy + 4 * chunk; uint64_t* py = px + 4 * chunk;
   uint64_t* scratch = py + 4 * chunk;
   hipStream_t s = ctx->stream;
-  launch::on_curve(s, curve, qx, qy, ctx->valid, n);
+  if (!known_valid) launch::on_curve(s, curve, qx, qy, ctx->valid, n);
   for (size_t first = 0; first < n; first += chunk) {
     const size_t m = (n - first) < chunk ? (n - first) : chunk;
     if (big) launch::base_windowed_big(s, curve, u1 + 4 * first, ctx->window16_table[curve], jx, jy, jz, m);   // u1*G
@@ -1185,7 +1186,7 @@ int double_scalar_mult_impl(ecsimd_hip_ctx* ctx, int curve, const uint64_t* u1, 
     launch::varwin_scalar_mult(s, curve, u2 + 4 * first, 4, qx + 4 * first, qy + 4 * first, ECSIMD_HIP_BASE_CLASSICAL, scratch, px, py, m);   // u2*Q
     launch::affine_add_batched(s, curve, gx, gy, px, py, rx + 4 * first, ry ? ry + 4 * first : nullptr, finite ? finite + first : nullptr, m);
   }
-  launch::clear_invalid(s, ctx->valid, rx, ry, finite, n);
+  launch::clear_invalid(s, known_valid ? known_valid : ctx->valid, rx, ry, finite, n);
   hipError_t e = hipGetLastError();
   return e == hipSuccess ? ECSIMD_HIP_OK : fail(ctx, e, "double_scalar_mult launch");
 }
@@ -1373,12 +1374,12 @@ void gc_safe_mult(hipStream_t s, const curve_record& rec, const gc_layout& L, ui
   if (oy) launch::gc_negate_where(s, rec.G, neg, oy, m);
 }
 int gc_double_scalar_mult(ecsimd_hip_ctx* ctx, int curve_of, const curve_record& rec, const uint64_t* u1, const uint64_t* u2, const uint64_t* qx, const uint64_t* qy,
-                          uint64_t* rx, uint64_t* ry, uint8_t* finite, size_t n, size_t reserve_behind) {
+                          uint64_t* rx, uint64_t* ry, uint8_t* finite, size_t n, size_t reserve_behind, const uint8_t* known_valid = nullptr) {
   (void)hipSetDevice(ctx->device);
   const bool win = gc_window_possible(rec);                         // u2 Q from the lane's own window table where the curve has a prime order n >= 2^255, else a ladder pass
   gc_layout L = gc_plan(nullptr, n, win);
   int rc = ensure_workspace(ctx, L.bytes + reserve_behind);
-  if (rc == ECSIMD_HIP_OK) rc = ensure_valid(ctx, (n + 15) / 16 * 16);
+  if (rc == ECSIMD_HIP_OK && !known_valid) rc = ensure_valid(ctx, (n + 15) / 16 * 16);
   if (rc != ECSIMD_HIP_OK) return rc;
   const uint32_t* comb = nullptr;                                   // u1 G from the generator's table where the curve has one (n >= 2^255), else a ladder pass
   const uint32_t* comb7 = nullptr;                                  // ... preferably the signed 7-bit comb (u1 is public: 36 additions instead of 63)
@@ -1396,7 +1397,7 @@ int gc_double_scalar_mult(ecsimd_hip_ctx* ctx, int curve_of, const curve_record&
   }
   L = gc_plan(ctx->workspace, n, win);
   hipStream_t s = ctx->stream;
-  launch::gc_on_curve(s, rec.G, qx, qy, ctx->valid, n);
+  if (!known_valid) launch::gc_on_curve(s, rec.G, qx, qy, ctx->valid, n);      // (ecdsa_recover built every Q[i] from the curve equation: known_valid says which lanes count)
   for (size_t first = 0; first < n; first += L.chunk) {
     const size_t m = (n - first) < L.chunk ? (n - first) : L.chunk;
     if (comb20 || comb7 || comb) {
@@ -1409,7 +1410,7 @@ int gc_double_scalar_mult(ecsimd_hip_ctx* ctx, int curve_of, const curve_record&
     else gc_safe_mult(s, rec, L, L.adj2, L.neg2, u2 + 4 * first, qx + 4 * first, qy + 4 * first, L.px, L.py, m);
     launch::gc_affine_add_batched(s, rec.G, L.gx, L.gy, L.px, L.py, rx + 4 * first, ry ? ry + 4 * first : nullptr, finite ? finite + first : nullptr, m);
   }
-  launch::clear_invalid(s, ctx->valid, rx, ry, finite, n);
+  launch::clear_invalid(s, known_valid ? known_valid : ctx->valid, rx, ry, finite, n);
   hipError_t e = hipGetLastError();
   return e == hipSuccess ? ECSIMD_HIP_OK : fail(ctx, e, "double_scalar_mult (registered curve) launch");
 }
@@ -1583,6 +1584,98 @@ int ecsimd_hip_ecdsa_sign(ecsimd_hip_ctx* ctx, int curve, const uint64_t* e, con
   // (the projective-coordinate leak), and the block outlives the call (grow-only, hipFree does not wipe).  Zero it on the same stream, behind the kernels.
   if (err == hipSuccess) err = hipMemsetAsync(ctx->workspace, 0, 4 * n * 32, st);
   return err == hipSuccess ? ECSIMD_HIP_OK : fail(ctx, err, "ecdsa_sign launch"); }
+
+// Public-key recovery (SEC 1 v2 4.1.6): R = (r + (v >> 1) n, the root of that parity) from k_recover.hip's lift, u1 = -e / r and u2 = s / r from its
+// scalar-field kernel, then u1 G + u2 R through double_scalar_mult's window loops, whose validation of R is skipped: R was just built from the curve
+// equation and the validity byte already says which lanes count.  ok = that byte && the sum is finite; (0, 0) elsewhere.  All data is public.
+int ecsimd_hip_ecdsa_recover(ecsimd_hip_ctx* ctx, int curve, const uint64_t* e, const uint64_t* r, const uint64_t* s_, const uint8_t* v,
+                             uint64_t* qx, uint64_t* qy, uint8_t* ok, size_t n) {
+  REQUIRE_CTX(); REQUIRE_PTR(e); REQUIRE_PTR(r); REQUIRE_PTR(s_); REQUIRE_PTR(qx);
+  if ((!v || !ok) && n) return bad(ctx, "v or ok is null");
+  if (qy && !aligned16(qy)) return bad(ctx, "qy is not 16-byte aligned");
+  const size_t flag_bytes = ((n + 15) / 16) * 16, extra = 4 * n * 32 + flag_bytes;       // u1, u2, Rx, Ry, the validity byte
+  if (curve >= ECSIMD_HIP_FIRST_REGISTERED_CURVE) {
+    curve_record rec; int rc = gc_require_ecdsa(ctx, curve, &rec); if (rc != ECSIMD_HIP_OK) return rc;
+    if (n == 0) return ECSIMD_HIP_OK;
+    if (n > (size_t)0x7fffffff * BLOCK) return bad(ctx, "batch too large");
+    (void)hipSetDevice(ctx->device);
+    const gc_layout L0 = gc_plan(nullptr, n, gc_window_possible(rec));
+    rc = ensure_workspace(ctx, L0.bytes + extra);
+    if (rc != ECSIMD_HIP_OK) return rc;
+    uint64_t* u1 = ctx->workspace + L0.bytes / 8; uint64_t* u2 = u1 + 4 * n; uint64_t* px = u2 + 4 * n; uint64_t* py = px + 4 * n;
+    uint8_t* valid = reinterpret_cast<uint8_t*>(py + 4 * n);
+    launch::gc_recover_lift(ctx->stream, rec.G, order_words(rec), r, v, px, py, valid, n);
+    launch::ecdsa_recover_scalars(ctx->stream, rec.N, e, r, s_, u1, u2, valid, n);
+    return gc_double_scalar_mult(ctx, curve, rec, u1, u2, px, py, qx, qy, ok, n, extra, valid);
+  }
+  REQUIRE_CURVE();
+  if (ctx->ref_square) return bad(ctx, "ecdsa_recover is not the reference's algorithm: no ECSIMD_HIP_REF_SQUARE_COMPAT form");
+  if (n == 0) return ECSIMD_HIP_OK;
+  if (n > (size_t)0x7fffffff * BLOCK) return bad(ctx, "batch too large");
+  (void)hipSetDevice(ctx->device);
+  gmod N; if (!lookup_modulus(curve == ECSIMD_HIP_P256 ? ECSIMD_HIP_FIELD_P256_ORDER : ECSIMD_HIP_FIELD_SECP256K1_ORDER, &N)) return bad(ctx, "group order missing from the registry");
+  const size_t front = verify_sizes(n).front;
+  // sizes the workspace (and builds the table) first, so that the pointers taken below stay valid
+  int rc = ensure_window_table(ctx, curve, (ctx->window16_table[curve] != nullptr || n >= BIG_TABLE_WORTH_IT) ? launch::BIG_WINDOW_BITS : SIGNED_WBITS);
+  if (rc == ECSIMD_HIP_OK) rc = ensure_workspace(ctx, front + extra);
+  if (rc != ECSIMD_HIP_OK) return rc;
+  uint64_t* u1 = ctx->workspace + front / 8; uint64_t* u2 = u1 + 4 * n; uint64_t* px = u2 + 4 * n; uint64_t* py = px + 4 * n;
+  uint8_t* valid = reinterpret_cast<uint8_t*>(py + 4 * n);
+  launch::words8 order; for (int i = 0; i < 8; ++i) order.w[i] = N.p[i];
+  launch::recover_lift(ctx->stream, curve, order, r, v, px, py, valid, n);
+  launch::ecdsa_recover_scalars(ctx->stream, N, e, r, s_, u1, u2, valid, n);
+  return double_scalar_mult_impl(ctx, curve, u1, u2, px, py, qx, qy, ok, n, extra, valid); }
+
+// Signing with the recovery id: ecdsa_sign's steps with y(k G) kept through the simultaneous inversion, then k_recover.hip's select-only kernel for
+// v = parity(y) | (x >= n ? 2 : 0) and the low-s rule.  The affine y joins the Jacobian k G and x in the workspace and is zeroed with them.
+int ecsimd_hip_ecdsa_sign_recoverable(ecsimd_hip_ctx* ctx, int curve, const uint64_t* e, const uint64_t* d, const uint64_t* k, uint64_t* r, uint64_t* s_, uint8_t* v, uint8_t* ok,
+                                      size_t n, int flags) {
+  REQUIRE_CTX(); REQUIRE_PTR(e); REQUIRE_PTR(d); REQUIRE_PTR(k); REQUIRE_PTR(r); REQUIRE_PTR(s_);
+  if ((!v || !ok) && n) return bad(ctx, "v or ok is null");
+  if (flags & ~ECSIMD_HIP_ECDSA_LOW_S) return bad(ctx, "ecdsa_sign_recoverable: unknown flag");
+  if (n != 0 && (overlaps(r, e) || overlaps(r, d) || overlaps(r, k) || overlaps(s_, e) || overlaps(s_, d) || overlaps(s_, k) || overlaps(r, s_))) return bad(ctx, "r and s must not alias an input or each other");   // (an empty batch has no arrays to alias)
+  const bool low_s = (flags & ECSIMD_HIP_ECDSA_LOW_S) != 0;
+  if (curve >= ECSIMD_HIP_FIRST_REGISTERED_CURVE) {
+    curve_record rec; int rc = gc_require_ecdsa(ctx, curve, &rec); if (rc != ECSIMD_HIP_OK) return rc;
+    if (n == 0) return ECSIMD_HIP_OK;
+    if (n > (size_t)0x7fffffff * BLOCK) return bad(ctx, "batch too large");
+    (void)hipSetDevice(ctx->device);
+    gc_layout L = gc_plan(nullptr, n);
+    if (L.chunk != n) return bad(ctx, "ecdsa_sign_recoverable on a registered curve: at most 2^22 signatures per call");
+    rc = ensure_workspace(ctx, L.bytes);
+    if (rc != ECSIMD_HIP_OK) return rc;
+    const uint32_t* comb = nullptr;                             // as in ecdsa_sign: the constant-time 5-bit comb where the curve has one, else the ladder
+    if (gc_comb_possible(rec)) { rc = ensure_gc_comb(ctx, curve, rec, &comb, 5); if (rc != ECSIMD_HIP_OK) { if (!capturing(ctx)) return rc; comb = nullptr; } }
+    L = gc_plan(ctx->workspace, n);
+    if (comb) {
+      launch::gc_base_windowed_s(ctx->stream, rec.G, order_words(rec), 5, k, comb, L.j[0], L.j[1], L.j[2], n);
+      launch::gc_to_affine_batched(ctx->stream, rec.G, L.j[0], L.j[1], L.j[2], L.gx, L.gy, n);
+    } else gc_safe_mult(ctx->stream, rec, L, L.adj1, L.neg1, k, nullptr, nullptr, L.gx, L.gy, n);
+    launch::ecdsa_sign_scalars(ctx->stream, rec.N, e, d, k, L.gx, r, s_, ok, n);
+    launch::sign_recovery_id(ctx->stream, order_words(rec), L.gx, L.gy, s_, ok, v, n, low_s);
+    hipError_t err = hipGetLastError();
+    if (err == hipSuccess) err = hipMemsetAsync(ctx->workspace, 0, L.bytes, ctx->stream);
+    return err == hipSuccess ? ECSIMD_HIP_OK : fail(ctx, err, "ecdsa_sign_recoverable (registered curve) launch");
+  }
+  REQUIRE_CURVE();
+  if (ctx->ref_square) return bad(ctx, "ecdsa_sign_recoverable is not the reference's algorithm: no ECSIMD_HIP_REF_SQUARE_COMPAT form");
+  if (n == 0) return ECSIMD_HIP_OK;
+  if (n > (size_t)0x7fffffff * BLOCK) return bad(ctx, "batch too large");
+  (void)hipSetDevice(ctx->device);
+  gmod N; if (!lookup_modulus(curve == ECSIMD_HIP_P256 ? ECSIMD_HIP_FIELD_P256_ORDER : ECSIMD_HIP_FIELD_SECP256K1_ORDER, &N)) return bad(ctx, "group order missing from the registry");
+  int rc = ensure_window_table(ctx, curve, CT_WBITS);
+  if (rc == ECSIMD_HIP_OK) rc = ensure_workspace(ctx, 5 * n * 32);
+  if (rc != ECSIMD_HIP_OK) return rc;
+  uint64_t* jx = ctx->workspace; uint64_t* jy = jx + 4 * n; uint64_t* jz = jy + 4 * n; uint64_t* rx = jz + 4 * n; uint64_t* ry = rx + 4 * n;
+  hipStream_t st = ctx->stream;
+  launch::words8 order; for (int i = 0; i < 8; ++i) order.w[i] = N.p[i];
+  launch::base_windowed_signed(st, curve, k, ctx->windowct_table[curve], jx, jy, jz, n, true);
+  launch::to_affine_batched(st, curve, jx, jy, jz, rx, ry, n, true);
+  launch::ecdsa_sign_scalars(st, N, e, d, k, rx, r, s_, ok, n);
+  launch::sign_recovery_id(st, order, rx, ry, s_, ok, v, n, low_s);
+  hipError_t err = hipGetLastError();
+  if (err == hipSuccess) err = hipMemsetAsync(ctx->workspace, 0, 5 * n * 32, st);     // the Jacobian k G and both affine coordinates (ecdsa_sign says why)
+  return err == hipSuccess ? ECSIMD_HIP_OK : fail(ctx, err, "ecdsa_sign_recoverable launch"); }
 
 int ecsimd_hip_fe29_raw(ecsimd_hip_ctx* ctx, int curve, int op, const int32_t* in, int32_t* out, size_t n, int swap) {
   REQUIRE_CTX(); if ((!in || !out) && n) return bad(ctx, "fe29_raw: null pointer");

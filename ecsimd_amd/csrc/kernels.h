@@ -102,6 +102,15 @@ void gc_sec1_decode(hipStream_t, const gcurve&, const uint8_t* in, uint64_t* x, 
 void gc_zdau_repeat(hipStream_t, const gcurve&, const uint64_t* px, const uint64_t* py, const uint64_t* pz, const uint64_t* qx, const uint64_t* qy,
                     uint64_t* rx, uint64_t* ry, uint64_t* sx, uint64_t* sy, uint64_t* oz, size_t n, int iters, uint64_t swap_bits, int radix);
 
+// k_recover.hip: ECDSA public-key recovery's front end (public data) and the recovery id of a signature just made (secret data: selects only).
+// recover_lift / gc_recover_lift: x = r + (v >> 1) n, y = the root of x^3 + a x + b with the parity of v; valid = v <= 3, x < p, the root exists (R = G where not).
+// ecdsa_recover_scalars: valid &= 1 <= r, s < n; u1 = -e / r, u2 = s / r modulo the order (0, 0 where not valid); one shared inversion per up to 128 elements.
+void recover_lift(hipStream_t, int curve, const words8& order, const uint64_t* r, const uint8_t* v, uint64_t* x, uint64_t* y, uint8_t* valid, size_t n);
+void gc_recover_lift(hipStream_t, const gcurve&, const words8& order, const uint64_t* r, const uint8_t* v, uint64_t* x, uint64_t* y, uint8_t* valid, size_t n);
+void ecdsa_recover_scalars(hipStream_t, const gmod& order, const uint64_t* e, const uint64_t* r, const uint64_t* s, uint64_t* u1, uint64_t* u2, uint8_t* valid, size_t n);
+// v = parity(y) | (x >= n ? 2 : 0), 0 where !ok; low_s: s > n / 2 becomes n - s and flips bit 0 of v.  (x, y) = the affine k G.
+void sign_recovery_id(hipStream_t, const words8& order, const uint64_t* x, const uint64_t* y, uint64_t* s, const uint8_t* ok, uint8_t* v, size_t n, bool low_s);
+
 // k_fe29_raw.hip: one function of fe29.cuh on raw 9-limb operands (the diagnostic entry ecsimd_hip_fe29_raw)
 enum fe29_raw_op { RAW_ZDAU = 0, RAW_MADD = 1, RAW_JDBL = 2, RAW_DBL_ADD = 3, RAW_MADDV = 4, RAW_PDBL = 5, RAW_PADD = 6, RAW_MUL = 7, RAW_SQR = 8, RAW_GJDBL = 9, RAW_ZADDU = 10 };
 constexpr int fe29_raw_inputs(int op) { return op == RAW_ZDAU ? 6 : op == RAW_MUL ? 2 : op == RAW_SQR ? 1 : (op == RAW_JDBL || op == RAW_PDBL) ? 3 : op == RAW_GJDBL ? 4 : 5; }

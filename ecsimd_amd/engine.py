@@ -11,6 +11,8 @@ import os
 
 import numpy as np
 
+from .flags import ECDSA_LOW_S
+
 P256, SECP256K1 = 0, 1
 CURVES = {"p256": P256, "secp256k1": SECP256K1}
 # field ids of the two group orders (include/ecsimd_hip.h enum ecsimd_hip_field): accepted wherever a method below takes a field's `curve`
@@ -383,6 +385,19 @@ class Engine:
         n = e.shape[0]; r, s, ok = self.empty(n), self.empty(n), self.flags(n)
         self._call("ecdsa_sign", C.c_int(curve), self._ptr(e), self._ptr(d), self._ptr(k), self._ptr(r), self._ptr(s), self._ptr(ok, 0), C.c_size_t(n))
         return r, s, ok
+
+    def ecdsa_recover(self, curve, e, r, s, v, x_only=False):
+        """ecsimd_hip_ecdsa_recover: (qx, qy, ok), the public key behind each signature (r, s) of the digest e with recovery id v (uint8 tensor)."""
+        n = e.shape[0]; qx, ok = self.empty(n), self.flags(n); qy = None if x_only else self.empty(n)
+        self._call("ecdsa_recover", C.c_int(curve), self._ptr(e), self._ptr(r), self._ptr(s), self._ptr(v, 0), self._ptr(qx), self._ptr(qy), self._ptr(ok, 0), C.c_size_t(n))
+        return qx, qy, ok
+
+    def ecdsa_sign_recoverable(self, curve, e, d, k, low_s=False):
+        """ecsimd_hip_ecdsa_sign_recoverable: (r, s, v, ok); v = parity(y(k G)) | (x(k G) >= n ? 2 : 0); low_s: s > n / 2 is returned as n - s, bit 0 of v flipped."""
+        n = e.shape[0]; r, s, v, ok = self.empty(n), self.empty(n), self.flags(n), self.flags(n)
+        self._call("ecdsa_sign_recoverable", C.c_int(curve), self._ptr(e), self._ptr(d), self._ptr(k), self._ptr(r), self._ptr(s), self._ptr(v, 0), self._ptr(ok, 0), C.c_size_t(n),
+                   C.c_int(ECDSA_LOW_S if low_s else 0))
+        return r, s, v, ok
 
     def fe29_raw(self, curve, op, inputs, swap=0):
         """ecsimd_hip_fe29_raw: one function of the reduced-radix layer on raw int32 limbs; `inputs` is an int32 tensor (n, NIN, 9); returns (n, NOUT, 9)."""

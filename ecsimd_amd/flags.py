@@ -12,3 +12,4 @@ ALG_CONSTANT_TIME = 128       # scalar_mult_base + ALG_WINDOWED: every table ent
 BASE_GENERATOR = 512          # ecsimd_hip_scalar_mult with x = y = NULL: the base point is the generator
 LADDER_RADIX32 = 256          # ladder only: the loop on 8 x 32-bit canonical words (rounds 1-3) instead of nine signed 29-bit limbs
 GROUP_NO_GATHER = 0x10000    # ecsimd_hip_group_scalar_mult only: compute without the exchange
+ECDSA_LOW_S = 1               # ecsimd_hip_ecdsa_sign_recoverable only: s > n / 2 is returned as n - s (and bit 0 of v flipped)

@@ -150,6 +150,25 @@ struct curve_group {
     hip::check(ecsimd_hip_ecdsa_sign(hip::context(), curve_id(), e.data(), d.data(), k.data(), r.data(), s.data(), ok.data(), d.size()), "ecsimd_hip_ecdsa_sign");
     return {r, s};
   }
+  // Public-key recovery (SEC 1 v2 4.1.6): the key Q behind each signature (r, s) of the digest e, given the recovery id v -- one byte per lane in a hip::mask's
+  // storage: bit 0 = the parity of y(k G), bit 1 = x(k G) >= n, as ecdsa_sign_recoverable returns it.  ok[i] is false -- and Q[i] = (0, 0) -- where v > 3, r or s
+  // is not in [1, n), r + (v >> 1) n is not the x of a curve point, or the recovered point is infinite.  Public data only.
+  static WCP ecdsa_recover(WBN const& e, WBN const& r, WBN const& s, hip::mask const& v, hip::mask& ok) {
+    same_length(r.size(), e.size(), "ecdsa_recover"); same_length(s.size(), e.size(), "ecdsa_recover"); same_length(v.size(), e.size(), "ecdsa_recover");
+    WCP q{WBN::uninitialized(e.size()), WBN::uninitialized(e.size())};
+    ok = hip::mask(e.size());
+    hip::check(ecsimd_hip_ecdsa_recover(hip::context(), curve_id(), e.data(), r.data(), s.data(), v.data(), q.x().data(), q.y().data(), ok.data(), e.size()), "ecsimd_hip_ecdsa_recover");
+    return q;
+  }
+  // ecdsa_sign that also returns the recovery id v (0 where ok[i] is false); low_s: s > n / 2 is returned as n - s and bit 0 of v flipped.
+  static std::pair<WBN, WBN> ecdsa_sign_recoverable(WBN const& e, WBN const& d, WBN const& k, hip::mask& v, hip::mask& ok, bool low_s = false) {
+    same_length(e.size(), d.size(), "ecdsa_sign_recoverable"); same_length(k.size(), d.size(), "ecdsa_sign_recoverable");
+    auto r = WBN::uninitialized(d.size()), s = WBN::uninitialized(d.size());
+    v = hip::mask(d.size()); ok = hip::mask(d.size());
+    hip::check(ecsimd_hip_ecdsa_sign_recoverable(hip::context(), curve_id(), e.data(), d.data(), k.data(), r.data(), s.data(), v.data(), ok.data(), d.size(),
+                                                 low_s ? ECSIMD_HIP_ECDSA_LOW_S : 0), "ecsimd_hip_ecdsa_sign_recoverable");
+    return {r, s};
+  }
   // ---- several GPUs: k[i] * P[i] for HOST arrays, sharded over a device group.  P affine classical (x, y);
   // the result is what scalar_mult(x, from_affine(P)) returns lane by lane -- Jacobian, Montgomery form -- or, with
   // affine_out, what .to_affine() of it returns.  Member m computes the slice device_group::shard_range(n, m, size());

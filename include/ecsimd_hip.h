@@ -195,7 +195,7 @@ int ecsimd_hip_register_modulus(const uint64_t p[4], int flags, int* field_id);
  * an id without it keeps the ladder for a variable base (BAD_ARG for the flag, ladder passes inside double_scalar_mult / ecdsa_verify).
  * Either returns the true k P for every k, (0, 0) for k = 0 mod n.  The other ALG_* shapes exist for the two built-in curves only), by affine_add, sec1_encode, sec1_decode and -- when n was given, p < 2n, and
  * n - u is a good ladder scalar for u in {n - 1, 2^256 - n - 1, 2^256 - n} (every prime-order curve of this size) -- by double_scalar_mult,
- * ecdsa_verify_rx, ecdsa_verify, ecdsa_sign: u1 G comes from the generator's signed comb -- from the 20-bit comb once that exists or the batch reaches 2^20 -- (sign: k G from the constant-time 5-bit comb), u2 Q (public) from the
+ * ecdsa_verify_rx, ecdsa_verify, ecdsa_recover, ecdsa_sign, ecdsa_sign_recoverable: u1 G comes from the generator's signed comb -- from the 20-bit comb once that exists or the batch reaches 2^20 -- (sign: k G from the constant-time 5-bit comb), u2 Q (public) from the
  * lane's window table -- correct for every scalar in [0, n); ecdsa_sign's scratch is zeroed like the built-in curves'.  (n < 2^255: passes of the ladder
  * instead, the scalars kept clear of its three degenerate values: u -> n - u and the result negated.)  Like the built-in curves', a call of
  * scalar_mult_base(OUT_AFFINE) without an algorithm flag on up to 2^16 lanes takes that comb (constant time) and returns the ladder's affine bits, its
@@ -385,6 +385,25 @@ int ecsimd_hip_ecdsa_verify(ecsimd_hip_ctx*, int curve, const uint64_t* e, const
  * condition, lane mask in force at a memory access, and address (tests/test_constant_time_isa.py).  The Jacobian k G and its x are zeroed in the context
  * workspace on the stream before the call returns.  r, s must not alias an input.  Workspace: 128 B per element. */
 int ecsimd_hip_ecdsa_sign(ecsimd_hip_ctx*, int curve, const uint64_t* e, const uint64_t* d, const uint64_t* k, uint64_t* r, uint64_t* s, uint8_t* ok, size_t n);
+/* Public-key recovery from n signatures (SEC 1 v2 4.1.6; not in the reference): the operation behind Ethereum-style transaction checking.  e, r, s as in
+ * ecdsa_verify (e is ANY 256-bit value, reduced mod n); v[i] = the recovery id, one byte per element: bit 0 = the parity of y(R), bit 1 = x(R) was >= n,
+ * R = k G of the signer.  Per element, with x = r + (v >> 1) n:  ok[i] = 1 iff v <= 3, 1 <= r, s < n, x < p, x^3 + a x + b is a square modulo p, and
+ * Q = (-e/r) G + (s/r) R is a finite point, R = (x, y) with y the root whose parity is v & 1.  Where ok[i] = 0, qx = qy = 0 (this library's point at infinity).
+ * qy may be NULL (x only).  One pass modulo p lifts r to R, one pass modulo n forms the two scalars (one constant-time division-step inversion of r shared by up
+ * to 128 signatures), then double_scalar_mult's window loops WITHOUT its validation of the point: R was just built from the curve equation.  Public data only
+ * (signatures and digests; the window kernels index tables by scalar digits and are not for secret scalars).  Any n (2^22 at a time through the window loops).
+ * Workspace: double_scalar_mult's plus 129 B per element. */
+int ecsimd_hip_ecdsa_recover(ecsimd_hip_ctx*, int curve, const uint64_t* e, const uint64_t* r, const uint64_t* s, const uint8_t* v,
+                             uint64_t* qx, uint64_t* qy, uint8_t* ok, size_t n);
+/* ecdsa_sign that also returns the recovery id: r, s, ok, the range checks, the aliasing rule and the treatment of d and k as SECRETS are ecdsa_sign's, bit for bit
+ * with flags = 0.  v[i] = parity(y(k G)) | (x(k G) >= n ? 2 : 0), and 0 where ok[i] = 0.  flags = ECSIMD_HIP_ECDSA_LOW_S: where s > n / 2 (integer halving) the call
+ * returns n - s and flips bit 0 of v (the canonical form Bitcoin and Ethereum ask for; still a valid signature of the same key).  y(k G) comes out of the same
+ * simultaneous inversion as x; v and the low-s rule are formed by selects only (tools/ct_check.py check_secret_flow on the shipped ISA, from the loads of the
+ * affine k G and of s: tests/test_ecdsa_recover_cpu.py) -- r, s and v are public once returned, a refused lane gives nothing away.  The Jacobian k G and BOTH its
+ * affine coordinates are zeroed in the context workspace on the stream before the call returns.  Workspace: 160 B per element. */
+enum { ECSIMD_HIP_ECDSA_LOW_S = 1 };
+int ecsimd_hip_ecdsa_sign_recoverable(ecsimd_hip_ctx*, int curve, const uint64_t* e, const uint64_t* d, const uint64_t* k, uint64_t* r, uint64_t* s, uint8_t* v, uint8_t* ok,
+                                      size_t n, int flags);
 /* Diagnostic (r5): ONE function of the reduced-radix layer the multiplication-bound loops run on (fe29.cuh: nine signed 29-bit limbs in 32-bit words,
  * Montgomery radix 2^261, lazy carries) on RAW operands -- int32 limbs exactly as a loop holds them between two operations: element e's coordinate c, limb l at
  * in[(e * NIN + c) * 9 + l] (device memory).  What tests use to hand the device the states and operand pairs at which the interval proofs of

@@ -97,6 +97,19 @@ for cv, nm in ((P256, "p256"), (SECP256K1, "secp256k1")):
     row(f"ecdsa_verify<{nm}> (e, r, s, Q -> ok: mod-n arithmetic on the device)", n2, timeit(lambda: e.ecdsa_verify(cv, u1, rr, ss, b2x, b2y), 5), dsm + 6 * 136, 161, "verifications")
     row(f"ecdsa_sign<{nm}> (e, d, k -> r, s: k G on the constant-time comb + mod-n arithmetic on the device)", n2, timeit(lambda: e.ecdsa_sign(cv, u1, rr, ss), 5),
         int((51 * 11 + 9 + 7) * 136), 160, "signatures")
+    # recovery: verification's sum + the lift of r (x^3 + a x + b, one square root: ~256 squarings + ~14 products) - the final comparison; real signatures,
+    # so that every lane lifts.  (e, r, s in, Qx, Qy out = 160 B + 2 flag bytes.)  Recoverable signing: + y in the affine conversion (7 products instead of 5).
+    sr, sg, sv, _ = e.ecdsa_sign_recoverable(cv, u1, rr, ss, low_s=True)
+    row(f"ecdsa_recover<{nm}> (e, r, s, v -> Q: lift + mod-n arithmetic on the device)", n2, timeit(lambda: e.ecdsa_recover(cv, u1, sr, sg, sv), 5), dsm + (6 + 4 + 270) * 136, 162, "recoveries")
+    row(f"ecdsa_sign_recoverable<{nm}> (e, d, k -> r, s, v; low s)", n2, timeit(lambda: e.ecdsa_sign_recoverable(cv, u1, rr, ss, low_s=True), 5),
+        int((51 * 11 + 9 + 9) * 136), 161, "signatures")
+    sys.path.insert(0, os.path.join(ROOT, "tools"))
+    from ecdsa_recover_model import chain_of_existing_calls
+    from ecsimd_amd.engine import ORDER_FIELD
+    params = dict(n=(0xffffffff00000000ffffffffffffffffbce6faada7179e84f3b9cac2fc632551, 0xfffffffffffffffffffffffffffffffebaaedce6af48a03bbfd25e8cd0364141)[cv])
+    row(f"recovery chained from the other public calls<{nm}> (the yardstick: every intermediate through HBM)", n2,
+        timeit(lambda: chain_of_existing_calls(e, cv, ORDER_FIELD[cv], params, u1, sr, sg, sv), 5), dsm + (6 + 4 + 270) * 136, 162 + 23 * 32, "recoveries")
+    del sr, sg, sv
     from ecsimd_amd.engine import ORDER_FIELD
     fo = ORDER_FIELD[cv]
     row(f"mgry_mul<order of {nm}> (run-time modulus, generic reduction)", n2, timeit(lambda: e.mgry_mul(fo, rr, ss)), 136, 96, "field mults")

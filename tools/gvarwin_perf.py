@@ -92,3 +92,12 @@ print(f"brainpoolP256r1 ecdsa_sign:   {ts:9.2f} ms per 2^{m.bit_length() - 1} si
 t = timed(lambda: eng.ecdsa_verify(cid, e, r_, s_, qx, qy))
 good = int(eng.to_numpy(eng.ecdsa_verify(cid, e, r_, s_, qx, qy)).sum()), int(eng.to_numpy(ok).sum())
 print(f"brainpoolP256r1 ecdsa_verify: {t:9.2f} ms per 2^{m.bit_length() - 1} signatures  {m / (t * 1e-3) / 1e6:8.2f} M/s   ({good[0]} of {good[1]} signed ones accepted)")
+
+# ... and the other two ECDSA operations on the same curve: recovery (the lift of r + the same sum, R not validated twice) and signing with the recovery id
+r2, s2, v2, ok2 = eng.ecdsa_sign_recoverable(cid, e, d, kk, low_s=True)
+tr = timed(lambda: eng.ecdsa_recover(cid, e, r2, s2, v2))
+back = eng.ecdsa_recover(cid, e, r2, s2, v2)
+same = int((back[0] == qx).all(dim=1).logical_and((back[1] == qy).all(dim=1)).sum())
+print(f"brainpoolP256r1 ecdsa_recover: {tr:8.2f} ms per 2^{m.bit_length() - 1} signatures  {m / (tr * 1e-3) / 1e6:8.2f} M/s   ({same} of {int(eng.to_numpy(ok2).sum())} keys come back)")
+tsr = timed(lambda: eng.ecdsa_sign_recoverable(cid, e, d, kk, low_s=True))
+print(f"brainpoolP256r1 ecdsa_sign_recoverable: {tsr:8.2f} ms per 2^{m.bit_length() - 1} signatures  {m / (tsr * 1e-3) / 1e6:8.2f} M/s   (ecdsa_sign: {ts:.2f} ms)")
