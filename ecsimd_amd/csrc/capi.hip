@@ -6,6 +6,7 @@
 // no LDS staging, no XCD-aware remap and no MFMA: workgroups never share data and HBM sees ~0.1 %
 // of its bandwidth.
 #include <hip/hip_runtime.h>
+#include <math.h>
 #include <stdint.h>
 #include <stdio.h>
 #include <string.h>
@@ -1676,6 +1677,102 @@ int ecsimd_hip_ecdsa_sign_recoverable(ecsimd_hip_ctx* ctx, int curve, const uint
   hipError_t err = hipGetLastError();
   if (err == hipSuccess) err = hipMemsetAsync(ctx->workspace, 0, 5 * n * 32, st);     // the Jacobian k G and both affine coordinates (ecdsa_sign says why)
   return err == hipSuccess ? ECSIMD_HIP_OK : fail(ctx, err, "ecdsa_sign_recoverable launch"); }
+
+// ---- SHA-256 and deterministic nonces (k_sha256.hip)
+int ecsimd_hip_sha256(ecsimd_hip_ctx* ctx, const uint8_t* msg, size_t msg_bytes, size_t stride_bytes, uint64_t* e, size_t n) {
+  REQUIRE_CTX(); REQUIRE_PTR(e);
+  if (!msg && n && msg_bytes) return bad(ctx, "msg is null");
+  if (stride_bytes < msg_bytes) return bad(ctx, "sha256: stride_bytes is smaller than msg_bytes");
+  if (msg_bytes > ((size_t)1 << 40)) return bad(ctx, "sha256: message too long");
+  RUN(launch::sha256(s, msg, msg_bytes, stride_bytes, e, n)); }
+
+namespace {
+// What the RFC 6979 kernels take from a curve: its order and C(n), the least C with (1 - n / 2^256)^C <= 2^-128 (double precision), which is the cap on
+// the candidates a lane may try.  qlen = 256 only: n >= 2^255, so that a candidate is the 256 bits of one HMAC and C(n) <= 128.
+struct nonce_plan { launch::words8 order; unsigned cap; };
+unsigned rfc6979_candidates_needed(const u256& n) {
+  u256 miss; const u256 zero = {{0, 0, 0, 0}};
+  (void)u_sub(miss, zero, n);                                         // 2^256 - n
+  double q = 0;
+  for (int i = 3; i >= 0; --i) q = q * 18446744073709551616.0 + (double)miss.l[i];
+  const double c = 128.0 / (256.0 - log2(q));
+  return (unsigned)ceil(c);
+}
+int nonce_lookup(ecsimd_hip_ctx* ctx, int curve, nonce_plan* out) {
+  u256 n;
+  if (curve >= ECSIMD_HIP_FIRST_REGISTERED_CURVE) {
+    curve_record rec; if (!lookup_curve_record(curve, &rec)) return bad(ctx, "unknown curve id");
+    if (!rec.has_order || !rec.ecdsa_ok) return bad(ctx, "RFC 6979 nonces need a curve registered with its group order n and the ECDSA capability");
+    if (!gc_comb_possible(rec)) return bad(ctx, "RFC 6979 nonces are supported where qlen = 256: this curve's order is below 2^255");
+    n = rec.n;
+  } else {
+    REQUIRE_CURVE();
+    n = order_of(curve);
+  }
+  for (int i = 0; i < 4; ++i) { out->order.w[2 * i] = (uint32_t)n.l[i]; out->order.w[2 * i + 1] = (uint32_t)(n.l[i] >> 32); }
+  out->cap = rfc6979_candidates_needed(n);
+  return ECSIMD_HIP_OK;
+}
+// per element behind `front` bytes of a chunk: the nonce (32 B), K as two midstates and V (96 B), the retry byte, a recovery id nobody asked for
+struct nonce_layout { uint64_t* k; void* state; uint8_t* retry; uint8_t* v; size_t bytes; };
+nonce_layout nonce_plan_ws(uint64_t* base, size_t front, size_t m) {
+  nonce_layout L; const size_t flags = ((m + 15) / 16) * 16;
+  uint8_t* p = reinterpret_cast<uint8_t*>(base) + front;
+  L.k = reinterpret_cast<uint64_t*>(p); L.state = p + 32 * m; L.retry = p + 128 * m; L.v = L.retry + flags;
+  L.bytes = 128 * m + 2 * flags;
+  return L;
+}
+}  // namespace
+
+int ecsimd_hip_rfc6979_nonce(ecsimd_hip_ctx* ctx, int curve, const uint64_t* e, const uint64_t* d, uint64_t* k, uint8_t* ok, size_t n) {
+  REQUIRE_CTX(); REQUIRE_PTR(e); REQUIRE_PTR(d); REQUIRE_PTR(k);
+  if (!ok && n) return bad(ctx, "ok is null");
+  nonce_plan P; int rc = nonce_lookup(ctx, curve, &P); if (rc != ECSIMD_HIP_OK) return rc;
+  if (n != 0 && (overlaps(k, e) || overlaps(k, d))) return bad(ctx, "k must not alias an input");
+  if (n == 0) return ECSIMD_HIP_OK;
+  (void)hipSetDevice(ctx->device);
+  const size_t chunk = n < GC_CHUNK ? n : GC_CHUNK;
+  rc = ensure_workspace(ctx, nonce_plan_ws(nullptr, 0, chunk).bytes);
+  if (rc != ECSIMD_HIP_OK) return rc;
+  hipError_t err = hipSuccess;
+  for (size_t first = 0; first < n && err == hipSuccess; first += chunk) {
+    const size_t m = n - first < chunk ? n - first : chunk;
+    const nonce_layout L = nonce_plan_ws(ctx->workspace, 0, m);
+    launch::rfc6979_nonce(ctx->stream, P.order, e + 4 * first, d + 4 * first, k + 4 * first, L.state, L.retry, ok + first, m, P.cap);
+    err = hipGetLastError();
+    if (err == hipSuccess) err = hipMemsetAsync(ctx->workspace, 0, L.bytes, ctx->stream);       // K, V and the retry bytes: gone before the call returns (L.k is unused here)
+  }
+  return err == hipSuccess ? ECSIMD_HIP_OK : fail(ctx, err, "rfc6979_nonce launch"); }
+
+// Deterministic signing: the nonce kernels write k into the context workspace, behind what ecdsa_sign_recoverable uses of it; then that call as it is -- the
+// constant-time comb, the simultaneous inversion, ecdsa_sign_scalars, sign_recovery_id -- so the output is the chain's, bit for bit.  At most 2^22 elements at a time.
+int ecsimd_hip_ecdsa_sign_deterministic(ecsimd_hip_ctx* ctx, int curve, const uint64_t* e, const uint64_t* d, uint64_t* r, uint64_t* s_, uint8_t* v, uint8_t* ok, size_t n, int flags) {
+  REQUIRE_CTX(); REQUIRE_PTR(e); REQUIRE_PTR(d); REQUIRE_PTR(r); REQUIRE_PTR(s_);
+  if (!ok && n) return bad(ctx, "ok is null");
+  if (flags & ~ECSIMD_HIP_ECDSA_LOW_S) return bad(ctx, "ecdsa_sign_deterministic: unknown flag");
+  nonce_plan P; int rc = nonce_lookup(ctx, curve, &P); if (rc != ECSIMD_HIP_OK) return rc;
+  if (ctx->ref_square) return bad(ctx, "ecdsa_sign_deterministic is not the reference's algorithm: no ECSIMD_HIP_REF_SQUARE_COMPAT form");
+  if (n != 0 && (overlaps(r, e) || overlaps(r, d) || overlaps(s_, e) || overlaps(s_, d) || overlaps(r, s_))) return bad(ctx, "r and s must not alias an input or each other");
+  if (n == 0) return ECSIMD_HIP_OK;
+  (void)hipSetDevice(ctx->device);
+  const size_t chunk = n < GC_CHUNK ? n : GC_CHUNK;
+  const size_t front = curve >= ECSIMD_HIP_FIRST_REGISTERED_CURVE ? gc_plan(nullptr, chunk).bytes : 5 * chunk * 32;     // ecdsa_sign_recoverable's own use of the workspace
+  // the first call per curve builds the comb's table and sizes the workspace: both before any pointer into the block is taken
+  rc = ensure_workspace(ctx, front + nonce_plan_ws(nullptr, 0, chunk).bytes);
+  if (rc != ECSIMD_HIP_OK) return rc;
+  for (size_t first = 0; first < n; first += chunk) {
+    const size_t m = n - first < chunk ? n - first : chunk;
+    const nonce_layout L = nonce_plan_ws(ctx->workspace, front, m);
+    launch::rfc6979_nonce(ctx->stream, P.order, e + 4 * first, d + 4 * first, L.k, L.state, L.retry, ok + first, m, P.cap);
+    hipError_t err = hipGetLastError();
+    if (err != hipSuccess) return fail(ctx, err, "ecdsa_sign_deterministic launch");
+    rc = ecsimd_hip_ecdsa_sign_recoverable(ctx, curve, e + 4 * first, d + 4 * first, L.k, r + 4 * first, s_ + 4 * first, v ? v + first : L.v, ok + first, m, flags);
+    // K, V, the last candidate and the nonce (and the unwanted v) are zeroed whatever the signing step said
+    err = hipMemsetAsync(L.k, 0, L.bytes, ctx->stream);
+    if (rc != ECSIMD_HIP_OK) return rc;
+    if (err != hipSuccess) return fail(ctx, err, "ecdsa_sign_deterministic: zeroing the workspace");
+  }
+  return ECSIMD_HIP_OK; }
 
 int ecsimd_hip_fe29_raw(ecsimd_hip_ctx* ctx, int curve, int op, const int32_t* in, int32_t* out, size_t n, int swap) {
   REQUIRE_CTX(); if ((!in || !out) && n) return bad(ctx, "fe29_raw: null pointer");

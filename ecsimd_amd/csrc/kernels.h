@@ -111,6 +111,12 @@ void ecdsa_recover_scalars(hipStream_t, const gmod& order, const uint64_t* e, co
 // v = parity(y) | (x >= n ? 2 : 0), 0 where !ok; low_s: s > n / 2 becomes n - s and flips bit 0 of v.  (x, y) = the affine k G.
 void sign_recovery_id(hipStream_t, const words8& order, const uint64_t* x, const uint64_t* y, uint64_t* s, const uint8_t* ok, uint8_t* v, size_t n, bool low_s);
 
+// k_sha256.hip: SHA-256 of n equal-length messages (message i at msg + i * stride_bytes; e = the digests as 256-bit integers), and the RFC 6979 nonce
+// (HMAC-SHA-256, qlen = 256): k = the nonce of (e, d), ok = 0 and k = 0 where d is not in [1, n - 1] or `cap` candidates were all out of range.  state: 96 B per
+// element (K as its two HMAC midstates, V), retry: one byte per element -- the one declassified bit, "the last candidate was rejected".  Secret: d, k, state.
+void sha256(hipStream_t, const uint8_t* msg, size_t msg_bytes, size_t stride_bytes, uint64_t* e, size_t n);
+void rfc6979_nonce(hipStream_t, const words8& order, const uint64_t* e, const uint64_t* d, uint64_t* k, void* state, uint8_t* retry, uint8_t* ok, size_t n, unsigned cap);
+
 // k_fe29_raw.hip: one function of fe29.cuh on raw 9-limb operands (the diagnostic entry ecsimd_hip_fe29_raw)
 enum fe29_raw_op { RAW_ZDAU = 0, RAW_MADD = 1, RAW_JDBL = 2, RAW_DBL_ADD = 3, RAW_MADDV = 4, RAW_PDBL = 5, RAW_PADD = 6, RAW_MUL = 7, RAW_SQR = 8, RAW_GJDBL = 9, RAW_ZADDU = 10 };
 constexpr int fe29_raw_inputs(int op) { return op == RAW_ZDAU ? 6 : op == RAW_MUL ? 2 : op == RAW_SQR ? 1 : (op == RAW_JDBL || op == RAW_PDBL) ? 3 : op == RAW_GJDBL ? 4 : 5; }

@@ -1,0 +1,142 @@
+// sha256.cuh -- SHA-256 (FIPS 180-4) with one message block per lane, and the HMAC-SHA-256 shapes RFC 6979 needs on top of it.
+//
+// The compression function keeps its eight state words and the sixteen-word rolling schedule in registers: all 64 rounds are unrolled, so every schedule
+// index is a compile-time value (an array indexed by a loop variable would go to scratch memory) and the round constants become literals of the additions.
+// Rotations are written as funnel shifts of a word with itself (v_alignbit_b32), Ch and Maj as bit selects (Ch(e, f, g) = bfi(e, f, g),
+// Maj(a, b, c) = bfi(a ^ b, c, b): v_bfi_b32 forms, which gfx950 issues as one three-input v_bitop3_b32 each).  Plain C++ only.  The shipped ISA has about
+// 1 500 VALU instructions per compression.
+//
+// Words are big-endian throughout, as SHA-256 reads them: a 256-bit integer held as eight little-endian 32-bit words w[0..7] (struct fe) enters a block
+// as w[7], w[6], ..., w[0] and a digest H0..H7 IS the integer with w[7 - j] = Hj -- no byte swap anywhere.
+#pragma once
+#include <stdint.h>
+#include "field.cuh"
+
+namespace ecsimd_hip {
+
+struct sha256_consts {
+  static constexpr uint32_t K[64] = {
+      0x428a2f98u, 0x71374491u, 0xb5c0fbcfu, 0xe9b5dba5u, 0x3956c25bu, 0x59f111f1u, 0x923f82a4u, 0xab1c5ed5u, 0xd807aa98u, 0x12835b01u, 0x243185beu, 0x550c7dc3u,
+      0x72be5d74u, 0x80deb1feu, 0x9bdc06a7u, 0xc19bf174u, 0xe49b69c1u, 0xefbe4786u, 0x0fc19dc6u, 0x240ca1ccu, 0x2de92c6fu, 0x4a7484aau, 0x5cb0a9dcu, 0x76f988dau,
+      0x983e5152u, 0xa831c66du, 0xb00327c8u, 0xbf597fc7u, 0xc6e00bf3u, 0xd5a79147u, 0x06ca6351u, 0x14292967u, 0x27b70a85u, 0x2e1b2138u, 0x4d2c6dfcu, 0x53380d13u,
+      0x650a7354u, 0x766a0abbu, 0x81c2c92eu, 0x92722c85u, 0xa2bfe8a1u, 0xa81a664bu, 0xc24b8b70u, 0xc76c51a3u, 0xd192e819u, 0xd6990624u, 0xf40e3585u, 0x106aa070u,
+      0x19a4c116u, 0x1e376c08u, 0x2748774cu, 0x34b0bcb5u, 0x391c0cb3u, 0x4ed8aa4au, 0x5b9cca4fu, 0x682e6ff3u, 0x748f82eeu, 0x78a5636fu, 0x84c87814u, 0x8cc70208u,
+      0x90befffau, 0xa4506cebu, 0xbef9a3f7u, 0xc67178f2u};
+  static constexpr uint32_t IV[8] = {0x6a09e667u, 0xbb67ae85u, 0x3c6ef372u, 0xa54ff53au, 0x510e527fu, 0x9b05688cu, 0x1f83d9abu, 0x5be0cd19u};
+};
+
+struct sha256_state { uint32_t h[8]; };
+struct sha256_block { uint32_t w[16]; };
+
+ECS_DEV uint32_t sha_rotr(uint32_t x, int n) { return (x >> n) | (x << (32 - n)); }                     // v_alignbit_b32 x, x, n
+ECS_DEV uint32_t sha_bfi(uint32_t m, uint32_t a, uint32_t b) { return b ^ (m & (a ^ b)); }              // m ? a : b bit by bit
+
+ECS_DEV sha256_state sha256_iv() {
+  sha256_state s;
+#pragma unroll
+  for (int i = 0; i < 8; ++i) s.h[i] = sha256_consts::IV[i];
+  return s;
+}
+
+// one block into the state; the block is taken by value (the schedule rolls over it)
+ECS_DEV void sha256_compress(sha256_state& s, sha256_block m) {
+  uint32_t a = s.h[0], b = s.h[1], c = s.h[2], d = s.h[3], e = s.h[4], f = s.h[5], g = s.h[6], h = s.h[7];
+#pragma unroll
+  for (int t = 0; t < 64; ++t) {
+    if (t >= 16) {
+      const uint32_t w15 = m.w[(t - 15) & 15], w2 = m.w[(t - 2) & 15];
+      const uint32_t s0 = sha_rotr(w15, 7) ^ sha_rotr(w15, 18) ^ (w15 >> 3);
+      const uint32_t s1 = sha_rotr(w2, 17) ^ sha_rotr(w2, 19) ^ (w2 >> 10);
+      m.w[t & 15] += s0 + m.w[(t - 7) & 15] + s1;
+    }
+    const uint32_t S1 = sha_rotr(e, 6) ^ sha_rotr(e, 11) ^ sha_rotr(e, 25);
+    const uint32_t S0 = sha_rotr(a, 2) ^ sha_rotr(a, 13) ^ sha_rotr(a, 22);
+    const uint32_t t1 = h + S1 + sha_bfi(e, f, g) + sha256_consts::K[t] + m.w[t & 15];
+    const uint32_t t2 = S0 + sha_bfi(a ^ b, c, b);
+    h = g; g = f; f = e; e = d + t1; d = c; c = b; b = a; a = t1 + t2;
+  }
+  s.h[0] += a; s.h[1] += b; s.h[2] += c; s.h[3] += d; s.h[4] += e; s.h[5] += f; s.h[6] += g; s.h[7] += h;
+}
+
+// ---- 256-bit integers <-> big-endian words
+ECS_DEV void sha_words_of(const fe& x, uint32_t (&be)[8]) {
+#pragma unroll
+  for (int j = 0; j < 8; ++j) be[j] = x.w[7 - j];
+}
+ECS_DEV fe sha_digest_fe(const sha256_state& s) {
+  fe r;
+#pragma unroll
+  for (int j = 0; j < 8; ++j) r.w[7 - j] = s.h[j];
+  return r;
+}
+
+// ---- HMAC-SHA-256 with a 32-byte key, as two midstates: the state after the key's ipad block and after its opad block.  Every HMAC under one key starts
+// from them instead of compressing the key again.
+struct hmac_key { sha256_state inner, outer; };
+
+ECS_DEV hmac_key hmac_key_from(const sha256_state& key) {              // key = 32 bytes as eight big-endian words, zero-padded to the block
+  sha256_block bi, bo;
+#pragma unroll
+  for (int j = 0; j < 16; ++j) {
+    const uint32_t kw = j < 8 ? key.h[j] : 0u;
+    bi.w[j] = kw ^ 0x36363636u;
+    bo.w[j] = kw ^ 0x5c5c5c5cu;
+  }
+  hmac_key k;
+  k.inner = sha256_iv(); sha256_compress(k.inner, bi);
+  k.outer = sha256_iv(); sha256_compress(k.outer, bo);
+  return k;
+}
+// the last block of a hash of total_bytes bytes whose final 32 (or 33) are v (and a zero byte): v, after_word, zeros, the bit length
+ECS_DEV sha256_block sha_tail_block32(const sha256_state& v, uint32_t after_word, uint32_t total_bytes) {
+  sha256_block b;
+#pragma unroll
+  for (int j = 0; j < 8; ++j) b.w[j] = v.h[j];
+  b.w[8] = after_word;                                                  // 0x80000000: the padding bit right behind v; 0x00800000: a zero byte, then the bit
+#pragma unroll
+  for (int j = 9; j < 15; ++j) b.w[j] = 0u;
+  b.w[15] = total_bytes * 8u;
+  return b;
+}
+// the outer hash: H(opad block || inner digest)
+ECS_DEV sha256_state hmac_finish(const hmac_key& k, const sha256_state& inner) {
+  sha256_state o = k.outer;
+  sha256_compress(o, sha_tail_block32(inner, 0x80000000u, 96u));
+  return o;
+}
+// HMAC_K(v), v = 32 bytes: two compressions
+ECS_DEV sha256_state hmac32(const hmac_key& k, const sha256_state& v) {
+  sha256_state in = k.inner;
+  sha256_compress(in, sha_tail_block32(v, 0x80000000u, 96u));
+  return hmac_finish(k, in);
+}
+// HMAC_K(v || 0x00): RFC 6979 3.2 h.3's key update; two compressions
+ECS_DEV sha256_state hmac32_zero(const hmac_key& k, const sha256_state& v) {
+  sha256_state in = k.inner;
+  sha256_compress(in, sha_tail_block32(v, 0x00800000u, 97u));
+  return hmac_finish(k, in);
+}
+// HMAC_K(v || sep || x || h), 97 bytes (RFC 6979 3.2 d and f; sep = 0x00 / 0x01; x, h = eight big-endian words each): three compressions.
+// The byte `sep` shifts x and h by one byte against the word grid: every word behind it is a funnel shift of two neighbours.
+ECS_DEV sha256_state hmac97(const hmac_key& k, const sha256_state& v, uint32_t sep, const uint32_t (&x)[8], const uint32_t (&h)[8]) {
+  auto join = [](uint32_t hi, uint32_t lo) { return (hi << 24) | (lo >> 8); };
+  sha256_block a, b;
+#pragma unroll
+  for (int j = 0; j < 8; ++j) a.w[j] = v.h[j];
+  a.w[8] = join(sep, x[0]);
+#pragma unroll
+  for (int j = 1; j < 8; ++j) a.w[8 + j] = join(x[j - 1], x[j]);
+  b.w[0] = join(x[7], h[0]);
+#pragma unroll
+  for (int j = 1; j < 8; ++j) b.w[j] = join(h[j - 1], h[j]);
+  b.w[8] = (h[7] << 24) | 0x00800000u;
+#pragma unroll
+  for (int j = 9; j < 15; ++j) b.w[j] = 0u;
+  b.w[15] = (64u + 97u) * 8u;
+  sha256_state in = k.inner;
+  sha256_compress(in, a);
+  sha256_compress(in, b);
+  return hmac_finish(k, in);
+}
+
+}  // namespace ecsimd_hip

@@ -399,6 +399,34 @@ class Engine:
                    C.c_int(ECDSA_LOW_S if low_s else 0))
         return r, s, v, ok
 
+    def sha256(self, msgs):
+        """ecsimd_hip_sha256: the digests of the rows of `msgs` (2-D uint8 device tensor, one message per row; rows may be strided, e.g. a column slice of a
+        wider record array) as (n, 4) integers, ready to be the `e` of the ECDSA calls."""
+        torch = self.torch
+        assert msgs.is_cuda and msgs.device.index == self.device, "tensor on the wrong device"
+        assert msgs.dtype == torch.uint8 and msgs.dim() == 2, (msgs.dtype, msgs.shape)
+        n, length = int(msgs.shape[0]), int(msgs.shape[1])
+        if n > 1 and length > 0 and (msgs.stride(1) != 1 or msgs.stride(0) < length):
+            msgs = msgs.contiguous()
+        stride = int(msgs.stride(0)) if n > 1 and length > 0 else length
+        e = self.empty(n)
+        self._bind_stream()
+        self._check(self.lib.ecsimd_hip_sha256(self.ctx, C.c_void_p(msgs.data_ptr() if n and length else 0), C.c_size_t(length), C.c_size_t(stride), C.c_void_p(e.data_ptr()), C.c_size_t(n)), "sha256")
+        return e
+
+    def rfc6979_nonce(self, curve, e, d):
+        """ecsimd_hip_rfc6979_nonce: (k, ok), the RFC 6979 (HMAC-SHA-256) nonce of each digest e and private key d; ok = 0 and k = 0 where d is not in [1, n - 1]."""
+        n = e.shape[0]; k, ok = self.empty(n), self.flags(n)
+        self._call("rfc6979_nonce", C.c_int(curve), self._ptr(e), self._ptr(d), self._ptr(k), self._ptr(ok, 0), C.c_size_t(n))
+        return k, ok
+
+    def ecdsa_sign_deterministic(self, curve, e, d, low_s=False, want_v=True):
+        """ecsimd_hip_ecdsa_sign_deterministic: (r, s, v, ok) with the RFC 6979 nonce of (e, d), made and wiped on the device; want_v=False passes v = NULL (v is None)."""
+        n = e.shape[0]; r, s, ok = self.empty(n), self.empty(n), self.flags(n); v = self.flags(n) if want_v else None
+        self._call("ecdsa_sign_deterministic", C.c_int(curve), self._ptr(e), self._ptr(d), self._ptr(r), self._ptr(s), self._ptr(v, 0), self._ptr(ok, 0), C.c_size_t(n),
+                   C.c_int(ECDSA_LOW_S if low_s else 0))
+        return r, s, v, ok
+
     def fe29_raw(self, curve, op, inputs, swap=0):
         """ecsimd_hip_fe29_raw: one function of the reduced-radix layer on raw int32 limbs; `inputs` is an int32 tensor (n, NIN, 9); returns (n, NOUT, 9)."""
         torch = self.torch

@@ -169,6 +169,23 @@ struct curve_group {
                                                  low_s ? ECSIMD_HIP_ECDSA_LOW_S : 0), "ecsimd_hip_ecdsa_sign_recoverable");
     return {r, s};
   }
+  // Deterministic signing (RFC 6979 with HMAC-SHA-256): ecdsa_sign_recoverable with the nonce of (e, d) made on the device and wiped before the call returns;
+  // the caller never sees it.  Bit for bit the chain rfc6979_nonce -> ecdsa_sign_recoverable.  Curves whose order is at least 2^255.
+  static std::pair<WBN, WBN> ecdsa_sign_deterministic(WBN const& e, WBN const& d, hip::mask& v, hip::mask& ok, bool low_s = false) {
+    same_length(e.size(), d.size(), "ecdsa_sign_deterministic");
+    auto r = WBN::uninitialized(d.size()), s = WBN::uninitialized(d.size());
+    v = hip::mask(d.size()); ok = hip::mask(d.size());
+    hip::check(ecsimd_hip_ecdsa_sign_deterministic(hip::context(), curve_id(), e.data(), d.data(), r.data(), s.data(), v.data(), ok.data(), d.size(),
+                                                   low_s ? ECSIMD_HIP_ECDSA_LOW_S : 0), "ecsimd_hip_ecdsa_sign_deterministic");
+    return {r, s};
+  }
+  // the nonce by itself (a SECRET: for callers that sign elsewhere); ok[i] is false and k[i] = 0 where d is not in [1, n)
+  static WBN rfc6979_nonce(WBN const& e, WBN const& d, hip::mask& ok) {
+    same_length(e.size(), d.size(), "rfc6979_nonce");
+    auto k = WBN::uninitialized(d.size()); ok = hip::mask(d.size());
+    hip::check(ecsimd_hip_rfc6979_nonce(hip::context(), curve_id(), e.data(), d.data(), k.data(), ok.data(), d.size()), "ecsimd_hip_rfc6979_nonce");
+    return k;
+  }
   // ---- several GPUs: k[i] * P[i] for HOST arrays, sharded over a device group.  P affine classical (x, y);
   // the result is what scalar_mult(x, from_affine(P)) returns lane by lane -- Jacobian, Montgomery form -- or, with
   // affine_out, what .to_affine() of it returns.  Member m computes the slice device_group::shard_range(n, m, size());

@@ -376,7 +376,8 @@ int ecsimd_hip_ecdsa_verify_rx(ecsimd_hip_ctx*, int curve, const uint64_t* u1, c
 int ecsimd_hip_ecdsa_verify(ecsimd_hip_ctx*, int curve, const uint64_t* e, const uint64_t* r, const uint64_t* s, const uint64_t* qx, const uint64_t* qy,
                             uint8_t* ok, size_t n);
 /* ECDSA signing of n digests (SEC 1 v2 4.1.3; not in the reference): e = the digest as an integer, d = the private key, k = the per-signature nonce --
- * the CALLER's (RFC 6979 or a DRBG: this library has no hash and no random source), 1 <= d, k < n.  R = k G comes from the constant-time comb (the kernel
+ * the CALLER's here (a DRBG's, or RFC 6979's: ecsimd_hip_rfc6979_nonce / ecsimd_hip_ecdsa_sign_deterministic below make that one on the device; this
+ * library has no random source), 1 <= d, k < n.  R = k G comes from the constant-time comb (the kernel
  * of ALG_WINDOWED | ALG_CONSTANT_TIME), r = x(R) mod n, s = k^-1 (e + r d) mod n on the device (generic Montgomery products on the order's field id, one
  * constant-time division-step inversion shared by up to 128 signatures).  ok[i] = 1 and (r, s) a valid signature, or ok[i] = 0 and r = s = 0 where d or k is
  * out of range or r or s came out 0 (probability ~2^-255: sign again with another nonce).  d and k are treated as SECRETS: no branch or address depends on
@@ -404,6 +405,34 @@ int ecsimd_hip_ecdsa_recover(ecsimd_hip_ctx*, int curve, const uint64_t* e, cons
 enum { ECSIMD_HIP_ECDSA_LOW_S = 1 };
 int ecsimd_hip_ecdsa_sign_recoverable(ecsimd_hip_ctx*, int curve, const uint64_t* e, const uint64_t* d, const uint64_t* k, uint64_t* r, uint64_t* s, uint8_t* v, uint8_t* ok,
                                       size_t n, int flags);
+/* SHA-256 (FIPS 180-4) of n messages of msg_bytes bytes each, message i at msg + i * stride_bytes (stride_bytes >= msg_bytes; device memory, any alignment --
+ * a base and a stride that are multiples of 4 are read a word at a time).  e[i] = SHA-256(message i) as the integer the ECDSA calls take: 4 x u64 little-endian
+ * limbs of the digest read as a big-endian number.  Public data.  msg_bytes = 0 is allowed (msg may then be NULL).  One message per lane, the state and the
+ * message schedule in registers; equal lengths only. */
+int ecsimd_hip_sha256(ecsimd_hip_ctx*, const uint8_t* msg, size_t msg_bytes, size_t stride_bytes, uint64_t* e, size_t n);
+/* The deterministic nonce of RFC 6979 section 3.2 with H = SHA-256 (HMAC-SHA-256), bit for bit: k[i] for digest e[i] and private key d[i].  Supported where
+ * qlen = 256, i.e. the group order n >= 2^255: the two built-in curves and every registered curve with the ECDSA capability and such an order (brainpoolP256r1,
+ * SM2, FRP256v1, ...); any other curve id is ECSIMD_HIP_ERR_BAD_ARG.  e is ANY 256-bit value, as in the other ECDSA calls: h1 = its 32 big-endian bytes,
+ * bits2octets(h1) = e - n where e >= n; RFC 6979 proper when e is a SHA-256 digest, and for another 256-bit digest what libsecp256k1 does.  ok[i] = 0 and
+ * k[i] = 0 where d is not in [1, n - 1].  d, the HMAC state (K, V), every candidate and k are SECRETS: no branch, address or lane mask in force at a memory
+ * access depends on them (tools/ct_check.py check_secret_flow on the shipped ISA: tests/test_ecdsa_deterministic_cpu.py) -- with the one exception RFC 6979
+ * itself makes: step h.3 loops while a candidate is outside [1, n - 1].  That one bit per candidate passes through a byte array of its own in the workspace,
+ * written by the first kernel and re-read as public data by the retry kernel; a rejected candidate says nothing about the accepted one.  A lane may try
+ * C(n) candidates, C(n) = ceil(128 / -log2(1 - n / 2^256)) evaluated in double precision when the curve is looked up (secp256k1 2, P-256 4, SM2 4, FRP256v1 31,
+ * brainpoolP256r1 82); a lane that exhausts them gets ok[i] = 0, k[i] = 0: probability (1 - n / 2^256)^C(n) <= 2^-128 per lane (SM2, whose 2^256 - n rounds to
+ * 2^224: 2^-128 (1 + 2^-95)).  16 SHA-256 compressions per lane and 8 per further candidate (the HMAC key midstates are kept).  Everything is stream-ordered;
+ * nothing is read back.  K, V and the retry bytes are zeroed in the workspace on the stream before the call returns.  k must not alias an input.  Any n (2^22
+ * at a time).  Workspace: 130 B per element. */
+int ecsimd_hip_rfc6979_nonce(ecsimd_hip_ctx*, int curve, const uint64_t* e, const uint64_t* d, uint64_t* k, uint8_t* ok, size_t n);
+/* ecdsa_sign_recoverable with k = the RFC 6979 nonce of (e, d), never seen by the caller: the nonce kernels write k into the context workspace, then exactly
+ * the kernels of ecdsa_sign_recoverable run, so r, s, v, ok are those of the chain rfc6979_nonce -> ecdsa_sign_recoverable bit for bit, on every curve and
+ * flag (ECSIMD_HIP_ECDSA_LOW_S).  v may be NULL.  Curves, the treatment of d and k as SECRETS, the cap on candidates and its probability: as for
+ * ecsimd_hip_rfc6979_nonce; ranges and aliasing: as for ecdsa_sign_recoverable.  ONE deviation from RFC 6979: where r or s comes out 0 (probability ~2^-255)
+ * the lane gets ok = 0, as in ecdsa_sign, instead of the next candidate.  K, V, the candidates and the nonce are zeroed in the workspace on the stream before
+ * the call returns, the Jacobian k G and its affine coordinates as in ecdsa_sign_recoverable.  Any n (2^22 at a time).  Workspace: ecdsa_sign_recoverable's
+ * (160 B per element on the built-in curves, 290 B on a registered one) plus 130 B per element. */
+int ecsimd_hip_ecdsa_sign_deterministic(ecsimd_hip_ctx*, int curve, const uint64_t* e, const uint64_t* d, uint64_t* r, uint64_t* s, uint8_t* v, uint8_t* ok,
+                                        size_t n, int flags);
 /* Diagnostic (r5): ONE function of the reduced-radix layer the multiplication-bound loops run on (fe29.cuh: nine signed 29-bit limbs in 32-bit words,
  * Montgomery radix 2^261, lazy carries) on RAW operands -- int32 limbs exactly as a loop holds them between two operations: element e's coordinate c, limb l at
  * in[(e * NIN + c) * 9 + l] (device memory).  What tests use to hand the device the states and operand pairs at which the interval proofs of

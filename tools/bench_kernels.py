@@ -55,6 +55,10 @@ for cv, nm in ((P256, "p256"), (SECP256K1, "secp256k1")):
     row(f"mgry_mul<{nm}> element-wise", n, timeit(lambda: e.mgry_mul(cv, a, b)), 136, 96, "field mults")
     row(f"mgry_sqr<{nm}> element-wise", n, timeit(lambda: e.mgry_sqr(cv, a)), 136, 64, "field mults")
 del by
+for length in (32, 64, 1000):
+    msgs = torch.randint(0, 256, (1 << 22, length), dtype=torch.uint8, device=e.tdev)
+    row(f"sha256 ({length}-byte messages)", 1 << 22, timeit(lambda: e.sha256(msgs), 5), 0, length + 32, "hashes")
+    del msgs
 n = 1 << 20                                                   # BASELINE configs[1]: point add + double, batch 2^20
 for cv, nm in ((P256, "p256"), (SECP256K1, "secp256k1")):
     s = e.fill_random(n, SEED, 2)
@@ -103,6 +107,9 @@ for cv, nm in ((P256, "p256"), (SECP256K1, "secp256k1")):
     row(f"ecdsa_recover<{nm}> (e, r, s, v -> Q: lift + mod-n arithmetic on the device)", n2, timeit(lambda: e.ecdsa_recover(cv, u1, sr, sg, sv), 5), dsm + (6 + 4 + 270) * 136, 162, "recoveries")
     row(f"ecdsa_sign_recoverable<{nm}> (e, d, k -> r, s, v; low s)", n2, timeit(lambda: e.ecdsa_sign_recoverable(cv, u1, rr, ss, low_s=True), 5),
         int((51 * 11 + 9 + 9) * 136), 161, "signatures")
+    # deterministic signing: + the RFC 6979 nonce, 16 SHA-256 compressions per lane (no multiply-adds: the VALU column stays 0 for the hash kernels)
+    row(f"rfc6979_nonce<{nm}> (e, d -> k: HMAC-SHA-256, 16 compressions)", n2, timeit(lambda: e.rfc6979_nonce(cv, u1, rr), 5), 0, 97, "nonces")
+    row(f"ecdsa_sign_deterministic<{nm}> (e, d -> r, s, v; low s)", n2, timeit(lambda: e.ecdsa_sign_deterministic(cv, u1, rr, low_s=True), 5), int((51 * 11 + 9 + 9) * 136), 129, "signatures")
     sys.path.insert(0, os.path.join(ROOT, "tools"))
     from ecdsa_recover_model import chain_of_existing_calls
     from ecsimd_amd.engine import ORDER_FIELD
