@@ -1774,6 +1774,93 @@ int ecsimd_hip_ecdsa_sign_deterministic(ecsimd_hip_ctx* ctx, int curve, const ui
   }
   return ECSIMD_HIP_OK; }
 
+// ---- BIP-340 Schnorr signatures on secp256k1 (k_schnorr.hip)
+namespace {
+int schnorr_common(ecsimd_hip_ctx* ctx, const char* what, const uint8_t* msg, size_t msg_bytes, size_t stride_bytes, size_t n, gmod* N, launch::words8* order) {
+  if (!msg && n && msg_bytes) return bad(ctx, "msg is null");
+  if (stride_bytes < msg_bytes) return bad(ctx, "schnorr: stride_bytes is smaller than msg_bytes");
+  if (msg_bytes > ((size_t)1 << 40)) return bad(ctx, "schnorr: message too long");
+  if (ctx->ref_square) { snprintf(ctx->err, sizeof ctx->err, "bad argument: %s is not the reference's algorithm: no ECSIMD_HIP_REF_SQUARE_COMPAT form", what); return ECSIMD_HIP_ERR_BAD_ARG; }
+  if (!lookup_modulus(ECSIMD_HIP_FIELD_SECP256K1_ORDER, N)) return bad(ctx, "group order missing from the registry");
+  for (int i = 0; i < 8; ++i) order->w[i] = N->p[i];
+  return ECSIMD_HIP_OK;
+}
+}  // namespace
+
+// Verification: k_schnorr_verify_front (the challenge, the lift, the range checks), then u1 G + u2 P through double_scalar_mult's window loops with the front end's
+// validity byte (P was just built from the curve equation: no second validation pass), then k_schnorr_accept.  One chunk of 2^22 at a time, all in the workspace
+// behind the window loops' own part: u1, u2, P, R (six arrays), the validity and the finite bytes.
+int ecsimd_hip_schnorr_verify(ecsimd_hip_ctx* ctx, const uint64_t* px, const uint8_t* msg, size_t msg_bytes, size_t stride_bytes,
+                              const uint64_t* r, const uint64_t* s_, uint8_t* ok, size_t n) {
+  REQUIRE_CTX(); REQUIRE_PTR(px); REQUIRE_PTR(r); REQUIRE_PTR(s_);
+  if (!ok && n) return bad(ctx, "ok is null");
+  gmod N; launch::words8 order;
+  int rc = schnorr_common(ctx, "schnorr_verify", msg, msg_bytes, stride_bytes, n, &N, &order); if (rc != ECSIMD_HIP_OK) return rc;
+  if (n == 0) return ECSIMD_HIP_OK;
+  (void)hipSetDevice(ctx->device);
+  const int curve = ECSIMD_HIP_SECP256K1;
+  const size_t chunk = n < VARWIN_CHUNK ? n : VARWIN_CHUNK, flag_bytes = ((chunk + 15) / 16) * 16;
+  const size_t front = verify_sizes(chunk).front, extra = 6 * chunk * 32 + 2 * flag_bytes;
+  // sizes the workspace (and builds the table) first, so that the pointers taken below stay valid
+  rc = ensure_window_table(ctx, curve, (ctx->window16_table[curve] != nullptr || n >= BIG_TABLE_WORTH_IT) ? launch::BIG_WINDOW_BITS : SIGNED_WBITS);
+  if (rc == ECSIMD_HIP_OK) rc = ensure_workspace(ctx, front + extra);
+  if (rc != ECSIMD_HIP_OK) return rc;
+  uint64_t* u1 = ctx->workspace + front / 8; uint64_t* u2 = u1 + 4 * chunk; uint64_t* qx = u2 + 4 * chunk; uint64_t* qy = qx + 4 * chunk;
+  uint64_t* rx = qy + 4 * chunk; uint64_t* ry = rx + 4 * chunk;
+  uint8_t* valid = reinterpret_cast<uint8_t*>(ry + 4 * chunk); uint8_t* fin = valid + flag_bytes;
+  for (size_t first = 0; first < n; first += chunk) {
+    const size_t m = n - first < chunk ? n - first : chunk;
+    launch::schnorr_verify_front(ctx->stream, order, px + 4 * first, r + 4 * first, s_ + 4 * first, msg ? msg + first * stride_bytes : nullptr, msg_bytes, stride_bytes, u1, u2, qx, qy, valid, m);
+    rc = double_scalar_mult_impl(ctx, curve, u1, u2, qx, qy, rx, ry, fin, m, extra, valid);
+    if (rc != ECSIMD_HIP_OK) return rc;
+    launch::schnorr_accept(ctx->stream, rx, ry, fin, r + 4 * first, ok + first, m);
+  }
+  hipError_t err = hipGetLastError();
+  return err == hipSuccess ? ECSIMD_HIP_OK : fail(ctx, err, "schnorr_verify launch"); }
+
+// Signing: d G on the constant-time comb with both coordinates through the simultaneous inversion, k_schnorr_nonce, k0 G the same way, k_schnorr_finish.  Per
+// element of a chunk: the Jacobian product (96 B, used twice), the affine d G and k0 G (64 B each), k0 (32 B) -- all zeroed behind the kernels (ecdsa_sign says why).
+int ecsimd_hip_schnorr_sign(ecsimd_hip_ctx* ctx, const uint64_t* d, const uint8_t* msg, size_t msg_bytes, size_t stride_bytes,
+                            const uint64_t* aux, uint64_t* px, uint64_t* r, uint64_t* s_, uint8_t* ok, size_t n) {
+  REQUIRE_CTX(); REQUIRE_PTR(d); REQUIRE_PTR(r); REQUIRE_PTR(s_);
+  if ((aux && !aligned16(aux)) || (px && !aligned16(px))) return bad(ctx, "aux or px is not 16-byte aligned");
+  if (!ok && n) return bad(ctx, "ok is null");
+  gmod N; launch::words8 order;
+  int rc = schnorr_common(ctx, "schnorr_sign", msg, msg_bytes, stride_bytes, n, &N, &order); if (rc != ECSIMD_HIP_OK) return rc;
+  if (n != 0) {
+    const void* in[3] = {d, aux, msg}; const void* out[3] = {r, s_, px};
+    for (int a = 0; a < 3; ++a) {
+      if (!out[a]) continue;
+      for (int b = 0; b < 3; ++b) if (in[b] && overlaps(out[a], in[b])) return bad(ctx, "r, s and px must not alias an input or each other");
+      for (int b = a + 1; b < 3; ++b) if (overlaps(out[a], out[b])) return bad(ctx, "r, s and px must not alias an input or each other");
+    }
+  }
+  if (n == 0) return ECSIMD_HIP_OK;
+  (void)hipSetDevice(ctx->device);
+  const int curve = ECSIMD_HIP_SECP256K1;
+  const size_t chunk = n < GC_CHUNK ? n : GC_CHUNK;
+  rc = ensure_window_table(ctx, curve, CT_WBITS);
+  if (rc == ECSIMD_HIP_OK) rc = ensure_workspace(ctx, 8 * chunk * 32);
+  if (rc != ECSIMD_HIP_OK) return rc;
+  uint64_t* jx = ctx->workspace; uint64_t* jy = jx + 4 * chunk; uint64_t* jz = jy + 4 * chunk;
+  uint64_t* xP = jz + 4 * chunk; uint64_t* yP = xP + 4 * chunk; uint64_t* xR = yP + 4 * chunk; uint64_t* yR = xR + 4 * chunk; uint64_t* k0 = yR + 4 * chunk;
+  hipStream_t st = ctx->stream;
+  hipError_t err = hipSuccess;
+  for (size_t first = 0; first < n && err == hipSuccess; first += chunk) {
+    const size_t m = n - first < chunk ? n - first : chunk;
+    const uint8_t* mp = msg ? msg + first * stride_bytes : nullptr;
+    launch::base_windowed_signed(st, curve, d + 4 * first, ctx->windowct_table[curve], jx, jy, jz, m, true);      // d >= n is reduced by the comb; the lane is refused below
+    launch::to_affine_batched(st, curve, jx, jy, jz, xP, yP, m, true);
+    launch::schnorr_nonce(st, order, d + 4 * first, aux ? aux + 4 * first : nullptr, xP, yP, mp, msg_bytes, stride_bytes, k0, m);
+    launch::base_windowed_signed(st, curve, k0, ctx->windowct_table[curve], jx, jy, jz, m, true);
+    launch::to_affine_batched(st, curve, jx, jy, jz, xR, yR, m, true);
+    launch::schnorr_finish(st, N, d + 4 * first, k0, xP, yP, xR, yR, mp, msg_bytes, stride_bytes, px ? px + 4 * first : nullptr, r + 4 * first, s_ + 4 * first, ok + first, m);
+    err = hipGetLastError();
+    hipError_t wiped = hipMemsetAsync(ctx->workspace, 0, 8 * chunk * 32, st);                                     // whatever the launches said
+    if (err == hipSuccess) err = wiped;
+  }
+  return err == hipSuccess ? ECSIMD_HIP_OK : fail(ctx, err, "schnorr_sign launch"); }
+
 int ecsimd_hip_fe29_raw(ecsimd_hip_ctx* ctx, int curve, int op, const int32_t* in, int32_t* out, size_t n, int swap) {
   REQUIRE_CTX(); if ((!in || !out) && n) return bad(ctx, "fe29_raw: null pointer");
   if (op < 0 || op > launch::RAW_ZADDU) return bad(ctx, "fe29_raw: unknown function");

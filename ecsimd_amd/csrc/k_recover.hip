@@ -14,7 +14,7 @@
 // lane was refused.  The affine k G and the s it may replace are as secret as the nonce until the lane is known to be good: selects only, no branch and no
 // address made of them (tools/ct_check.py check_secret_flow holds the ISA to that).
 #include "kernels.h"
-#include "point.cuh"
+#include "lift.cuh"
 #include "gcurve.cuh"
 
 namespace ecsimd_hip {
@@ -23,56 +23,14 @@ using launch::BLOCK;
 using launch::words8;
 #define GID size_t i = (size_t)blockIdx.x * BLOCK + threadIdx.x; if (i >= n) return
 
-ECS_DEV fe w8_words(const words8& a) {
-  fe r;
-#pragma unroll
-  for (int k = 0; k < 8; ++k) r.w[k] = a.w[k];
-  return r;
-}
-ECS_DEV fe fe_zero() {
-  fe r;
-#pragma unroll
-  for (int k = 0; k < 8; ++k) r.w[k] = 0;
-  return r;
-}
-// x = r + j n (j = bit 1 of v) as a 256-bit integer; false where v > 3 or the sum does not fit
-ECS_DEV bool lift_x(const fe& r, uint32_t v, const words8& order, fe& x) {
-  fe add = w8_words(order);
-  const uint32_t take = 0u - ((v >> 1) & 1u);
-#pragma unroll
-  for (int k = 0; k < 8; ++k) add.w[k] &= take;
-  x = r;
-  const uint32_t carry = add8(x, add);
-  return v <= 3u && carry == 0u;
-}
-// the root with the parity of v's bit 0: y or p - y (false where that is p itself: y = 0 has no odd twin)
-ECS_DEV bool pick_parity(fe& y, uint32_t v, const fe& P) {
-  fe neg;
-  (void)sub8_3(neg, P, y);
-  const bool flip = ((y.w[0] ^ v) & 1u) != 0u;
-  const bool zero = g_is_zero(y);
-  if (flip) y = neg;
-  return !(flip && zero);
-}
-
-// built-in curves: the arithmetic of k_compute_y (k_point.inc) in the curve's fast domain
+// built-in curves: lift.cuh's lift_x and lift_y
 template <int C> __global__ void __launch_bounds__(BLOCK) k_recover_lift(words8 order, const uint64_t* __restrict__ rv, const uint8_t* __restrict__ vv,
                                                                          uint64_t* __restrict__ ox, uint64_t* __restrict__ oy, uint8_t* __restrict__ valid, size_t n) {
   GID;
-  constexpr int CI = curve_domain<C>::fast;
   const uint32_t v = vv[i];
-  const fe P = FE_CONST(C, P);
-  fe x;
+  fe x, y;
   bool ok = lift_x(fe_load(rv, i), v, order, x);
-  ok = ok && g_less(x, P);
-  const fe xm = classical_to_fast<C>(x);
-  fe rhs = fe_mul<CI>(fe_sqr<CI>(xm), xm);
-  if constexpr (curve_prime<C>::is_p256) rhs = fe_sub<CI>(fe_add<CI>(rhs, FE_CONST(CI, BM)), fe_add<CI>(fe_dbl<CI>(xm), xm));   // a = -3
-  else rhs = fe_add<CI>(rhs, FE_CONST(CI, BM));                                                                              // a = 0
-  const fe root = fe_sqrt_candidate<CI>(rhs);
-  ok = ok && fe_eq(fe_sqr<CI>(root), rhs);
-  fe y = fast_to_classical<C>(root);
-  ok = pick_parity(y, v, P) && ok;
+  ok = lift_y<C>(x, v, y) && ok;
   if (!ok) { x = FE_CONST(C, GX); y = FE_CONST(C, GY); }
   fe_store(ox, i, x); fe_store(oy, i, y);
   valid[i] = (uint8_t)ok;

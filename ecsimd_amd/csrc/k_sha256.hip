@@ -26,44 +26,8 @@ typedef __attribute__((address_space(1))) volatile uint8_t retry_byte;
 // msg_bytes, stride and `aligned` (the base and the stride are multiples of 4) are the same for every lane: all the branches below are uniform.
 __global__ void __launch_bounds__(BLOCK) k_sha256(const uint8_t* __restrict__ msg, size_t msg_bytes, size_t stride, uint64_t* __restrict__ out, size_t n, uint32_t aligned) {
   GID;
-  const uint8_t* p = msg + i * stride;
   sha256_state s = sha256_iv();
-  const size_t blocks = (msg_bytes + 9 + 63) / 64;
-#pragma unroll 1
-  for (size_t b = 0; b < blocks; ++b) {
-    const size_t base = 64 * b;
-    sha256_block m;
-    if (base + 64 <= msg_bytes) {
-      if (aligned) {
-        const uint32_t* q = reinterpret_cast<const uint32_t*>(p + base);
-#pragma unroll
-        for (int j = 0; j < 16; ++j) m.w[j] = __builtin_bswap32(q[j]);
-      } else {
-#pragma unroll
-        for (int j = 0; j < 16; ++j)
-          m.w[j] = ((uint32_t)p[base + 4 * j] << 24) | ((uint32_t)p[base + 4 * j + 1] << 16) | ((uint32_t)p[base + 4 * j + 2] << 8) | (uint32_t)p[base + 4 * j + 3];
-      }
-    } else {                                                   // the message ends in or before this block: its bytes, 0x80, zeros, and the bit length at the very end
-#pragma unroll
-      for (int j = 0; j < 16; ++j) {
-        uint32_t w = 0;
-#pragma unroll
-        for (int t = 0; t < 4; ++t) {
-          const size_t q = base + 4 * j + t;
-          uint32_t byte = 0;
-          if (q < msg_bytes) byte = p[q];
-          else if (q == msg_bytes) byte = 0x80u;
-          w = (w << 8) | byte;
-        }
-        m.w[j] = w;
-      }
-      if (b + 1 == blocks) {
-        m.w[14] = (uint32_t)(((uint64_t)msg_bytes * 8u) >> 32);
-        m.w[15] = (uint32_t)((uint64_t)msg_bytes * 8u);
-      }
-    }
-    sha256_compress(s, m);
-  }
+  sha256_absorb_message(s, msg + i * stride, msg_bytes, aligned, 0);
   fe_store(out, i, sha_digest_fe(s));
 }
 

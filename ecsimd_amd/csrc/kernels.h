@@ -117,6 +117,18 @@ void sign_recovery_id(hipStream_t, const words8& order, const uint64_t* x, const
 void sha256(hipStream_t, const uint8_t* msg, size_t msg_bytes, size_t stride_bytes, uint64_t* e, size_t n);
 void rfc6979_nonce(hipStream_t, const words8& order, const uint64_t* e, const uint64_t* d, uint64_t* k, void* state, uint8_t* retry, uint8_t* ok, size_t n, unsigned cap);
 
+// k_schnorr.hip: BIP-340 on secp256k1.  Verification (public data): schnorr_verify_front writes u1 = s, u2 = n - e mod n with e = the challenge hash of
+// (r, px, message), (x, y) = the even-y lift of px (G where there is none) and valid = lift && r < p && s < n (u1 = u2 = 0 where not); schnorr_accept:
+// ok = finite && x == r && y even for the sum (x, y).  Signing (SECRET d, aux, k0 and both affine products: selects only): schnorr_nonce writes k0 from
+// (d, aux or NULL, the affine d G, message), 0 where d is not in [1, n - 1]; schnorr_finish writes r, s, px (may be NULL) and ok from (d, k0, d G, k0 G, message).
+void schnorr_verify_front(hipStream_t, const words8& order, const uint64_t* px, const uint64_t* r, const uint64_t* s, const uint8_t* msg, size_t msg_bytes, size_t stride_bytes,
+                          uint64_t* u1, uint64_t* u2, uint64_t* x, uint64_t* y, uint8_t* valid, size_t n);
+void schnorr_accept(hipStream_t, const uint64_t* x, const uint64_t* y, const uint8_t* finite, const uint64_t* r, uint8_t* ok, size_t n);
+void schnorr_nonce(hipStream_t, const words8& order, const uint64_t* d, const uint64_t* aux, const uint64_t* px, const uint64_t* py, const uint8_t* msg, size_t msg_bytes,
+                   size_t stride_bytes, uint64_t* k0, size_t n);
+void schnorr_finish(hipStream_t, const gmod& order, const uint64_t* d, const uint64_t* k0, const uint64_t* xP, const uint64_t* yP, const uint64_t* xR, const uint64_t* yR,
+                    const uint8_t* msg, size_t msg_bytes, size_t stride_bytes, uint64_t* px, uint64_t* r, uint64_t* s, uint8_t* ok, size_t n);
+
 // k_fe29_raw.hip: one function of fe29.cuh on raw 9-limb operands (the diagnostic entry ecsimd_hip_fe29_raw)
 enum fe29_raw_op { RAW_ZDAU = 0, RAW_MADD = 1, RAW_JDBL = 2, RAW_DBL_ADD = 3, RAW_MADDV = 4, RAW_PDBL = 5, RAW_PADD = 6, RAW_MUL = 7, RAW_SQR = 8, RAW_GJDBL = 9, RAW_ZADDU = 10 };
 constexpr int fe29_raw_inputs(int op) { return op == RAW_ZDAU ? 6 : op == RAW_MUL ? 2 : op == RAW_SQR ? 1 : (op == RAW_JDBL || op == RAW_PDBL) ? 3 : op == RAW_GJDBL ? 4 : 5; }

@@ -58,6 +58,49 @@ ECS_DEV void sha256_compress(sha256_state& s, sha256_block m) {
   s.h[0] += a; s.h[1] += b; s.h[2] += c; s.h[3] += d; s.h[4] += e; s.h[5] += f; s.h[6] += g; s.h[7] += h;
 }
 
+// The rest of a hash whose first prefix_bytes bytes (a multiple of 64) are in the state already: the msg_bytes bytes at p, the padding and the bit length
+// of the whole.  msg_bytes, prefix_bytes and `aligned` (p and the stride between the lanes' messages are multiples of 4: word loads) are the same on every
+// lane, so every branch here is uniform; the last one or two blocks are padded in registers.
+ECS_DEV void sha256_absorb_message(sha256_state& s, const uint8_t* __restrict__ p, size_t msg_bytes, uint32_t aligned, size_t prefix_bytes) {
+  const size_t blocks = (msg_bytes + 9 + 63) / 64;
+  const uint64_t bits = ((uint64_t)prefix_bytes + (uint64_t)msg_bytes) * 8u;
+#pragma unroll 1
+  for (size_t b = 0; b < blocks; ++b) {
+    const size_t base = 64 * b;
+    sha256_block m;
+    if (base + 64 <= msg_bytes) {
+      if (aligned) {
+        const uint32_t* q = reinterpret_cast<const uint32_t*>(p + base);
+#pragma unroll
+        for (int j = 0; j < 16; ++j) m.w[j] = __builtin_bswap32(q[j]);
+      } else {
+#pragma unroll
+        for (int j = 0; j < 16; ++j)
+          m.w[j] = ((uint32_t)p[base + 4 * j] << 24) | ((uint32_t)p[base + 4 * j + 1] << 16) | ((uint32_t)p[base + 4 * j + 2] << 8) | (uint32_t)p[base + 4 * j + 3];
+      }
+    } else {                                                   // the message ends in or before this block: its bytes, 0x80, zeros, and the bit length at the very end
+#pragma unroll
+      for (int j = 0; j < 16; ++j) {
+        uint32_t w = 0;
+#pragma unroll
+        for (int t = 0; t < 4; ++t) {
+          const size_t q = base + 4 * j + t;
+          uint32_t byte = 0;
+          if (q < msg_bytes) byte = p[q];
+          else if (q == msg_bytes) byte = 0x80u;
+          w = (w << 8) | byte;
+        }
+        m.w[j] = w;
+      }
+      if (b + 1 == blocks) {
+        m.w[14] = (uint32_t)(bits >> 32);
+        m.w[15] = (uint32_t)bits;
+      }
+    }
+    sha256_compress(s, m);
+  }
+}
+
 // ---- 256-bit integers <-> big-endian words
 ECS_DEV void sha_words_of(const fe& x, uint32_t (&be)[8]) {
 #pragma unroll

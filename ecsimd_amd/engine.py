@@ -427,6 +427,35 @@ class Engine:
                    C.c_int(ECDSA_LOW_S if low_s else 0))
         return r, s, v, ok
 
+    def _messages(self, msgs, n):
+        """(pointer, length, stride) of a 2-D uint8 device tensor with one message per row (rows may be strided), as ecsimd_hip_sha256 and the Schnorr calls take it."""
+        torch = self.torch
+        assert msgs.is_cuda and msgs.device.index == self.device, "tensor on the wrong device"
+        assert msgs.dtype == torch.uint8 and msgs.dim() == 2, (msgs.dtype, msgs.shape)
+        if int(msgs.shape[0]) != n:
+            raise EcsimdHipError(f"operands disagree on the batch length: {sorted((n, int(msgs.shape[0])))}")
+        length = int(msgs.shape[1])
+        if n > 1 and length > 0 and (msgs.stride(1) != 1 or msgs.stride(0) < length):
+            msgs = msgs.contiguous()
+        stride = int(msgs.stride(0)) if n > 1 and length > 0 else length
+        return msgs, C.c_void_p(msgs.data_ptr() if n and length else 0), C.c_size_t(length), C.c_size_t(stride)
+
+    def schnorr_verify(self, px, msgs, r, s):
+        """ecsimd_hip_schnorr_verify: ok, one byte per lane, for BIP-340 signatures (r, s) of the rows of `msgs` (2-D uint8 device tensor, rows may be strided)
+        under the x-only public keys px.  secp256k1; public data only."""
+        n = px.shape[0]; ok = self.flags(n)
+        keep, mp, length, stride = self._messages(msgs, n)
+        self._call("schnorr_verify", self._ptr(px), mp, length, stride, self._ptr(r), self._ptr(s), self._ptr(ok, 0), C.c_size_t(n))
+        return ok
+
+    def schnorr_sign(self, d, msgs, aux=None, want_px=True):
+        """ecsimd_hip_schnorr_sign: (px, r, s, ok), BIP-340 default signing of the rows of `msgs` with the SECRET keys d and the auxiliary randomness aux ((n, 4)
+        integers; None = 32 zero bytes); px = the x-only public keys (None with want_px=False).  ok = 0 and zeros where d is not in [1, n - 1]."""
+        n = d.shape[0]; r, s, ok = self.empty(n), self.empty(n), self.flags(n); px = self.empty(n) if want_px else None
+        keep, mp, length, stride = self._messages(msgs, n)
+        self._call("schnorr_sign", self._ptr(d), mp, length, stride, self._ptr(aux), self._ptr(px), self._ptr(r), self._ptr(s), self._ptr(ok, 0), C.c_size_t(n))
+        return px, r, s, ok
+
     def fe29_raw(self, curve, op, inputs, swap=0):
         """ecsimd_hip_fe29_raw: one function of the reduced-radix layer on raw int32 limbs; `inputs` is an int32 tensor (n, NIN, 9); returns (n, NOUT, 9)."""
         torch = self.torch

@@ -4,8 +4,11 @@
 #ifndef ECSIMD_CURVE_GROUP_H
 #define ECSIMD_CURVE_GROUP_H
 #include <ecsimd/device_group.h>
+#include <ecsimd/curve_secp256k1.h>
 #include <ecsimd/jacobian_curve_point.h>
+#include <ecsimd/sha256.h>
 #include <optional>
+#include <type_traits>
 
 namespace ecsimd {
 template <class Curve>
@@ -185,6 +188,24 @@ struct curve_group {
     auto k = WBN::uninitialized(d.size()); ok = hip::mask(d.size());
     hip::check(ecsimd_hip_rfc6979_nonce(hip::context(), curve_id(), e.data(), d.data(), k.data(), ok.data(), d.size()), "ecsimd_hip_rfc6979_nonce");
     return k;
+  }
+  // ---- BIP-340 Schnorr signatures: defined for secp256k1 only, so these two members exist in curve_group<curve_secp256k1> and nowhere else.
+  // Verification of the signatures (r, s) of the messages m (hip::messages: equal lengths, any stride) under the x-only public keys px.  Public data only.
+  static hip::mask schnorr_verify(WBN const& px, hip::messages const& m, WBN const& r, WBN const& s) requires std::is_same_v<Curve, curve_secp256k1> {
+    same_length(px.size(), m.size(), "schnorr_verify"); same_length(r.size(), m.size(), "schnorr_verify"); same_length(s.size(), m.size(), "schnorr_verify");
+    hip::mask ok(m.size());
+    hip::check(ecsimd_hip_schnorr_verify(hip::context(), px.data(), m.data(), m.msg_bytes(), m.stride_bytes(), r.data(), s.data(), ok.data(), m.size()), "ecsimd_hip_schnorr_verify");
+    return ok;
+  }
+  // Default signing with the SECRET keys d and the auxiliary randomness aux (nullptr: 32 zero bytes): returns (r, s), px = the x-only public keys.  ok[i] is
+  // false -- and r = s = px = 0 -- where d is not in [1, n).  Both products run on the constant-time comb; no branch or address depends on d, aux or the nonce.
+  static std::pair<WBN, WBN> schnorr_sign(WBN const& d, hip::messages const& m, WBN& px, hip::mask& ok, WBN const* aux = nullptr) requires std::is_same_v<Curve, curve_secp256k1> {
+    same_length(d.size(), m.size(), "schnorr_sign"); if (aux) same_length(aux->size(), m.size(), "schnorr_sign");
+    auto r = WBN::uninitialized(d.size()), s = WBN::uninitialized(d.size());
+    px = WBN::uninitialized(d.size()); ok = hip::mask(d.size());
+    hip::check(ecsimd_hip_schnorr_sign(hip::context(), d.data(), m.data(), m.msg_bytes(), m.stride_bytes(), aux ? aux->data() : nullptr, px.data(), r.data(), s.data(), ok.data(),
+                                       d.size()), "ecsimd_hip_schnorr_sign");
+    return {r, s};
   }
   // ---- several GPUs: k[i] * P[i] for HOST arrays, sharded over a device group.  P affine classical (x, y);
   // the result is what scalar_mult(x, from_affine(P)) returns lane by lane -- Jacobian, Montgomery form -- or, with

@@ -433,6 +433,28 @@ int ecsimd_hip_rfc6979_nonce(ecsimd_hip_ctx*, int curve, const uint64_t* e, cons
  * (160 B per element on the built-in curves, 290 B on a registered one) plus 130 B per element. */
 int ecsimd_hip_ecdsa_sign_deterministic(ecsimd_hip_ctx*, int curve, const uint64_t* e, const uint64_t* d, uint64_t* r, uint64_t* s, uint8_t* v, uint8_t* ok,
                                         size_t n, int flags);
+/* BIP-340 Schnorr signatures (Bitcoin Taproot, Nostr).  Defined for secp256k1 only: no curve id, ECSIMD_HIP_SECP256K1 throughout.  Keys, r, s and aux are 4 x u64
+ * little-endian limbs per element like everything else (the integer whose 32 big-endian bytes the BIP writes); message i lies at msg + i * stride_bytes and is
+ * msg_bytes long, as for ecsimd_hip_sha256 (any length including 0, msg may then be NULL; any alignment, word loads where base and stride are multiples of 4).
+ * Tagged hashes start from the midstate of their tag block, a constant: with 32-byte messages a challenge or nonce hash is two SHA-256 compressions, the aux hash
+ * one.  Stream-ordered, nothing is read back.  No ECSIMD_HIP_REF_SQUARE_COMPAT form (ERR_BAD_ARG on a context with that option).  Any n (2^22 at a time).
+ *
+ * Verify (BIP-340 "Verify"), PUBLIC data: ok[i] = 1 iff px < p and lifts to the even-y point P, r < p, s < n, and R = s G - e P is finite, has even y and
+ * x(R) == r, with e = int(SHA256(tag || tag || bytes(r) || bytes(px) || m)) mod n, tag = SHA256("BIP0340/challenge").  One kernel hashes, lifts and range-checks
+ * (no inversion modulo n, unlike ECDSA), double_scalar_mult's window loops form the sum (indexed by scalar digits: not for secrets), one kernel accepts.
+ * Workspace: double_scalar_mult's plus 194 B per element of a chunk. */
+int ecsimd_hip_schnorr_verify(ecsimd_hip_ctx*, const uint64_t* px, const uint8_t* msg, size_t msg_bytes, size_t stride_bytes,
+                              const uint64_t* r, const uint64_t* s, uint8_t* ok, size_t n);
+/* Sign (BIP-340 "Default Signing", bit for bit): d = the secret key, aux = 32 bytes of auxiliary randomness per element as an integer (big-endian bytes = the
+ * BIP's aux_rand), or NULL = 32 zero bytes (what libsecp256k1 does for a null aux_rand32).  px (optional output, may be NULL) = x(d G), the x-only public key.
+ * ok[i] = 0 and r = s = px = 0 where d is not in [1, n - 1] or the nonce came out 0 (probability 2^-256).  The signature is not re-verified: a caller who wants the
+ * BIP's recommended check calls ecsimd_hip_schnorr_verify on the result.  d, aux, d' (d or n - d), t, the nonce hash, the nonce k0, k, the Jacobian and the affine
+ * d G and k0 G are SECRETS until returned: both products run on the constant-time comb (the kernel of ALG_WINDOWED | ALG_CONSTANT_TIME) and the select-only
+ * simultaneous inversion, the two kernels around them select by masks -- no branch, address or lane mask in force at a memory access depends on a secret, and
+ * unlike RFC 6979 no bit is declassified (tools/ct_check.py check_secret_flow on the shipped ISA: tests/test_schnorr_cpu.py).  Every workspace byte the call
+ * used is zeroed on the stream before it returns.  r, s and px must not alias an input or each other.  Workspace: 256 B per element of a chunk. */
+int ecsimd_hip_schnorr_sign(ecsimd_hip_ctx*, const uint64_t* d, const uint8_t* msg, size_t msg_bytes, size_t stride_bytes,
+                            const uint64_t* aux, uint64_t* px, uint64_t* r, uint64_t* s, uint8_t* ok, size_t n);
 /* Diagnostic (r5): ONE function of the reduced-radix layer the multiplication-bound loops run on (fe29.cuh: nine signed 29-bit limbs in 32-bit words,
  * Montgomery radix 2^261, lazy carries) on RAW operands -- int32 limbs exactly as a loop holds them between two operations: element e's coordinate c, limb l at
  * in[(e * NIN + c) * 9 + l] (device memory).  What tests use to hand the device the states and operand pairs at which the interval proofs of

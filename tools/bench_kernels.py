@@ -116,6 +116,17 @@ for cv, nm in ((P256, "p256"), (SECP256K1, "secp256k1")):
     params = dict(n=(0xffffffff00000000ffffffffffffffffbce6faada7179e84f3b9cac2fc632551, 0xfffffffffffffffffffffffffffffffebaaedce6af48a03bbfd25e8cd0364141)[cv])
     row(f"recovery chained from the other public calls<{nm}> (the yardstick: every intermediate through HBM)", n2,
         timeit(lambda: chain_of_existing_calls(e, cv, ORDER_FIELD[cv], params, u1, sr, sg, sv), 5), dsm + (6 + 4 + 270) * 136, 162 + 23 * 32, "recoveries")
+    if cv == SECP256K1:
+        # BIP-340 (32-byte messages): verification = recovery's lift and sum without the shared inversion modulo n, plus 2 SHA-256 compressions per lane;
+        # signing = two combs and two affine conversions with y, 5 compressions, 2 generic products.  The yardstick goes through the host three times.
+        import bip340_model
+        m32 = torch.randint(0, 256, (n2, 32), dtype=torch.uint8, device=e.tdev)
+        bpx, br, bs, _ = e.schnorr_sign(rr, m32)
+        row("schnorr_verify (px, m, r, s -> ok: challenge hash + lift + sum + acceptance on the device)", n2, timeit(lambda: e.schnorr_verify(bpx, m32, br, bs), 5), dsm + (4 + 270) * 136, 129, "verifications")
+        row("schnorr_sign (d, m -> px, r, s; aux = NULL)", n2, timeit(lambda: e.schnorr_sign(rr, m32), 5), int((2 * (51 * 11 + 9) + 2) * 136), 161, "signatures")
+        row("schnorr verification chained from the other public calls (the yardstick: sha256, sec1_decode, double_scalar_mult, numpy on the host)", n2,
+            timeit(lambda: bip340_model.chain_of_existing_calls(e, bpx, m32, br, bs), 3), dsm + (4 + 270) * 136, 129 + 30 * 32, "verifications")
+        del m32, bpx, br, bs
     del sr, sg, sv
     from ecsimd_amd.engine import ORDER_FIELD
     fo = ORDER_FIELD[cv]
