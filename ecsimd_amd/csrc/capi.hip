@@ -504,7 +504,7 @@ void u_limbs29(int32_t (&out)[9], const u256& v) {                      // tight
     out[i] = (int32_t)(w & (i < 8 ? 0x1fffffffu : 0xffffffu));
   }
 }
-struct curve_record { gcurve G; u256 a, b, n; bool has_order; gmod N; bool ecdsa_ok; bool prime_order; };
+struct curve_record { gcurve G; u256 a, b, n; bool has_order; gmod N; bool ecdsa_ok; bool prime_order; bool order_wrong; };   // order_wrong: n looks like THE group order (prime, in p's Hasse interval) and n G != O
 // What a per-lane window table of a VARIABLE base needs beyond the recoding's n >= 2^255: every point on the curve but infinity has order exactly n, so that
 // "no addition inside the loop is exceptional" -- a statement about scalars modulo the ORDER OF THE POINT -- holds for every valid input, not only for
 // multiples of the generator.  That is: the group has order n (n divides #E and lies in p's Hasse interval, where no second multiple of an n >= 2^255 fits)
@@ -545,6 +545,35 @@ bool u_probable_prime(const u256& n) {
     if (witness) return false;
   }
   return true;
+}
+// n G = O on the host, once per registration: Jacobian double-and-add from the top bit over u_mul_mod (Z = 0: infinity; ~6 000 products, a few ms).
+// A prime n in p's Hasse interval that does not annihilate G is a wrong parameter set, and the comb and the window loop recode modulo n.
+u256 u_sub_mod(const u256& a, const u256& b, const u256& p) { u256 t; if (u_is_zero(b)) return a; (void)u_sub(t, p, b); return u_add_mod(a, t, p); }
+bool u_order_annihilates(const u256& gx, const u256& gy, const u256& a, const u256& p, const u256& n) {
+  const u256 zero = {{0, 0, 0, 0}}, one = {{1, 0, 0, 0}};
+  u256 X = zero, Y = one, Z = zero;
+  auto M = [&](const u256& u, const u256& v) { return u_mul_mod(u, v, p); };
+  auto dbl = [&]() {
+    if (u_is_zero(Z)) return;
+    const u256 YY = M(Y, Y), ZZ = M(Z, Z), XX = M(X, X);
+    u256 S = M(X, YY); u_dbl_mod(S, p); u_dbl_mod(S, p);                                       // 4 X Y^2
+    const u256 Mm = u_add_mod(u_add_mod(u_add_mod(XX, XX, p), XX, p), M(a, M(ZZ, ZZ)), p);     // 3 X^2 + a Z^4
+    const u256 X3 = u_sub_mod(M(Mm, Mm), u_add_mod(S, S, p), p);
+    u256 Y4 = M(YY, YY); u_dbl_mod(Y4, p); u_dbl_mod(Y4, p); u_dbl_mod(Y4, p);                  // 8 Y^4
+    u256 Z3 = M(Y, Z); u_dbl_mod(Z3, p);                                                       // (Y = 0: a point of order two, Z3 = 0)
+    Y = u_sub_mod(M(Mm, u_sub_mod(S, X3, p)), Y4, p); X = X3; Z = Z3;
+  };
+  for (int i = 255; i >= 0; --i) {
+    dbl();
+    if (!((n.l[i >> 6] >> (i & 63)) & 1u)) continue;
+    if (u_is_zero(Z)) { X = gx; Y = gy; Z = one; continue; }
+    const u256 ZZ = M(Z, Z), H = u_sub_mod(M(gx, ZZ), X, p), R = u_sub_mod(M(gy, M(Z, ZZ)), Y, p);
+    if (u_is_zero(H)) { if (u_is_zero(R)) dbl(); else Z = zero; continue; }                     // the same point: double; opposite points: infinity
+    const u256 HH = M(H, H), HHH = M(H, HH), V = M(X, HH);
+    const u256 X3 = u_sub_mod(u_sub_mod(M(R, R), HHH, p), u_add_mod(V, V, p), p);
+    Y = u_sub_mod(M(R, u_sub_mod(V, X3, p)), M(Y, HHH), p); X = X3; Z = M(Z, H);
+  }
+  return u_is_zero(Z);
 }
 struct curve_registry { std::mutex mu; std::vector<curve_record> curves; };
 curve_registry& curves() { static curve_registry r; return r; }
@@ -713,8 +742,11 @@ int ecsimd_hip_register_curve(const uint64_t p[4], const uint64_t a[4], const ui
     rec.a = A; rec.b = B; rec.n = N; rec.has_order = n != nullptr;
     rec.ecdsa_ok = false;
     if (n) {
-      // ECDSA on this curve multiplies through the reference's ladder, which is wrong at n - 1, 2^256 - n - 1 and 2^256 - n: such a scalar u is replaced by n - u
-      // (k_gc_ladder_safe_scalars).  That needs n - u to be a good scalar in turn; and x mod n by ONE conditional subtraction needs p < 2n.
+      // ECDSA on this curve multiplies through the reference's ladder.  For n >= 2^255 the ladder is wrong at n - 1, 2^256 - n - 1 and 2^256 - n alone: such a
+      // scalar u is replaced by n - u (k_gc_ladder_safe_scalars).  That needs n - u to be a good scalar in turn; and x mod n by ONE conditional subtraction
+      // needs p < 2n.  Below 2^255 every zero bit above the top of u is one more ladder step that can meet infinity: the wrong scalars are then u | 1 = 2^j mod n
+      // for every j from n's bit length to 256 (tools/ladder_degenerate_model.py; 2^192 - n and its neighbour on P-192), which that kernel does not know:
+      // no ECDSA there.
       rec.N = make_gmod(n, GMOD_PRIME);
       u256 s3[3], alt, twice;
       ladder_degenerate_points(N, s3);
@@ -724,7 +756,7 @@ int ecsimd_hip_register_curve(const uint64_t p[4], const uint64_t a[4], const ui
       for (int i = 3; i > 0; --i) twice.l[i] = (N.l[i] << 1) | (N.l[i - 1] >> 63);
       twice.l[0] = N.l[0] << 1;
       const bool p_below_2n = top || !u_geq(P, twice);
-      rec.ecdsa_ok = safe && p_below_2n;
+      rec.ecdsa_ok = safe && p_below_2n && top;
     }
     gcurve& G = rec.G;
     G.F = make_gmod(p, GMOD_PRIME);                                 // registering a CURVE vouches that p is prime
@@ -737,17 +769,26 @@ int ecsimd_hip_register_curve(const uint64_t p[4], const uint64_t a[4], const ui
     u_limbs29(G.r29.in, u_shl_mod(one, 266, P));                    // 2^266 mod p: x 2^256 -> x 2^261 through one product / 2^261
     u_limbs29(G.r29.out, u_shl_mod(one, 256, P));                   // 2^256 mod p: back
     curve_registry& r = curves();
+    auto find = [&]() -> int {
+      for (size_t i = 0; i < r.curves.size(); ++i) {
+        const curve_record& o = r.curves[i];
+        if (!memcmp(o.G.F.p, G.F.p, 32) && u_eq(o.a, A) && u_eq(o.b, B) && !memcmp(o.G.gx, G.gx, 32) && !memcmp(o.G.gy, G.gy, 32) &&
+            o.has_order == rec.has_order && (!rec.has_order || u_eq(o.n, N))) return FIRST_CURVE_ID + (int)i;
+      }
+      return -1;
+    };
+    { std::lock_guard<std::mutex> g(r.mu); const int id = find(); if (id >= 0) { *curve_id = id; return ECSIMD_HIP_OK; } }
+    // A new record only, and outside the registry's lock (~0.1 s of host arithmetic): is n a prime in p's Hasse interval, and then: is it G's order?  One that
+    // is not -- a neighbouring prime, a typo -- gets neither the comb nor the window loop nor ECDSA, all of which compute modulo n; the ladder does not.
+    rec.prime_order = rec.has_order && (N.l[3] >> 63) != 0 && u_hasse(N, P) && u_probable_prime(N);
+    rec.order_wrong = rec.prime_order && !u_order_annihilates(GX, GY, A, P, N);
+    if (rec.order_wrong) { rec.prime_order = false; rec.ecdsa_ok = false; }
     std::lock_guard<std::mutex> g(r.mu);
     // Entries are keyed on the curve AND the order it was registered with (none is a value of its own): what an id does -- the small-batch route of
     // scalar_mult_base, the comb, ECDSA -- depends on n, so a later registration with another n (or the first one with any) must never change the
     // behaviour of an id somebody else holds (the rule the modulus registry follows for its PRIME flag).
-    for (size_t i = 0; i < r.curves.size(); ++i) {
-      const curve_record& o = r.curves[i];
-      if (!memcmp(o.G.F.p, G.F.p, 32) && u_eq(o.a, A) && u_eq(o.b, B) && !memcmp(o.G.gx, G.gx, 32) && !memcmp(o.G.gy, G.gy, 32) &&
-          o.has_order == rec.has_order && (!rec.has_order || u_eq(o.n, N))) { *curve_id = FIRST_CURVE_ID + (int)i; return ECSIMD_HIP_OK; }
-    }
+    { const int id = find(); if (id >= 0) { *curve_id = id; return ECSIMD_HIP_OK; } }                 // (another thread registered the same curve meanwhile)
     if (r.curves.size() >= (size_t)MAX_CURVES) return ECSIMD_HIP_ERR_BAD_ARG;
-    rec.prime_order = rec.has_order && (N.l[3] >> 63) != 0 && u_hasse(N, P) && u_probable_prime(N);   // (a new record only: ~0.1 s of host arithmetic)
     r.curves.push_back(rec);
     *curve_id = FIRST_CURVE_ID + (int)r.curves.size() - 1;
     return ECSIMD_HIP_OK;
@@ -759,7 +800,7 @@ int ecsimd_hip_curve_capabilities(int curve, int* caps) {
   const int all = ECSIMD_HIP_CURVE_HAS_ORDER | ECSIMD_HIP_CURVE_COMB | ECSIMD_HIP_CURVE_ECDSA | ECSIMD_HIP_CURVE_WINDOW_VARIABLE_BASE;
   if (curve == ECSIMD_HIP_P256 || curve == ECSIMD_HIP_SECP256K1) { *caps = all; return ECSIMD_HIP_OK; }
   curve_record rec; if (!lookup_curve_record(curve, &rec)) return ECSIMD_HIP_ERR_BAD_ARG;
-  const bool comb = rec.has_order && (rec.n.l[3] >> 63) != 0;
+  const bool comb = rec.has_order && (rec.n.l[3] >> 63) != 0 && !rec.order_wrong;
   *caps = (rec.has_order ? ECSIMD_HIP_CURVE_HAS_ORDER : 0) | (comb ? ECSIMD_HIP_CURVE_COMB : 0) | (rec.has_order && rec.ecdsa_ok ? ECSIMD_HIP_CURVE_ECDSA : 0) |
           (comb && rec.prime_order ? ECSIMD_HIP_CURVE_WINDOW_VARIABLE_BASE : 0);
   return ECSIMD_HIP_OK;
@@ -1194,8 +1235,9 @@ int double_scalar_mult_impl(ecsimd_hip_ctx* ctx, int curve, const uint64_t* u1, 
 }  // namespace
 
 // ---- u1 G + u2 Q, ECDSA verification and signing on a curve registered at run time: with the group order (n >= 2^255) u1 G from the generator's comb
-// (k_gcomb.hip) and u2 Q from the lane's own window table (k_gvarwin.hip: verification's scalars are public); without it the reference's ladder twice, the
-// scalars kept clear of its three degenerate values (k_gc_ladder_safe_scalars); one shared inversion per product, a batched affine addition.
+// (k_gcomb.hip) and u2 Q from the lane's own window table (k_gvarwin.hip: verification's scalars are public); a ladder pass (gc_safe_mult) stands in for u2 Q where n is not a
+// checked prime order, and for u1 G where the comb's table does not exist yet and a stream capture forbids building it -- ECDSA asks n >= 2^255 -- the
+// scalars kept clear of its degenerate values (three, as n >= 2^255 is asked at registration: k_gc_ladder_safe_scalars); one shared inversion per product, a batched affine addition.
 namespace {
 constexpr size_t GC_CHUNK = (size_t)1 << 22;
 constexpr size_t GC_BIG_TABLE_WORTH_IT = (size_t)1 << 20;          // u1 G + u2 Q on a registered curve: batches from here on build the 20-bit comb (0.3 s, 436 MB) on first use
@@ -1215,7 +1257,7 @@ gc_layout gc_plan(uint64_t* base, size_t n, bool win = false) {
 // The comb of a registered curve (k_gcomb.hip): 64 windows x 8 odd multiples (2d + 1) 16^w G, then k* G and the record {k*, 0} (k_affine.inc comb_special's
 // layout).  Needs the order (the recoding works modulo n) with n >= 2^255 (k mod n by one subtraction).  Every entry comes from the reference's ladder on this
 // curve -- whose degenerate scalars the entries' multipliers must not be (checked; k* by way of n - k* if it is one) -- through the shared inversion.
-bool gc_comb_possible(const curve_record& rec) { return rec.has_order && (rec.n.l[3] >> 63) != 0; }
+bool gc_comb_possible(const curve_record& rec) { return rec.has_order && (rec.n.l[3] >> 63) != 0 && !rec.order_wrong; }
 bool gc_window_possible(const curve_record& rec) { return gc_comb_possible(rec) && rec.prime_order; }    // a variable base: every point has order n (curve_record)
 // bits = 4: that table (summed from the top); bits = 7 / 5 / 20: the signed comb's 37 windows x 64 / the constant-time comb's 52 windows x 16 / the device-memory
 // comb's 13 windows x 2^19 (436 MB; 1.3 GB of temporary memory and 6.8 M ladder passes, ~0.3 s, at its build) odd multiples (2d + 1) 2^(bits w) G (summed from
@@ -1223,7 +1265,7 @@ bool gc_window_possible(const curve_record& rec) { return gc_comb_possible(rec) 
 int ensure_gc_comb(ecsimd_hip_ctx* ctx, int curve, const curve_record& rec, const uint32_t** out, int bits = 4) {
   auto slot = [bits](ecsimd_hip_ctx::gcomb_entry& t) -> uint32_t*& { return bits == 4 ? t.table : bits == 7 ? t.table7 : bits == 20 ? t.table20 : t.table5; };
   for (auto& t : ctx->gcomb) if (t.curve == curve && slot(t)) { *out = slot(t); return ECSIMD_HIP_OK; }
-  if (!gc_comb_possible(rec)) return bad(ctx, "the windowed algorithms on a registered curve need its group order n, n >= 2^255");
+  if (!gc_comb_possible(rec)) return bad(ctx, "the windowed algorithms on a registered curve need its group order n, n >= 2^255 (and n G = O where n is a prime in p's Hasse interval)");
   if (capturing(ctx)) return bad(ctx, "a window table would have to be built during stream capture: run this call once before capturing");
   static_assert(launch::GCOMB_WINDOWS == 64 && launch::GCOMB_ENTRIES == 8 && launch::GCOMB7_WINDOWS == 37 && launch::GCOMB7_ENTRIES == 64 && launch::GCOMB5_WINDOWS == 52 &&
                 launch::GCOMB5_ENTRIES == 16 && launch::GCOMB20_WINDOWS == 13 && launch::GCOMB20_ENTRIES == 1 << 19, "plan_comb: ceil(256 / bits) windows x 2^(bits - 1) entries");
@@ -1294,7 +1336,7 @@ int run_gcomb(ecsimd_hip_ctx* ctx, int curve, const uint64_t* k, uint64_t* ox, u
   if (!(flags & ECSIMD_HIP_OUT_AFFINE)) return bad(ctx, "ALG_WINDOWED needs OUT_AFFINE");
   if (ctx->ref_square || (flags & (ECSIMD_HIP_REF_SQUARE_COMPAT | ECSIMD_HIP_LADDER_RADIX32))) return bad(ctx, "ALG_WINDOWED is not the reference's algorithm: no ECSIMD_HIP_REF_SQUARE_COMPAT / LADDER_RADIX32 form");
   curve_record rec; if (!lookup_curve_record(curve, &rec)) return bad(ctx, "unknown curve id");
-  if (n == 0) return gc_comb_possible(rec) ? ECSIMD_HIP_OK : bad(ctx, "the windowed algorithms on a registered curve need its group order n, n >= 2^255");
+  if (n == 0) return gc_comb_possible(rec) ? ECSIMD_HIP_OK : bad(ctx, "the windowed algorithms on a registered curve need its group order n, n >= 2^255 (and n G = O where n is a prime in p's Hasse interval)");
   if (n > (size_t)0x7fffffff * BLOCK) return bad(ctx, "batch too large");
   (void)hipSetDevice(ctx->device);
   const uint32_t* table = nullptr;
@@ -1319,7 +1361,7 @@ int run_gvarwin(ecsimd_hip_ctx* ctx, int curve, const uint64_t* k, int k_stride,
   if (ctx->ref_square || (flags & ECSIMD_HIP_REF_SQUARE_COMPAT)) return bad(ctx, "ALG_WINDOWED is not the reference's algorithm: no ECSIMD_HIP_REF_SQUARE_COMPAT form");
   if (flags & ECSIMD_HIP_LADDER_RADIX32) return bad(ctx, "LADDER_RADIX32 selects a ladder loop: not with ALG_WINDOWED");
   curve_record rec; if (!lookup_curve_record(curve, &rec)) return bad(ctx, "unknown curve id");
-  if (!gc_comb_possible(rec)) return bad(ctx, "the windowed algorithms on a registered curve need its group order n, n >= 2^255");
+  if (!gc_comb_possible(rec)) return bad(ctx, "the windowed algorithms on a registered curve need its group order n, n >= 2^255 (and n G = O where n is a prime in p's Hasse interval)");
   if (!gc_window_possible(rec)) return bad(ctx, "ALG_WINDOWED on a variable base needs a group of prime order: n is not a prime in p's Hasse interval (the ladder has no such condition)");
   if (n == 0) return ECSIMD_HIP_OK;
   hipError_t e = hipSetDevice(ctx->device);
@@ -1363,7 +1405,8 @@ int gc_small_base(ecsimd_hip_ctx* ctx, int curve, const uint64_t* k, uint64_t* o
 int gc_require_ecdsa(ecsimd_hip_ctx* ctx, int curve, curve_record* rec) {
   if (!lookup_curve_record(curve, rec)) return bad(ctx, "unknown curve id");
   if (!rec->has_order) return bad(ctx, "this curve was registered without its group order n");
-  if (!rec->ecdsa_ok) return bad(ctx, "ECDSA on a registered curve needs p < 2n and n - u a good ladder scalar for the ladder's three degenerate u");
+  if (rec->order_wrong) return bad(ctx, "ECDSA on a registered curve needs its group order n, n >= 2^255: this n is a prime in p's Hasse interval and n G != O");
+  if (!rec->ecdsa_ok) return bad(ctx, "ECDSA on a registered curve needs an order n >= 2^255 (the ladder's further degenerate scalars below it are not worked around), p < 2n, and n - u a good ladder scalar for the three degenerate u");
   if (ctx->ref_square) return bad(ctx, "not the reference's algorithm: no ECSIMD_HIP_REF_SQUARE_COMPAT form");
   return ECSIMD_HIP_OK;
 }
@@ -1542,7 +1585,7 @@ int ecsimd_hip_ecdsa_sign(ecsimd_hip_ctx* ctx, int curve, const uint64_t* e, con
   REQUIRE_CTX(); REQUIRE_PTR(e); REQUIRE_PTR(d); REQUIRE_PTR(k); REQUIRE_PTR(r); REQUIRE_PTR(s_);
   if (!ok && n) return bad(ctx, "ok is null");
   if (curve >= ECSIMD_HIP_FIRST_REGISTERED_CURVE) {
-    // signing on a registered curve: k G from the constant-time comb of its generator (k_gcomb.hip; n < 2^255: through the reference's ladder, constant-time as it
+    // signing on a registered curve: k G from the constant-time comb of its generator (k_gcomb.hip; an id without a comb: through the reference's ladder, constant-time as it
     // is -- tests/test_constant_time_isa.py holds both to the ISA), x by the select-only shared inversion, then the scalar-field kernel with the record's order
     curve_record rec; int rc = gc_require_ecdsa(ctx, curve, &rec); if (rc != ECSIMD_HIP_OK) return rc;
     if (overlaps(r, e) || overlaps(r, d) || overlaps(r, k) || overlaps(s_, e) || overlaps(s_, d) || overlaps(s_, k) || overlaps(r, s_)) return bad(ctx, "r and s must not alias an input or each other");
@@ -1702,8 +1745,9 @@ int nonce_lookup(ecsimd_hip_ctx* ctx, int curve, nonce_plan* out) {
   u256 n;
   if (curve >= ECSIMD_HIP_FIRST_REGISTERED_CURVE) {
     curve_record rec; if (!lookup_curve_record(curve, &rec)) return bad(ctx, "unknown curve id");
-    if (!rec.has_order || !rec.ecdsa_ok) return bad(ctx, "RFC 6979 nonces need a curve registered with its group order n and the ECDSA capability");
+    if (!rec.has_order) return bad(ctx, "RFC 6979 nonces need a curve registered with its group order n and the ECDSA capability");
     if (!gc_comb_possible(rec)) return bad(ctx, "RFC 6979 nonces are supported where qlen = 256: this curve's order is below 2^255");
+    if (!rec.ecdsa_ok) return bad(ctx, "RFC 6979 nonces need a curve registered with its group order n and the ECDSA capability");
     n = rec.n;
   } else {
     REQUIRE_CURVE();

@@ -163,10 +163,11 @@ __global__ void __launch_bounds__(BLOCK) k_gc_x_mod_n_equals(gmod N, const uint6
   g_cond_sub(v, 0, N);
   ok[i] = (uint8_t)(finite[i] != 0 && fe_eq(v, LD(r)));
 }
-// The reference's ladder (curve_group.h:189-218 as written) returns a meaningless point at three scalars: n - 1, 2^256 - n - 1 and 2^256 - n (the Joye ladder
+// The reference's ladder (curve_group.h:189-218 as written) returns a meaningless point, for an order n >= 2^255, at three scalars: n - 1, 2^256 - n - 1 and 2^256 - n (the Joye ladder
 // keeps R0 + R1 = 2^i P and meets n P = infinity inside a formula).  ECDSA on a registered curve multiplies through that ladder, so a
 // scalar u < n that IS one of them is replaced by n - u here and the product's y negated afterwards (neg[i] = 1): u P = -((n - u) P).  The host has checked
-// at registration that n - u is not degenerate in turn.  Selects only: the scalar may be a nonce.
+// at registration that n - u is not degenerate in turn, and that n >= 2^255: below it the list is longer (u | 1 = 2^j mod n, bitlen(n) <= j <= 256) and the
+// curve gets no ECDSA.  Selects only: the scalar may be a nonce.
 __global__ void __launch_bounds__(BLOCK) k_gc_ladder_safe_scalars(gmod N, const uint64_t* __restrict__ u, uint64_t* __restrict__ adj, uint8_t* __restrict__ neg, size_t n) {
   GID; const fe k = LD(u), order = g_words(N.p);
   fe zero, one, nm1, c, cm1, alt;

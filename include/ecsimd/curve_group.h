@@ -74,6 +74,7 @@ struct curve_group {
 
   // ---- extensions (not in the reference): affine-level entry points over the faster algorithms of the C ABI.
   // Same points as to_affine() of the ladder's result for every scalar where the ladder is non-degenerate.
+  // (The ladder fallback returns the LADDER's point, not k P, at the ladder's degenerate scalars: n - 1 and k | 1 = 2^j mod n for bitlen(n) <= j <= 256.)
   // k[i] * P[i], P affine classical -> affine classical.  windowed: per-element tables of 8 multiples of P + signed 4-bit
   // windows (ECSIMD_HIP_ALG_WINDOWED); otherwise the reference ladder followed by one simultaneous inversion.  A curve registered at run time has the
   // tables when it names a prime order N >= 2^255 (ECSIMD_HIP_CURVE_WINDOW_VARIABLE_BASE); without it the same points come from the ladder.
@@ -95,7 +96,7 @@ struct curve_group {
   // (one that names its order N) has the signed 7-bit table of its generator in LDS instead (36 mixed additions).
   static WCP scalar_mult_base_affine(WBN const& x) {
     WCP r{WBN::uninitialized(x.size()), WBN::uninitialized(x.size())};
-    const int alg = curve_id() >= ECSIMD_HIP_FIRST_REGISTERED_CURVE ? ECSIMD_HIP_ALG_WINDOWED_SIGNED : ECSIMD_HIP_ALG_WINDOWED_BIG;
+    const int alg = !can(ECSIMD_HIP_CURVE_COMB) ? 0 : curve_id() >= ECSIMD_HIP_FIRST_REGISTERED_CURVE ? ECSIMD_HIP_ALG_WINDOWED_SIGNED : ECSIMD_HIP_ALG_WINDOWED_BIG;   // (no order, or n < 2^255: no table, the ladder)
     hip::check(ecsimd_hip_scalar_mult_base(hip::context(), curve_id(), x.data(), r.x().data(), r.y().data(), nullptr, x.size(),
                                            ECSIMD_HIP_OUT_AFFINE | alg), "ecsimd_hip_scalar_mult_base");
     return r;
@@ -114,8 +115,9 @@ struct curve_group {
   // window read, the wanted one kept under lane masks, no address or branch formed from the scalar; 6.7 x the ladder on G.  Affine classical.
   static WCP scalar_mult_base_affine_secret(WBN const& x) {
     WCP r{WBN::uninitialized(x.size()), WBN::uninitialized(x.size())};
+    const int alg = can(ECSIMD_HIP_CURVE_COMB) ? (ECSIMD_HIP_ALG_WINDOWED | ECSIMD_HIP_ALG_CONSTANT_TIME) : 0;      // (without the comb: the ladder, constant-time as it is; its point, not k G, at its degenerate scalars)
     hip::check(ecsimd_hip_scalar_mult_base(hip::context(), curve_id(), x.data(), r.x().data(), r.y().data(), nullptr, x.size(),
-                                           ECSIMD_HIP_OUT_AFFINE | ECSIMD_HIP_ALG_WINDOWED | ECSIMD_HIP_ALG_CONSTANT_TIME), "ecsimd_hip_scalar_mult_base");
+                                           ECSIMD_HIP_OUT_AFFINE | alg), "ecsimd_hip_scalar_mult_base");
     return r;
   }
   // u1[i] * G + u2[i] * Q[i] (the ECDSA-verification shape), affine classical; finite[i] is false where the sum

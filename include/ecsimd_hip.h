@@ -193,11 +193,13 @@ int ecsimd_hip_register_modulus(const uint64_t p[4], int flags, int* field_id);
  * secret scalars like the built-in curves' form (1.3 x the ladder).  The group must have prime order (cofactor 1: every valid point then has order n, which
  * is what "no addition inside the loop is exceptional" rests on) -- CHECKED at registration (n in p's Hasse interval, Miller-Rabin: ecsimd_hip_curve_capabilities);
  * an id without it keeps the ladder for a variable base (BAD_ARG for the flag, ladder passes inside double_scalar_mult / ecdsa_verify).
- * Either returns the true k P for every k, (0, 0) for k = 0 mod n.  The other ALG_* shapes exist for the two built-in curves only), by affine_add, sec1_encode, sec1_decode and -- when n was given, p < 2n, and
+ * Either returns the true k P for every k, (0, 0) for k = 0 mod n.  The other ALG_* shapes exist for the two built-in curves only), by affine_add, sec1_encode, sec1_decode and -- when n was given, n >= 2^255, p < 2n, and
  * n - u is a good ladder scalar for u in {n - 1, 2^256 - n - 1, 2^256 - n} (every prime-order curve of this size) -- by double_scalar_mult,
  * ecdsa_verify_rx, ecdsa_verify, ecdsa_recover, ecdsa_sign, ecdsa_sign_recoverable: u1 G comes from the generator's signed comb -- from the 20-bit comb once that exists or the batch reaches 2^20 -- (sign: k G from the constant-time 5-bit comb), u2 Q (public) from the
- * lane's window table -- correct for every scalar in [0, n); ecdsa_sign's scratch is zeroed like the built-in curves'.  (n < 2^255: passes of the ladder
- * instead, the scalars kept clear of its three degenerate values: u -> n - u and the result negated.)  Like the built-in curves', a call of
+ * lane's window table -- correct for every scalar in [0, n); ecdsa_sign's scratch is zeroed like the built-in curves'.  (Where an id has no comb or window table a
+ * product is a pass of the ladder, the scalar kept clear of its three degenerate values: u -> n - u and the result negated.  n < 2^255: NO ECDSA -- BAD_ARG from
+ * all of these.  There the ladder is wrong wherever u | 1 = 2^j mod n for a j from n's bit length to 256, not at three scalars: 2^192 - n and 2^192 - n - 1 on
+ * P-192, hundreds on a 13-bit order; tools/ladder_degenerate_model.py)  Like the built-in curves', a call of
  * scalar_mult_base(OUT_AFFINE) without an algorithm flag on up to 2^16 lanes takes that comb (constant time) and returns the ladder's affine bits, its
  * three degenerate scalars included.  And, as a FIELD id, by every element-wise field entry point.  Same level-J parity as the built-in curves: X, Y, Z are
  * the bits the reference instantiated with this Curve returns.  The ladder's 254 iterations run on nine signed 29-bit limbs with the dense p in SGPRs
@@ -205,9 +207,13 @@ int ecsimd_hip_register_modulus(const uint64_t p[4], int flags, int* field_id);
  * Process-wide, thread-safe, ids live as long as the process. */
 enum { ECSIMD_HIP_CURVE_GENERIC_KERNELS = 1 };
 /* What an id can do beyond the reference's layers (host only, no context): caps = a mask of
- *   HAS_ORDER (registered with n), COMB (ALG_WINDOWED [| ALG_CONSTANT_TIME] on its generator: n >= 2^255), ECDSA (double_scalar_mult, ecdsa_*: p < 2n and the
- *   ladder's degenerate scalars have good images), WINDOW_VARIABLE_BASE (ALG_WINDOWED [| ALG_CONSTANT_TIME] on a variable base: n >= 2^255, n lies in p's Hasse
- *   interval -- so the group HAS order n -- and n passes Miller-Rabin: every point but infinity has order n).  The two built-in ids report all four. */
+ *   HAS_ORDER (registered with n), COMB (ALG_WINDOWED [| ALG_CONSTANT_TIME] on its generator: n >= 2^255), ECDSA (double_scalar_mult, ecdsa_*: n >= 2^255, p < 2n and the
+ *   ladder's three degenerate scalars have good images), WINDOW_VARIABLE_BASE (ALG_WINDOWED [| ALG_CONSTANT_TIME] on a variable base: n >= 2^255, n lies in p's Hasse
+ *   interval -- so the group HAS order n -- and n passes Miller-Rabin: every point but infinity has order n).  The two built-in ids report all four.
+ *   An n that passes those two tests and is NOT the generator's order (n G != O, checked once on the host: a neighbouring prime, a typo) gets HAS_ORDER
+ *   alone: no COMB, no WINDOW_VARIABLE_BASE, no ECDSA.  A composite n, or one outside the Hasse interval, is taken on the caller's word for the
+ *   generator's comb as before.  ECDSA also on an id whose n >= 2^255 fails the prime-order test: u2 Q then runs on the ladder, whose three-scalar
+ *   work-around is complete for n >= 2^255. */
 enum { ECSIMD_HIP_CURVE_HAS_ORDER = 1, ECSIMD_HIP_CURVE_COMB = 2, ECSIMD_HIP_CURVE_ECDSA = 4, ECSIMD_HIP_CURVE_WINDOW_VARIABLE_BASE = 8 };
 int ecsimd_hip_curve_capabilities(int curve, int* caps);
 int ecsimd_hip_register_curve(const uint64_t p[4], const uint64_t a[4], const uint64_t b[4], const uint64_t gx[4], const uint64_t gy[4],

@@ -476,6 +476,39 @@ TEST(Curves, EcdsaAndSec1OnARegisteredCurve) {
   EXPECT_TRUE(refused);
 }
 
+// A registered curve WITHOUT the generator's comb -- no order at all, or an order below 2^255 (NIST P-192, FIPS 186-4 D.1.2.1) -- keeps the fixed-base pair:
+// scalar_mult_base_affine and scalar_mult_base_affine_secret serve the ladder's points instead of asking for a table the id cannot have (BAD_ARG before).
+// An order below 2^255 also means no ECDSA: the ladder that would serve it is wrong at more scalars than the three worked around.
+struct curve_nist_p192_n {
+  using bn_type = bignum_256;
+  using P  = bn256_constant<0x0000000000000000ull, 0xffffffffffffffffull, 0xfffffffffffffffeull, 0xffffffffffffffffull>;
+  using A  = bn256_constant<0x0000000000000000ull, 0xffffffffffffffffull, 0xfffffffffffffffeull, 0xfffffffffffffffcull>;
+  using B  = bn256_constant<0x0000000000000000ull, 0x64210519e59c80e7ull, 0x0fa7e9ab72243049ull, 0xfeb8deecc146b9b1ull>;
+  using Gx = bn256_constant<0x0000000000000000ull, 0x188da80eb03090f6ull, 0x7cbf20eb43a18800ull, 0xf4ff0afd82ff1012ull>;
+  using Gy = bn256_constant<0x0000000000000000ull, 0x07192b95ffc8da78ull, 0x631011ed6b24cdd5ull, 0x73f977a11e794811ull>;
+  using N  = bn256_constant<0x0000000000000000ull, 0xffffffffffffffffull, 0xffffffff99def836ull, 0x146bc9b1b4d22831ull>;
+};
+template <class K> static void fixed_base_pair_equals_the_ladder() {
+  using KG = curve_group<K>;
+  EXPECT_TRUE(KG::curve_id() >= ECSIMD_HIP_FIRST_REGISTERED_CURVE && !KG::can(ECSIMD_HIP_CURVE_COMB));
+  const W256 ks(300, [](size_t i, size_t) { bignum_256 b; b.limbs = {0x9e3779b97f4a7c15ull * (i + 1), i * 77, ~i, i < 150 ? 0ull : 0x0123456789abcdefull ^ (i << 20)}; return b; });
+  const auto ladder = KG::scalar_mult(ks, KG::WJG(300)).to_affine();
+  const auto plain = KG::scalar_mult_base_affine(ks), secret = KG::scalar_mult_base_affine_secret(ks);
+  EXPECT_TRUE(all(plain.x() == ladder.x()) && all(plain.y() == ladder.y()));
+  EXPECT_TRUE(all(secret.x() == ladder.x()) && all(secret.y() == ladder.y()));
+}
+TEST(Curves, FixedBasePairOnACurveWithoutTheComb) {
+  fixed_base_pair_equals_the_ladder<curve_brainpoolp256r1>();                                     // no order
+  fixed_base_pair_equals_the_ladder<curve_nist_p192_n>();                                         // an order below 2^255
+  using KG = curve_group<curve_nist_p192_n>;
+  EXPECT_TRUE(KG::can(ECSIMD_HIP_CURVE_HAS_ORDER) && !KG::can(ECSIMD_HIP_CURVE_ECDSA) && !KG::can(ECSIMD_HIP_CURVE_WINDOW_VARIABLE_BASE));
+  const auto five = "0000000000000000000000000000000000000000000000000000000000000005"_hex;
+  bool refused = false; hip::mask ok;
+  try { (void)KG::ecdsa_sign(splat<W256>(five), splat<W256>(five), splat<W256>(five), ok); }
+  catch (std::exception const&) { refused = true; }
+  EXPECT_TRUE(refused);
+}
+
 // The curve structs' constants equal the engine's own table (ecsimd_hip_get_constant: 0 p, 1 a, 2 b, 3 Gx, 4 Gy) and
 // the hexadecimal literals of the standards documents.
 template <class K> static void constants_match_engine() {
