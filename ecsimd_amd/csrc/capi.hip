@@ -1818,6 +1818,64 @@ int ecsimd_hip_ecdsa_sign_deterministic(ecsimd_hip_ctx* ctx, int curve, const ui
   }
   return ECSIMD_HIP_OK; }
 
+// ---- Keccak-256, Ethereum addresses and address recovery (k_keccak.hip); public data throughout
+int ecsimd_hip_keccak256(ecsimd_hip_ctx* ctx, const uint8_t* msg, size_t msg_bytes, size_t stride_bytes, const uint32_t* lens, uint64_t* e, size_t n) {
+  REQUIRE_CTX(); REQUIRE_PTR(e);
+  if (lens) msg_bytes = 0;                                                        // (ignored: every lane has its own length)
+  if (!msg && n && (msg_bytes || (lens && stride_bytes))) return bad(ctx, "msg is null");
+  if (lens && (reinterpret_cast<uintptr_t>(lens) & 3u)) return bad(ctx, "lens is not 4-byte aligned");
+  if (stride_bytes < msg_bytes) return bad(ctx, "keccak256: stride_bytes is smaller than msg_bytes");
+  if (msg_bytes > ((size_t)1 << 40)) return bad(ctx, "keccak256: message too long");
+  RUN(launch::keccak256(s, msg, msg_bytes, stride_bytes, lens, e, n)); }
+
+int ecsimd_hip_eth_address(ecsimd_hip_ctx* ctx, const uint64_t* qx, const uint64_t* qy, uint8_t* addr, size_t n) {
+  REQUIRE_CTX(); REQUIRE_PTR(qx); REQUIRE_PTR(qy);
+  if (!addr && n) return bad(ctx, "addr is null");
+  if (reinterpret_cast<uintptr_t>(addr) & 3u) return bad(ctx, "addr is not 4-byte aligned");
+  RUN(launch::eth_address(s, qx, qy, nullptr, addr, n)); }
+
+// Per chunk: k_eth_recovery_id writes the recovery id the lift is to see (0xff where v, or the low-s rule, refuses the lane: the lift refuses every id above 3),
+// then ecdsa_recover's chain as it is -- recover_lift, ecdsa_recover_scalars, double_scalar_mult_impl with the validity byte -- into the caller's qx / qy or
+// into the workspace, then k_eth_address with the call's ok.  Behind the window loops' part of the workspace: u1, u2, R (four arrays), the key (two), two byte arrays.
+int ecsimd_hip_eth_recover(ecsimd_hip_ctx* ctx, const uint64_t* e, const uint64_t* r, const uint64_t* s_, const uint8_t* v,
+                           uint8_t* addr, uint64_t* qx, uint64_t* qy, uint8_t* ok, size_t n, int flags) {
+  REQUIRE_CTX(); REQUIRE_PTR(e); REQUIRE_PTR(r); REQUIRE_PTR(s_);
+  if ((!v || !ok || !addr) && n) return bad(ctx, "v, addr or ok is null");
+  if (reinterpret_cast<uintptr_t>(addr) & 3u) return bad(ctx, "addr is not 4-byte aligned");
+  if ((qx == nullptr) != (qy == nullptr)) return bad(ctx, "eth_recover: qx and qy are both given or both NULL");
+  if (qx && (!aligned16(qx) || !aligned16(qy))) return bad(ctx, "qx or qy is not 16-byte aligned");
+  if (flags & ~ECSIMD_HIP_ETH_REQUIRE_LOW_S) return bad(ctx, "eth_recover: unknown flag");
+  if (ctx->ref_square) return bad(ctx, "eth_recover is not the reference's algorithm: no ECSIMD_HIP_REF_SQUARE_COMPAT form");
+  if (n == 0) return ECSIMD_HIP_OK;
+  if (n > (size_t)0x7fffffff * BLOCK) return bad(ctx, "batch too large");
+  (void)hipSetDevice(ctx->device);
+  const int curve = ECSIMD_HIP_SECP256K1;
+  gmod N; if (!lookup_modulus(ECSIMD_HIP_FIELD_SECP256K1_ORDER, &N)) return bad(ctx, "group order missing from the registry");
+  launch::words8 order, half;
+  for (int i = 0; i < 8; ++i) order.w[i] = N.p[i];
+  for (int i = 0; i < 8; ++i) half.w[i] = (order.w[i] >> 1) | (i < 7 ? order.w[i + 1] << 31 : 0u);
+  const size_t chunk = n < VARWIN_CHUNK ? n : VARWIN_CHUNK, flag_bytes = ((chunk + 15) / 16) * 16;
+  const size_t front = verify_sizes(chunk).front, extra = 6 * chunk * 32 + 2 * flag_bytes;
+  // sizes the workspace (and builds the table) first, so that the pointers taken below stay valid
+  int rc = ensure_window_table(ctx, curve, (ctx->window16_table[curve] != nullptr || n >= BIG_TABLE_WORTH_IT) ? launch::BIG_WINDOW_BITS : SIGNED_WBITS);
+  if (rc == ECSIMD_HIP_OK) rc = ensure_workspace(ctx, front + extra);
+  if (rc != ECSIMD_HIP_OK) return rc;
+  uint64_t* u1 = ctx->workspace + front / 8; uint64_t* u2 = u1 + 4 * chunk; uint64_t* px = u2 + 4 * chunk; uint64_t* py = px + 4 * chunk;
+  uint64_t* kx = py + 4 * chunk; uint64_t* ky = kx + 4 * chunk;
+  uint8_t* valid = reinterpret_cast<uint8_t*>(ky + 4 * chunk); uint8_t* id = valid + flag_bytes;
+  for (size_t first = 0; first < n; first += chunk) {
+    const size_t m = n - first < chunk ? n - first : chunk;
+    uint64_t* ox = qx ? qx + 4 * first : kx; uint64_t* oy = qy ? qy + 4 * first : ky;
+    launch::eth_recovery_id(ctx->stream, half, v + first, s_ + 4 * first, id, m, (flags & ECSIMD_HIP_ETH_REQUIRE_LOW_S) != 0);
+    launch::recover_lift(ctx->stream, curve, order, r + 4 * first, id, px, py, valid, m);
+    launch::ecdsa_recover_scalars(ctx->stream, N, e + 4 * first, r + 4 * first, s_ + 4 * first, u1, u2, valid, m);
+    rc = double_scalar_mult_impl(ctx, curve, u1, u2, px, py, ox, oy, ok + first, m, extra, valid);
+    if (rc != ECSIMD_HIP_OK) return rc;
+    launch::eth_address(ctx->stream, ox, oy, ok + first, addr + 20 * first, m);
+  }
+  hipError_t err = hipGetLastError();
+  return err == hipSuccess ? ECSIMD_HIP_OK : fail(ctx, err, "eth_recover launch"); }
+
 // ---- BIP-340 Schnorr signatures on secp256k1 (k_schnorr.hip)
 namespace {
 int schnorr_common(ecsimd_hip_ctx* ctx, const char* what, const uint8_t* msg, size_t msg_bytes, size_t stride_bytes, size_t n, gmod* N, launch::words8* order) {

@@ -117,6 +117,14 @@ void sign_recovery_id(hipStream_t, const words8& order, const uint64_t* x, const
 void sha256(hipStream_t, const uint8_t* msg, size_t msg_bytes, size_t stride_bytes, uint64_t* e, size_t n);
 void rfc6979_nonce(hipStream_t, const words8& order, const uint64_t* e, const uint64_t* d, uint64_t* k, void* state, uint8_t* retry, uint8_t* ok, size_t n, unsigned cap);
 
+// k_keccak.hip: Keccak-256 (the original padding: 0x01 ... 0x80, rate 136) of n messages, one per lane, and what Ethereum makes of it.  PUBLIC data only.
+// keccak256: message i at msg + i * stride_bytes, lens[i] bytes of it where lens != NULL (lens[i] <= stride_bytes), else msg_bytes; e = the digests as 256-bit
+// integers (sha256's convention).  eth_address: the low 20 bytes of Keccak-256(be32(qx) || be32(qy)) at addr + 20 i (addr 4-byte aligned), 20 zero bytes where
+// ok != NULL and ok[i] = 0.  eth_recovery_id: v in {0, 1, 27, 28} -> 0 / 1, anything else (and, with low_s, s > half = n / 2) -> 0xff, which recover_lift refuses.
+void keccak256(hipStream_t, const uint8_t* msg, size_t msg_bytes, size_t stride_bytes, const uint32_t* lens, uint64_t* e, size_t n);
+void eth_address(hipStream_t, const uint64_t* qx, const uint64_t* qy, const uint8_t* ok, uint8_t* addr, size_t n);
+void eth_recovery_id(hipStream_t, const words8& half, const uint8_t* v, const uint64_t* s, uint8_t* out, size_t n, bool low_s);
+
 // k_schnorr.hip: BIP-340 on secp256k1.  Verification (public data): schnorr_verify_front writes u1 = s, u2 = n - e mod n with e = the challenge hash of
 // (r, px, message), (x, y) = the even-y lift of px (G where there is none) and valid = lift && r < p && s < n (u1 = u2 = 0 where not); schnorr_accept:
 // ok = finite && x == r && y even for the sum (x, y).  Signing (SECRET d, aux, k0 and both affine products: selects only): schnorr_nonce writes k0 from

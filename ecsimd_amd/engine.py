@@ -11,7 +11,7 @@ import os
 
 import numpy as np
 
-from .flags import ECDSA_LOW_S
+from .flags import ECDSA_LOW_S, ETH_REQUIRE_LOW_S
 
 P256, SECP256K1 = 0, 1
 CURVES = {"p256": P256, "secp256k1": SECP256K1}
@@ -455,6 +455,39 @@ class Engine:
         keep, mp, length, stride = self._messages(msgs, n)
         self._call("schnorr_sign", self._ptr(d), mp, length, stride, self._ptr(aux), self._ptr(px), self._ptr(r), self._ptr(s), self._ptr(ok, 0), C.c_size_t(n))
         return px, r, s, ok
+
+    def keccak256(self, msgs, lens=None):
+        """ecsimd_hip_keccak256: Keccak-256 (Ethereum's: pad byte 0x01, not SHA-3) of the rows of `msgs` (2-D uint8 device tensor, rows may be strided) as (n, 4)
+        integers, ready to be the `e` of the ECDSA calls.  lens (optional int32 / uint32 device tensor of n lengths, each <= the row length): lane i hashes the
+        first lens[i] bytes of its row."""
+        n = int(msgs.shape[0]); e = self.empty(n)
+        keep, mp, length, stride = self._messages(msgs, n)
+        lp = C.c_void_p(0)
+        if lens is not None:
+            torch = self.torch
+            assert lens.is_cuda and lens.device.index == self.device and lens.is_contiguous() and lens.dim() == 1, "lens: a contiguous 1-D tensor on the engine's device"
+            assert lens.dtype in (torch.int32, torch.uint32), lens.dtype
+            if int(lens.shape[0]) != n:
+                raise EcsimdHipError(f"keccak256: operands disagree on the batch length: {sorted((n, int(lens.shape[0])))}")
+            lp = C.c_void_p(lens.data_ptr())
+        self._call("keccak256", mp, length, stride, lp, self._ptr(e), C.c_size_t(n))
+        return e
+
+    def eth_address(self, qx, qy):
+        """ecsimd_hip_eth_address: (n, 20) uint8, the Ethereum address of each public key (qx, qy) -- the last 20 bytes of Keccak-256 over its 64 big-endian bytes."""
+        n = qx.shape[0]; addr = self.torch.empty((n, 20), dtype=self.torch.uint8, device=self.tdev)
+        self._call("eth_address", self._ptr(qx), self._ptr(qy), self._bytes_ptr(addr), C.c_size_t(n))
+        return addr
+
+    def eth_recover(self, e, r, s, v, require_low_s=False, want_key=False):
+        """ecsimd_hip_eth_recover: (addr, ok), or (addr, qx, qy, ok) with want_key: the sender address behind each secp256k1 signature (r, s, v) of the digest e.
+        v (uint8 tensor) is 0, 1, 27 or 28; anything else, a signature ecdsa_recover refuses and, with require_low_s, s > n / 2 give ok = 0, a zero address and a
+        zero key.  Without want_key the recovered key never leaves the context workspace."""
+        n = e.shape[0]; addr = self.torch.empty((n, 20), dtype=self.torch.uint8, device=self.tdev); ok = self.flags(n)
+        qx, qy = (self.empty(n), self.empty(n)) if want_key else (None, None)
+        self._call("eth_recover", self._ptr(e), self._ptr(r), self._ptr(s), self._ptr(v, 0), self._bytes_ptr(addr), self._ptr(qx), self._ptr(qy), self._ptr(ok, 0), C.c_size_t(n),
+                   C.c_int(ETH_REQUIRE_LOW_S if require_low_s else 0))
+        return (addr, qx, qy, ok) if want_key else (addr, ok)
 
     def fe29_raw(self, curve, op, inputs, swap=0):
         """ecsimd_hip_fe29_raw: one function of the reduced-radix layer on raw int32 limbs; `inputs` is an int32 tensor (n, NIN, 9); returns (n, NOUT, 9)."""

@@ -13,3 +13,4 @@ BASE_GENERATOR = 512          # ecsimd_hip_scalar_mult with x = y = NULL: the ba
 LADDER_RADIX32 = 256          # ladder only: the loop on 8 x 32-bit canonical words (rounds 1-3) instead of nine signed 29-bit limbs
 GROUP_NO_GATHER = 0x10000    # ecsimd_hip_group_scalar_mult only: compute without the exchange
 ECDSA_LOW_S = 1               # ecsimd_hip_ecdsa_sign_recoverable only: s > n / 2 is returned as n - s (and bit 0 of v flipped)
+ETH_REQUIRE_LOW_S = 1         # ecsimd_hip_eth_recover only: s > n / 2 is refused (EIP-2)

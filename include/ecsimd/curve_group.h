@@ -6,6 +6,7 @@
 #include <ecsimd/device_group.h>
 #include <ecsimd/curve_secp256k1.h>
 #include <ecsimd/jacobian_curve_point.h>
+#include <ecsimd/keccak256.h>
 #include <ecsimd/sha256.h>
 #include <optional>
 #include <type_traits>
@@ -208,6 +209,23 @@ struct curve_group {
     hip::check(ecsimd_hip_schnorr_sign(hip::context(), d.data(), m.data(), m.msg_bytes(), m.stride_bytes(), aux ? aux->data() : nullptr, px.data(), r.data(), s.data(), ok.data(),
                                        d.size()), "ecsimd_hip_schnorr_sign");
     return {r, s};
+  }
+  // ---- Ethereum: secp256k1 only, like the Schnorr members.  Public data only.
+  // The addresses of the public keys q: the last 20 bytes of Keccak-256 over each key's 64 big-endian bytes.  No validation: the 64 bytes are hashed as given.
+  static hip::addresses eth_address(WCP const& q) requires std::is_same_v<Curve, curve_secp256k1> {
+    hip::addresses a(q.x().size());
+    hip::check(ecsimd_hip_eth_address(hip::context(), q.x().data(), q.y().data(), a.data(), a.size()), "ecsimd_hip_eth_address");
+    return a;
+  }
+  // ecrecover: the sender address behind each signature (r, s) of the digest e (hip::keccak256 of the signing bytes), v = 0, 1, 27 or 28 in a hip::mask's storage.
+  // ok[i] is false -- and the address 20 zero bytes -- where v is anything else, where ecdsa_recover refuses the signature, and, with
+  // ECSIMD_HIP_ETH_REQUIRE_LOW_S in flags, where s > n / 2.  The recovered key stays on the device and is not returned.
+  static hip::addresses eth_recover(WBN const& e, WBN const& r, WBN const& s, hip::mask const& v, hip::mask& ok, int flags = 0) requires std::is_same_v<Curve, curve_secp256k1> {
+    same_length(r.size(), e.size(), "eth_recover"); same_length(s.size(), e.size(), "eth_recover"); same_length(v.size(), e.size(), "eth_recover");
+    hip::addresses a(e.size());
+    ok = hip::mask(e.size());
+    hip::check(ecsimd_hip_eth_recover(hip::context(), e.data(), r.data(), s.data(), v.data(), a.data(), nullptr, nullptr, ok.data(), e.size(), flags), "ecsimd_hip_eth_recover");
+    return a;
   }
   // ---- several GPUs: k[i] * P[i] for HOST arrays, sharded over a device group.  P affine classical (x, y);
   // the result is what scalar_mult(x, from_affine(P)) returns lane by lane -- Jacobian, Montgomery form -- or, with

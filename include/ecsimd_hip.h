@@ -461,6 +461,31 @@ int ecsimd_hip_schnorr_verify(ecsimd_hip_ctx*, const uint64_t* px, const uint8_t
  * used is zeroed on the stream before it returns.  r, s and px must not alias an input or each other.  Workspace: 256 B per element of a chunk. */
 int ecsimd_hip_schnorr_sign(ecsimd_hip_ctx*, const uint64_t* d, const uint8_t* msg, size_t msg_bytes, size_t stride_bytes,
                             const uint64_t* aux, uint64_t* px, uint64_t* r, uint64_t* s, uint8_t* ok, size_t n);
+/* Keccak-256 as Ethereum uses it: the original Keccak padding (pad byte 0x01, final bit 0x80, rate 136), NOT NIST's SHA-3 (pad byte 0x06).  Message i lies at
+ * msg + i * stride_bytes (device memory, any alignment: 8-byte loads where base and stride are multiples of 8, 4-byte loads where they are multiples of 4, byte
+ * loads otherwise).  lens = NULL: every message is msg_bytes long (stride_bytes >= msg_bytes; 0 is allowed, msg may then be NULL) and every branch is uniform.
+ * lens != NULL (n x u32, device memory): lane i absorbs lens[i] bytes, lens[i] <= stride_bytes (a larger value is read as stride_bytes), msg_bytes is ignored and
+ * the block loop runs per lane.  Any length, any number of blocks.  e[i] = the digest as the integer the ECDSA calls take, as ecsimd_hip_sha256 writes it: 4 x u64
+ * little-endian limbs of the digest read as a big-endian number.  PUBLIC data: the loads and the loop follow the message lengths; do not hash a secret with it.
+ * One message per lane, the 25 lanes of the state in registers, the 24 rounds unrolled.  Stream-ordered; no workspace. */
+int ecsimd_hip_keccak256(ecsimd_hip_ctx*, const uint8_t* msg, size_t msg_bytes, size_t stride_bytes, const uint32_t* lens, uint64_t* e, size_t n);
+/* Ethereum addresses of n public keys: addr[20 i .. 20 i + 19] = the last 20 bytes of Keccak-256(be32(qx[i]) || be32(qy[i])), one permutation per lane.  No
+ * validation: the call hashes the 64 bytes it is given (for the point at infinity (0, 0) that is the address of 64 zero bytes).  addr: device memory, 4-byte
+ * aligned.  PUBLIC data.  Stream-ordered; no workspace.  (The address of a SECRET key d: ecsimd_hip_scalar_mult_base with ECSIMD_HIP_ALG_WINDOWED |
+ * ECSIMD_HIP_ALG_CONSTANT_TIME | ECSIMD_HIP_OUT_AFFINE, then this call on the public result.) */
+int ecsimd_hip_eth_address(ecsimd_hip_ctx*, const uint64_t* qx, const uint64_t* qy, uint8_t* addr, size_t n);
+/* Ethereum's ecrecover over n signatures: the sender's address straight from (e, r, s, v), secp256k1 only (no curve id).  e is any 256-bit value (for a
+ * transaction: ecsimd_hip_keccak256 of its signing bytes).  v[i] must be 0, 1, 27 or 28; 27 and 28 mean 0 and 1; every other value is refused -- ecdsa_recover's
+ * 2 and 3 included: Ethereum does not accept x(R) >= n.  ok[i] = 1 iff v[i] is accepted and ecsimd_hip_ecdsa_recover with that recovery id (0 or 1) sets it;
+ * flags = ECSIMD_HIP_ETH_REQUIRE_LOW_S additionally asks s <= n / 2 (EIP-2).  addr as for ecsimd_hip_eth_address; where ok[i] = 0 it is 20 zero bytes and
+ * qx = qy = 0.  qx and qy are optional outputs (NULL, or both given): with NULL the recovered key stays in the context workspace and never reaches caller memory.
+ * Per chunk of 2^22 lanes: one kernel maps v (and the low-s rule) to a recovery id or to the value the lift refuses, then ecdsa_recover's own kernels -- the lift,
+ * the scalars modulo n, the window loops without re-validation -- then the address kernel on the affine result.  Stream-ordered, nothing is read back.  PUBLIC
+ * data only.  No ECSIMD_HIP_REF_SQUARE_COMPAT form (ERR_BAD_ARG on a context with that option).  Any n.  Workspace: double_scalar_mult's plus 194 B per element of
+ * a chunk (ecdsa_recover's 129, the key's 64, the recovery id's 1). */
+enum { ECSIMD_HIP_ETH_REQUIRE_LOW_S = 1 };
+int ecsimd_hip_eth_recover(ecsimd_hip_ctx*, const uint64_t* e, const uint64_t* r, const uint64_t* s, const uint8_t* v,
+                           uint8_t* addr, uint64_t* qx, uint64_t* qy, uint8_t* ok, size_t n, int flags);
 /* Diagnostic (r5): ONE function of the reduced-radix layer the multiplication-bound loops run on (fe29.cuh: nine signed 29-bit limbs in 32-bit words,
  * Montgomery radix 2^261, lazy carries) on RAW operands -- int32 limbs exactly as a loop holds them between two operations: element e's coordinate c, limb l at
  * in[(e * NIN + c) * 9 + l] (device memory).  What tests use to hand the device the states and operand pairs at which the interval proofs of
