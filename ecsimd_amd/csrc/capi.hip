@@ -1876,6 +1876,123 @@ int ecsimd_hip_eth_recover(ecsimd_hip_ctx* ctx, const uint64_t* e, const uint64_
   hipError_t err = hipGetLastError();
   return err == hipSuccess ? ECSIMD_HIP_OK : fail(ctx, err, "eth_recover launch"); }
 
+// ---- Bitcoin: RIPEMD-160, HASH160, double SHA-256, public-key hashes (k_btc.hip); public data throughout, no workspace
+namespace {
+int btc_hash_args(ecsimd_hip_ctx* ctx, const char* what, const uint8_t* msg, size_t msg_bytes, size_t stride_bytes, const void* out, size_t n) {
+  if (!out && n) return bad(ctx, "the output is null");
+  if (!msg && n && msg_bytes) return bad(ctx, "msg is null");
+  if (stride_bytes < msg_bytes || msg_bytes > ((size_t)1 << 40)) {
+    snprintf(ctx->err, sizeof ctx->err, "bad argument: %s: %s", what, stride_bytes < msg_bytes ? "stride_bytes is smaller than msg_bytes" : "message too long");
+    return ECSIMD_HIP_ERR_BAD_ARG;
+  }
+  return ECSIMD_HIP_OK;
+}
+}  // namespace
+
+int ecsimd_hip_ripemd160(ecsimd_hip_ctx* ctx, const uint8_t* msg, size_t msg_bytes, size_t stride_bytes, uint8_t* out20, size_t n) {
+  REQUIRE_CTX();
+  int rc = btc_hash_args(ctx, "ripemd160", msg, msg_bytes, stride_bytes, out20, n); if (rc != ECSIMD_HIP_OK) return rc;
+  if (reinterpret_cast<uintptr_t>(out20) & 3u) return bad(ctx, "out20 is not 4-byte aligned");
+  RUN(launch::ripemd160(s, msg, msg_bytes, stride_bytes, out20, n)); }
+
+int ecsimd_hip_hash160(ecsimd_hip_ctx* ctx, const uint8_t* msg, size_t msg_bytes, size_t stride_bytes, uint8_t* out20, size_t n) {
+  REQUIRE_CTX();
+  int rc = btc_hash_args(ctx, "hash160", msg, msg_bytes, stride_bytes, out20, n); if (rc != ECSIMD_HIP_OK) return rc;
+  if (reinterpret_cast<uintptr_t>(out20) & 3u) return bad(ctx, "out20 is not 4-byte aligned");
+  RUN(launch::hash160(s, msg, msg_bytes, stride_bytes, out20, n)); }
+
+int ecsimd_hip_sha256d(ecsimd_hip_ctx* ctx, const uint8_t* msg, size_t msg_bytes, size_t stride_bytes, uint64_t* e, size_t n) {
+  REQUIRE_CTX(); REQUIRE_PTR(e);
+  int rc = btc_hash_args(ctx, "sha256d", msg, msg_bytes, stride_bytes, e, n); if (rc != ECSIMD_HIP_OK) return rc;
+  RUN(launch::sha256d(s, msg, msg_bytes, stride_bytes, e, n)); }
+
+int ecsimd_hip_btc_pubkey_hash(ecsimd_hip_ctx* ctx, const uint64_t* qx, const uint64_t* qy, uint8_t* out20, size_t n, int compressed) {
+  REQUIRE_CTX(); REQUIRE_PTR(qx); REQUIRE_PTR(qy);
+  if (!out20 && n) return bad(ctx, "out20 is null");
+  if (reinterpret_cast<uintptr_t>(out20) & 3u) return bad(ctx, "out20 is not 4-byte aligned");
+  RUN(launch::btc_pubkey_hash(s, qx, qy, out20, n, compressed != 0)); }
+
+// ---- BIP-341 Taproot key tweaks on secp256k1 (k_btc.hip)
+namespace {
+// Q = lift_x(px) + t G per chunk of 2^22: k_tweak_front (the lift, t given or hashed, the range check), t G on the public comb -- the big table in device memory
+// on the terms double_scalar_mult_impl uses it, else the signed 7-bit comb in LDS --, k_tweak_add (complete: t = 0, the tangent, the opposite), ONE simultaneous
+// inversion that keeps y, k_tweak_accept.  Per element of a chunk: the lifted P, later the affine Q (64 B), t (32 B), the Jacobian sum (96 B) and the validity byte.
+int xonly_tweak_chain(ecsimd_hip_ctx* ctx, const char* what, int mode, const uint64_t* px, const uint64_t* t_or_merkle, uint64_t* qx, uint8_t* parity, uint8_t* ok, size_t n) {
+  if (ctx->ref_square) { snprintf(ctx->err, sizeof ctx->err, "bad argument: %s is not the reference's algorithm: no ECSIMD_HIP_REF_SQUARE_COMPAT form", what); return ECSIMD_HIP_ERR_BAD_ARG; }
+  gmod N; if (!lookup_modulus(ECSIMD_HIP_FIELD_SECP256K1_ORDER, &N)) return bad(ctx, "group order missing from the registry");
+  launch::words8 order; for (int i = 0; i < 8; ++i) order.w[i] = N.p[i];
+  if (n == 0) return ECSIMD_HIP_OK;
+  (void)hipSetDevice(ctx->device);
+  const int curve = ECSIMD_HIP_SECP256K1;
+  const size_t chunk = n < GC_CHUNK ? n : GC_CHUNK, flag_bytes = ((chunk + 15) / 16) * 16;
+  const bool big = ctx->window16_table[curve] != nullptr || n >= BIG_TABLE_WORTH_IT;
+  int rc = ensure_window_table(ctx, curve, big ? launch::BIG_WINDOW_BITS : SIGNED_WBITS);
+  if (rc == ECSIMD_HIP_OK) rc = ensure_workspace(ctx, 6 * chunk * 32 + flag_bytes);
+  if (rc != ECSIMD_HIP_OK) return rc;
+  uint64_t* jx = ctx->workspace; uint64_t* jy = jx + 4 * chunk; uint64_t* jz = jy + 4 * chunk;
+  uint64_t* x = jz + 4 * chunk; uint64_t* y = x + 4 * chunk; uint64_t* tt = y + 4 * chunk;
+  uint8_t* valid = reinterpret_cast<uint8_t*>(tt + 4 * chunk);
+  hipStream_t st = ctx->stream;
+  for (size_t first = 0; first < n; first += chunk) {
+    const size_t m = n - first < chunk ? n - first : chunk;
+    launch::tweak_front(st, order, mode, px + 4 * first, t_or_merkle ? t_or_merkle + 4 * first : nullptr, x, y, tt, valid, m);
+    if (big) launch::base_windowed_big(st, curve, tt, ctx->window16_table[curve], jx, jy, jz, m);
+    else launch::base_windowed_signed(st, curve, tt, ctx->window6_table[curve], jx, jy, jz, m, false);
+    launch::tweak_add(st, jx, jy, jz, x, y, m);
+    launch::to_affine_batched(st, curve, jx, jy, jz, x, y, m, true);                                   // the lifted P is spent: its place takes the affine Q
+    launch::tweak_accept(st, x, y, jz, valid, qx + 4 * first, parity + first, ok + first, m);
+  }
+  hipError_t err = hipGetLastError();
+  return err == hipSuccess ? ECSIMD_HIP_OK : fail(ctx, err, what);
+}
+}  // namespace
+
+int ecsimd_hip_xonly_tweak_add(ecsimd_hip_ctx* ctx, const uint64_t* px, const uint64_t* t, uint64_t* qx, uint8_t* parity, uint8_t* ok, size_t n) {
+  REQUIRE_CTX(); REQUIRE_PTR(px); REQUIRE_PTR(t); REQUIRE_PTR(qx);
+  if ((!parity || !ok) && n) return bad(ctx, "parity or ok is null");
+  if (n != 0 && (overlaps(qx, px) || overlaps(qx, t))) return bad(ctx, "qx must not alias an input");
+  return xonly_tweak_chain(ctx, "xonly_tweak_add", launch::TWEAK_GIVEN, px, t, qx, parity, ok, n); }
+
+int ecsimd_hip_taproot_tweak_pubkey(ecsimd_hip_ctx* ctx, const uint64_t* px, const uint64_t* merkle_root, uint64_t* qx, uint8_t* parity, uint8_t* ok, size_t n) {
+  REQUIRE_CTX(); REQUIRE_PTR(px); REQUIRE_PTR(qx);
+  if (merkle_root && !aligned16(merkle_root)) return bad(ctx, "merkle_root is not 16-byte aligned");
+  if ((!parity || !ok) && n) return bad(ctx, "parity or ok is null");
+  if (n != 0 && (overlaps(qx, px) || (merkle_root && overlaps(qx, merkle_root)))) return bad(ctx, "qx must not alias an input");
+  return xonly_tweak_chain(ctx, "taproot_tweak_pubkey", merkle_root ? launch::TWEAK_MERKLE_ROOT : launch::TWEAK_KEY_PATH, px, merkle_root, qx, parity, ok, n); }
+
+// The secret key of the output key: d G on the constant-time comb with both coordinates through the simultaneous inversion (schnorr_sign's two launches for d G),
+// then k_taproot_seckey.  Per element of a chunk: the Jacobian product (96 B) and the affine d G (64 B) -- all zeroed behind the kernels (ecdsa_sign says why).
+int ecsimd_hip_taproot_tweak_seckey(ecsimd_hip_ctx* ctx, const uint64_t* d, const uint64_t* merkle_root, uint64_t* d_out, uint64_t* px, uint8_t* ok, size_t n) {
+  REQUIRE_CTX(); REQUIRE_PTR(d); REQUIRE_PTR(d_out);
+  if ((merkle_root && !aligned16(merkle_root)) || (px && !aligned16(px))) return bad(ctx, "merkle_root or px is not 16-byte aligned");
+  if (!ok && n) return bad(ctx, "ok is null");
+  if (ctx->ref_square) return bad(ctx, "taproot_tweak_seckey is not the reference's algorithm: no ECSIMD_HIP_REF_SQUARE_COMPAT form");
+  gmod N; if (!lookup_modulus(ECSIMD_HIP_FIELD_SECP256K1_ORDER, &N)) return bad(ctx, "group order missing from the registry");
+  if (n != 0) {
+    if (overlaps(d_out, d) || (merkle_root && overlaps(d_out, merkle_root)) || (px && (overlaps(px, d) || overlaps(px, d_out) || (merkle_root && overlaps(px, merkle_root)))))
+      return bad(ctx, "d_out and px must not alias an input or each other");
+  }
+  if (n == 0) return ECSIMD_HIP_OK;
+  (void)hipSetDevice(ctx->device);
+  const int curve = ECSIMD_HIP_SECP256K1;
+  const size_t chunk = n < GC_CHUNK ? n : GC_CHUNK;
+  int rc = ensure_window_table(ctx, curve, CT_WBITS);
+  if (rc == ECSIMD_HIP_OK) rc = ensure_workspace(ctx, 5 * chunk * 32);
+  if (rc != ECSIMD_HIP_OK) return rc;
+  uint64_t* jx = ctx->workspace; uint64_t* jy = jx + 4 * chunk; uint64_t* jz = jy + 4 * chunk; uint64_t* xP = jz + 4 * chunk; uint64_t* yP = xP + 4 * chunk;
+  hipStream_t st = ctx->stream;
+  hipError_t err = hipSuccess;
+  for (size_t first = 0; first < n && err == hipSuccess; first += chunk) {
+    const size_t m = n - first < chunk ? n - first : chunk;
+    launch::base_windowed_signed(st, curve, d + 4 * first, ctx->windowct_table[curve], jx, jy, jz, m, true);      // d >= n is reduced by the comb; the lane is refused below
+    launch::to_affine_batched(st, curve, jx, jy, jz, xP, yP, m, true);
+    launch::taproot_seckey(st, N, d + 4 * first, merkle_root ? merkle_root + 4 * first : nullptr, xP, yP, d_out + 4 * first, px ? px + 4 * first : nullptr, ok + first, m);
+    err = hipGetLastError();
+    hipError_t wiped = hipMemsetAsync(ctx->workspace, 0, 5 * chunk * 32, st);                                     // whatever the launches said
+    if (err == hipSuccess) err = wiped;
+  }
+  return err == hipSuccess ? ECSIMD_HIP_OK : fail(ctx, err, "taproot_tweak_seckey launch"); }
+
 // ---- BIP-340 Schnorr signatures on secp256k1 (k_schnorr.hip)
 namespace {
 int schnorr_common(ecsimd_hip_ctx* ctx, const char* what, const uint8_t* msg, size_t msg_bytes, size_t stride_bytes, size_t n, gmod* N, launch::words8* order) {

@@ -137,6 +137,23 @@ void schnorr_nonce(hipStream_t, const words8& order, const uint64_t* d, const ui
 void schnorr_finish(hipStream_t, const gmod& order, const uint64_t* d, const uint64_t* k0, const uint64_t* xP, const uint64_t* yP, const uint64_t* xR, const uint64_t* yR,
                     const uint8_t* msg, size_t msg_bytes, size_t stride_bytes, uint64_t* px, uint64_t* r, uint64_t* s, uint8_t* ok, size_t n);
 
+// k_btc.hip: what Bitcoin makes of SHA-256 and secp256k1.  The hashes (PUBLIC data; messages as for sha256): ripemd160 and hash160 = RIPEMD160(SHA256(m)) write
+// 20 bytes per lane at out20 + 20 i (4-byte aligned), sha256d = SHA256(SHA256(m)) writes e as sha256 does, btc_pubkey_hash = hash160 of the SEC1 encoding of
+// (qx, qy), built in registers.  The Taproot tweaks: tweak_front writes (x, y) = the even-y lift of px (G where the lane is refused), tt = t (mode 0), or
+// int(H_TapTweak(px)) / int(H_TapTweak(px || merkle)) (modes 1 / 2), 0 where refused, and valid = lift && t < n; tweak_add: J += (x, y), complete (J Jacobian in
+// the fast domain, Z = 0 is infinity); tweak_accept: ok = valid && Z != 0, qx = ax and parity = ay & 1 under it.  taproot_seckey (SECRET d, the affine d G,
+// d_out: selects only): d_out = (d or n - d by the parity of y(d G)) + t mod n, px (may be NULL) = x(d G), all 0 where d is not in [1, n - 1], t >= n or the sum is 0.
+enum tweak_mode { TWEAK_GIVEN = 0, TWEAK_KEY_PATH = 1, TWEAK_MERKLE_ROOT = 2 };
+void ripemd160(hipStream_t, const uint8_t* msg, size_t msg_bytes, size_t stride_bytes, uint8_t* out20, size_t n);
+void hash160(hipStream_t, const uint8_t* msg, size_t msg_bytes, size_t stride_bytes, uint8_t* out20, size_t n);
+void sha256d(hipStream_t, const uint8_t* msg, size_t msg_bytes, size_t stride_bytes, uint64_t* e, size_t n);
+void btc_pubkey_hash(hipStream_t, const uint64_t* qx, const uint64_t* qy, uint8_t* out20, size_t n, bool compressed);
+void tweak_front(hipStream_t, const words8& order, int mode, const uint64_t* px, const uint64_t* t_or_merkle, uint64_t* x, uint64_t* y, uint64_t* tt, uint8_t* valid, size_t n);
+void tweak_add(hipStream_t, uint64_t* jx, uint64_t* jy, uint64_t* jz, const uint64_t* x, const uint64_t* y, size_t n);
+void tweak_accept(hipStream_t, const uint64_t* ax, const uint64_t* ay, const uint64_t* jz, const uint8_t* valid, uint64_t* qx, uint8_t* parity, uint8_t* ok, size_t n);
+void taproot_seckey(hipStream_t, const gmod& order, const uint64_t* d, const uint64_t* merkle, const uint64_t* xP, const uint64_t* yP, uint64_t* d_out, uint64_t* px,
+                    uint8_t* ok, size_t n);
+
 // k_fe29_raw.hip: one function of fe29.cuh on raw 9-limb operands (the diagnostic entry ecsimd_hip_fe29_raw)
 enum fe29_raw_op { RAW_ZDAU = 0, RAW_MADD = 1, RAW_JDBL = 2, RAW_DBL_ADD = 3, RAW_MADDV = 4, RAW_PDBL = 5, RAW_PADD = 6, RAW_MUL = 7, RAW_SQR = 8, RAW_GJDBL = 9, RAW_ZADDU = 10 };
 constexpr int fe29_raw_inputs(int op) { return op == RAW_ZDAU ? 6 : op == RAW_MUL ? 2 : op == RAW_SQR ? 1 : (op == RAW_JDBL || op == RAW_PDBL) ? 3 : op == RAW_GJDBL ? 4 : 5; }

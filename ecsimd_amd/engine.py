@@ -489,6 +489,51 @@ class Engine:
                    C.c_int(ETH_REQUIRE_LOW_S if require_low_s else 0))
         return (addr, qx, qy, ok) if want_key else (addr, ok)
 
+    def _digest20(self, name, msgs):
+        n = int(msgs.shape[0]); out = self.torch.empty((n, 20), dtype=self.torch.uint8, device=self.tdev)
+        keep, mp, length, stride = self._messages(msgs, n)
+        self._call(name, mp, length, stride, self._bytes_ptr(out), C.c_size_t(n))
+        return out
+
+    def ripemd160(self, msgs):
+        """ecsimd_hip_ripemd160: (n, 20) uint8, RIPEMD-160 of the rows of `msgs` (2-D uint8 device tensor, rows may be strided).  Public data."""
+        return self._digest20("ripemd160", msgs)
+
+    def hash160(self, msgs):
+        """ecsimd_hip_hash160: (n, 20) uint8, RIPEMD-160(SHA-256(row)) of the rows of `msgs`.  Public data."""
+        return self._digest20("hash160", msgs)
+
+    def sha256d(self, msgs):
+        """ecsimd_hip_sha256d: SHA-256(SHA-256(row)) of the rows of `msgs` as (n, 4) integers, as sha256 returns its digests.  Public data."""
+        n = int(msgs.shape[0]); e = self.empty(n)
+        keep, mp, length, stride = self._messages(msgs, n)
+        self._call("sha256d", mp, length, stride, self._ptr(e), C.c_size_t(n))
+        return e
+
+    def btc_pubkey_hash(self, qx, qy, compressed=True):
+        """ecsimd_hip_btc_pubkey_hash: (n, 20) uint8, HASH160 of the SEC1 encoding (33 bytes, or 65 with compressed=False) of each secp256k1 public key (qx, qy)."""
+        n = qx.shape[0]; out = self.torch.empty((n, 20), dtype=self.torch.uint8, device=self.tdev)
+        self._call("btc_pubkey_hash", self._ptr(qx), self._ptr(qy), self._bytes_ptr(out), C.c_size_t(n), C.c_int(1 if compressed else 0))
+        return out
+
+    def xonly_tweak_add(self, px, t):
+        """ecsimd_hip_xonly_tweak_add: (qx, parity, ok) of Q = lift_x(px) + t G on secp256k1; ok = 0 and zeros where px does not lift, t >= n or Q is infinite."""
+        n = px.shape[0]; qx, parity, ok = self.empty(n), self.flags(n), self.flags(n)
+        self._call("xonly_tweak_add", self._ptr(px), self._ptr(t), self._ptr(qx), self._ptr(parity, 0), self._ptr(ok, 0), C.c_size_t(n))
+        return qx, parity, ok
+
+    def taproot_tweak_pubkey(self, px, merkle_root=None):
+        """ecsimd_hip_taproot_tweak_pubkey: (qx, parity, ok), the BIP-341 output key of each internal key px; merkle_root None = key-path-only spending."""
+        n = px.shape[0]; qx, parity, ok = self.empty(n), self.flags(n), self.flags(n)
+        self._call("taproot_tweak_pubkey", self._ptr(px), self._ptr(merkle_root), self._ptr(qx), self._ptr(parity, 0), self._ptr(ok, 0), C.c_size_t(n))
+        return qx, parity, ok
+
+    def taproot_tweak_seckey(self, d, merkle_root=None, want_px=True):
+        """ecsimd_hip_taproot_tweak_seckey: (d_out, px, ok), the SECRET key of the BIP-341 output key of each secret key d and px = x(d G) (None with want_px=False)."""
+        n = d.shape[0]; d_out, ok = self.empty(n), self.flags(n); px = self.empty(n) if want_px else None
+        self._call("taproot_tweak_seckey", self._ptr(d), self._ptr(merkle_root), self._ptr(d_out), self._ptr(px), self._ptr(ok, 0), C.c_size_t(n))
+        return d_out, px, ok
+
     def fe29_raw(self, curve, op, inputs, swap=0):
         """ecsimd_hip_fe29_raw: one function of the reduced-radix layer on raw int32 limbs; `inputs` is an int32 tensor (n, NIN, 9); returns (n, NOUT, 9)."""
         torch = self.torch

@@ -7,6 +7,7 @@
 #include <ecsimd/curve_secp256k1.h>
 #include <ecsimd/jacobian_curve_point.h>
 #include <ecsimd/keccak256.h>
+#include <ecsimd/hash160.h>
 #include <ecsimd/sha256.h>
 #include <optional>
 #include <type_traits>
@@ -226,6 +227,37 @@ struct curve_group {
     ok = hip::mask(e.size());
     hip::check(ecsimd_hip_eth_recover(hip::context(), e.data(), r.data(), s.data(), v.data(), a.data(), nullptr, nullptr, ok.data(), e.size(), flags), "ecsimd_hip_eth_recover");
     return a;
+  }
+  // ---- Bitcoin: secp256k1 only, like the Schnorr and the Ethereum members.
+  // HASH160 of the SEC1 encoding of the public keys q (33 bytes, or 65 with compressed = false): what a P2PKH / P2WPKH output holds.  No validation.  Public data.
+  static hip::digests20 btc_pubkey_hash(WCP const& q, bool compressed = true) requires std::is_same_v<Curve, curve_secp256k1> {
+    hip::digests20 h(q.x().size());
+    hip::check(ecsimd_hip_btc_pubkey_hash(hip::context(), q.x().data(), q.y().data(), h.data(), h.size(), compressed ? 1 : 0), "ecsimd_hip_btc_pubkey_hash");
+    return h;
+  }
+  // x(Q) for Q = lift_x(px) + t G; parity[i] = y(Q) & 1; ok[i] is false -- and x(Q) = 0 -- where px does not lift, t >= n or Q is infinite.  Public data.
+  static WBN xonly_tweak_add(WBN const& px, WBN const& t, hip::mask& parity, hip::mask& ok) requires std::is_same_v<Curve, curve_secp256k1> {
+    same_length(px.size(), t.size(), "xonly_tweak_add");
+    auto qx = WBN::uninitialized(px.size()); parity = hip::mask(px.size()); ok = hip::mask(px.size());
+    hip::check(ecsimd_hip_xonly_tweak_add(hip::context(), px.data(), t.data(), qx.data(), parity.data(), ok.data(), px.size()), "ecsimd_hip_xonly_tweak_add");
+    return qx;
+  }
+  // BIP-341: the output key of the internal keys px, tweaked by H_TapTweak(px || merkle_root), or by H_TapTweak(px) with merkle_root = nullptr.  Public data.
+  static WBN taproot_tweak_pubkey(WBN const& px, hip::mask& parity, hip::mask& ok, WBN const* merkle_root = nullptr) requires std::is_same_v<Curve, curve_secp256k1> {
+    if (merkle_root) same_length(px.size(), merkle_root->size(), "taproot_tweak_pubkey");
+    auto qx = WBN::uninitialized(px.size()); parity = hip::mask(px.size()); ok = hip::mask(px.size());
+    hip::check(ecsimd_hip_taproot_tweak_pubkey(hip::context(), px.data(), merkle_root ? merkle_root->data() : nullptr, qx.data(), parity.data(), ok.data(), px.size()),
+               "ecsimd_hip_taproot_tweak_pubkey");
+    return qx;
+  }
+  // BIP-341: the SECRET key of that output key from the secret keys d, ready for schnorr_sign; px = x(d G), the internal keys.  ok[i] is false -- and both are
+  // 0 -- where d is not in [1, n), the tweak is >= n or the sum is 0.  d G runs on the constant-time comb; no branch or address depends on d or the result.
+  static WBN taproot_tweak_seckey(WBN const& d, WBN& px, hip::mask& ok, WBN const* merkle_root = nullptr) requires std::is_same_v<Curve, curve_secp256k1> {
+    if (merkle_root) same_length(d.size(), merkle_root->size(), "taproot_tweak_seckey");
+    auto out = WBN::uninitialized(d.size()); px = WBN::uninitialized(d.size()); ok = hip::mask(d.size());
+    hip::check(ecsimd_hip_taproot_tweak_seckey(hip::context(), d.data(), merkle_root ? merkle_root->data() : nullptr, out.data(), px.data(), ok.data(), d.size()),
+               "ecsimd_hip_taproot_tweak_seckey");
+    return out;
   }
   // ---- several GPUs: k[i] * P[i] for HOST arrays, sharded over a device group.  P affine classical (x, y);
   // the result is what scalar_mult(x, from_affine(P)) returns lane by lane -- Jacobian, Montgomery form -- or, with

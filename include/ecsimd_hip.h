@@ -486,6 +486,51 @@ int ecsimd_hip_eth_address(ecsimd_hip_ctx*, const uint64_t* qx, const uint64_t* 
 enum { ECSIMD_HIP_ETH_REQUIRE_LOW_S = 1 };
 int ecsimd_hip_eth_recover(ecsimd_hip_ctx*, const uint64_t* e, const uint64_t* r, const uint64_t* s, const uint8_t* v,
                            uint8_t* addr, uint64_t* qx, uint64_t* qy, uint8_t* ok, size_t n, int flags);
+/* Bitcoin's hashes over n equal-length messages, message i at msg + i * stride_bytes, msg_bytes long, as for ecsimd_hip_sha256: any length including 0 (msg may
+ * then be NULL), stride_bytes >= msg_bytes, any alignment (word loads where base and stride are multiples of 4, byte loads otherwise).  PUBLIC data: the loads
+ * and the block loop follow the length; do not hash a secret with these.  out20: n x 20 bytes of device memory, 4-byte aligned: lane i's digest at out20 + 20 i,
+ * its bytes in order.  Stream-ordered; no workspace.  One message per lane; RIPEMD-160's five state words and sixteen message words stay in registers, its
+ * 80 + 80 steps are unrolled.
+ *   ripemd160   RIPEMD-160(m).
+ *   hash160     RIPEMD-160(SHA-256(m)): what a P2PKH / P2WPKH output holds of a key, a P2SH output of a script.  The SHA-256 digest enters the RIPEMD block in
+ *               registers: c + 1 compressions for a message of c SHA-256 blocks.
+ *   sha256d     SHA-256(SHA-256(m)): transaction ids, legacy and segwit-v0 signature hashes, Base58Check checksums.  e[i] = the digest as ecsimd_hip_sha256
+ *               writes it: 4 x u64 little-endian limbs of the digest read as a big-endian number (16-byte aligned).  c + 1 compressions. */
+int ecsimd_hip_ripemd160(ecsimd_hip_ctx*, const uint8_t* msg, size_t msg_bytes, size_t stride_bytes, uint8_t* out20, size_t n);
+int ecsimd_hip_hash160(ecsimd_hip_ctx*, const uint8_t* msg, size_t msg_bytes, size_t stride_bytes, uint8_t* out20, size_t n);
+int ecsimd_hip_sha256d(ecsimd_hip_ctx*, const uint8_t* msg, size_t msg_bytes, size_t stride_bytes, uint64_t* e, size_t n);
+/* HASH160 of the SEC1 encoding of n public keys (qx, qy), 4 x u64 limbs each: compressed != 0: (02 | parity of qy) || be32(qx), 33 bytes, one SHA-256 and one
+ * RIPEMD-160 compression; compressed == 0: 04 || be32(qx) || be32(qy), 65 bytes, two and one.  The encoding is built in registers and never reaches memory.  No
+ * validation: the call hashes the encoding of the integers it is given ((0, 0) hashes as 02 || 32 zero bytes does).  out20 as above.  PUBLIC data.
+ * Stream-ordered; no workspace.  (The hash of a SECRET key d's public key: ecsimd_hip_scalar_mult_base with ECSIMD_HIP_ALG_WINDOWED |
+ * ECSIMD_HIP_ALG_CONSTANT_TIME | ECSIMD_HIP_OUT_AFFINE, then this call on the public result.) */
+int ecsimd_hip_btc_pubkey_hash(ecsimd_hip_ctx*, const uint64_t* qx, const uint64_t* qy, uint8_t* out20, size_t n, int compressed);
+/* BIP-341 Taproot key tweaks.  secp256k1 only: no curve id.  Keys, tweaks and merkle roots are 4 x u64 little-endian limbs per element (the integer whose 32
+ * big-endian bytes the BIP writes), 16-byte aligned.  Stream-ordered, nothing is read back.  No ECSIMD_HIP_REF_SQUARE_COMPAT form (ERR_BAD_ARG on a context with
+ * that option).  Any n (2^22 at a time).
+ *
+ * xonly_tweak_add, PUBLIC data: Q = P + t G with P = the even-y point of x coordinate px.  ok[i] = 1 iff px < p and lifts, t < n and Q is finite; then
+ * qx = x(Q) and parity = y(Q) & 1, else qx = 0 and parity = 0.  t = 0 is valid and gives Q = P: qx = px, parity = 0.  t G = P (a doubling) is handled; t G = -P
+ * gives ok = 0.  Per chunk: one kernel lifts and range-checks, t G comes from the public comb (indexed by the digits of t: not for secrets -- the 20-bit table in
+ * device memory once it exists or n >= 2^16, else the signed 7-bit table in LDS), one kernel adds, ONE simultaneous inversion, one kernel accepts.  qx must not
+ * alias an input.  Workspace: 193 B per element of a chunk.
+ *
+ * taproot_tweak_pubkey, PUBLIC data: the same with t = int(SHA256(tag || tag || be32(px) || h)), tag = SHA256("TapTweak"), made in the first kernel from the tag
+ * block's midstate.  merkle_root = NULL (the call's, not the lane's): key-path-only spending, no h: 32 bytes of data, one compression; otherwise h = merkle_root[i],
+ * two compressions.  t is NOT reduced modulo n: t >= n gives ok = 0 (probability ~2^-128).  The hash cannot be 0 in practice; if it were, the lane would return
+ * what xonly_tweak_add returns for t = 0: ok = 1, qx = px, parity = 0.  The caller checks a control block by comparing qx and parity (ecsimd_hip_cmp_eq).
+ * Workspace as above.
+ *
+ * taproot_tweak_seckey, SECRET data: d_out = d' + t mod n with d' = d where y(d G) is even, n - d where it is odd, and t as above from x(d G) -- the secret key of
+ * the output key Q, ready for ecsimd_hip_schnorr_sign.  px (optional output, may be NULL) = x(d G), the internal x-only key.  ok[i] = 0 and d_out = px = 0 where d
+ * is not in [1, n - 1], t >= n, or the sum is 0 (t = 0 would give d_out = d').  d, d', d_out, the Jacobian and the affine d G are SECRETS until returned, and so is
+ * t while px is: d G runs on the constant-time comb (the kernel of ALG_WINDOWED | ALG_CONSTANT_TIME) and the select-only simultaneous inversion, the kernel behind
+ * them selects by masks -- no branch, address or lane mask in force at a memory access depends on a secret and no bit is declassified (tools/ct_check.py
+ * check_secret_flow on the shipped ISA: tests/test_btc_cpu.py).  merkle_root is public but treated no differently.  Every workspace byte the call used is zeroed
+ * on the stream before it returns, whatever the launches said.  d_out and px must not alias an input or each other.  Workspace: 160 B per element of a chunk. */
+int ecsimd_hip_xonly_tweak_add(ecsimd_hip_ctx*, const uint64_t* px, const uint64_t* t, uint64_t* qx, uint8_t* parity, uint8_t* ok, size_t n);
+int ecsimd_hip_taproot_tweak_pubkey(ecsimd_hip_ctx*, const uint64_t* px, const uint64_t* merkle_root, uint64_t* qx, uint8_t* parity, uint8_t* ok, size_t n);
+int ecsimd_hip_taproot_tweak_seckey(ecsimd_hip_ctx*, const uint64_t* d, const uint64_t* merkle_root, uint64_t* d_out, uint64_t* px, uint8_t* ok, size_t n);
 /* Diagnostic (r5): ONE function of the reduced-radix layer the multiplication-bound loops run on (fe29.cuh: nine signed 29-bit limbs in 32-bit words,
  * Montgomery radix 2^261, lazy carries) on RAW operands -- int32 limbs exactly as a loop holds them between two operations: element e's coordinate c, limb l at
  * in[(e * NIN + c) * 9 + l] (device memory).  What tests use to hand the device the states and operand pairs at which the interval proofs of
