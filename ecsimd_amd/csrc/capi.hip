@@ -2120,4 +2120,127 @@ int ecsimd_hip_peak_mad32(ecsimd_hip_ctx* ctx, int iters, double* mads, double* 
   *ms = t; *mads = (double)blocks * BLOCK * (double)iters * launch::PEAK_MADS_PER_LANE_PER_ITER;
   return ECSIMD_HIP_OK; }
 
+
+// ---- SHA-512, HMAC-SHA-512 (k_sha512.hip); public data, no workspace
+int ecsimd_hip_sha512(ecsimd_hip_ctx* ctx, const uint8_t* msg, size_t msg_bytes, size_t stride_bytes, uint8_t* out64, size_t n) {
+  REQUIRE_CTX();
+  int rc = btc_hash_args(ctx, "sha512", msg, msg_bytes, stride_bytes, out64, n); if (rc != ECSIMD_HIP_OK) return rc;
+  if (!aligned16(out64)) return bad(ctx, "out64 is not 16-byte aligned");
+  RUN(launch::sha512(s, msg, msg_bytes, stride_bytes, out64, n)); }
+
+int ecsimd_hip_hmac_sha512(ecsimd_hip_ctx* ctx, const uint8_t* key, size_t key_bytes, size_t key_stride_bytes, const uint8_t* msg, size_t msg_bytes, size_t stride_bytes,
+                           uint8_t* out64, size_t n) {
+  REQUIRE_CTX();
+  int rc = btc_hash_args(ctx, "hmac_sha512", msg, msg_bytes, stride_bytes, out64, n); if (rc != ECSIMD_HIP_OK) return rc;
+  if (!aligned16(out64)) return bad(ctx, "out64 is not 16-byte aligned");
+  if (!key && n && key_bytes) return bad(ctx, "key is null");
+  if ((key_stride_bytes != 0 && key_stride_bytes < key_bytes) || key_bytes > ((size_t)1 << 40)) return bad(ctx, "hmac_sha512: key_stride_bytes is smaller than key_bytes, or the key is too long");
+  RUN(launch::hmac_sha512(s, key, key_bytes, key_stride_bytes, msg, msg_bytes, stride_bytes, out64, n)); }
+
+// ---- BIP-32 key derivation on secp256k1 (k_bip32.hip)
+namespace {
+int bip32_common(ecsimd_hip_ctx* ctx, const char* what, const uint32_t* index, gmod* N, launch::words8* order) {
+  if (reinterpret_cast<uintptr_t>(index) & 3u) return bad(ctx, "index is not 4-byte aligned");
+  if (ctx->ref_square) { snprintf(ctx->err, sizeof ctx->err, "bad argument: %s is not the reference's algorithm: no ECSIMD_HIP_REF_SQUARE_COMPAT form", what); return ECSIMD_HIP_ERR_BAD_ARG; }
+  if (!lookup_modulus(ECSIMD_HIP_FIELD_SECP256K1_ORDER, N)) return bad(ctx, "group order missing from the registry");
+  for (int i = 0; i < 8; ++i) order->w[i] = N->p[i];
+  return ECSIMD_HIP_OK;
+}
+bool any_alias(const void* const* out, int outs, const void* const* in, int ins) {
+  for (int a = 0; a < outs; ++a) {
+    for (int b = 0; b < ins; ++b) if (in[b] && overlaps(out[a], in[b])) return true;
+    for (int b = a + 1; b < outs; ++b) if (overlaps(out[a], out[b])) return true;
+  }
+  return false;
+}
+}  // namespace
+
+int ecsimd_hip_bip32_master(ecsimd_hip_ctx* ctx, const uint8_t* seed, size_t seed_bytes, size_t stride_bytes, uint64_t* k, uint64_t* c, uint8_t* ok, size_t n) {
+  REQUIRE_CTX(); REQUIRE_PTR(k); REQUIRE_PTR(c);
+  if ((!ok || !seed) && n) return bad(ctx, "seed or ok is null");
+  if (seed_bytes < 16 || seed_bytes > 64) return bad(ctx, "bip32_master: seed_bytes is outside 16 .. 64");
+  if (stride_bytes < seed_bytes) return bad(ctx, "bip32_master: stride_bytes is smaller than seed_bytes");
+  gmod N; launch::words8 order;
+  int rc = bip32_common(ctx, "bip32_master", nullptr, &N, &order); if (rc != ECSIMD_HIP_OK) return rc;
+  if (n != 0) { const void* out[3] = {k, c, ok}; const void* in[1] = {seed}; if (any_alias(out, 3, in, 1)) return bad(ctx, "k, c and ok must not alias an input or each other"); }
+  RUN(launch::bip32_master(s, order, seed, seed_bytes, stride_bytes, k, c, ok, n)); }
+
+// Without the caller's promise, per chunk of 2^22: k_par G on the constant-time comb with both coordinates through the simultaneous inversion
+// (taproot_tweak_seckey's two launches), then k_bip32_ckd_priv<true>.  Per element of a chunk: the Jacobian product (96 B) and the affine k_par G (64 B) -- all
+// zeroed behind the kernels (ecdsa_sign says why).  With the promise (or index == NULL and a hardened index_all): k_bip32_ckd_priv<false> alone, no workspace.
+int ecsimd_hip_bip32_ckd_priv(ecsimd_hip_ctx* ctx, const uint64_t* k_par, const uint64_t* c_par, const uint32_t* index, uint32_t index_all, uint64_t* k_child, uint64_t* c_child,
+                              uint8_t* ok, size_t n, int flags) {
+  REQUIRE_CTX(); REQUIRE_PTR(k_par); REQUIRE_PTR(c_par); REQUIRE_PTR(k_child); REQUIRE_PTR(c_child);
+  if (!ok && n) return bad(ctx, "ok is null");
+  if (flags & ~ECSIMD_HIP_BIP32_ALL_HARDENED) return bad(ctx, "bip32_ckd_priv: unknown flag");
+  gmod N; launch::words8 order;
+  int rc = bip32_common(ctx, "bip32_ckd_priv", index, &N, &order); if (rc != ECSIMD_HIP_OK) return rc;
+  if (n != 0) {
+    const void* out[3] = {k_child, c_child, ok}; const void* in[3] = {k_par, c_par, index};
+    if (any_alias(out, 3, in, 3)) return bad(ctx, "k_child, c_child and ok must not alias an input or each other");
+  }
+  if (n == 0) return ECSIMD_HIP_OK;
+  (void)hipSetDevice(ctx->device);
+  const int curve = ECSIMD_HIP_SECP256K1;
+  const size_t chunk = n < GC_CHUNK ? n : GC_CHUNK;
+  const bool hardened_only = (flags & ECSIMD_HIP_BIP32_ALL_HARDENED) != 0 || (!index && (index_all >> 31) != 0);
+  hipStream_t st = ctx->stream;
+  hipError_t err = hipSuccess;
+  if (hardened_only) {                                         // no workspace: nothing to chunk
+    if (n > (size_t)0x7fffffff * BLOCK) return bad(ctx, "batch too large");
+    launch::bip32_ckd_priv(st, N, k_par, c_par, index, index_all, nullptr, nullptr, k_child, c_child, ok, n);
+    err = hipGetLastError();
+    return err == hipSuccess ? ECSIMD_HIP_OK : fail(ctx, err, "bip32_ckd_priv launch");
+  }
+  rc = ensure_window_table(ctx, curve, CT_WBITS);
+  if (rc == ECSIMD_HIP_OK) rc = ensure_workspace(ctx, 5 * chunk * 32);
+  if (rc != ECSIMD_HIP_OK) return rc;
+  uint64_t* jx = ctx->workspace; uint64_t* jy = jx + 4 * chunk; uint64_t* jz = jy + 4 * chunk; uint64_t* xP = jz + 4 * chunk; uint64_t* yP = xP + 4 * chunk;
+  for (size_t first = 0; first < n && err == hipSuccess; first += chunk) {
+    const size_t m = n - first < chunk ? n - first : chunk;
+    launch::base_windowed_signed(st, curve, k_par + 4 * first, ctx->windowct_table[curve], jx, jy, jz, m, true);  // k_par >= n is reduced by the comb; the lane is refused below
+    launch::to_affine_batched(st, curve, jx, jy, jz, xP, yP, m, true);
+    launch::bip32_ckd_priv(st, N, k_par + 4 * first, c_par + 4 * first, index ? index + first : nullptr, index_all, xP, yP, k_child + 4 * first, c_child + 4 * first, ok + first, m);
+    err = hipGetLastError();
+    hipError_t wiped = hipMemsetAsync(ctx->workspace, 0, 5 * chunk * 32, st);                                     // whatever the launches said
+    if (err == hipSuccess) err = wiped;
+  }
+  return err == hipSuccess ? ECSIMD_HIP_OK : fail(ctx, err, "bip32_ckd_priv launch"); }
+
+// (cx, cy) = IL G + K per chunk of 2^22: k_bip32_ckd_pub_front (the hash, the curve equation, the range checks), then xonly_tweak_chain's middle -- IL G on the
+// public comb, k_tweak_add, ONE simultaneous inversion that keeps y --, then k_bip32_ckd_pub_accept.  Per element of a chunk: K, later the affine sum (64 B),
+// IL (32 B), the Jacobian sum (96 B) and the validity byte.  The child chain code goes straight to its output.
+int ecsimd_hip_bip32_ckd_pub(ecsimd_hip_ctx* ctx, const uint64_t* qx, const uint64_t* qy, const uint64_t* c_par, const uint32_t* index, uint32_t index_all, uint64_t* cx, uint64_t* cy,
+                             uint64_t* c_child, uint8_t* ok, size_t n) {
+  REQUIRE_CTX(); REQUIRE_PTR(qx); REQUIRE_PTR(qy); REQUIRE_PTR(c_par); REQUIRE_PTR(cx); REQUIRE_PTR(cy); REQUIRE_PTR(c_child);
+  if (!ok && n) return bad(ctx, "ok is null");
+  gmod N; launch::words8 order;
+  int rc = bip32_common(ctx, "bip32_ckd_pub", index, &N, &order); if (rc != ECSIMD_HIP_OK) return rc;
+  if (n != 0) {
+    const void* out[4] = {cx, cy, c_child, ok}; const void* in[4] = {qx, qy, c_par, index};
+    if (any_alias(out, 4, in, 4)) return bad(ctx, "cx, cy, c_child and ok must not alias an input or each other");
+  }
+  if (n == 0) return ECSIMD_HIP_OK;
+  (void)hipSetDevice(ctx->device);
+  const int curve = ECSIMD_HIP_SECP256K1;
+  const size_t chunk = n < GC_CHUNK ? n : GC_CHUNK, flag_bytes = ((chunk + 15) / 16) * 16;
+  const bool big = ctx->window16_table[curve] != nullptr || n >= BIG_TABLE_WORTH_IT;
+  rc = ensure_window_table(ctx, curve, big ? launch::BIG_WINDOW_BITS : SIGNED_WBITS);
+  if (rc == ECSIMD_HIP_OK) rc = ensure_workspace(ctx, 6 * chunk * 32 + flag_bytes);
+  if (rc != ECSIMD_HIP_OK) return rc;
+  uint64_t* jx = ctx->workspace; uint64_t* jy = jx + 4 * chunk; uint64_t* jz = jy + 4 * chunk;
+  uint64_t* x = jz + 4 * chunk; uint64_t* y = x + 4 * chunk; uint64_t* tt = y + 4 * chunk;
+  uint8_t* valid = reinterpret_cast<uint8_t*>(tt + 4 * chunk);
+  hipStream_t st = ctx->stream;
+  for (size_t first = 0; first < n; first += chunk) {
+    const size_t m = n - first < chunk ? n - first : chunk;
+    launch::bip32_ckd_pub_front(st, order, qx + 4 * first, qy + 4 * first, c_par + 4 * first, index ? index + first : nullptr, index_all, x, y, tt, c_child + 4 * first, valid, m);
+    if (big) launch::base_windowed_big(st, curve, tt, ctx->window16_table[curve], jx, jy, jz, m);
+    else launch::base_windowed_signed(st, curve, tt, ctx->window6_table[curve], jx, jy, jz, m, false);
+    launch::tweak_add(st, jx, jy, jz, x, y, m);
+    launch::to_affine_batched(st, curve, jx, jy, jz, x, y, m, true);                                   // K is spent: its place takes the affine sum
+    launch::bip32_ckd_pub_accept(st, x, y, jz, valid, cx + 4 * first, cy + 4 * first, c_child + 4 * first, ok + first, m);
+  }
+  hipError_t err = hipGetLastError();
+  return err == hipSuccess ? ECSIMD_HIP_OK : fail(ctx, err, "bip32_ckd_pub launch"); }
 }  // extern "C"

@@ -154,6 +154,24 @@ void tweak_accept(hipStream_t, const uint64_t* ax, const uint64_t* ay, const uin
 void taproot_seckey(hipStream_t, const gmod& order, const uint64_t* d, const uint64_t* merkle, const uint64_t* xP, const uint64_t* yP, uint64_t* d_out, uint64_t* px,
                     uint8_t* ok, size_t n);
 
+// k_sha512.hip: SHA-512 and HMAC-SHA-512 of n equal-length messages (PUBLIC data; messages as for sha256); 64 digest bytes per lane at out64 + 64 i (16-byte
+// aligned).  hmac_sha512: lane i's key at key + i * key_stride_bytes (0: one key for the call), zero-padded to a block or, beyond 128 bytes, hashed first.
+void sha512(hipStream_t, const uint8_t* msg, size_t msg_bytes, size_t stride_bytes, uint8_t* out64, size_t n);
+void hmac_sha512(hipStream_t, const uint8_t* key, size_t key_bytes, size_t key_stride_bytes, const uint8_t* msg, size_t msg_bytes, size_t stride_bytes, uint8_t* out64, size_t n);
+
+// k_bip32.hip: BIP-32 on secp256k1.  index == NULL: every lane uses index_all.  bip32_master (SECRET seed, k, c: selects only): (k, c) = the halves of
+// HMAC-SHA512("Bitcoin seed", seed), seed_bytes in [16, 64]; zeros and ok = 0 where k = 0 or k >= n.  bip32_ckd_priv (SECRET k_par, c_par, the affine k_par G,
+// k_child, c_child: selects only): CKDpriv; (xP, yP) = the affine k_par G, or both NULL: the kernel without point arrays, which refuses every lane whose index
+// is not hardened.  bip32_ckd_pub_front (PUBLIC): t = IL, c_child = IR, (x, y) = K, valid = index < 2^31 && K on the curve && IL < n (t = 0, c_child = 0 and
+// K = G where not); bip32_ckd_pub_accept: ok = valid && Z != 0, (cx, cy) = (ax, ay) under it, c_child zeroed where not.
+void bip32_master(hipStream_t, const words8& order, const uint8_t* seed, size_t seed_bytes, size_t stride_bytes, uint64_t* k, uint64_t* c, uint8_t* ok, size_t n);
+void bip32_ckd_priv(hipStream_t, const gmod& order, const uint64_t* k_par, const uint64_t* c_par, const uint32_t* index, uint32_t index_all, const uint64_t* xP, const uint64_t* yP,
+                    uint64_t* k_child, uint64_t* c_child, uint8_t* ok, size_t n);
+void bip32_ckd_pub_front(hipStream_t, const words8& order, const uint64_t* qx, const uint64_t* qy, const uint64_t* c_par, const uint32_t* index, uint32_t index_all, uint64_t* x,
+                         uint64_t* y, uint64_t* t, uint64_t* c_child, uint8_t* valid, size_t n);
+void bip32_ckd_pub_accept(hipStream_t, const uint64_t* ax, const uint64_t* ay, const uint64_t* jz, const uint8_t* valid, uint64_t* cx, uint64_t* cy, uint64_t* c_child, uint8_t* ok,
+                          size_t n);
+
 // k_fe29_raw.hip: one function of fe29.cuh on raw 9-limb operands (the diagnostic entry ecsimd_hip_fe29_raw)
 enum fe29_raw_op { RAW_ZDAU = 0, RAW_MADD = 1, RAW_JDBL = 2, RAW_DBL_ADD = 3, RAW_MADDV = 4, RAW_PDBL = 5, RAW_PADD = 6, RAW_MUL = 7, RAW_SQR = 8, RAW_GJDBL = 9, RAW_ZADDU = 10 };
 constexpr int fe29_raw_inputs(int op) { return op == RAW_ZDAU ? 6 : op == RAW_MUL ? 2 : op == RAW_SQR ? 1 : (op == RAW_JDBL || op == RAW_PDBL) ? 3 : op == RAW_GJDBL ? 4 : 5; }

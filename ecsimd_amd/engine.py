@@ -11,7 +11,7 @@ import os
 
 import numpy as np
 
-from .flags import ECDSA_LOW_S, ETH_REQUIRE_LOW_S
+from .flags import BIP32_ALL_HARDENED, ECDSA_LOW_S, ETH_REQUIRE_LOW_S
 
 P256, SECP256K1 = 0, 1
 CURVES = {"p256": P256, "secp256k1": SECP256K1}
@@ -533,6 +533,77 @@ class Engine:
         n = d.shape[0]; d_out, ok = self.empty(n), self.flags(n); px = self.empty(n) if want_px else None
         self._call("taproot_tweak_seckey", self._ptr(d), self._ptr(merkle_root), self._ptr(d_out), self._ptr(px), self._ptr(ok, 0), C.c_size_t(n))
         return d_out, px, ok
+
+    def sha512(self, msgs):
+        """ecsimd_hip_sha512: (n, 64) uint8, SHA-512 of the rows of `msgs` (2-D uint8 device tensor, rows may be strided).  Public data."""
+        n = int(msgs.shape[0]); out = self.torch.empty((n, 64), dtype=self.torch.uint8, device=self.tdev)
+        keep, mp, length, stride = self._messages(msgs, n)
+        self._call("sha512", mp, length, stride, self._bytes_ptr(out), C.c_size_t(n))
+        return out
+
+    def hmac_sha512(self, keys, msgs):
+        """ecsimd_hip_hmac_sha512: (n, 64) uint8, HMAC-SHA-512 of the rows of `msgs` under `keys`: a 1-D uint8 device tensor is ONE key for the whole call, a 2-D
+        one holds a key per row (rows may be strided).  Public data."""
+        torch = self.torch
+        n = int(msgs.shape[0]); out = torch.empty((n, 64), dtype=torch.uint8, device=self.tdev)
+        keep, mp, length, stride = self._messages(msgs, n)
+        assert keys.is_cuda and keys.device.index == self.device and keys.dtype == torch.uint8 and keys.dim() in (1, 2), (keys.dtype, keys.shape)
+        if keys.dim() == 1:
+            keys = keys.contiguous()
+            kp, klen, kstride = C.c_void_p(keys.data_ptr() if keys.shape[0] else 0), C.c_size_t(int(keys.shape[0])), C.c_size_t(0)
+        else:
+            keys, kp, klen, kstride = self._messages(keys, n)
+        self._call("hmac_sha512", kp, klen, kstride, mp, length, stride, self._bytes_ptr(out), C.c_size_t(n))
+        return out
+
+    def _index(self, index, n, what):
+        """(pointer, index_all) of a BIP-32 index argument: an int for every lane, or an int32 / uint32 device tensor of n indices."""
+        if isinstance(index, (int, np.integer)):
+            index = int(index)
+            if not 0 <= index < 1 << 32:
+                raise EcsimdHipError(f"{what}: the index {index} is not a 32-bit value")
+            return C.c_void_p(0), C.c_uint32(index)
+        torch = self.torch
+        assert index.is_cuda and index.device.index == self.device and index.is_contiguous() and index.dim() == 1, "index: a contiguous 1-D tensor on the engine's device"
+        assert index.dtype in (torch.int32, torch.uint32), index.dtype
+        if int(index.shape[0]) != n:
+            raise EcsimdHipError(f"{what}: operands disagree on the batch length: {sorted((n, int(index.shape[0])))}")
+        return C.c_void_p(index.data_ptr() if n else 0), C.c_uint32(0)
+
+    def bip32_master(self, seeds):
+        """ecsimd_hip_bip32_master: (k, c, ok), the BIP-32 master key and chain code of each SECRET seed, a row of `seeds` (2-D uint8 device tensor of 16 .. 64
+        columns, rows may be strided).  ok = 0 and zeros where the left half of the hash is 0 or >= n."""
+        n = int(seeds.shape[0]); k, c, ok = self.empty(n), self.empty(n), self.flags(n)
+        keep, sp, length, stride = self._messages(seeds, n)
+        self._call("bip32_master", sp, length, stride, self._ptr(k), self._ptr(c), self._ptr(ok, 0), C.c_size_t(n))
+        return k, c, ok
+
+    def bip32_ckd_priv(self, k, c, index, all_hardened=False):
+        """ecsimd_hip_bip32_ckd_priv: (k_child, c_child, ok), BIP-32's CKDpriv of the SECRET keys k and chain codes c at `index` (an int, or an int32 / uint32
+        device tensor with one index per lane).  all_hardened: the caller's promise that every index is >= 2^31 -- no point multiplication then; a lane that breaks
+        it is refused.  ok = 0 and zeros where k is not in [1, n - 1]."""
+        n = k.shape[0]; kc, cc, ok = self.empty(n), self.empty(n), self.flags(n)
+        ip, iall = self._index(index, n, "bip32_ckd_priv")
+        self._call("bip32_ckd_priv", self._ptr(k), self._ptr(c), ip, iall, self._ptr(kc), self._ptr(cc), self._ptr(ok, 0), C.c_size_t(n),
+                   C.c_int(BIP32_ALL_HARDENED if all_hardened else 0))
+        return kc, cc, ok
+
+    def bip32_ckd_pub(self, qx, qy, c, index):
+        """ecsimd_hip_bip32_ckd_pub: (cx, cy, c_child, ok), BIP-32's CKDpub of the public keys (qx, qy) and chain codes c at `index` (as for bip32_ckd_priv).
+        ok = 0 and zeros for a hardened index and for a key that is not on the curve.  Public data."""
+        n = qx.shape[0]; cx, cy, cc, ok = self.empty(n), self.empty(n), self.empty(n), self.flags(n)
+        ip, iall = self._index(index, n, "bip32_ckd_pub")
+        self._call("bip32_ckd_pub", self._ptr(qx), self._ptr(qy), self._ptr(c), ip, iall, self._ptr(cx), self._ptr(cy), self._ptr(cc), self._ptr(ok, 0), C.c_size_t(n))
+        return cx, cy, cc, ok
+
+    def bip32_derive_priv(self, k, c, path):
+        """(k, c, ok) at the end of `path` (a list of ints, one index per level, the same for every lane) below the SECRET nodes (k, c): a host loop of
+        bip32_ckd_priv, on the hardened-only route at hardened levels.  ok is the AND of the levels' masks (a refused lane's zero key is refused again below)."""
+        ok = self.torch.ones((k.shape[0],), dtype=self.torch.uint8, device=self.tdev)
+        for index in path:
+            k, c, level_ok = self.bip32_ckd_priv(k, c, int(index), all_hardened=int(index) >= 1 << 31)
+            ok = ok & level_ok
+        return k, c, ok
 
     def fe29_raw(self, curve, op, inputs, swap=0):
         """ecsimd_hip_fe29_raw: one function of the reduced-radix layer on raw int32 limbs; `inputs` is an int32 tensor (n, NIN, 9); returns (n, NOUT, 9)."""

@@ -14,3 +14,4 @@ LADDER_RADIX32 = 256          # ladder only: the loop on 8 x 32-bit canonical wo
 GROUP_NO_GATHER = 0x10000    # ecsimd_hip_group_scalar_mult only: compute without the exchange
 ECDSA_LOW_S = 1               # ecsimd_hip_ecdsa_sign_recoverable only: s > n / 2 is returned as n - s (and bit 0 of v flipped)
 ETH_REQUIRE_LOW_S = 1         # ecsimd_hip_eth_recover only: s > n / 2 is refused (EIP-2)
+BIP32_ALL_HARDENED = 1        # ecsimd_hip_bip32_ckd_priv only: every index has bit 31 set (no point multiplication; a lane that breaks the promise is refused)

@@ -9,6 +9,7 @@
 #include <ecsimd/keccak256.h>
 #include <ecsimd/hash160.h>
 #include <ecsimd/sha256.h>
+#include <ecsimd/sha512.h>
 #include <optional>
 #include <type_traits>
 
@@ -259,6 +260,42 @@ struct curve_group {
                "ecsimd_hip_taproot_tweak_seckey");
     return out;
   }
+  // ---- BIP-32 key derivation: secp256k1 only.  Keys and chain codes are the integers whose 32 big-endian bytes the BIP writes; an index >= 2^31 is hardened.
+  // The master key and chain code of the SECRET seeds (16 .. 64 bytes each, one length); ok[i] is false -- and both are 0 -- where the key would be 0 or >= n.
+  static WBN bip32_master(hip::messages const& seeds, WBN& c, hip::mask& ok) requires std::is_same_v<Curve, curve_secp256k1> {
+    auto k = WBN::uninitialized(seeds.size()); c = WBN::uninitialized(seeds.size()); ok = hip::mask(seeds.size());
+    hip::check(ecsimd_hip_bip32_master(hip::context(), seeds.data(), seeds.msg_bytes(), seeds.stride_bytes(), k.data(), c.data(), ok.data(), seeds.size()), "ecsimd_hip_bip32_master");
+    return k;
+  }
+  // CKDpriv of the SECRET nodes (k, c) at one index for every lane, or at index[i]; c_child is written, the child key returned.  ok[i] is false -- and both are
+  // 0 -- where k is not in [1, n).  flags: ECSIMD_HIP_BIP32_ALL_HARDENED, the promise that every index is hardened (no point multiplication).  A hardened index for
+  // every lane takes that route by itself.  k G runs on the constant-time comb; no branch or address depends on k, c or the results.
+  static WBN bip32_ckd_priv(WBN const& k, WBN const& c, uint32_t index, WBN& c_child, hip::mask& ok, int flags = 0) requires std::is_same_v<Curve, curve_secp256k1> {
+    return bip32_ckd_priv_impl(k, c, nullptr, index, c_child, ok, flags);
+  }
+  static WBN bip32_ckd_priv(WBN const& k, WBN const& c, hip::indices const& index, WBN& c_child, hip::mask& ok, int flags = 0) requires std::is_same_v<Curve, curve_secp256k1> {
+    same_length(k.size(), index.size(), "bip32_ckd_priv");
+    return bip32_ckd_priv_impl(k, c, index.data(), 0, c_child, ok, flags);
+  }
+  // CKDpub of the public nodes (q, c): the child point; ok[i] is false -- and the outputs 0 -- for a hardened index and for a q that is not on the curve.  Public data.
+  static WCP bip32_ckd_pub(WCP const& q, WBN const& c, uint32_t index, WBN& c_child, hip::mask& ok) requires std::is_same_v<Curve, curve_secp256k1> {
+    return bip32_ckd_pub_impl(q, c, nullptr, index, c_child, ok);
+  }
+  static WCP bip32_ckd_pub(WCP const& q, WBN const& c, hip::indices const& index, WBN& c_child, hip::mask& ok) requires std::is_same_v<Curve, curve_secp256k1> {
+    same_length(c.size(), index.size(), "bip32_ckd_pub");
+    return bip32_ckd_pub_impl(q, c, index.data(), 0, c_child, ok);
+  }
+  // the node at the end of `path` below the SECRET nodes (k, c): one bip32_ckd_priv per level; ok is the AND of the levels' masks
+  static WBN bip32_derive_priv(WBN const& k, WBN const& c, std::vector<uint32_t> const& path, WBN& c_out, hip::mask& ok) requires std::is_same_v<Curve, curve_secp256k1> {
+    WBN key = k; c_out = c; ok = hip::mask::filled(k.size(), true);
+    for (uint32_t index : path) {
+      WBN cc; hip::mask level;
+      key = bip32_ckd_priv(key, c_out, index, cc, level);
+      c_out = cc;
+      ok = ok && level;
+    }
+    return key;
+  }
   // ---- several GPUs: k[i] * P[i] for HOST arrays, sharded over a device group.  P affine classical (x, y);
   // the result is what scalar_mult(x, from_affine(P)) returns lane by lane -- Jacobian, Montgomery form -- or, with
   // affine_out, what .to_affine() of it returns.  Member m computes the slice device_group::shard_range(n, m, size());
@@ -276,6 +313,19 @@ struct curve_group {
     return r;
   }
  private:
+  static WBN bip32_ckd_priv_impl(WBN const& k, WBN const& c, const uint32_t* index, uint32_t index_all, WBN& c_child, hip::mask& ok, int flags) {
+    same_length(k.size(), c.size(), "bip32_ckd_priv");
+    auto out = WBN::uninitialized(k.size()); c_child = WBN::uninitialized(k.size()); ok = hip::mask(k.size());
+    hip::check(ecsimd_hip_bip32_ckd_priv(hip::context(), k.data(), c.data(), index, index_all, out.data(), c_child.data(), ok.data(), k.size(), flags), "ecsimd_hip_bip32_ckd_priv");
+    return out;
+  }
+  static WCP bip32_ckd_pub_impl(WCP const& q, WBN const& c, const uint32_t* index, uint32_t index_all, WBN& c_child, hip::mask& ok) {
+    same_length(q.x().size(), c.size(), "bip32_ckd_pub");
+    auto cx = WBN::uninitialized(c.size()); auto cy = WBN::uninitialized(c.size()); c_child = WBN::uninitialized(c.size()); ok = hip::mask(c.size());
+    hip::check(ecsimd_hip_bip32_ckd_pub(hip::context(), q.x().data(), q.y().data(), c.data(), index, index_all, cx.data(), cy.data(), c_child.data(), ok.data(), c.size()),
+               "ecsimd_hip_bip32_ckd_pub");
+    return WCP{cx, cy};
+  }
   // The C ABI takes one length for all operands (in the reference it is a property of the type): a shorter batch would be
   // read or written out of bounds on the device.
   static void same_length(size_t a, size_t b, const char* what) {

@@ -531,6 +531,51 @@ int ecsimd_hip_btc_pubkey_hash(ecsimd_hip_ctx*, const uint64_t* qx, const uint64
 int ecsimd_hip_xonly_tweak_add(ecsimd_hip_ctx*, const uint64_t* px, const uint64_t* t, uint64_t* qx, uint8_t* parity, uint8_t* ok, size_t n);
 int ecsimd_hip_taproot_tweak_pubkey(ecsimd_hip_ctx*, const uint64_t* px, const uint64_t* merkle_root, uint64_t* qx, uint8_t* parity, uint8_t* ok, size_t n);
 int ecsimd_hip_taproot_tweak_seckey(ecsimd_hip_ctx*, const uint64_t* d, const uint64_t* merkle_root, uint64_t* d_out, uint64_t* px, uint8_t* ok, size_t n);
+/* SHA-512 and HMAC-SHA-512 (RFC 2104) over n equal-length messages, message i at msg + i * stride_bytes, msg_bytes long, as for ecsimd_hip_sha256: any length
+ * including 0 (msg may then be NULL), stride_bytes >= msg_bytes, any alignment (word loads where base and stride are multiples of 4, byte loads otherwise).
+ * PUBLIC data: the loads and the block loop follow the length; do not hash a secret with these.  out64: n x 64 bytes of device memory, 16-byte aligned: lane
+ * i's digest at out64 + 64 i, its bytes in order.  Stream-ordered; no workspace.  One message per lane; the eight 64-bit state words and the sixteen-word
+ * schedule stay in registers, the 80 rounds are unrolled.
+ *   sha512        SHA-512(m): c compressions for a message of c 128-byte blocks (padding and the 128-bit length included).
+ *   hmac_sha512   HMAC(key, m).  Lane i's key: key_bytes bytes at key + i * key_stride_bytes; key_stride_bytes == 0: ONE key for the whole call (otherwise
+ *                 key_stride_bytes >= key_bytes).  A key of at most 128 bytes is zero-padded to one block, a longer one is hashed first.  The key's ipad and
+ *                 opad blocks are compressed once each, the message is absorbed behind the first, ONE outer block finishes: c + 3 compressions. */
+int ecsimd_hip_sha512(ecsimd_hip_ctx*, const uint8_t* msg, size_t msg_bytes, size_t stride_bytes, uint8_t* out64, size_t n);
+int ecsimd_hip_hmac_sha512(ecsimd_hip_ctx*, const uint8_t* key, size_t key_bytes, size_t key_stride_bytes,
+                           const uint8_t* msg, size_t msg_bytes, size_t stride_bytes, uint8_t* out64, size_t n);
+/* BIP-32 hierarchical key derivation.  secp256k1 only: no curve id.  Keys and chain codes are 4 x u64 little-endian limbs per element (the integer whose 32
+ * big-endian bytes the BIP writes), 16-byte aligned.  index: n x u32 of device memory, 4-byte aligned, one index per lane; index == NULL: every lane uses
+ * index_all.  An index is PUBLIC; i >= 2^31 is a hardened one.  Stream-ordered, nothing is read back.  No ECSIMD_HIP_REF_SQUARE_COMPAT form (ERR_BAD_ARG on a
+ * context with that option).  Any n (2^22 at a time); outputs must not alias inputs or each other.  Depth, parent fingerprint (the first four bytes of
+ * ecsimd_hip_btc_pubkey_hash) and the Base58Check strings are the caller's bookkeeping.
+ * Three refusals exist that no test can reach -- IL >= n, a child key of 0, an infinite child point: each has probability about 2^-128 and an input that
+ * provokes one would have to invert HMAC-SHA-512.
+ *
+ * bip32_master, SECRET data: I = HMAC-SHA512("Bitcoin seed", seed), k = IL, c = IR.  Lane i's seed: seed_bytes bytes (16 .. 64, the same for every lane, else
+ * ERR_BAD_ARG) at seed + i * stride_bytes, any alignment.  The key's two midstates are compile-time constants: two compressions per lane.  ok[i] = 0 and
+ * k = c = 0 where IL = 0 or IL >= n.  Masks and selects only; only the public length steers the loads.  No workspace.
+ *
+ * bip32_ckd_priv, SECRET data: I = HMAC-SHA512(c_par, 00 || ser256(k_par) || ser32(i)) for a hardened i, HMAC-SHA512(c_par, serP(k_par G) || ser32(i))
+ * otherwise; k_child = IL + k_par mod n, c_child = IR.  ok[i] = 0 and k_child = c_child = 0 where k_par is not in [1, n - 1], IL >= n or k_child = 0.  k_par,
+ * c_par, the Jacobian and the affine k_par G, I, k_child and c_child are SECRETS: k_par G runs on the constant-time comb (the kernel of ALG_WINDOWED |
+ * ALG_CONSTANT_TIME) and the select-only simultaneous inversion, the kernel behind them builds the 37 bytes in registers, chooses between the two forms by a
+ * select on bit 31 of the index and selects by masks -- no branch, address or lane mask in force at a memory access depends on a secret and no bit is
+ * declassified (tools/ct_check.py check_secret_flow on the shipped ISA: tests/test_bip32_cpu.py).  Four compressions per lane.
+ * flags = ECSIMD_HIP_BIP32_ALL_HARDENED: the caller's promise that every index has bit 31 set; the comb and the inversion are skipped and no workspace is used.  A
+ * lane that breaks the promise returns ok = 0 and zeros.  With index == NULL the call sees index_all and takes that route by itself.  Every workspace byte the
+ * call used is zeroed on the stream before it returns, whatever the launches said.  Workspace: 160 B per element of a chunk, none on the hardened-only route.
+ *
+ * bip32_ckd_pub, PUBLIC data: I = HMAC-SHA512(c_par, serP(K) || ser32(i)) with K = (qx, qy); (cx, cy) = IL G + K, c_child = IR.  ok[i] = 1 iff i < 2^31, K is
+ * on the curve (qx, qy < p), IL < n and the sum is finite; else cx = cy = c_child = 0.  Per chunk: one kernel hashes and validates, IL G comes from the public
+ * comb (indexed by the digits of IL: not for secrets), k_tweak_add adds, ONE simultaneous inversion, one kernel accepts -- the chain of
+ * ecsimd_hip_xonly_tweak_add, keeping both coordinates.  Workspace: 193 B per element of a chunk. */
+enum { ECSIMD_HIP_BIP32_ALL_HARDENED = 1 };
+int ecsimd_hip_bip32_master(ecsimd_hip_ctx*, const uint8_t* seed, size_t seed_bytes, size_t stride_bytes,
+                            uint64_t* k, uint64_t* c, uint8_t* ok, size_t n);
+int ecsimd_hip_bip32_ckd_priv(ecsimd_hip_ctx*, const uint64_t* k_par, const uint64_t* c_par, const uint32_t* index, uint32_t index_all,
+                              uint64_t* k_child, uint64_t* c_child, uint8_t* ok, size_t n, int flags);
+int ecsimd_hip_bip32_ckd_pub(ecsimd_hip_ctx*, const uint64_t* qx, const uint64_t* qy, const uint64_t* c_par, const uint32_t* index, uint32_t index_all,
+                             uint64_t* cx, uint64_t* cy, uint64_t* c_child, uint8_t* ok, size_t n);
 /* Diagnostic (r5): ONE function of the reduced-radix layer the multiplication-bound loops run on (fe29.cuh: nine signed 29-bit limbs in 32-bit words,
  * Montgomery radix 2^261, lazy carries) on RAW operands -- int32 limbs exactly as a loop holds them between two operations: element e's coordinate c, limb l at
  * in[(e * NIN + c) * 9 + l] (device memory).  What tests use to hand the device the states and operand pairs at which the interval proofs of
