@@ -10,6 +10,7 @@
 #include <stdint.h>
 #include <stdio.h>
 #include <string.h>
+#include <initializer_list>
 #include <mutex>
 #include <new>
 #include <vector>
@@ -104,6 +105,29 @@ int bad(ecsimd_hip_ctx* ctx, const char* what) {
   return ECSIMD_HIP_ERR_BAD_ARG;
 }
 bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15u) == 0; }
+bool overlaps(const void* a, const void* b) { return a == b; }
+// An output that is one of the inputs (a null input is an argument the caller left out) or another output.
+bool any_alias(std::initializer_list<const void*> out, std::initializer_list<const void*> in) {
+  for (auto a = out.begin(); a != out.end(); ++a) {
+    for (const void* b : in) if (b && overlaps(*a, b)) return true;
+    for (auto b = a + 1; b != out.end(); ++b) if (overlaps(*a, *b)) return true;
+  }
+  return false;
+}
+
+// The way into every batched call, behind its argument checks: an empty batch is done, one launch covers at most 2^31 - 1 workgroups, the context's device is
+// current.  ENTER_ANY_SIZE: the calls that go through the batch in chunks (or in a strided loop) and so take any n.
+constexpr size_t MAX_LAUNCH = (size_t)0x7fffffff * BLOCK;
+#define ENTER_IF(one_launch) do { \
+    if (n == 0) return ECSIMD_HIP_OK; \
+    if ((one_launch) && n > MAX_LAUNCH) return bad(ctx, "batch too large"); \
+    hipError_t e0_ = hipSetDevice(ctx->device); if (e0_ != hipSuccess) return fail(ctx, e0_, "hipSetDevice"); } while (0)
+#define ENTER() ENTER_IF(true)
+#define ENTER_ANY_SIZE() ENTER_IF(false)
+// for (first, m) over a batch of n in chunks of `chunk`: m is the chunk's length, the last one's may be shorter
+#define FOR_CHUNKS(first, m, n, chunk) \
+  for (size_t first = 0, m = (n) < (chunk) ? (n) : (chunk); first < (n); first += (chunk), m = (n) - first < (chunk) ? (n) - first : (chunk))
+size_t chunk_of(size_t n, size_t most) { return n < most ? n : most; }
 
 #define REQUIRE_CTX() do { if (!ctx) return ECSIMD_HIP_ERR_BAD_ARG; } while (0)
 #define REQUIRE_PTR(p) do { if (!(p) && n) return bad(ctx, #p " is null"); if (!aligned16(p)) return bad(ctx, #p " is not 16-byte aligned"); } while (0)
@@ -115,9 +139,7 @@ bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15u) ==
 #define GENERIC_CURVE(call) do { if (curve >= ECSIMD_HIP_FIRST_REGISTERED_CURVE) { gcurve GC; if (!lookup_curve(curve, &GC)) return bad(ctx, "unknown curve id"); RUN(call); } } while (0)
 // Enqueue one launcher call on the context's stream; report launch errors.
 #define RUN(call) do { \
-    if (n == 0) return ECSIMD_HIP_OK; \
-    if (n > (size_t)0x7fffffff * BLOCK) return bad(ctx, "batch too large"); \
-    hipError_t e0_ = hipSetDevice(ctx->device); if (e0_ != hipSuccess) return fail(ctx, e0_, "hipSetDevice"); \
+    ENTER(); \
     hipStream_t s = ctx->stream; (void)s; \
     call; \
     hipError_t e_ = hipGetLastError(); if (e_ != hipSuccess) return fail(ctx, e_, #call); \
@@ -126,6 +148,10 @@ bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15u) ==
 void words_to_limbs(const uint32_t (&w)[8], uint64_t out[4]) {
   for (int i = 0; i < 4; ++i) out[i] = (uint64_t)w[2 * i] | ((uint64_t)w[2 * i + 1] << 32);
 }
+void limbs_to_words(const uint64_t l[4], uint32_t (&w)[8]) {
+  for (int i = 0; i < 4; ++i) { w[2 * i] = (uint32_t)l[i]; w[2 * i + 1] = (uint32_t)(l[i] >> 32); }
+}
+launch::words8 words8_of(const uint64_t l[4]) { launch::words8 w; limbs_to_words(l, w.w); return w; }     // a 256-bit value as the kernels take it by value
 
 // 256-bit host arithmetic (table plans, run-time moduli and curves): four 64-bit limbs, least significant first
 struct u256 { uint64_t l[4]; };
@@ -147,29 +173,43 @@ bool capturing(ecsimd_hip_ctx* ctx) {
   if (hipStreamIsCapturing(ctx->stream, &st) != hipSuccess) { (void)hipGetLastError(); return false; }
   return st != hipStreamCaptureStatusNone;
 }
-int ensure_workspace(ecsimd_hip_ctx* ctx, size_t bytes) {
-  if (ctx->workspace_bytes >= bytes) return ECSIMD_HIP_OK;
+template <class T>
+int ensure_block(ecsimd_hip_ctx* ctx, T*& block, size_t& have, size_t bytes, const char* during_capture, const char* what) {
+  if (have >= bytes) return ECSIMD_HIP_OK;
   // Growing frees the old block: pointers a hipGraph captured earlier would dangle, and a capture in progress can neither
   // synchronise nor allocate.  The caller warms the path up at its largest batch BEFORE capturing (include/ecsimd_hip.h).
-  if (capturing(ctx)) return bad(ctx, "the context workspace would have to grow during stream capture: run this call once at the largest batch size before capturing");
+  if (capturing(ctx)) return bad(ctx, during_capture);
   hipError_t e = hipStreamSynchronize(ctx->stream);
-  if (e == hipSuccess && ctx->workspace) e = hipFree(ctx->workspace);
-  ctx->workspace = nullptr; ctx->workspace_bytes = 0;
-  if (e == hipSuccess) e = hipMalloc(&ctx->workspace, bytes);
-  if (e != hipSuccess) return fail(ctx, e, "workspace hipMalloc");
-  ctx->workspace_bytes = bytes;
+  if (e == hipSuccess && block) e = hipFree(block);
+  block = nullptr; have = 0;
+  if (e == hipSuccess) e = hipMalloc(&block, bytes);
+  if (e != hipSuccess) return fail(ctx, e, what);
+  have = bytes;
   return ECSIMD_HIP_OK;
 }
-
+int ensure_workspace(ecsimd_hip_ctx* ctx, size_t bytes) {
+  return ensure_block(ctx, ctx->workspace, ctx->workspace_bytes, bytes, "the context workspace would have to grow during stream capture: run this call once at the largest batch size before capturing", "workspace hipMalloc");
+}
 int ensure_valid(ecsimd_hip_ctx* ctx, size_t bytes) {
-  if (ctx->valid_bytes >= bytes) return ECSIMD_HIP_OK;
-  if (capturing(ctx)) return bad(ctx, "the validity buffer would have to grow during stream capture: run this call once at the largest batch size before capturing");
-  hipError_t e = hipStreamSynchronize(ctx->stream);
-  if (e == hipSuccess && ctx->valid) e = hipFree(ctx->valid);
-  ctx->valid = nullptr; ctx->valid_bytes = 0;
-  if (e == hipSuccess) e = hipMalloc(&ctx->valid, bytes);
-  if (e != hipSuccess) return fail(ctx, e, "validity buffer hipMalloc");
-  ctx->valid_bytes = bytes;
+  return ensure_block(ctx, ctx->valid, ctx->valid_bytes, bytes, "the validity buffer would have to grow during stream capture: run this call once at the largest batch size before capturing", "validity buffer hipMalloc");
+}
+
+// A bump pointer over the workspace: limbs for m elements (32 B each), flag bytes for m elements (rounded up to 16), raw bytes.  A call carves twice with the
+// same function: from a null base, where only `bytes` counts -- the size to ask ensure_workspace for --, and from ctx->workspace, which places the arrays.
+struct carve { uint8_t* base; size_t bytes; };
+carve carve_from(void* base) { return {static_cast<uint8_t*>(base), 0}; }
+void* carve_bytes(carve& c, size_t bytes) { void* p = c.base ? c.base + c.bytes : nullptr; c.bytes += bytes; return p; }
+uint64_t* carve_limbs(carve& c, size_t m) { return static_cast<uint64_t*>(carve_bytes(c, m * 32)); }
+size_t flag_bytes(size_t m) { return (m + 15) / 16 * 16; }
+uint8_t* carve_flags(carve& c, size_t m) { return static_cast<uint8_t*>(carve_bytes(c, flag_bytes(m))); }
+struct jacobian { uint64_t *x, *y, *z; };
+jacobian carve_jacobian(carve& c, size_t m) { jacobian j; j.x = carve_limbs(c, m); j.y = carve_limbs(c, m); j.z = carve_limbs(c, m); return j; }
+// The Jacobian product of n lanes at the start of the workspace, grown to hold it: all that a product whose affine result goes to the caller's arrays needs.
+size_t jacobian_bytes(size_t n) { carve c = carve_from(nullptr); (void)carve_jacobian(c, n); return c.bytes; }
+int ensure_jacobian(ecsimd_hip_ctx* ctx, size_t n, jacobian* j) {
+  int rc = ensure_workspace(ctx, jacobian_bytes(n));
+  if (rc != ECSIMD_HIP_OK) return rc;
+  carve c = carve_from(ctx->workspace); *j = carve_jacobian(c, n);
   return ECSIMD_HIP_OK;
 }
 
@@ -282,23 +322,63 @@ int ensure_window_table(ecsimd_hip_ctx* ctx, int curve, int bits) {
   return ECSIMD_HIP_OK;
 }
 
-bool overlaps(const void* a, const void* b) { return a == b; }
-
 // The kernel instance an entry point runs: the API curve, or its reference-square twin (field.cuh) when the
 // context option or the call's ECSIMD_HIP_REF_SQUARE_COMPAT flag asks for the reference's bits.
+bool wants_compat(const ecsimd_hip_ctx* ctx, int flags = 0) { return ctx->ref_square || (flags & ECSIMD_HIP_REF_SQUARE_COMPAT); }
 int instance(const ecsimd_hip_ctx* ctx, int curve, int flags = 0) {
-  return (ctx->ref_square || (flags & ECSIMD_HIP_REF_SQUARE_COMPAT)) ? curve + (CURVE_P256_REFSQR - CURVE_P256) : curve;
+  return wants_compat(ctx, flags) ? curve + (CURVE_P256_REFSQR - CURVE_P256) : curve;
 }
 static_assert(CURVE_SECP256K1_REFSQR - CURVE_SECP256K1 == CURVE_P256_REFSQR - CURVE_P256, "instance() adds one offset");
-#define NO_COMPAT(what) do { if (ctx->ref_square || (flags & ECSIMD_HIP_REF_SQUARE_COMPAT)) return bad(ctx, what " is not the reference's algorithm: no ECSIMD_HIP_REF_SQUARE_COMPAT form"); } while (0)
+// What every call that is not the reference's own ladder or formulas answers to wants_compat(); what = the call (nullptr: the message names none).
+int refuse_compat(ecsimd_hip_ctx* ctx, const char* what) {
+  snprintf(ctx->err, sizeof ctx->err, "bad argument: %s%snot the reference's algorithm: no ECSIMD_HIP_REF_SQUARE_COMPAT form", what ? what : "", what ? " is " : "");
+  return ECSIMD_HIP_ERR_BAD_ARG;
+}
+#define NO_COMPAT(what) do { if (wants_compat(ctx, flags)) return refuse_compat(ctx, what); } while (0)
+
+// ---- the steps the entry points share
+// The group order of a built-in curve, as the scalar-field kernels (gmod) and the others (words) take it.
+struct group_order { gmod N; launch::words8 words; };
+bool lookup_modulus(int id, gmod* out);          // the modulus registry, below
+int builtin_order(ecsimd_hip_ctx* ctx, int curve, group_order* out) {
+  if (!lookup_modulus(curve == ECSIMD_HIP_P256 ? ECSIMD_HIP_FIELD_P256_ORDER : ECSIMD_HIP_FIELD_SECP256K1_ORDER, &out->N)) return bad(ctx, "group order missing from the registry");
+  for (int i = 0; i < 8; ++i) out->words.w[i] = out->N.p[i];
+  return ECSIMD_HIP_OK;
+}
+
+// k G for SECRET k on a built-in curve: the constant-time 5-bit comb (ensure_window_table(CT_WBITS) first), then the simultaneous inversion; y == nullptr: x only.
+// Stream-ordered, nothing read back.  The Jacobian product j and, where x / y lie in the workspace, the affine point are the caller's to wipe: with a public
+// function of the point (ECDSA's r), the Z of the unnormalised k G gives bits of k away (the projective-coordinate leak), and the block outlives the call
+// (grow-only, hipFree does not wipe).
+void secret_base_product(ecsimd_hip_ctx* ctx, int curve, const uint64_t* k, const jacobian& j, uint64_t* x, uint64_t* y, size_t m) {
+  launch::base_windowed_signed(ctx->stream, curve, k, ctx->windowct_table[curve], j.x, j.y, j.z, m, true);      // k >= n is reduced by the comb; the caller's kernel refuses the lane
+  launch::to_affine_batched(ctx->stream, curve, j.x, j.y, j.z, x, y, m, true);
+}
+// The end of a scope that left secrets in the first `bytes` of the workspace (its carve's total): zero them on the same stream, behind the scope's launches and
+// whatever those said -- `launches` is their hipGetLastError().  Returns the first error of the two.
+hipError_t wipe_workspace(ecsimd_hip_ctx* ctx, size_t bytes, hipError_t launches) {
+  const hipError_t wiped = hipMemsetAsync(ctx->workspace, 0, bytes, ctx->stream);
+  return launches != hipSuccess ? launches : wiped;
+}
+
+// u G for PUBLIC u on a built-in curve: the 20-bit comb in device memory (436 MB per curve, built on first use) once that table exists or a batch of `batch`
+// elements is large enough to pay for building it; smaller batches take the signed 7-bit comb in LDS.  Ensures the table, then launches m lanes of it; u == nullptr:
+// the table only, for a caller that sizes its workspace and launches its front end before its chunk loop gets here.
+constexpr size_t BIG_TABLE_WORTH_IT = (size_t)1 << 16;
+int public_base_product(ecsimd_hip_ctx* ctx, int curve, size_t batch, const uint64_t* u = nullptr, const jacobian* j = nullptr, size_t m = 0) {
+  const bool big = ctx->window16_table[curve] != nullptr || batch >= BIG_TABLE_WORTH_IT;
+  int rc = ensure_window_table(ctx, curve, big ? launch::BIG_WINDOW_BITS : SIGNED_WBITS);
+  if (rc != ECSIMD_HIP_OK || !u) return rc;
+  if (big) launch::base_windowed_big(ctx->stream, curve, u, ctx->window16_table[curve], j->x, j->y, j->z, m);
+  else launch::base_windowed_signed(ctx->stream, curve, u, ctx->window6_table[curve], j->x, j->y, j->z, m, false);
+  return ECSIMD_HIP_OK;
+}
 
 // The reference ladder, then (for OUT_AFFINE) one simultaneous inversion over the whole batch.
 int run_ladder(ecsimd_hip_ctx* ctx, int curve, const uint64_t* k, int k_stride, const uint64_t* x, const uint64_t* y,
                uint64_t* ox, uint64_t* oy, uint64_t* oz, size_t n, int flags) {
-  if (n == 0) return ECSIMD_HIP_OK;
-  if (n > (size_t)0x7fffffff * BLOCK) return bad(ctx, "batch too large");
-  hipError_t e = hipSetDevice(ctx->device);
-  if (e != hipSuccess) return fail(ctx, e, "hipSetDevice");
+  ENTER();
+  hipError_t e;
   if ((flags & ECSIMD_HIP_OUT_AFFINE) && oy == nullptr && curve == ECSIMD_HIP_P256 && instance(ctx, curve, flags) == curve) {
     // x only: the ladder without Z (point.cuh scalar_mult_ladder_x) -- 8M + 6S per bit instead of 9M + 7S
     int rc = ensure_workspace(ctx, launch::scalar_mult_x_scratch_bytes(n));
@@ -308,14 +388,13 @@ int run_ladder(ecsimd_hip_ctx* ctx, int curve, const uint64_t* k, int k_stride, 
     return e == hipSuccess ? ECSIMD_HIP_OK : fail(ctx, e, "scalar_mult (x only) launch");
   }
   if (flags & ECSIMD_HIP_OUT_AFFINE) {
-    int rc = ensure_workspace(ctx, 3 * n * 32);
+    jacobian j; int rc = ensure_jacobian(ctx, n, &j);
     if (rc != ECSIMD_HIP_OK) return rc;
-    uint64_t* jx = ctx->workspace; uint64_t* jy = jx + 4 * n; uint64_t* jz = jy + 4 * n;
     const int cv = instance(ctx, curve, flags);
-    launch::scalar_mult(ctx->stream, cv, k, k_stride, x, y, jx, jy, jz, n, flags);
+    launch::scalar_mult(ctx->stream, cv, k, k_stride, x, y, j.x, j.y, j.z, n, flags);
     // reference-square instances: to_affine() per element with the reference's own power ladder (gfp.h:42-44)
-    if (cv != curve) launch::to_affine(ctx->stream, cv, jx, jy, jz, ox, oy, n);
-    else launch::to_affine_batched(ctx->stream, curve, jx, jy, jz, ox, oy, n, true);
+    if (cv != curve) launch::to_affine(ctx->stream, cv, j.x, j.y, j.z, ox, oy, n);
+    else launch::to_affine_batched(ctx->stream, curve, j.x, j.y, j.z, ox, oy, n, true);
   } else {
     launch::scalar_mult(ctx->stream, instance(ctx, curve, flags), k, k_stride, x, y, ox, oy, oz, n, flags);
   }
@@ -343,23 +422,19 @@ int run_gladder(ecsimd_hip_ctx* ctx, int curve, const uint64_t* k, int k_stride,
     return run_gvarwin(ctx, curve, k, k_stride, x, y, ox, oy, n, flags, 0);   // k P from the lane's own table of odd multiples (k_gvarwin.hip); ALG_CONSTANT_TIME: every entry read in every window
   if (flags & (ECSIMD_HIP_ALG_WINDOWED | ECSIMD_HIP_ALG_WINDOWED_SIGNED | ECSIMD_HIP_ALG_WINDOWED_BIG | ECSIMD_HIP_ALG_NO_ENDOMORPHISM | ECSIMD_HIP_ALG_CONSTANT_TIME))
     return bad(ctx, "a registered curve has the reference's ladder, ALG_WINDOWED [| ALG_CONSTANT_TIME] for its generator and for a variable base, and ALG_WINDOWED_SIGNED / ALG_WINDOWED_BIG for its generator: the other combinations (the GLV split, constant-time forms of the signed and big combs) exist for P-256 and secp256k1 or not at all");
-  if (n == 0) return ECSIMD_HIP_OK;
-  if (n > (size_t)0x7fffffff * BLOCK) return bad(ctx, "batch too large");
-  hipError_t e = hipSetDevice(ctx->device);
-  if (e != hipSuccess) return fail(ctx, e, "hipSetDevice");
-  const bool ref = ctx->ref_square || (flags & ECSIMD_HIP_REF_SQUARE_COMPAT);
+  ENTER();
+  const bool ref = wants_compat(ctx, flags);
   const int lf = (flags & (ECSIMD_HIP_BASE_MGRY | ECSIMD_HIP_LADDER_RADIX32)) | (ref ? ECSIMD_HIP_REF_SQUARE_COMPAT : 0);
   if (flags & ECSIMD_HIP_OUT_AFFINE) {
-    int rc = ensure_workspace(ctx, 3 * n * 32);
+    jacobian j; int rc = ensure_jacobian(ctx, n, &j);
     if (rc != ECSIMD_HIP_OK) return rc;
-    uint64_t* jx = ctx->workspace; uint64_t* jy = jx + 4 * n; uint64_t* jz = jy + 4 * n;
-    launch::gc_scalar_mult(ctx->stream, GC, k, k_stride, x, y, jx, jy, jz, n, lf);
-    if (ref) launch::gc_to_affine(ctx->stream, GC, jx, jy, jz, ox, oy, n, true);       // the reference's own power ladder per element (gfp.h:42-44)
-    else launch::gc_to_affine_batched(ctx->stream, GC, jx, jy, jz, ox, oy, n);
+    launch::gc_scalar_mult(ctx->stream, GC, k, k_stride, x, y, j.x, j.y, j.z, n, lf);
+    if (ref) launch::gc_to_affine(ctx->stream, GC, j.x, j.y, j.z, ox, oy, n, true);       // the reference's own power ladder per element (gfp.h:42-44)
+    else launch::gc_to_affine_batched(ctx->stream, GC, j.x, j.y, j.z, ox, oy, n);
   } else {
     launch::gc_scalar_mult(ctx->stream, GC, k, k_stride, x, y, ox, oy, oz, n, lf);
   }
-  e = hipGetLastError();
+  hipError_t e = hipGetLastError();
   return e == hipSuccess ? ECSIMD_HIP_OK : fail(ctx, e, "scalar_mult (registered curve) launch");
 }
 
@@ -368,18 +443,14 @@ int run_gladder(ecsimd_hip_ctx* ctx, int curve, const uint64_t* k, int k_stride,
 constexpr size_t VARWIN_CHUNK = (size_t)1 << 22;
 int run_varwin(ecsimd_hip_ctx* ctx, int curve, const uint64_t* k, int k_stride, const uint64_t* x, const uint64_t* y,
                uint64_t* ox, uint64_t* oy, size_t n, int flags, size_t reserve) {
-  if (n == 0) return ECSIMD_HIP_OK;
-  hipError_t e = hipSetDevice(ctx->device);
-  if (e != hipSuccess) return fail(ctx, e, "hipSetDevice");
-  const size_t chunk = n < VARWIN_CHUNK ? n : VARWIN_CHUNK;
+  ENTER_ANY_SIZE();
+  const size_t chunk = chunk_of(n, VARWIN_CHUNK);
   int rc = ensure_workspace(ctx, reserve + launch::varwin_scratch_bytes(chunk));
   if (rc != ECSIMD_HIP_OK) return rc;
   uint64_t* scratch = ctx->workspace + reserve / 8;
-  for (size_t first = 0; first < n; first += chunk) {
-    const size_t m = (n - first) < chunk ? (n - first) : chunk;
+  FOR_CHUNKS(first, m, n, chunk)
     launch::varwin_scalar_mult(ctx->stream, curve, k + (size_t)k_stride * first, k_stride, x + 4 * first, y + 4 * first, flags, scratch, ox + 4 * first, oy ? oy + 4 * first : nullptr, m);
-  }
-  e = hipGetLastError();
+  hipError_t e = hipGetLastError();
   return e == hipSuccess ? ECSIMD_HIP_OK : fail(ctx, e, "scalar_mult (windowed) launch");
 }
 }  // namespace
@@ -428,7 +499,7 @@ void u_dbl_mod(u256& a, const u256& p) {                       // a < p  ->  2a 
   a.l[0] <<= 1;
   if (top || u_geq(a, p)) { u256 t; (void)u_sub(t, a, p); a = t; }
 }
-void u_words(uint32_t (&w)[8], const u256& v) { for (int i = 0; i < 4; ++i) { w[2 * i] = (uint32_t)v.l[i]; w[2 * i + 1] = (uint32_t)(v.l[i] >> 32); } }
+void u_words(uint32_t (&w)[8], const u256& v) { limbs_to_words(v.l, w); }
 gmod make_gmod(const uint64_t pl[4], uint32_t flags) {
   gmod M; memset(&M, 0, sizeof M);
   u256 p; for (int i = 0; i < 4; ++i) p.l[i] = pl[i];
@@ -880,9 +951,8 @@ int ecsimd_hip_mask_op(ecsimd_hip_ctx* ctx, int op, const uint8_t* a, const uint
 int ecsimd_hip_mask_count(ecsimd_hip_ctx* ctx, const uint8_t* a, size_t n, size_t* count) {
   REQUIRE_CTX(); if (!count) return bad(ctx, "count is null");
   *count = 0;
-  if (n == 0) return ECSIMD_HIP_OK;
-  if (!a) return bad(ctx, "mask pointer is null");
-  (void)hipSetDevice(ctx->device);
+  if (!a && n) return bad(ctx, "mask pointer is null");
+  ENTER_ANY_SIZE();
   unsigned long long* slot = reinterpret_cast<unsigned long long*>(ctx->sink + 1024 - 16);     // 8-byte slot next to the shared scalar
   hipError_t e = hipMemsetAsync(slot, 0, sizeof *slot, ctx->stream);
   if (e == hipSuccess) { launch::mask_count(ctx->stream, a, n, slot); e = hipGetLastError(); }
@@ -913,13 +983,13 @@ int ecsimd_hip_wide4_to_lanes(ecsimd_hip_ctx* ctx, const void* wides, size_t rec
   REQUIRE_CTX(); const size_t n = 4 * n_wides; REQUIRE_PTR(out); if (!wides && n) return bad(ctx, "wides is null");
   if (static_cast<const void*>(out) == wides) return bad(ctx, "the transposition is not in place: out must not alias wides");
   if (record_bytes < 128 || (record_bytes & 7u) || (offset_bytes & 7u) || offset_bytes + 128 > record_bytes || (reinterpret_cast<uintptr_t>(wides) & 7u)) return bad(ctx, "a wide is 128 bytes at an 8-byte aligned offset inside its record");
-  if (n_wides > (size_t)0x7fffffff * (BLOCK / 4)) return bad(ctx, "batch too large");
+  if (n_wides > MAX_LAUNCH / 4) return bad(ctx, "batch too large");
   RUN(launch::wide4_to_lanes(s, wides, record_bytes, offset_bytes, out, n)); }
 int ecsimd_hip_lanes_to_wide4(ecsimd_hip_ctx* ctx, const uint64_t* in, void* wides, size_t record_bytes, size_t offset_bytes, size_t n_wides) {
   REQUIRE_CTX(); const size_t n = 4 * n_wides; REQUIRE_PTR(in); if (!wides && n) return bad(ctx, "wides is null");
   if (static_cast<const void*>(in) == wides) return bad(ctx, "the transposition is not in place: wides must not alias in");
   if (record_bytes < 128 || (record_bytes & 7u) || (offset_bytes & 7u) || offset_bytes + 128 > record_bytes || (reinterpret_cast<uintptr_t>(wides) & 7u)) return bad(ctx, "a wide is 128 bytes at an 8-byte aligned offset inside its record");
-  if (n_wides > (size_t)0x7fffffff * (BLOCK / 4)) return bad(ctx, "batch too large");
+  if (n_wides > MAX_LAUNCH / 4) return bad(ctx, "batch too large");
   RUN(launch::lanes_to_wide4(s, in, wides, record_bytes, offset_bytes, n)); }
 int ecsimd_hip_mask_bit(ecsimd_hip_ctx* ctx, const uint64_t* a, int bit, uint8_t* flag, size_t n) {
   REQUIRE_CTX(); REQUIRE_PTR(a); if (!flag && n) return bad(ctx, "flag is null"); if (bit < 0 || bit > 255) return bad(ctx, "bit index");
@@ -955,7 +1025,7 @@ int ecsimd_hip_mgry_to_classical(ecsimd_hip_ctx* ctx, int curve, const uint64_t*
   REQUIRE_CTX(); REQUIRE_PTR(a); REQUIRE_PTR(out); FIELD_OR_CURVE(launch::gfield_unop(s, M, launch::F_TO_CLASSICAL, a, out, n, false)); RUN(launch::field_unop(s, instance(ctx, curve), launch::F_TO_CLASSICAL, a, out, n)); }
 int ecsimd_hip_mgry_pow(ecsimd_hip_ctx* ctx, int curve, const uint64_t* a, const uint64_t exponent[4], uint64_t* out, size_t n) {
   REQUIRE_CTX(); REQUIRE_PTR(a); REQUIRE_PTR(out); if (!exponent) return bad(ctx, "exponent is null");
-  launch::words8 e; for (int i = 0; i < 4; ++i) { e.w[2 * i] = (uint32_t)exponent[i]; e.w[2 * i + 1] = (uint32_t)(exponent[i] >> 32); }
+  const launch::words8 e = words8_of(exponent);
   FIELD_OR_CURVE(launch::gfield_pow(s, M, a, e, out, n, ctx->ref_square != 0));
   RUN(launch::mgry_pow(s, instance(ctx, curve), a, e, out, n)); }
 int ecsimd_hip_gfp_inverse(ecsimd_hip_ctx* ctx, int curve, const uint64_t* a, uint64_t* out, size_t n) {
@@ -990,7 +1060,7 @@ int ecsimd_hip_to_affine(ecsimd_hip_ctx* ctx, int curve, const uint64_t* jx, con
   REQUIRE_CTX(); REQUIRE_PTR(jx); REQUIRE_PTR(jy); REQUIRE_PTR(jz); REQUIRE_PTR(x);
   if (y && !aligned16(y)) return bad(ctx, "y is not 16-byte aligned");       // y == NULL: the x coordinate only
   // Simultaneous inversion uses x[] as scratch: only when the outputs do not alias the inputs.
-  const bool alias = overlaps(x, jx) || overlaps(x, jy) || overlaps(x, jz) || (y && (overlaps(y, jx) || overlaps(y, jy) || overlaps(y, jz) || overlaps(x, y)));
+  const bool alias = any_alias({x, y}, {jx, jy, jz});
   if (alias || ctx->ref_square) GENERIC_CURVE(launch::gc_to_affine(s, GC, jx, jy, jz, x, y, n, ctx->ref_square != 0));
   GENERIC_CURVE(launch::gc_to_affine_batched(s, GC, jx, jy, jz, x, y, n));
   REQUIRE_CURVE();
@@ -1032,6 +1102,22 @@ int ecsimd_hip_trplu(ecsimd_hip_ctx* ctx, int curve, uint64_t* px, uint64_t* py,
   REQUIRE_CTX(); REQUIRE_PTR(px); REQUIRE_PTR(py); REQUIRE_PTR(pz); REQUIRE_PTR(rx); REQUIRE_PTR(ry); REQUIRE_PTR(rz); GENERIC_CURVE(launch::gc_trplu(s, GC, px, py, pz, rx, ry, rz, n, ctx->ref_square != 0));
   REQUIRE_CURVE(); RUN(launch::trplu(s, instance(ctx, curve), px, py, pz, rx, ry, rz, n)); }
 
+// scalar_mult and scalar_mult_1s behind their argument checks: k_stride = 4 (a scalar per lane) or 0 (one for all).
+static int variable_base_mult(ecsimd_hip_ctx* ctx, int curve, const uint64_t* k, int k_stride, const uint64_t* x, const uint64_t* y, uint64_t* ox, uint64_t* oy, uint64_t* oz, size_t n, int flags) {
+  if (curve >= ECSIMD_HIP_FIRST_REGISTERED_CURVE) return run_gladder(ctx, curve, k, k_stride, x, y, ox, oy, oz, n, flags);
+  REQUIRE_CURVE();
+  if (flags & (ECSIMD_HIP_ALG_WINDOWED | ECSIMD_HIP_ALG_WINDOWED_SIGNED)) {
+    // per-lane window tables (8 multiples of P) in HBM + signed 4-bit windows (k_varwin.inc): a different algorithm from
+    // the reference ladder, so affine output only (SURVEY.md 8(a) level A)
+    if (!(flags & ECSIMD_HIP_OUT_AFFINE)) return bad(ctx, "ALG_WINDOWED needs OUT_AFFINE");
+    if ((flags & ECSIMD_HIP_ALG_CONSTANT_TIME) && (flags & ECSIMD_HIP_ALG_WINDOWED_SIGNED)) return bad(ctx, "ALG_CONSTANT_TIME modifies ALG_WINDOWED only, not ALG_WINDOWED_SIGNED");
+    NO_COMPAT("ALG_WINDOWED");
+    return run_varwin(ctx, curve, k, k_stride, x, y, ox, oy, n, flags, 0);
+  }
+  if (flags & ECSIMD_HIP_ALG_CONSTANT_TIME) return bad(ctx, "ALG_CONSTANT_TIME modifies ALG_WINDOWED (the ladder is constant-time as it is)");
+  return run_ladder(ctx, curve, k, k_stride, x, y, ox, oy, oz, n, flags);
+}
+
 int ecsimd_hip_scalar_mult(ecsimd_hip_ctx* ctx, int curve, const uint64_t* k, const uint64_t* x, const uint64_t* y, uint64_t* ox, uint64_t* oy, uint64_t* oz, size_t n, int flags) {
   REQUIRE_CTX();
   // no base point AND the caller says so (BASE_GENERATOR): the generator.  Two null pointers alone are an error, as they were before round 4 -- a caller whose
@@ -1041,18 +1127,7 @@ int ecsimd_hip_scalar_mult(ecsimd_hip_ctx* ctx, int curve, const uint64_t* k, co
   if (flags & ECSIMD_HIP_BASE_GENERATOR) return bad(ctx, "BASE_GENERATOR takes x = y = NULL");
   REQUIRE_PTR(k); REQUIRE_PTR(x); REQUIRE_PTR(y); REQUIRE_PTR(ox); REQUIRE_OUT_Y(oy);
   if (!(flags & ECSIMD_HIP_OUT_AFFINE)) REQUIRE_PTR(oz);
-  if (curve >= ECSIMD_HIP_FIRST_REGISTERED_CURVE) return run_gladder(ctx, curve, k, 4, x, y, ox, oy, oz, n, flags);
-  REQUIRE_CURVE();
-  if (flags & (ECSIMD_HIP_ALG_WINDOWED | ECSIMD_HIP_ALG_WINDOWED_SIGNED)) {
-    // per-lane window tables (8 multiples of P) in HBM + signed 4-bit windows (k_varwin.inc): a different algorithm from
-    // the reference ladder, so affine output only (SURVEY.md 8(a) level A)
-    if (!(flags & ECSIMD_HIP_OUT_AFFINE)) return bad(ctx, "ALG_WINDOWED needs OUT_AFFINE");
-    if ((flags & ECSIMD_HIP_ALG_CONSTANT_TIME) && (flags & ECSIMD_HIP_ALG_WINDOWED_SIGNED)) return bad(ctx, "ALG_CONSTANT_TIME modifies ALG_WINDOWED only, not ALG_WINDOWED_SIGNED");
-    NO_COMPAT("ALG_WINDOWED");
-    return run_varwin(ctx, curve, k, 4, x, y, ox, oy, n, flags, 0);
-  }
-  if (flags & ECSIMD_HIP_ALG_CONSTANT_TIME) return bad(ctx, "ALG_CONSTANT_TIME modifies ALG_WINDOWED (the ladder is constant-time as it is)");
-  return run_ladder(ctx, curve, k, 4, x, y, ox, oy, oz, n, flags); }
+  return variable_base_mult(ctx, curve, k, 4, x, y, ox, oy, oz, n, flags); }
 // ---- host arrays in, host arrays out: the PCIe-inclusive form of scalar_mult.  Chunks of 2^19 elements alternate between this context and a helper context (a
 // second HIP stream): while the ladder of one chunk runs, the calling thread copies the next chunk in on the other side and launches it, then waits for the
 // previous chunk and copies it out -- the copies of one chunk overlap the ladder of its neighbour and the GPU always has a launch queued; the caller's arrays
@@ -1121,20 +1196,10 @@ int ecsimd_hip_scalar_mult_1s(ecsimd_hip_ctx* ctx, int curve, const uint64_t k1[
   REQUIRE_CTX(); REQUIRE_PTR(x); REQUIRE_PTR(y); REQUIRE_PTR(ox); REQUIRE_OUT_Y(oy); if (!k1) return bad(ctx, "k1 is null");
   if (!(flags & ECSIMD_HIP_OUT_AFFINE)) REQUIRE_PTR(oz);
   if (curve < ECSIMD_HIP_FIRST_REGISTERED_CURVE) REQUIRE_CURVE();
-  launch::words8 w; for (int i = 0; i < 4; ++i) { w.w[2 * i] = (uint32_t)k1[i]; w.w[2 * i + 1] = (uint32_t)(k1[i] >> 32); }
   uint32_t* kdev = ctx->sink + 1024 - 8;    // 32-byte aligned slot at the end of the scratch page
-  if (n == 0) return ECSIMD_HIP_OK;
-  (void)hipSetDevice(ctx->device);
-  store_words(ctx->stream, w, kdev);
-  if (curve >= ECSIMD_HIP_FIRST_REGISTERED_CURVE) return run_gladder(ctx, curve, reinterpret_cast<const uint64_t*>(kdev), 0, x, y, ox, oy, oz, n, flags);
-  if (flags & (ECSIMD_HIP_ALG_WINDOWED | ECSIMD_HIP_ALG_WINDOWED_SIGNED)) {
-    if (!(flags & ECSIMD_HIP_OUT_AFFINE)) return bad(ctx, "ALG_WINDOWED needs OUT_AFFINE");
-    if ((flags & ECSIMD_HIP_ALG_CONSTANT_TIME) && (flags & ECSIMD_HIP_ALG_WINDOWED_SIGNED)) return bad(ctx, "ALG_CONSTANT_TIME modifies ALG_WINDOWED only, not ALG_WINDOWED_SIGNED");
-    NO_COMPAT("ALG_WINDOWED");
-    return run_varwin(ctx, curve, reinterpret_cast<const uint64_t*>(kdev), 0, x, y, ox, oy, n, flags, 0);
-  }
-  if (flags & ECSIMD_HIP_ALG_CONSTANT_TIME) return bad(ctx, "ALG_CONSTANT_TIME modifies ALG_WINDOWED (the ladder is constant-time as it is)");
-  return run_ladder(ctx, curve, reinterpret_cast<const uint64_t*>(kdev), 0, x, y, ox, oy, oz, n, flags); }
+  ENTER_ANY_SIZE();
+  store_words(ctx->stream, words8_of(k1), kdev);
+  return variable_base_mult(ctx, curve, reinterpret_cast<const uint64_t*>(kdev), 0, x, y, ox, oy, oz, n, flags); }
 int ecsimd_hip_scalar_mult_base(ecsimd_hip_ctx* ctx, int curve, const uint64_t* k, uint64_t* ox, uint64_t* oy, uint64_t* oz, size_t n, int flags) {
   REQUIRE_CTX(); REQUIRE_PTR(k); REQUIRE_PTR(ox); REQUIRE_OUT_Y(oy);
   flags &= ~ECSIMD_HIP_BASE_GENERATOR;                            // (implied here)
@@ -1154,17 +1219,21 @@ int ecsimd_hip_scalar_mult_base(ecsimd_hip_ctx* ctx, int curve, const uint64_t* 
     const bool ct = (flags & ECSIMD_HIP_ALG_CONSTANT_TIME) != 0;
     if (ct && (big || six)) return bad(ctx, "ALG_CONSTANT_TIME modifies ALG_WINDOWED only (its own 5-bit comb in LDS), not ALG_WINDOWED_SIGNED / ALG_WINDOWED_BIG");
     NO_COMPAT("ALG_WINDOWED");
-    if (n == 0) return ECSIMD_HIP_OK;
-    (void)hipSetDevice(ctx->device);
+    ENTER();
+    jacobian j;
     int rc = ensure_window_table(ctx, curve, big ? launch::BIG_WINDOW_BITS : six ? SIGNED_WBITS : ct ? CT_WBITS : 4);    // ALG_CONSTANT_TIME: its own 5-bit comb
-    if (rc == ECSIMD_HIP_OK) rc = ensure_workspace(ctx, 3 * n * 32);
+    if (rc == ECSIMD_HIP_OK) rc = ensure_jacobian(ctx, n, &j);
     if (rc != ECSIMD_HIP_OK) return rc;
-    uint64_t* jx = ctx->workspace; uint64_t* jy = jx + 4 * n; uint64_t* jz = jy + 4 * n;
-    RUN(((big ? launch::base_windowed_big(s, curve, k, ctx->window16_table[curve], jx, jy, jz, n)
-          : six ? launch::base_windowed_signed(s, curve, k, ctx->window6_table[curve], jx, jy, jz, n, false)
-          : ct ? launch::base_windowed_signed(s, curve, k, ctx->windowct_table[curve], jx, jy, jz, n, true)
-               : launch::base_windowed(s, curve, k, ctx->window_table[curve], jx, jy, jz, n, false)),
-         launch::to_affine_batched(s, curve, jx, jy, jz, ox, oy, n, true)));
+    hipStream_t s = ctx->stream;
+    if (ct) secret_base_product(ctx, curve, k, j, ox, oy, n);            // (no wipe: the product is the call's result, in the caller's arrays)
+    else {
+      if (big) launch::base_windowed_big(s, curve, k, ctx->window16_table[curve], j.x, j.y, j.z, n);
+      else if (six) launch::base_windowed_signed(s, curve, k, ctx->window6_table[curve], j.x, j.y, j.z, n, false);
+      else launch::base_windowed(s, curve, k, ctx->window_table[curve], j.x, j.y, j.z, n, false);
+      launch::to_affine_batched(s, curve, j.x, j.y, j.z, ox, oy, n, true);
+    }
+    hipError_t e = hipGetLastError();
+    return e == hipSuccess ? ECSIMD_HIP_OK : fail(ctx, e, "scalar_mult_base (windowed) launch");
   }
   if (flags & ECSIMD_HIP_ALG_CONSTANT_TIME) return bad(ctx, "ALG_CONSTANT_TIME modifies ALG_WINDOWED (the ladder is constant-time as it is)");
   // Small batches, affine output, no algorithm asked for: a launch of the ladder costs its 254 iterations however few lanes it has (1.3 ms), the
@@ -1173,18 +1242,15 @@ int ecsimd_hip_scalar_mult_base(ecsimd_hip_ctx* ctx, int curve, const uint64_t* 
   // scalars, and there the lanes take the ladder's own (meaningless, but the reference's) coordinates from a 288-byte record: the same bits out.
   if ((flags & ECSIMD_HIP_OUT_AFFINE) && n <= SMALL_BASE_MAX && !(flags & (ECSIMD_HIP_REF_SQUARE_COMPAT | ECSIMD_HIP_LADDER_RADIX32)) && !ctx->ref_square &&
       !capturing_needs_build(ctx, curve)) {
-    if (n == 0) return ECSIMD_HIP_OK;
-    (void)hipSetDevice(ctx->device);
+    ENTER_ANY_SIZE();                                                       // (n <= SMALL_BASE_MAX)
+    jacobian j;
     int rc = ensure_window_table(ctx, curve, CT_WBITS);
     const bool x_is_exact = (oy == nullptr && curve == ECSIMD_HIP_P256);    // the P-256 x-only ladder returns the true x for every k already
     if (rc == ECSIMD_HIP_OK && !x_is_exact) rc = ensure_base_special(ctx, curve);
-    if (rc == ECSIMD_HIP_OK) rc = ensure_workspace(ctx, 3 * n * 32);
+    if (rc == ECSIMD_HIP_OK) rc = ensure_jacobian(ctx, n, &j);
     if (rc != ECSIMD_HIP_OK) return rc;
-    uint64_t* jx = ctx->workspace; uint64_t* jy = jx + 4 * n; uint64_t* jz = jy + 4 * n;
-    hipStream_t s = ctx->stream;
-    launch::base_windowed_signed(s, curve, k, ctx->windowct_table[curve], jx, jy, jz, n, true);
-    launch::to_affine_batched(s, curve, jx, jy, jz, ox, oy, n, true);
-    if (!x_is_exact) launch::patch_special(s, k, ctx->base_special[curve], ox, oy, n);
+    secret_base_product(ctx, curve, k, j, ox, oy, n);                       // (no wipe, as in the ALG_CONSTANT_TIME branch above)
+    if (!x_is_exact) launch::patch_special(ctx->stream, k, ctx->base_special[curve], ox, oy, n);
     hipError_t e = hipGetLastError();
     return e == hipSuccess ? ECSIMD_HIP_OK : fail(ctx, e, "scalar_mult_base (small batch) launch");
   }
@@ -1193,7 +1259,7 @@ int ecsimd_hip_affine_add(ecsimd_hip_ctx* ctx, int curve, const uint64_t* ax, co
                           uint64_t* rx, uint64_t* ry, uint8_t* finite, size_t n) {
   REQUIRE_CTX(); if (curve < ECSIMD_HIP_FIRST_REGISTERED_CURVE) REQUIRE_CURVE(); REQUIRE_PTR(ax); REQUIRE_PTR(ay); REQUIRE_PTR(bx); REQUIRE_PTR(by); REQUIRE_PTR(rx);
   if (ry && !aligned16(ry)) return bad(ctx, "ry is not 16-byte aligned");
-  if (overlaps(rx, ax) || overlaps(rx, ay) || overlaps(rx, bx) || overlaps(rx, by)) return bad(ctx, "rx must not alias an input (it is the inversion scratch)");
+  if (any_alias({rx}, {ax, ay, bx, by})) return bad(ctx, "rx must not alias an input (it is the inversion scratch)");
   GENERIC_CURVE(launch::gc_affine_add_batched(s, GC, ax, ay, bx, by, rx, ry, finite, n));
   RUN(launch::affine_add_batched(s, curve, ax, ay, bx, by, rx, ry, finite, n)); }
 
@@ -1204,29 +1270,32 @@ int ecsimd_hip_affine_add(ecsimd_hip_ctx* ctx, int curve, const uint64_t* ax, co
 // u1*G comes from the 20-bit window table in device memory (436 MB per curve, built on first use) once that table
 // exists or the batch is large enough to pay for building it; smaller batches take the signed 7-bit table in LDS.
 namespace {
-constexpr size_t BIG_TABLE_WORTH_IT = (size_t)1 << 16;
+// per chunk: the Jacobian u1 G, the affine u1 G and u2 Q, the window loop's per-lane tables
+struct dsm_layout { size_t chunk; jacobian j; uint64_t *gx, *gy, *px, *py, *tables; size_t bytes; };
+dsm_layout dsm_plan(void* base, size_t n) {
+  dsm_layout L; L.chunk = chunk_of(n, VARWIN_CHUNK);
+  carve c = carve_from(base);
+  L.j = carve_jacobian(c, L.chunk); L.gx = carve_limbs(c, L.chunk); L.gy = carve_limbs(c, L.chunk); L.px = carve_limbs(c, L.chunk); L.py = carve_limbs(c, L.chunk);
+  L.tables = static_cast<uint64_t*>(carve_bytes(c, launch::varwin_scratch_bytes(L.chunk)));
+  L.bytes = c.bytes;
+  return L;
+}
+// The caller has gone through ENTER; `reserve_behind` bytes behind the layout are the caller's and stay untouched.
 int double_scalar_mult_impl(ecsimd_hip_ctx* ctx, int curve, const uint64_t* u1, const uint64_t* u2, const uint64_t* qx, const uint64_t* qy,
                             uint64_t* rx, uint64_t* ry, uint8_t* finite, size_t n, size_t reserve_behind, const uint8_t* known_valid = nullptr) {
   // known_valid (ecdsa_recover): the caller built every Q[i] from the curve equation and says which lanes count -- no second validation pass
-  (void)hipSetDevice(ctx->device);
-  const size_t chunk = n < VARWIN_CHUNK ? n : VARWIN_CHUNK;
-  const bool big = ctx->window16_table[curve] != nullptr || n >= BIG_TABLE_WORTH_IT;
-  int rc = ensure_window_table(ctx, curve, big ? launch::BIG_WINDOW_BITS : SIGNED_WBITS);
-  if (rc == ECSIMD_HIP_OK) rc = ensure_workspace(ctx, 7 * chunk * 32 + launch::varwin_scratch_bytes(chunk) + reserve_behind);   // 3 Jacobian + 2 x 2 affine + tables
-  if (rc == ECSIMD_HIP_OK && !known_valid) rc = ensure_valid(ctx, (n + 15) / 16 * 16);
+  int rc = public_base_product(ctx, curve, n);
+  if (rc == ECSIMD_HIP_OK) rc = ensure_workspace(ctx, dsm_plan(nullptr, n).bytes + reserve_behind);
+  if (rc == ECSIMD_HIP_OK && !known_valid) rc = ensure_valid(ctx, flag_bytes(n));
   if (rc != ECSIMD_HIP_OK) return rc;
-  uint64_t* jx = ctx->workspace; uint64_t* jy = jx + 4 * chunk; uint64_t* jz = jy + 4 * chunk;
-  uint64_t* gx = jz + 4 * chunk; uint64_t* gy = gx + 4 * chunk; uint64_t* px = gy + 4 * chunk; uint64_t* py = px + 4 * chunk;
-  uint64_t* scratch = py + 4 * chunk;
+  const dsm_layout L = dsm_plan(ctx->workspace, n);
   hipStream_t s = ctx->stream;
   if (!known_valid) launch::on_curve(s, curve, qx, qy, ctx->valid, n);
-  for (size_t first = 0; first < n; first += chunk) {
-    const size_t m = (n - first) < chunk ? (n - first) : chunk;
-    if (big) launch::base_windowed_big(s, curve, u1 + 4 * first, ctx->window16_table[curve], jx, jy, jz, m);   // u1*G
-    else launch::base_windowed_signed(s, curve, u1 + 4 * first, ctx->window6_table[curve], jx, jy, jz, m, false);
-    launch::to_affine_batched(s, curve, jx, jy, jz, gx, gy, m, true);
-    launch::varwin_scalar_mult(s, curve, u2 + 4 * first, 4, qx + 4 * first, qy + 4 * first, ECSIMD_HIP_BASE_CLASSICAL, scratch, px, py, m);   // u2*Q
-    launch::affine_add_batched(s, curve, gx, gy, px, py, rx + 4 * first, ry ? ry + 4 * first : nullptr, finite ? finite + first : nullptr, m);
+  FOR_CHUNKS(first, m, n, L.chunk) {
+    (void)public_base_product(ctx, curve, n, u1 + 4 * first, &L.j, m);                                          // u1*G (the table is there)
+    launch::to_affine_batched(s, curve, L.j.x, L.j.y, L.j.z, L.gx, L.gy, m, true);
+    launch::varwin_scalar_mult(s, curve, u2 + 4 * first, 4, qx + 4 * first, qy + 4 * first, ECSIMD_HIP_BASE_CLASSICAL, L.tables, L.px, L.py, m);   // u2*Q
+    launch::affine_add_batched(s, curve, L.gx, L.gy, L.px, L.py, rx + 4 * first, ry ? ry + 4 * first : nullptr, finite ? finite + first : nullptr, m);
   }
   launch::clear_invalid(s, known_valid ? known_valid : ctx->valid, rx, ry, finite, n);
   hipError_t e = hipGetLastError();
@@ -1240,18 +1309,17 @@ int double_scalar_mult_impl(ecsimd_hip_ctx* ctx, int curve, const uint64_t* u1, 
 // scalars kept clear of its degenerate values (three, as n >= 2^255 is asked at registration: k_gc_ladder_safe_scalars); one shared inversion per product, a batched affine addition.
 namespace {
 constexpr size_t GC_CHUNK = (size_t)1 << 22;
-constexpr size_t GC_BIG_TABLE_WORTH_IT = (size_t)1 << 20;          // u1 G + u2 Q on a registered curve: batches from here on build the 20-bit comb (0.3 s, 436 MB) on first use
+constexpr size_t GC_BIG_COMB_WORTH_IT = (size_t)1 << 20;          // u1 G + u2 Q on a registered curve: batches from here on build the 20-bit comb (0.3 s, 436 MB) on first use
 struct gc_layout { size_t chunk; uint64_t *adj1, *adj2, *j[3], *gx, *gy, *px, *py, *win; uint8_t *neg1, *neg2; size_t bytes; };
 // win: u2 Q goes through the window loop (k_gvarwin.hip), whose per-lane tables follow the nine arrays
 gc_layout gc_plan(uint64_t* base, size_t n, bool win = false) {
-  gc_layout L; L.chunk = n < GC_CHUNK ? n : GC_CHUNK;
-  uint64_t* p = base; const size_t e = 4 * L.chunk;
-  L.adj1 = p; p += e; L.adj2 = p; p += e; for (int i = 0; i < 3; ++i) { L.j[i] = p; p += e; }
-  L.gx = p; p += e; L.gy = p; p += e; L.px = p; p += e; L.py = p; p += e;
-  const size_t wbytes = win ? launch::gc_varwin_scratch_bytes(L.chunk) : 0;
-  L.win = win ? p : nullptr; p += wbytes / 8;
-  L.neg1 = reinterpret_cast<uint8_t*>(p); L.neg2 = L.neg1 + ((L.chunk + 15) / 16) * 16;
-  L.bytes = 9 * L.chunk * 32 + wbytes + 2 * (((L.chunk + 15) / 16) * 16);
+  gc_layout L; L.chunk = chunk_of(n, GC_CHUNK);
+  carve c = carve_from(base);
+  L.adj1 = carve_limbs(c, L.chunk); L.adj2 = carve_limbs(c, L.chunk); for (int i = 0; i < 3; ++i) L.j[i] = carve_limbs(c, L.chunk);
+  L.gx = carve_limbs(c, L.chunk); L.gy = carve_limbs(c, L.chunk); L.px = carve_limbs(c, L.chunk); L.py = carve_limbs(c, L.chunk);
+  L.win = win ? static_cast<uint64_t*>(carve_bytes(c, launch::gc_varwin_scratch_bytes(L.chunk))) : nullptr;
+  L.neg1 = carve_flags(c, L.chunk); L.neg2 = carve_flags(c, L.chunk);
+  L.bytes = c.bytes;
   return L;
 }
 // The comb of a registered curve (k_gcomb.hip): 64 windows x 8 odd multiples (2d + 1) 16^w G, then k* G and the record {k*, 0} (k_affine.inc comb_special's
@@ -1327,7 +1395,7 @@ int ensure_gc_base_special(ecsimd_hip_ctx* ctx, int curve, const curve_record& r
   (void)hipFree(r);
   return bad(ctx, "base_special: the curve's table is missing");
 }
-launch::words8 order_words(const curve_record& rec) { launch::words8 w; for (int i = 0; i < 4; ++i) { w.w[2 * i] = (uint32_t)rec.n.l[i]; w.w[2 * i + 1] = (uint32_t)(rec.n.l[i] >> 32); } return w; }
+launch::words8 order_words(const curve_record& rec) { return words8_of(rec.n.l); }
 }  // namespace
 namespace {
 // scalar_mult_base(registered curve, ALG_WINDOWED [| ALG_CONSTANT_TIME] | OUT_AFFINE): the comb, then the shared inversion -- the true k G for every k
@@ -1337,19 +1405,17 @@ int run_gcomb(ecsimd_hip_ctx* ctx, int curve, const uint64_t* k, uint64_t* ox, u
   if (ctx->ref_square || (flags & (ECSIMD_HIP_REF_SQUARE_COMPAT | ECSIMD_HIP_LADDER_RADIX32))) return bad(ctx, "ALG_WINDOWED is not the reference's algorithm: no ECSIMD_HIP_REF_SQUARE_COMPAT / LADDER_RADIX32 form");
   curve_record rec; if (!lookup_curve_record(curve, &rec)) return bad(ctx, "unknown curve id");
   if (n == 0) return gc_comb_possible(rec) ? ECSIMD_HIP_OK : bad(ctx, "the windowed algorithms on a registered curve need its group order n, n >= 2^255 (and n G = O where n is a prime in p's Hasse interval)");
-  if (n > (size_t)0x7fffffff * BLOCK) return bad(ctx, "batch too large");
-  (void)hipSetDevice(ctx->device);
-  const uint32_t* table = nullptr;
+  ENTER();
+  const uint32_t* table = nullptr; jacobian j;
   const bool seven = (flags & ECSIMD_HIP_ALG_WINDOWED_SIGNED) != 0;     // signed 7-bit windows in 148 KiB of LDS: 36 additions instead of 63 (public scalars)
   const bool big = (flags & ECSIMD_HIP_ALG_WINDOWED_BIG) != 0;          // 20-bit windows over 436 MB in device memory: 12 additions (public scalars)
   const bool five = !seven && !big && (flags & ECSIMD_HIP_ALG_CONSTANT_TIME) != 0;   // the constant-time comb: 5-bit windows, 51 additions, every entry of a window read
   int rc = ensure_gc_comb(ctx, curve, rec, &table, seven ? 7 : big ? 20 : five ? 5 : 4);
-  if (rc == ECSIMD_HIP_OK) rc = ensure_workspace(ctx, 3 * n * 32);
+  if (rc == ECSIMD_HIP_OK) rc = ensure_jacobian(ctx, n, &j);
   if (rc != ECSIMD_HIP_OK) return rc;
-  uint64_t* jx = ctx->workspace; uint64_t* jy = jx + 4 * n; uint64_t* jz = jy + 4 * n;
-  if (seven || five || big) launch::gc_base_windowed_s(ctx->stream, rec.G, order_words(rec), seven ? 7 : big ? 20 : 5, k, table, jx, jy, jz, n);
-  else launch::gc_base_windowed(ctx->stream, rec.G, order_words(rec), k, table, jx, jy, jz, n, false);
-  launch::gc_to_affine_batched(ctx->stream, rec.G, jx, jy, jz, ox, oy, n);
+  if (seven || five || big) launch::gc_base_windowed_s(ctx->stream, rec.G, order_words(rec), seven ? 7 : big ? 20 : 5, k, table, j.x, j.y, j.z, n);
+  else launch::gc_base_windowed(ctx->stream, rec.G, order_words(rec), k, table, j.x, j.y, j.z, n, false);
+  launch::gc_to_affine_batched(ctx->stream, rec.G, j.x, j.y, j.z, ox, oy, n);
   hipError_t e = hipGetLastError();
   return e == hipSuccess ? ECSIMD_HIP_OK : fail(ctx, e, "scalar_mult_base (registered curve, windowed) launch");
 }
@@ -1358,24 +1424,20 @@ int run_gcomb(ecsimd_hip_ctx* ctx, int curve, const uint64_t* k, uint64_t* ox, u
 // (640 B of scratch per lane).  `reserve` bytes at the start of the workspace stay untouched (gc_double_scalar_mult).
 int run_gvarwin(ecsimd_hip_ctx* ctx, int curve, const uint64_t* k, int k_stride, const uint64_t* x, const uint64_t* y, uint64_t* ox, uint64_t* oy, size_t n, int flags, size_t reserve) {
   if (!(flags & ECSIMD_HIP_OUT_AFFINE)) return bad(ctx, "ALG_WINDOWED needs OUT_AFFINE");
-  if (ctx->ref_square || (flags & ECSIMD_HIP_REF_SQUARE_COMPAT)) return bad(ctx, "ALG_WINDOWED is not the reference's algorithm: no ECSIMD_HIP_REF_SQUARE_COMPAT form");
+  NO_COMPAT("ALG_WINDOWED");
   if (flags & ECSIMD_HIP_LADDER_RADIX32) return bad(ctx, "LADDER_RADIX32 selects a ladder loop: not with ALG_WINDOWED");
   curve_record rec; if (!lookup_curve_record(curve, &rec)) return bad(ctx, "unknown curve id");
   if (!gc_comb_possible(rec)) return bad(ctx, "the windowed algorithms on a registered curve need its group order n, n >= 2^255 (and n G = O where n is a prime in p's Hasse interval)");
   if (!gc_window_possible(rec)) return bad(ctx, "ALG_WINDOWED on a variable base needs a group of prime order: n is not a prime in p's Hasse interval (the ladder has no such condition)");
-  if (n == 0) return ECSIMD_HIP_OK;
-  hipError_t e = hipSetDevice(ctx->device);
-  if (e != hipSuccess) return fail(ctx, e, "hipSetDevice");
-  const size_t chunk = n < VARWIN_CHUNK ? n : VARWIN_CHUNK;
+  ENTER_ANY_SIZE();
+  const size_t chunk = chunk_of(n, VARWIN_CHUNK);
   int rc = ensure_workspace(ctx, reserve + launch::gc_varwin_scratch_bytes(chunk));
   if (rc != ECSIMD_HIP_OK) return rc;
   uint64_t* scratch = ctx->workspace + reserve / 8;
-  for (size_t first = 0; first < n; first += chunk) {
-    const size_t m = (n - first) < chunk ? (n - first) : chunk;
+  FOR_CHUNKS(first, m, n, chunk)
     launch::gc_varwin_scalar_mult(ctx->stream, rec.G, order_words(rec), k + (size_t)k_stride * first, k_stride, x + 4 * first, y + 4 * first, flags & (ECSIMD_HIP_BASE_MGRY | ECSIMD_HIP_ALG_CONSTANT_TIME),
                                   scratch, ox + 4 * first, oy ? oy + 4 * first : nullptr, m);
-  }
-  e = hipGetLastError();
+  hipError_t e = hipGetLastError();
   return e == hipSuccess ? ECSIMD_HIP_OK : fail(ctx, e, "scalar_mult (registered curve, windowed) launch");
 }
 // scalar_mult_base(registered curve, OUT_AFFINE, no ALG_* / ladder flag) on up to 2^16 lanes: as for the built-in curves (ecsimd_hip_scalar_mult_base below) a
@@ -1391,13 +1453,12 @@ int gc_small_base(ecsimd_hip_ctx* ctx, int curve, const uint64_t* k, uint64_t* o
   int rc = ensure_gc_comb(ctx, curve, rec, &table);
   if (rc == ECSIMD_HIP_OK) rc = ensure_gc_base_special(ctx, curve, rec, &special);
   if (rc != ECSIMD_HIP_OK) { ctx->err[0] = 0; return GC_NOT_TAKEN; }                     // (a capture in progress and nothing built yet, a curve whose table cannot be built: the ladder)
-  if (capturing(ctx) && ctx->workspace_bytes < 3 * n * 32) return GC_NOT_TAKEN;
-  rc = ensure_workspace(ctx, 3 * n * 32);
+  if (capturing(ctx) && ctx->workspace_bytes < jacobian_bytes(n)) return GC_NOT_TAKEN;
+  jacobian j; rc = ensure_jacobian(ctx, n, &j);
   if (rc != ECSIMD_HIP_OK) return rc;
-  uint64_t* jx = ctx->workspace; uint64_t* jy = jx + 4 * n; uint64_t* jz = jy + 4 * n;
   hipStream_t s = ctx->stream;
-  launch::gc_base_windowed(s, rec.G, order_words(rec), k, table, jx, jy, jz, n, true);
-  launch::gc_to_affine_batched(s, rec.G, jx, jy, jz, ox, oy, n);
+  launch::gc_base_windowed(s, rec.G, order_words(rec), k, table, j.x, j.y, j.z, n, true);
+  launch::gc_to_affine_batched(s, rec.G, j.x, j.y, j.z, ox, oy, n);
   launch::patch_special(s, k, special, ox, oy, n);
   hipError_t e = hipGetLastError();
   return e == hipSuccess ? ECSIMD_HIP_OK : fail(ctx, e, "scalar_mult_base (registered curve, small batch) launch");
@@ -1407,7 +1468,7 @@ int gc_require_ecdsa(ecsimd_hip_ctx* ctx, int curve, curve_record* rec) {
   if (!rec->has_order) return bad(ctx, "this curve was registered without its group order n");
   if (rec->order_wrong) return bad(ctx, "ECDSA on a registered curve needs its group order n, n >= 2^255: this n is a prime in p's Hasse interval and n G != O");
   if (!rec->ecdsa_ok) return bad(ctx, "ECDSA on a registered curve needs an order n >= 2^255 (the ladder's further degenerate scalars below it are not worked around), p < 2n, and n - u a good ladder scalar for the three degenerate u");
-  if (ctx->ref_square) return bad(ctx, "not the reference's algorithm: no ECSIMD_HIP_REF_SQUARE_COMPAT form");
+  if (wants_compat(ctx)) return refuse_compat(ctx, nullptr);
   return ECSIMD_HIP_OK;
 }
 // one product k P (P = G when x == nullptr) -> affine classical (ox, oy), correct for EVERY k < n; oy may be null (x only: the negation does not touch x)
@@ -1419,19 +1480,18 @@ void gc_safe_mult(hipStream_t s, const curve_record& rec, const gc_layout& L, ui
 }
 int gc_double_scalar_mult(ecsimd_hip_ctx* ctx, int curve_of, const curve_record& rec, const uint64_t* u1, const uint64_t* u2, const uint64_t* qx, const uint64_t* qy,
                           uint64_t* rx, uint64_t* ry, uint8_t* finite, size_t n, size_t reserve_behind, const uint8_t* known_valid = nullptr) {
-  (void)hipSetDevice(ctx->device);
   const bool win = gc_window_possible(rec);                         // u2 Q from the lane's own window table where the curve has a prime order n >= 2^255, else a ladder pass
   gc_layout L = gc_plan(nullptr, n, win);
   int rc = ensure_workspace(ctx, L.bytes + reserve_behind);
-  if (rc == ECSIMD_HIP_OK && !known_valid) rc = ensure_valid(ctx, (n + 15) / 16 * 16);
+  if (rc == ECSIMD_HIP_OK && !known_valid) rc = ensure_valid(ctx, flag_bytes(n));
   if (rc != ECSIMD_HIP_OK) return rc;
-  const uint32_t* comb = nullptr;                                   // u1 G from the generator's table where the curve has one (n >= 2^255), else a ladder pass
+  const uint32_t* comb = nullptr;                                  // u1 G from the generator's table where the curve has one (n >= 2^255), else a ladder pass
   const uint32_t* comb7 = nullptr;                                  // ... preferably the signed 7-bit comb (u1 is public: 36 additions instead of 63)
   const uint32_t* comb20 = nullptr;                                 // ... or the 20-bit comb in device memory (12 additions) once it exists or the batch pays for its 436 MB
   if (gc_comb_possible(rec)) {
     bool have20 = false;
     for (auto& t : ctx->gcomb) if (t.curve == curve_of && t.table20) have20 = true;
-    if (have20 || (n >= GC_BIG_TABLE_WORTH_IT && !capturing(ctx))) { rc = ensure_gc_comb(ctx, curve_of, rec, &comb20, 20); if (rc != ECSIMD_HIP_OK) comb20 = nullptr; }
+    if (have20 || (n >= GC_BIG_COMB_WORTH_IT && !capturing(ctx))) { rc = ensure_gc_comb(ctx, curve_of, rec, &comb20, 20); if (rc != ECSIMD_HIP_OK) comb20 = nullptr; }
     rc = comb20 ? ECSIMD_HIP_OK : ensure_gc_comb(ctx, curve_of, rec, &comb7, 7);
     if (rc != ECSIMD_HIP_OK) {
       if (!capturing(ctx)) return rc;
@@ -1442,8 +1502,7 @@ int gc_double_scalar_mult(ecsimd_hip_ctx* ctx, int curve_of, const curve_record&
   L = gc_plan(ctx->workspace, n, win);
   hipStream_t s = ctx->stream;
   if (!known_valid) launch::gc_on_curve(s, rec.G, qx, qy, ctx->valid, n);      // (ecdsa_recover built every Q[i] from the curve equation: known_valid says which lanes count)
-  for (size_t first = 0; first < n; first += L.chunk) {
-    const size_t m = (n - first) < L.chunk ? (n - first) : L.chunk;
+  FOR_CHUNKS(first, m, n, L.chunk) {
     if (comb20 || comb7 || comb) {
       if (comb20) launch::gc_base_windowed_s(s, rec.G, order_words(rec), 20, u1 + 4 * first, comb20, L.j[0], L.j[1], L.j[2], m);
       else if (comb7) launch::gc_base_windowed_s(s, rec.G, order_words(rec), 7, u1 + 4 * first, comb7, L.j[0], L.j[1], L.j[2], m);
@@ -1458,16 +1517,29 @@ int gc_double_scalar_mult(ecsimd_hip_ctx* ctx, int curve_of, const curve_record&
   hipError_t e = hipGetLastError();
   return e == hipSuccess ? ECSIMD_HIP_OK : fail(ctx, e, "double_scalar_mult (registered curve) launch");
 }
+// ECDSA's acceptance test on top of a double product: behind that product's own `front` bytes of the workspace, the sums' x coordinates and finite flags; behind
+// those, `extra` bytes that stay untouched for the caller (ecdsa_verify's u1, u2 and range flags).
+struct verify_layout { uint64_t* rx; uint8_t* fin; size_t behind; };
+verify_layout verify_plan(void* base, size_t front, size_t n) {
+  verify_layout V; carve c = carve_from(base);
+  (void)carve_bytes(c, front); V.rx = carve_limbs(c, n); V.fin = carve_flags(c, n); V.behind = c.bytes - front;
+  return V;
+}
+// ecdsa_verify's own arrays behind verify_plan's: u1 = e / s, u2 = r / s and the range flags
+struct verify_scalars { uint64_t *u1, *u2; uint8_t* in_range; size_t extra; };
+verify_scalars verify_scalars_plan(void* base, size_t front, size_t n) {
+  verify_scalars S; carve c = carve_from(base);
+  (void)carve_bytes(c, front); S.u1 = carve_limbs(c, n); S.u2 = carve_limbs(c, n); S.in_range = carve_flags(c, n); S.extra = c.bytes - front;
+  return S;
+}
 int gc_ecdsa_verify_rx(ecsimd_hip_ctx* ctx, int curve_of, const curve_record& rec, const uint64_t* u1, const uint64_t* u2, const uint64_t* qx, const uint64_t* qy, const uint64_t* r, uint8_t* ok, size_t n, size_t extra) {
-  const gc_layout L0 = gc_plan(nullptr, n, gc_window_possible(rec));
-  const size_t behind = n * 32 + ((n + 15) / 16) * 16;
-  int rc = ensure_workspace(ctx, L0.bytes + behind + extra);
+  const size_t front = gc_plan(nullptr, n, gc_window_possible(rec)).bytes, behind = verify_plan(nullptr, front, n).behind;
+  int rc = ensure_workspace(ctx, front + behind + extra);
   if (rc != ECSIMD_HIP_OK) return rc;
-  uint64_t* rx = ctx->workspace + L0.bytes / 8;
-  uint8_t* fin = reinterpret_cast<uint8_t*>(rx + 4 * n);
-  rc = gc_double_scalar_mult(ctx, curve_of, rec, u1, u2, qx, qy, rx, nullptr, fin, n, behind + extra);
+  const verify_layout V = verify_plan(ctx->workspace, front, n);
+  rc = gc_double_scalar_mult(ctx, curve_of, rec, u1, u2, qx, qy, V.rx, nullptr, V.fin, n, behind + extra);
   if (rc != ECSIMD_HIP_OK) return rc;
-  launch::gc_x_mod_n_equals(ctx->stream, rec.N, rx, fin, r, ok, n);
+  launch::gc_x_mod_n_equals(ctx->stream, rec.N, V.rx, V.fin, r, ok, n);
   hipError_t e = hipGetLastError();
   return e == hipSuccess ? ECSIMD_HIP_OK : fail(ctx, e, "ecdsa_verify_rx (registered curve) launch");
 }
@@ -1484,36 +1556,27 @@ int ecsimd_hip_double_scalar_mult(ecsimd_hip_ctx* ctx, int curve, const uint64_t
   if (ry && !aligned16(ry)) return bad(ctx, "ry is not 16-byte aligned");
   if (curve >= ECSIMD_HIP_FIRST_REGISTERED_CURVE) {
     curve_record rec; int rc = gc_require_ecdsa(ctx, curve, &rec); if (rc != ECSIMD_HIP_OK) return rc;
-    if (n == 0) return ECSIMD_HIP_OK;
+    ENTER_ANY_SIZE();
     return gc_double_scalar_mult(ctx, curve, rec, u1, u2, qx, qy, rx, ry, finite, n, 0);
   }
   REQUIRE_CURVE();
-  if (ctx->ref_square) return bad(ctx, "double_scalar_mult is not the reference's algorithm: no ECSIMD_HIP_REF_SQUARE_COMPAT form");
-  if (n == 0) return ECSIMD_HIP_OK;
+  if (wants_compat(ctx)) return refuse_compat(ctx, "double_scalar_mult");
+  ENTER_ANY_SIZE();
   return double_scalar_mult_impl(ctx, curve, u1, u2, qx, qy, rx, ry, finite, n, 0); }
 
 // ECDSA's acceptance test on top of double_scalar_mult: ok[i] = Q[i] is a valid public key && u1*G + u2*Q is finite && its x mod n == r[i].
-// `extra` bytes are kept untouched at the end of the workspace for the caller (ecdsa_verify's u1, u2 and range flags).
 namespace {
-struct verify_layout { size_t front, behind; };
-verify_layout verify_sizes(size_t n) {
-  const size_t chunk = n < VARWIN_CHUNK ? n : VARWIN_CHUNK;
-  return {7 * chunk * 32 + launch::varwin_scratch_bytes(chunk), n * 32 + ((n + 15) / 16) * 16};
-}
 int ecdsa_verify_rx_impl(ecsimd_hip_ctx* ctx, int curve, const uint64_t* u1, const uint64_t* u2, const uint64_t* qx, const uint64_t* qy,
                          const uint64_t* r, uint8_t* ok, size_t n, size_t extra) {
-  (void)hipSetDevice(ctx->device);
-  // x coordinates and the finite flags of the sums live behind double_scalar_mult's own workspace use
-  const verify_layout L = verify_sizes(n);
+  const size_t front = dsm_plan(nullptr, n).bytes, behind = verify_plan(nullptr, front, n).behind;
   // sizes the workspace (and builds the table) first, so that the pointers taken below stay valid
-  int rc = ensure_window_table(ctx, curve, (ctx->window16_table[curve] != nullptr || n >= BIG_TABLE_WORTH_IT) ? launch::BIG_WINDOW_BITS : SIGNED_WBITS);
-  if (rc == ECSIMD_HIP_OK) rc = ensure_workspace(ctx, L.front + L.behind + extra);
+  int rc = public_base_product(ctx, curve, n);
+  if (rc == ECSIMD_HIP_OK) rc = ensure_workspace(ctx, front + behind + extra);
   if (rc != ECSIMD_HIP_OK) return rc;
-  uint64_t* rx = ctx->workspace + L.front / 8;
-  uint8_t* fin = reinterpret_cast<uint8_t*>(rx + 4 * n);
-  rc = double_scalar_mult_impl(ctx, curve, u1, u2, qx, qy, rx, nullptr, fin, n, L.behind + extra);
+  const verify_layout V = verify_plan(ctx->workspace, front, n);
+  rc = double_scalar_mult_impl(ctx, curve, u1, u2, qx, qy, V.rx, nullptr, V.fin, n, behind + extra);
   if (rc != ECSIMD_HIP_OK) return rc;
-  launch::x_mod_n_equals(ctx->stream, curve, rx, fin, r, ok, n);       // fin is 0 for the lanes whose Q failed validation
+  launch::x_mod_n_equals(ctx->stream, curve, V.rx, V.fin, r, ok, n);       // fin is 0 for the lanes whose Q failed validation
   hipError_t e = hipGetLastError();
   return e == hipSuccess ? ECSIMD_HIP_OK : fail(ctx, e, "ecdsa_verify_rx launch");
 }
@@ -1525,13 +1588,12 @@ int ecsimd_hip_ecdsa_verify_rx(ecsimd_hip_ctx* ctx, int curve, const uint64_t* u
   if (!ok && n) return bad(ctx, "ok is null");
   if (curve >= ECSIMD_HIP_FIRST_REGISTERED_CURVE) {
     curve_record rec; int rc = gc_require_ecdsa(ctx, curve, &rec); if (rc != ECSIMD_HIP_OK) return rc;
-    if (n == 0) return ECSIMD_HIP_OK;
-    (void)hipSetDevice(ctx->device);
+    ENTER_ANY_SIZE();
     return gc_ecdsa_verify_rx(ctx, curve, rec, u1, u2, qx, qy, r, ok, n, 0);
   }
   REQUIRE_CURVE();
-  if (ctx->ref_square) return bad(ctx, "ecdsa_verify_rx is not the reference's algorithm: no ECSIMD_HIP_REF_SQUARE_COMPAT form");
-  if (n == 0) return ECSIMD_HIP_OK;
+  if (wants_compat(ctx)) return refuse_compat(ctx, "ecdsa_verify_rx");
+  ENTER_ANY_SIZE();
   return ecdsa_verify_rx_impl(ctx, curve, u1, u2, qx, qy, r, ok, n, 0); }
 
 // The whole verification (SEC 1 v2 4.1.4, FIPS 186-5 6.4.2): range checks and u1 = e / s, u2 = r / s modulo the group order on the device
@@ -1543,183 +1605,150 @@ int ecsimd_hip_ecdsa_verify(ecsimd_hip_ctx* ctx, int curve, const uint64_t* e, c
   if (curve >= ECSIMD_HIP_FIRST_REGISTERED_CURVE) {
     // the same verification on a registered curve: u1, u2 modulo ITS order (the record's field of n), then two ladders, an affine addition, x mod n = r
     curve_record rec; int rc = gc_require_ecdsa(ctx, curve, &rec); if (rc != ECSIMD_HIP_OK) return rc;
-    if (n == 0) return ECSIMD_HIP_OK;
-    if (n > (size_t)0x7fffffff * BLOCK) return bad(ctx, "batch too large");
-    (void)hipSetDevice(ctx->device);
-    const gc_layout L0 = gc_plan(nullptr, n, gc_window_possible(rec));
-    const size_t behind = n * 32 + ((n + 15) / 16) * 16, extra = 2 * n * 32 + ((n + 15) / 16) * 16;
-    rc = ensure_workspace(ctx, L0.bytes + behind + extra);
+    ENTER();
+    const size_t front = gc_plan(nullptr, n, gc_window_possible(rec)).bytes, inner = front + verify_plan(nullptr, front, n).behind;
+    rc = ensure_workspace(ctx, inner + verify_scalars_plan(nullptr, inner, n).extra);
     if (rc != ECSIMD_HIP_OK) return rc;
-    uint64_t* u1 = ctx->workspace + (L0.bytes + behind) / 8; uint64_t* u2 = u1 + 4 * n;
-    uint8_t* in_range = reinterpret_cast<uint8_t*>(u2 + 4 * n);
-    launch::ecdsa_scalars(ctx->stream, rec.N, e, r, s_, u1, u2, in_range, n);
-    rc = gc_ecdsa_verify_rx(ctx, curve, rec, u1, u2, qx, qy, r, ok, n, extra);
+    const verify_scalars S = verify_scalars_plan(ctx->workspace, inner, n);
+    launch::ecdsa_scalars(ctx->stream, rec.N, e, r, s_, S.u1, S.u2, S.in_range, n);
+    rc = gc_ecdsa_verify_rx(ctx, curve, rec, S.u1, S.u2, qx, qy, r, ok, n, S.extra);
     if (rc != ECSIMD_HIP_OK) return rc;
-    launch::mask_op(ctx->stream, ECSIMD_HIP_MASK_AND, ok, in_range, ok, n);
+    launch::mask_op(ctx->stream, ECSIMD_HIP_MASK_AND, ok, S.in_range, ok, n);
     hipError_t err = hipGetLastError();
     return err == hipSuccess ? ECSIMD_HIP_OK : fail(ctx, err, "ecdsa_verify (registered curve) launch");
   }
   REQUIRE_CURVE();
-  if (ctx->ref_square) return bad(ctx, "ecdsa_verify is not the reference's algorithm: no ECSIMD_HIP_REF_SQUARE_COMPAT form");
-  if (n == 0) return ECSIMD_HIP_OK;
-  if (n > (size_t)0x7fffffff * BLOCK) return bad(ctx, "batch too large");
-  (void)hipSetDevice(ctx->device);
-  gmod N; if (!lookup_modulus(curve == ECSIMD_HIP_P256 ? ECSIMD_HIP_FIELD_P256_ORDER : ECSIMD_HIP_FIELD_SECP256K1_ORDER, &N)) return bad(ctx, "group order missing from the registry");
-  const verify_layout L = verify_sizes(n);
-  const size_t extra = 2 * n * 32 + ((n + 15) / 16) * 16;        // u1, u2, range flags
-  int rc = ensure_window_table(ctx, curve, (ctx->window16_table[curve] != nullptr || n >= BIG_TABLE_WORTH_IT) ? launch::BIG_WINDOW_BITS : SIGNED_WBITS);
-  if (rc == ECSIMD_HIP_OK) rc = ensure_workspace(ctx, L.front + L.behind + extra);
+  if (wants_compat(ctx)) return refuse_compat(ctx, "ecdsa_verify");
+  ENTER();
+  group_order O; int rc = builtin_order(ctx, curve, &O); if (rc != ECSIMD_HIP_OK) return rc;
+  const size_t front = dsm_plan(nullptr, n).bytes, inner = front + verify_plan(nullptr, front, n).behind;
+  rc = public_base_product(ctx, curve, n);
+  if (rc == ECSIMD_HIP_OK) rc = ensure_workspace(ctx, inner + verify_scalars_plan(nullptr, inner, n).extra);
   if (rc != ECSIMD_HIP_OK) return rc;
-  uint64_t* u1 = ctx->workspace + (L.front + L.behind) / 8;
-  uint64_t* u2 = u1 + 4 * n;
-  uint8_t* in_range = reinterpret_cast<uint8_t*>(u2 + 4 * n);
-  launch::ecdsa_scalars(ctx->stream, N, e, r, s_, u1, u2, in_range, n);
-  rc = ecdsa_verify_rx_impl(ctx, curve, u1, u2, qx, qy, r, ok, n, extra);     // the workspace is already this large: nothing moves
+  const verify_scalars S = verify_scalars_plan(ctx->workspace, inner, n);
+  launch::ecdsa_scalars(ctx->stream, O.N, e, r, s_, S.u1, S.u2, S.in_range, n);
+  rc = ecdsa_verify_rx_impl(ctx, curve, S.u1, S.u2, qx, qy, r, ok, n, S.extra);     // the workspace is already this large: nothing moves
   if (rc != ECSIMD_HIP_OK) return rc;
-  launch::mask_op(ctx->stream, ECSIMD_HIP_MASK_AND, ok, in_range, ok, n);      // u1 = u2 = 0 already fails (the sum is infinite); the flag says why
+  launch::mask_op(ctx->stream, ECSIMD_HIP_MASK_AND, ok, S.in_range, ok, n);      // u1 = u2 = 0 already fails (the sum is infinite); the flag says why
   hipError_t err = hipGetLastError();
   return err == hipSuccess ? ECSIMD_HIP_OK : fail(ctx, err, "ecdsa_verify launch"); }
 
-// Signing: R = k G on the constant-time comb (the kernel behind ALG_WINDOWED | ALG_CONSTANT_TIME), x only; then the scalar-field half.
+// Signing: R = k G on the constant-time comb (the kernel behind ALG_WINDOWED | ALG_CONSTANT_TIME), then the scalar-field half.  v == nullptr (ecdsa_sign): x(R)
+// only.  Otherwise (ecdsa_sign_recoverable) y(R) is kept through the simultaneous inversion and k_recover.hip's select-only kernel adds
+// v = parity(y) | (x >= n ? 2 : 0) and the low-s rule; the affine y joins the Jacobian k G and x in the workspace and is zeroed with them.
+namespace {
+struct sign_layout { jacobian j; uint64_t *rx, *ry; size_t bytes; };     // the Jacobian k G, x(k G) and, for the recovery id, y(k G)
+sign_layout sign_plan(void* base, size_t n, bool keep_y) {
+  sign_layout L; carve c = carve_from(base);
+  L.j = carve_jacobian(c, n); L.rx = carve_limbs(c, n); L.ry = keep_y ? carve_limbs(c, n) : nullptr; L.bytes = c.bytes;
+  return L;
+}
+int ecdsa_sign_builtin(ecsimd_hip_ctx* ctx, int curve, const uint64_t* e, const uint64_t* d, const uint64_t* k, uint64_t* r, uint64_t* s_, uint8_t* v, uint8_t* ok, size_t n, bool low_s) {
+  ENTER();
+  group_order O; int rc = builtin_order(ctx, curve, &O); if (rc != ECSIMD_HIP_OK) return rc;
+  rc = ensure_window_table(ctx, curve, CT_WBITS);
+  if (rc == ECSIMD_HIP_OK) rc = ensure_workspace(ctx, sign_plan(nullptr, n, v != nullptr).bytes);
+  if (rc != ECSIMD_HIP_OK) return rc;
+  const sign_layout L = sign_plan(ctx->workspace, n, v != nullptr);
+  secret_base_product(ctx, curve, k, L.j, L.rx, L.ry, n);
+  launch::ecdsa_sign_scalars(ctx->stream, O.N, e, d, k, L.rx, r, s_, ok, n);
+  if (v) launch::sign_recovery_id(ctx->stream, O.words, L.rx, L.ry, s_, ok, v, n, low_s);
+  const hipError_t err = wipe_workspace(ctx, L.bytes, hipGetLastError());
+  return err == hipSuccess ? ECSIMD_HIP_OK : fail(ctx, err, v ? "ecdsa_sign_recoverable launch" : "ecdsa_sign launch");
+}
+// On a registered curve: k G from the constant-time comb of its generator (k_gcomb.hip: 5-bit windows, every entry of a window read) where the curve has one; else,
+// and where no table exists yet and a capture in progress forbids building it, through the reference's ladder, constant-time as it is (tests/test_constant_time_isa.py
+// holds both to the ISA); the select-only shared inversion; then the scalar-field kernel with the record's order.  One launch: at most 2^22 signatures.
+int ecdsa_sign_registered(ecsimd_hip_ctx* ctx, int curve, const curve_record& rec, const uint64_t* e, const uint64_t* d, const uint64_t* k, uint64_t* r, uint64_t* s_, uint8_t* v, uint8_t* ok,
+                          size_t n, bool low_s) {
+  ENTER();
+  gc_layout L = gc_plan(nullptr, n);
+  if (L.chunk != n) return bad(ctx, v ? "ecdsa_sign_recoverable on a registered curve: at most 2^22 signatures per call" : "ecdsa_sign on a registered curve: at most 2^22 signatures per call");
+  int rc = ensure_workspace(ctx, L.bytes);
+  if (rc != ECSIMD_HIP_OK) return rc;
+  const uint32_t* comb = nullptr;
+  if (gc_comb_possible(rec)) { rc = ensure_gc_comb(ctx, curve, rec, &comb, 5); if (rc != ECSIMD_HIP_OK) { if (!capturing(ctx)) return rc; comb = nullptr; } }
+  L = gc_plan(ctx->workspace, n);
+  uint64_t* ry = v ? L.gy : nullptr;
+  if (comb) {
+    launch::gc_base_windowed_s(ctx->stream, rec.G, order_words(rec), 5, k, comb, L.j[0], L.j[1], L.j[2], n);
+    launch::gc_to_affine_batched(ctx->stream, rec.G, L.j[0], L.j[1], L.j[2], L.gx, ry, n);
+  } else gc_safe_mult(ctx->stream, rec, L, L.adj1, L.neg1, k, nullptr, nullptr, L.gx, ry, n);          // (the negation of a degenerate nonce's product does not touch x)
+  launch::ecdsa_sign_scalars(ctx->stream, rec.N, e, d, k, L.gx, r, s_, ok, n);
+  if (v) launch::sign_recovery_id(ctx->stream, order_words(rec), L.gx, L.gy, s_, ok, v, n, low_s);
+  const hipError_t err = wipe_workspace(ctx, L.bytes, hipGetLastError());                              // the nonce's adjusted copy, the Jacobian k G and the affine point
+  return err == hipSuccess ? ECSIMD_HIP_OK : fail(ctx, err, v ? "ecdsa_sign_recoverable (registered curve) launch" : "ecdsa_sign (registered curve) launch");
+}
+}  // namespace
+
 int ecsimd_hip_ecdsa_sign(ecsimd_hip_ctx* ctx, int curve, const uint64_t* e, const uint64_t* d, const uint64_t* k, uint64_t* r, uint64_t* s_, uint8_t* ok, size_t n) {
   REQUIRE_CTX(); REQUIRE_PTR(e); REQUIRE_PTR(d); REQUIRE_PTR(k); REQUIRE_PTR(r); REQUIRE_PTR(s_);
   if (!ok && n) return bad(ctx, "ok is null");
-  if (curve >= ECSIMD_HIP_FIRST_REGISTERED_CURVE) {
-    // signing on a registered curve: k G from the constant-time comb of its generator (k_gcomb.hip; an id without a comb: through the reference's ladder, constant-time as it
-    // is -- tests/test_constant_time_isa.py holds both to the ISA), x by the select-only shared inversion, then the scalar-field kernel with the record's order
-    curve_record rec; int rc = gc_require_ecdsa(ctx, curve, &rec); if (rc != ECSIMD_HIP_OK) return rc;
-    if (overlaps(r, e) || overlaps(r, d) || overlaps(r, k) || overlaps(s_, e) || overlaps(s_, d) || overlaps(s_, k) || overlaps(r, s_)) return bad(ctx, "r and s must not alias an input or each other");
-    if (n == 0) return ECSIMD_HIP_OK;
-    if (n > (size_t)0x7fffffff * BLOCK) return bad(ctx, "batch too large");
-    (void)hipSetDevice(ctx->device);
-    gc_layout L = gc_plan(nullptr, n);
-    if (L.chunk != n) return bad(ctx, "ecdsa_sign on a registered curve: at most 2^22 signatures per call");
-    rc = ensure_workspace(ctx, L.bytes);
-    if (rc != ECSIMD_HIP_OK) return rc;
-    const uint32_t* comb = nullptr;                             // k G from the generator's constant-time comb (5-bit windows, every entry of a window read), where the curve has one
-    if (gc_comb_possible(rec)) { rc = ensure_gc_comb(ctx, curve, rec, &comb, 5); if (rc != ECSIMD_HIP_OK) { if (!capturing(ctx)) return rc; comb = nullptr; } }   // (no table yet and a capture in progress: the ladder)
-    L = gc_plan(ctx->workspace, n);
-    if (comb) {
-      launch::gc_base_windowed_s(ctx->stream, rec.G, order_words(rec), 5, k, comb, L.j[0], L.j[1], L.j[2], n);
-      launch::gc_to_affine_batched(ctx->stream, rec.G, L.j[0], L.j[1], L.j[2], L.gx, nullptr, n);
-    } else gc_safe_mult(ctx->stream, rec, L, L.adj1, L.neg1, k, nullptr, nullptr, L.gx, nullptr, n);  // x(k G): the negation of a degenerate nonce's product does not touch x
-    launch::ecdsa_sign_scalars(ctx->stream, rec.N, e, d, k, L.gx, r, s_, ok, n);
-    hipError_t err = hipGetLastError();
-    if (err == hipSuccess) err = hipMemsetAsync(ctx->workspace, 0, L.bytes, ctx->stream);              // the nonce's adjusted copy, the Jacobian k G and x: gone before the call returns
-    return err == hipSuccess ? ECSIMD_HIP_OK : fail(ctx, err, "ecdsa_sign (registered curve) launch");
-  }
-  REQUIRE_CURVE();
-  if (ctx->ref_square) return bad(ctx, "ecdsa_sign is not the reference's algorithm: no ECSIMD_HIP_REF_SQUARE_COMPAT form");
-  if (overlaps(r, e) || overlaps(r, d) || overlaps(r, k) || overlaps(s_, e) || overlaps(s_, d) || overlaps(s_, k) || overlaps(r, s_)) return bad(ctx, "r and s must not alias an input or each other");
-  if (n == 0) return ECSIMD_HIP_OK;
-  if (n > (size_t)0x7fffffff * BLOCK) return bad(ctx, "batch too large");
-  (void)hipSetDevice(ctx->device);
-  gmod N; if (!lookup_modulus(curve == ECSIMD_HIP_P256 ? ECSIMD_HIP_FIELD_P256_ORDER : ECSIMD_HIP_FIELD_SECP256K1_ORDER, &N)) return bad(ctx, "group order missing from the registry");
-  int rc = ensure_window_table(ctx, curve, CT_WBITS);
-  if (rc == ECSIMD_HIP_OK) rc = ensure_workspace(ctx, 4 * n * 32);
-  if (rc != ECSIMD_HIP_OK) return rc;
-  uint64_t* jx = ctx->workspace; uint64_t* jy = jx + 4 * n; uint64_t* jz = jy + 4 * n; uint64_t* rx = jz + 4 * n;
-  hipStream_t st = ctx->stream;
-  launch::base_windowed_signed(st, curve, k, ctx->windowct_table[curve], jx, jy, jz, n, true);      // k >= n is reduced by the comb; the lane is refused below
-  launch::to_affine_batched(st, curve, jx, jy, jz, rx, nullptr, n, true);
-  launch::ecdsa_sign_scalars(st, N, e, d, k, rx, r, s_, ok, n);
-  hipError_t err = hipGetLastError();
-  // The workspace held the Jacobian k G (X, Y, Z) and its affine x: with the public r, the Z of an unnormalised k G gives bits of the nonce away
-  // (the projective-coordinate leak), and the block outlives the call (grow-only, hipFree does not wipe).  Zero it on the same stream, behind the kernels.
-  if (err == hipSuccess) err = hipMemsetAsync(ctx->workspace, 0, 4 * n * 32, st);
-  return err == hipSuccess ? ECSIMD_HIP_OK : fail(ctx, err, "ecdsa_sign launch"); }
+  curve_record rec;
+  if (curve >= ECSIMD_HIP_FIRST_REGISTERED_CURVE) { int rc = gc_require_ecdsa(ctx, curve, &rec); if (rc != ECSIMD_HIP_OK) return rc; }
+  else { REQUIRE_CURVE(); if (wants_compat(ctx)) return refuse_compat(ctx, "ecdsa_sign"); }
+  if (any_alias({r, s_}, {e, d, k})) return bad(ctx, "r and s must not alias an input or each other");
+  return curve >= ECSIMD_HIP_FIRST_REGISTERED_CURVE ? ecdsa_sign_registered(ctx, curve, rec, e, d, k, r, s_, nullptr, ok, n, false) : ecdsa_sign_builtin(ctx, curve, e, d, k, r, s_, nullptr, ok, n, false); }
 
 // Public-key recovery (SEC 1 v2 4.1.6): R = (r + (v >> 1) n, the root of that parity) from k_recover.hip's lift, u1 = -e / r and u2 = s / r from its
 // scalar-field kernel, then u1 G + u2 R through double_scalar_mult's window loops, whose validation of R is skipped: R was just built from the curve
 // equation and the validity byte already says which lanes count.  ok = that byte && the sum is finite; (0, 0) elsewhere.  All data is public.
+namespace {
+// behind the double product's `front` bytes, per element of a chunk: u1, u2, the lifted R and `more` further arrays, then the validity byte and `more_flags` further byte arrays
+struct recover_layout { uint64_t *u1, *u2, *px, *py, *more[2]; uint8_t *valid, *more_flags; size_t extra; };
+recover_layout recover_plan(void* base, size_t front, size_t m, int more = 0, bool more_flags = false) {
+  recover_layout L; carve c = carve_from(base);
+  (void)carve_bytes(c, front); L.u1 = carve_limbs(c, m); L.u2 = carve_limbs(c, m); L.px = carve_limbs(c, m); L.py = carve_limbs(c, m);
+  for (int i = 0; i < 2; ++i) L.more[i] = i < more ? carve_limbs(c, m) : nullptr;
+  L.valid = carve_flags(c, m); L.more_flags = more_flags ? carve_flags(c, m) : nullptr;
+  L.extra = c.bytes - front;
+  return L;
+}
+}  // namespace
 int ecsimd_hip_ecdsa_recover(ecsimd_hip_ctx* ctx, int curve, const uint64_t* e, const uint64_t* r, const uint64_t* s_, const uint8_t* v,
                              uint64_t* qx, uint64_t* qy, uint8_t* ok, size_t n) {
   REQUIRE_CTX(); REQUIRE_PTR(e); REQUIRE_PTR(r); REQUIRE_PTR(s_); REQUIRE_PTR(qx);
   if ((!v || !ok) && n) return bad(ctx, "v or ok is null");
   if (qy && !aligned16(qy)) return bad(ctx, "qy is not 16-byte aligned");
-  const size_t flag_bytes = ((n + 15) / 16) * 16, extra = 4 * n * 32 + flag_bytes;       // u1, u2, Rx, Ry, the validity byte
   if (curve >= ECSIMD_HIP_FIRST_REGISTERED_CURVE) {
     curve_record rec; int rc = gc_require_ecdsa(ctx, curve, &rec); if (rc != ECSIMD_HIP_OK) return rc;
-    if (n == 0) return ECSIMD_HIP_OK;
-    if (n > (size_t)0x7fffffff * BLOCK) return bad(ctx, "batch too large");
-    (void)hipSetDevice(ctx->device);
-    const gc_layout L0 = gc_plan(nullptr, n, gc_window_possible(rec));
-    rc = ensure_workspace(ctx, L0.bytes + extra);
+    ENTER();
+    const size_t front = gc_plan(nullptr, n, gc_window_possible(rec)).bytes;
+    rc = ensure_workspace(ctx, front + recover_plan(nullptr, front, n).extra);
     if (rc != ECSIMD_HIP_OK) return rc;
-    uint64_t* u1 = ctx->workspace + L0.bytes / 8; uint64_t* u2 = u1 + 4 * n; uint64_t* px = u2 + 4 * n; uint64_t* py = px + 4 * n;
-    uint8_t* valid = reinterpret_cast<uint8_t*>(py + 4 * n);
-    launch::gc_recover_lift(ctx->stream, rec.G, order_words(rec), r, v, px, py, valid, n);
-    launch::ecdsa_recover_scalars(ctx->stream, rec.N, e, r, s_, u1, u2, valid, n);
-    return gc_double_scalar_mult(ctx, curve, rec, u1, u2, px, py, qx, qy, ok, n, extra, valid);
+    const recover_layout L = recover_plan(ctx->workspace, front, n);
+    launch::gc_recover_lift(ctx->stream, rec.G, order_words(rec), r, v, L.px, L.py, L.valid, n);
+    launch::ecdsa_recover_scalars(ctx->stream, rec.N, e, r, s_, L.u1, L.u2, L.valid, n);
+    return gc_double_scalar_mult(ctx, curve, rec, L.u1, L.u2, L.px, L.py, qx, qy, ok, n, L.extra, L.valid);
   }
   REQUIRE_CURVE();
-  if (ctx->ref_square) return bad(ctx, "ecdsa_recover is not the reference's algorithm: no ECSIMD_HIP_REF_SQUARE_COMPAT form");
-  if (n == 0) return ECSIMD_HIP_OK;
-  if (n > (size_t)0x7fffffff * BLOCK) return bad(ctx, "batch too large");
-  (void)hipSetDevice(ctx->device);
-  gmod N; if (!lookup_modulus(curve == ECSIMD_HIP_P256 ? ECSIMD_HIP_FIELD_P256_ORDER : ECSIMD_HIP_FIELD_SECP256K1_ORDER, &N)) return bad(ctx, "group order missing from the registry");
-  const size_t front = verify_sizes(n).front;
+  if (wants_compat(ctx)) return refuse_compat(ctx, "ecdsa_recover");
+  ENTER();
+  group_order O; int rc = builtin_order(ctx, curve, &O); if (rc != ECSIMD_HIP_OK) return rc;
+  const size_t front = dsm_plan(nullptr, n).bytes;
   // sizes the workspace (and builds the table) first, so that the pointers taken below stay valid
-  int rc = ensure_window_table(ctx, curve, (ctx->window16_table[curve] != nullptr || n >= BIG_TABLE_WORTH_IT) ? launch::BIG_WINDOW_BITS : SIGNED_WBITS);
-  if (rc == ECSIMD_HIP_OK) rc = ensure_workspace(ctx, front + extra);
+  rc = public_base_product(ctx, curve, n);
+  if (rc == ECSIMD_HIP_OK) rc = ensure_workspace(ctx, front + recover_plan(nullptr, front, n).extra);
   if (rc != ECSIMD_HIP_OK) return rc;
-  uint64_t* u1 = ctx->workspace + front / 8; uint64_t* u2 = u1 + 4 * n; uint64_t* px = u2 + 4 * n; uint64_t* py = px + 4 * n;
-  uint8_t* valid = reinterpret_cast<uint8_t*>(py + 4 * n);
-  launch::words8 order; for (int i = 0; i < 8; ++i) order.w[i] = N.p[i];
-  launch::recover_lift(ctx->stream, curve, order, r, v, px, py, valid, n);
-  launch::ecdsa_recover_scalars(ctx->stream, N, e, r, s_, u1, u2, valid, n);
-  return double_scalar_mult_impl(ctx, curve, u1, u2, px, py, qx, qy, ok, n, extra, valid); }
+  const recover_layout L = recover_plan(ctx->workspace, front, n);
+  launch::recover_lift(ctx->stream, curve, O.words, r, v, L.px, L.py, L.valid, n);
+  launch::ecdsa_recover_scalars(ctx->stream, O.N, e, r, s_, L.u1, L.u2, L.valid, n);
+  return double_scalar_mult_impl(ctx, curve, L.u1, L.u2, L.px, L.py, qx, qy, ok, n, L.extra, L.valid); }
 
-// Signing with the recovery id: ecdsa_sign's steps with y(k G) kept through the simultaneous inversion, then k_recover.hip's select-only kernel for
-// v = parity(y) | (x >= n ? 2 : 0) and the low-s rule.  The affine y joins the Jacobian k G and x in the workspace and is zeroed with them.
 int ecsimd_hip_ecdsa_sign_recoverable(ecsimd_hip_ctx* ctx, int curve, const uint64_t* e, const uint64_t* d, const uint64_t* k, uint64_t* r, uint64_t* s_, uint8_t* v, uint8_t* ok,
                                       size_t n, int flags) {
   REQUIRE_CTX(); REQUIRE_PTR(e); REQUIRE_PTR(d); REQUIRE_PTR(k); REQUIRE_PTR(r); REQUIRE_PTR(s_);
   if ((!v || !ok) && n) return bad(ctx, "v or ok is null");
   if (flags & ~ECSIMD_HIP_ECDSA_LOW_S) return bad(ctx, "ecdsa_sign_recoverable: unknown flag");
-  if (n != 0 && (overlaps(r, e) || overlaps(r, d) || overlaps(r, k) || overlaps(s_, e) || overlaps(s_, d) || overlaps(s_, k) || overlaps(r, s_))) return bad(ctx, "r and s must not alias an input or each other");   // (an empty batch has no arrays to alias)
+  if (n != 0 && any_alias({r, s_}, {e, d, k})) return bad(ctx, "r and s must not alias an input or each other");   // (an empty batch has no arrays to alias)
   const bool low_s = (flags & ECSIMD_HIP_ECDSA_LOW_S) != 0;
   if (curve >= ECSIMD_HIP_FIRST_REGISTERED_CURVE) {
     curve_record rec; int rc = gc_require_ecdsa(ctx, curve, &rec); if (rc != ECSIMD_HIP_OK) return rc;
-    if (n == 0) return ECSIMD_HIP_OK;
-    if (n > (size_t)0x7fffffff * BLOCK) return bad(ctx, "batch too large");
-    (void)hipSetDevice(ctx->device);
-    gc_layout L = gc_plan(nullptr, n);
-    if (L.chunk != n) return bad(ctx, "ecdsa_sign_recoverable on a registered curve: at most 2^22 signatures per call");
-    rc = ensure_workspace(ctx, L.bytes);
-    if (rc != ECSIMD_HIP_OK) return rc;
-    const uint32_t* comb = nullptr;                             // as in ecdsa_sign: the constant-time 5-bit comb where the curve has one, else the ladder
-    if (gc_comb_possible(rec)) { rc = ensure_gc_comb(ctx, curve, rec, &comb, 5); if (rc != ECSIMD_HIP_OK) { if (!capturing(ctx)) return rc; comb = nullptr; } }
-    L = gc_plan(ctx->workspace, n);
-    if (comb) {
-      launch::gc_base_windowed_s(ctx->stream, rec.G, order_words(rec), 5, k, comb, L.j[0], L.j[1], L.j[2], n);
-      launch::gc_to_affine_batched(ctx->stream, rec.G, L.j[0], L.j[1], L.j[2], L.gx, L.gy, n);
-    } else gc_safe_mult(ctx->stream, rec, L, L.adj1, L.neg1, k, nullptr, nullptr, L.gx, L.gy, n);
-    launch::ecdsa_sign_scalars(ctx->stream, rec.N, e, d, k, L.gx, r, s_, ok, n);
-    launch::sign_recovery_id(ctx->stream, order_words(rec), L.gx, L.gy, s_, ok, v, n, low_s);
-    hipError_t err = hipGetLastError();
-    if (err == hipSuccess) err = hipMemsetAsync(ctx->workspace, 0, L.bytes, ctx->stream);
-    return err == hipSuccess ? ECSIMD_HIP_OK : fail(ctx, err, "ecdsa_sign_recoverable (registered curve) launch");
+    return ecdsa_sign_registered(ctx, curve, rec, e, d, k, r, s_, v, ok, n, low_s);
   }
   REQUIRE_CURVE();
-  if (ctx->ref_square) return bad(ctx, "ecdsa_sign_recoverable is not the reference's algorithm: no ECSIMD_HIP_REF_SQUARE_COMPAT form");
-  if (n == 0) return ECSIMD_HIP_OK;
-  if (n > (size_t)0x7fffffff * BLOCK) return bad(ctx, "batch too large");
-  (void)hipSetDevice(ctx->device);
-  gmod N; if (!lookup_modulus(curve == ECSIMD_HIP_P256 ? ECSIMD_HIP_FIELD_P256_ORDER : ECSIMD_HIP_FIELD_SECP256K1_ORDER, &N)) return bad(ctx, "group order missing from the registry");
-  int rc = ensure_window_table(ctx, curve, CT_WBITS);
-  if (rc == ECSIMD_HIP_OK) rc = ensure_workspace(ctx, 5 * n * 32);
-  if (rc != ECSIMD_HIP_OK) return rc;
-  uint64_t* jx = ctx->workspace; uint64_t* jy = jx + 4 * n; uint64_t* jz = jy + 4 * n; uint64_t* rx = jz + 4 * n; uint64_t* ry = rx + 4 * n;
-  hipStream_t st = ctx->stream;
-  launch::words8 order; for (int i = 0; i < 8; ++i) order.w[i] = N.p[i];
-  launch::base_windowed_signed(st, curve, k, ctx->windowct_table[curve], jx, jy, jz, n, true);
-  launch::to_affine_batched(st, curve, jx, jy, jz, rx, ry, n, true);
-  launch::ecdsa_sign_scalars(st, N, e, d, k, rx, r, s_, ok, n);
-  launch::sign_recovery_id(st, order, rx, ry, s_, ok, v, n, low_s);
-  hipError_t err = hipGetLastError();
-  if (err == hipSuccess) err = hipMemsetAsync(ctx->workspace, 0, 5 * n * 32, st);     // the Jacobian k G and both affine coordinates (ecdsa_sign says why)
-  return err == hipSuccess ? ECSIMD_HIP_OK : fail(ctx, err, "ecdsa_sign_recoverable launch"); }
+  if (wants_compat(ctx)) return refuse_compat(ctx, "ecdsa_sign_recoverable");
+  return ecdsa_sign_builtin(ctx, curve, e, d, k, r, s_, v, ok, n, low_s); }
 
 // ---- SHA-256 and deterministic nonces (k_sha256.hip)
 int ecsimd_hip_sha256(ecsimd_hip_ctx* ctx, const uint8_t* msg, size_t msg_bytes, size_t stride_bytes, uint64_t* e, size_t n) {
@@ -1753,17 +1782,16 @@ int nonce_lookup(ecsimd_hip_ctx* ctx, int curve, nonce_plan* out) {
     REQUIRE_CURVE();
     n = order_of(curve);
   }
-  for (int i = 0; i < 4; ++i) { out->order.w[2 * i] = (uint32_t)n.l[i]; out->order.w[2 * i + 1] = (uint32_t)(n.l[i] >> 32); }
+  out->order = words8_of(n.l);
   out->cap = rfc6979_candidates_needed(n);
   return ECSIMD_HIP_OK;
 }
 // per element behind `front` bytes of a chunk: the nonce (32 B), K as two midstates and V (96 B), the retry byte, a recovery id nobody asked for
 struct nonce_layout { uint64_t* k; void* state; uint8_t* retry; uint8_t* v; size_t bytes; };
 nonce_layout nonce_plan_ws(uint64_t* base, size_t front, size_t m) {
-  nonce_layout L; const size_t flags = ((m + 15) / 16) * 16;
-  uint8_t* p = reinterpret_cast<uint8_t*>(base) + front;
-  L.k = reinterpret_cast<uint64_t*>(p); L.state = p + 32 * m; L.retry = p + 128 * m; L.v = L.retry + flags;
-  L.bytes = 128 * m + 2 * flags;
+  nonce_layout L; carve c = carve_from(base);
+  (void)carve_bytes(c, front); L.k = carve_limbs(c, m); L.state = carve_bytes(c, 96 * m); L.retry = carve_flags(c, m); L.v = carve_flags(c, m);
+  L.bytes = c.bytes - front;
   return L;
 }
 }  // namespace
@@ -1772,19 +1800,17 @@ int ecsimd_hip_rfc6979_nonce(ecsimd_hip_ctx* ctx, int curve, const uint64_t* e, 
   REQUIRE_CTX(); REQUIRE_PTR(e); REQUIRE_PTR(d); REQUIRE_PTR(k);
   if (!ok && n) return bad(ctx, "ok is null");
   nonce_plan P; int rc = nonce_lookup(ctx, curve, &P); if (rc != ECSIMD_HIP_OK) return rc;
-  if (n != 0 && (overlaps(k, e) || overlaps(k, d))) return bad(ctx, "k must not alias an input");
-  if (n == 0) return ECSIMD_HIP_OK;
-  (void)hipSetDevice(ctx->device);
-  const size_t chunk = n < GC_CHUNK ? n : GC_CHUNK;
+  if (n != 0 && any_alias({k}, {e, d})) return bad(ctx, "k must not alias an input");
+  ENTER_ANY_SIZE();
+  const size_t chunk = chunk_of(n, GC_CHUNK);
   rc = ensure_workspace(ctx, nonce_plan_ws(nullptr, 0, chunk).bytes);
   if (rc != ECSIMD_HIP_OK) return rc;
   hipError_t err = hipSuccess;
-  for (size_t first = 0; first < n && err == hipSuccess; first += chunk) {
-    const size_t m = n - first < chunk ? n - first : chunk;
+  FOR_CHUNKS(first, m, n, chunk) {
     const nonce_layout L = nonce_plan_ws(ctx->workspace, 0, m);
     launch::rfc6979_nonce(ctx->stream, P.order, e + 4 * first, d + 4 * first, k + 4 * first, L.state, L.retry, ok + first, m, P.cap);
-    err = hipGetLastError();
-    if (err == hipSuccess) err = hipMemsetAsync(ctx->workspace, 0, L.bytes, ctx->stream);       // K, V and the retry bytes: gone before the call returns (L.k is unused here)
+    err = wipe_workspace(ctx, L.bytes, hipGetLastError());       // K, V and the retry bytes: gone before the call returns (L.k is unused here)
+    if (err != hipSuccess) break;
   }
   return err == hipSuccess ? ECSIMD_HIP_OK : fail(ctx, err, "rfc6979_nonce launch"); }
 
@@ -1795,17 +1821,15 @@ int ecsimd_hip_ecdsa_sign_deterministic(ecsimd_hip_ctx* ctx, int curve, const ui
   if (!ok && n) return bad(ctx, "ok is null");
   if (flags & ~ECSIMD_HIP_ECDSA_LOW_S) return bad(ctx, "ecdsa_sign_deterministic: unknown flag");
   nonce_plan P; int rc = nonce_lookup(ctx, curve, &P); if (rc != ECSIMD_HIP_OK) return rc;
-  if (ctx->ref_square) return bad(ctx, "ecdsa_sign_deterministic is not the reference's algorithm: no ECSIMD_HIP_REF_SQUARE_COMPAT form");
-  if (n != 0 && (overlaps(r, e) || overlaps(r, d) || overlaps(s_, e) || overlaps(s_, d) || overlaps(r, s_))) return bad(ctx, "r and s must not alias an input or each other");
-  if (n == 0) return ECSIMD_HIP_OK;
-  (void)hipSetDevice(ctx->device);
-  const size_t chunk = n < GC_CHUNK ? n : GC_CHUNK;
-  const size_t front = curve >= ECSIMD_HIP_FIRST_REGISTERED_CURVE ? gc_plan(nullptr, chunk).bytes : 5 * chunk * 32;     // ecdsa_sign_recoverable's own use of the workspace
+  if (wants_compat(ctx)) return refuse_compat(ctx, "ecdsa_sign_deterministic");
+  if (n != 0 && any_alias({r, s_}, {e, d})) return bad(ctx, "r and s must not alias an input or each other");
+  ENTER_ANY_SIZE();
+  const size_t chunk = chunk_of(n, GC_CHUNK);
+  const size_t front = curve >= ECSIMD_HIP_FIRST_REGISTERED_CURVE ? gc_plan(nullptr, chunk).bytes : sign_plan(nullptr, chunk, true).bytes;     // ecdsa_sign_recoverable's own use of the workspace
   // the first call per curve builds the comb's table and sizes the workspace: both before any pointer into the block is taken
   rc = ensure_workspace(ctx, front + nonce_plan_ws(nullptr, 0, chunk).bytes);
   if (rc != ECSIMD_HIP_OK) return rc;
-  for (size_t first = 0; first < n; first += chunk) {
-    const size_t m = n - first < chunk ? n - first : chunk;
+  FOR_CHUNKS(first, m, n, chunk) {
     const nonce_layout L = nonce_plan_ws(ctx->workspace, front, m);
     launch::rfc6979_nonce(ctx->stream, P.order, e + 4 * first, d + 4 * first, L.k, L.state, L.retry, ok + first, m, P.cap);
     hipError_t err = hipGetLastError();
@@ -1845,31 +1869,24 @@ int ecsimd_hip_eth_recover(ecsimd_hip_ctx* ctx, const uint64_t* e, const uint64_
   if ((qx == nullptr) != (qy == nullptr)) return bad(ctx, "eth_recover: qx and qy are both given or both NULL");
   if (qx && (!aligned16(qx) || !aligned16(qy))) return bad(ctx, "qx or qy is not 16-byte aligned");
   if (flags & ~ECSIMD_HIP_ETH_REQUIRE_LOW_S) return bad(ctx, "eth_recover: unknown flag");
-  if (ctx->ref_square) return bad(ctx, "eth_recover is not the reference's algorithm: no ECSIMD_HIP_REF_SQUARE_COMPAT form");
-  if (n == 0) return ECSIMD_HIP_OK;
-  if (n > (size_t)0x7fffffff * BLOCK) return bad(ctx, "batch too large");
-  (void)hipSetDevice(ctx->device);
+  if (wants_compat(ctx)) return refuse_compat(ctx, "eth_recover");
+  ENTER();
   const int curve = ECSIMD_HIP_SECP256K1;
-  gmod N; if (!lookup_modulus(ECSIMD_HIP_FIELD_SECP256K1_ORDER, &N)) return bad(ctx, "group order missing from the registry");
-  launch::words8 order, half;
-  for (int i = 0; i < 8; ++i) order.w[i] = N.p[i];
-  for (int i = 0; i < 8; ++i) half.w[i] = (order.w[i] >> 1) | (i < 7 ? order.w[i + 1] << 31 : 0u);
-  const size_t chunk = n < VARWIN_CHUNK ? n : VARWIN_CHUNK, flag_bytes = ((chunk + 15) / 16) * 16;
-  const size_t front = verify_sizes(chunk).front, extra = 6 * chunk * 32 + 2 * flag_bytes;
+  group_order O; int rc = builtin_order(ctx, curve, &O); if (rc != ECSIMD_HIP_OK) return rc;
+  launch::words8 half;
+  for (int i = 0; i < 8; ++i) half.w[i] = (O.words.w[i] >> 1) | (i < 7 ? O.words.w[i + 1] << 31 : 0u);
+  const size_t chunk = chunk_of(n, VARWIN_CHUNK), front = dsm_plan(nullptr, chunk).bytes;
   // sizes the workspace (and builds the table) first, so that the pointers taken below stay valid
-  int rc = ensure_window_table(ctx, curve, (ctx->window16_table[curve] != nullptr || n >= BIG_TABLE_WORTH_IT) ? launch::BIG_WINDOW_BITS : SIGNED_WBITS);
-  if (rc == ECSIMD_HIP_OK) rc = ensure_workspace(ctx, front + extra);
+  rc = public_base_product(ctx, curve, n);
+  if (rc == ECSIMD_HIP_OK) rc = ensure_workspace(ctx, front + recover_plan(nullptr, front, chunk, 2, true).extra);
   if (rc != ECSIMD_HIP_OK) return rc;
-  uint64_t* u1 = ctx->workspace + front / 8; uint64_t* u2 = u1 + 4 * chunk; uint64_t* px = u2 + 4 * chunk; uint64_t* py = px + 4 * chunk;
-  uint64_t* kx = py + 4 * chunk; uint64_t* ky = kx + 4 * chunk;
-  uint8_t* valid = reinterpret_cast<uint8_t*>(ky + 4 * chunk); uint8_t* id = valid + flag_bytes;
-  for (size_t first = 0; first < n; first += chunk) {
-    const size_t m = n - first < chunk ? n - first : chunk;
-    uint64_t* ox = qx ? qx + 4 * first : kx; uint64_t* oy = qy ? qy + 4 * first : ky;
-    launch::eth_recovery_id(ctx->stream, half, v + first, s_ + 4 * first, id, m, (flags & ECSIMD_HIP_ETH_REQUIRE_LOW_S) != 0);
-    launch::recover_lift(ctx->stream, curve, order, r + 4 * first, id, px, py, valid, m);
-    launch::ecdsa_recover_scalars(ctx->stream, N, e + 4 * first, r + 4 * first, s_ + 4 * first, u1, u2, valid, m);
-    rc = double_scalar_mult_impl(ctx, curve, u1, u2, px, py, ox, oy, ok + first, m, extra, valid);
+  const recover_layout L = recover_plan(ctx->workspace, front, chunk, 2, true);      // more: the key where the caller does not want it; more_flags: the recovery id
+  FOR_CHUNKS(first, m, n, chunk) {
+    uint64_t* ox = qx ? qx + 4 * first : L.more[0]; uint64_t* oy = qy ? qy + 4 * first : L.more[1];
+    launch::eth_recovery_id(ctx->stream, half, v + first, s_ + 4 * first, L.more_flags, m, (flags & ECSIMD_HIP_ETH_REQUIRE_LOW_S) != 0);
+    launch::recover_lift(ctx->stream, curve, O.words, r + 4 * first, L.more_flags, L.px, L.py, L.valid, m);
+    launch::ecdsa_recover_scalars(ctx->stream, O.N, e + 4 * first, r + 4 * first, s_ + 4 * first, L.u1, L.u2, L.valid, m);
+    rc = double_scalar_mult_impl(ctx, curve, L.u1, L.u2, L.px, L.py, ox, oy, ok + first, m, L.extra, L.valid);
     if (rc != ECSIMD_HIP_OK) return rc;
     launch::eth_address(ctx->stream, ox, oy, ok + first, addr + 20 * first, m);
   }
@@ -1914,33 +1931,40 @@ int ecsimd_hip_btc_pubkey_hash(ecsimd_hip_ctx* ctx, const uint64_t* qx, const ui
 
 // ---- BIP-341 Taproot key tweaks on secp256k1 (k_btc.hip)
 namespace {
-// Q = lift_x(px) + t G per chunk of 2^22: k_tweak_front (the lift, t given or hashed, the range check), t G on the public comb -- the big table in device memory
-// on the terms double_scalar_mult_impl uses it, else the signed 7-bit comb in LDS --, k_tweak_add (complete: t = 0, the tangent, the opposite), ONE simultaneous
-// inversion that keeps y, k_tweak_accept.  Per element of a chunk: the lifted P, later the affine Q (64 B), t (32 B), the Jacobian sum (96 B) and the validity byte.
+// What xonly_tweak_chain and bip32_ckd_pub share, Q = P + t G between a front end and an accept kernel.  Per element of a chunk: the Jacobian sum (96 B), P, later
+// the affine Q (64 B), t (32 B) and the validity byte.
+struct tweak_layout { size_t chunk; jacobian j; uint64_t *x, *y, *t; uint8_t* valid; size_t bytes; };
+tweak_layout tweak_plan(void* base, size_t n) {
+  tweak_layout L; L.chunk = chunk_of(n, GC_CHUNK);
+  carve c = carve_from(base);
+  L.j = carve_jacobian(c, L.chunk); L.x = carve_limbs(c, L.chunk); L.y = carve_limbs(c, L.chunk); L.t = carve_limbs(c, L.chunk); L.valid = carve_flags(c, L.chunk);
+  L.bytes = c.bytes;
+  return L;
+}
+int tweak_prepare(ecsimd_hip_ctx* ctx, size_t n, tweak_layout* L) {
+  int rc = public_base_product(ctx, ECSIMD_HIP_SECP256K1, n);
+  if (rc == ECSIMD_HIP_OK) rc = ensure_workspace(ctx, tweak_plan(nullptr, n).bytes);
+  if (rc == ECSIMD_HIP_OK) *L = tweak_plan(ctx->workspace, n);
+  return rc;
+}
+// (x, y) + t G for m lanes of a batch of n: t G on the public comb, k_tweak_add, the inversion -- the spent point's place takes the affine sum, j.z stays for the accept kernel
+void tweak_middle(ecsimd_hip_ctx* ctx, size_t n, const tweak_layout& L, size_t m) {
+  (void)public_base_product(ctx, ECSIMD_HIP_SECP256K1, n, L.t, &L.j, m);
+  launch::tweak_add(ctx->stream, L.j.x, L.j.y, L.j.z, L.x, L.y, m);
+  launch::to_affine_batched(ctx->stream, ECSIMD_HIP_SECP256K1, L.j.x, L.j.y, L.j.z, L.x, L.y, m, true);
+}
+// Q = lift_x(px) + t G per chunk of 2^22: k_tweak_front (the lift, t given or hashed, the range check), t G on the public comb, k_tweak_add (complete: t = 0, the
+// tangent, the opposite), ONE simultaneous inversion that keeps y, k_tweak_accept.
 int xonly_tweak_chain(ecsimd_hip_ctx* ctx, const char* what, int mode, const uint64_t* px, const uint64_t* t_or_merkle, uint64_t* qx, uint8_t* parity, uint8_t* ok, size_t n) {
-  if (ctx->ref_square) { snprintf(ctx->err, sizeof ctx->err, "bad argument: %s is not the reference's algorithm: no ECSIMD_HIP_REF_SQUARE_COMPAT form", what); return ECSIMD_HIP_ERR_BAD_ARG; }
-  gmod N; if (!lookup_modulus(ECSIMD_HIP_FIELD_SECP256K1_ORDER, &N)) return bad(ctx, "group order missing from the registry");
-  launch::words8 order; for (int i = 0; i < 8; ++i) order.w[i] = N.p[i];
-  if (n == 0) return ECSIMD_HIP_OK;
-  (void)hipSetDevice(ctx->device);
-  const int curve = ECSIMD_HIP_SECP256K1;
-  const size_t chunk = n < GC_CHUNK ? n : GC_CHUNK, flag_bytes = ((chunk + 15) / 16) * 16;
-  const bool big = ctx->window16_table[curve] != nullptr || n >= BIG_TABLE_WORTH_IT;
-  int rc = ensure_window_table(ctx, curve, big ? launch::BIG_WINDOW_BITS : SIGNED_WBITS);
-  if (rc == ECSIMD_HIP_OK) rc = ensure_workspace(ctx, 6 * chunk * 32 + flag_bytes);
+  if (wants_compat(ctx)) return refuse_compat(ctx, what);
+  group_order O; int rc = builtin_order(ctx, ECSIMD_HIP_SECP256K1, &O); if (rc != ECSIMD_HIP_OK) return rc;
+  ENTER_ANY_SIZE();
+  tweak_layout L; rc = tweak_prepare(ctx, n, &L);
   if (rc != ECSIMD_HIP_OK) return rc;
-  uint64_t* jx = ctx->workspace; uint64_t* jy = jx + 4 * chunk; uint64_t* jz = jy + 4 * chunk;
-  uint64_t* x = jz + 4 * chunk; uint64_t* y = x + 4 * chunk; uint64_t* tt = y + 4 * chunk;
-  uint8_t* valid = reinterpret_cast<uint8_t*>(tt + 4 * chunk);
-  hipStream_t st = ctx->stream;
-  for (size_t first = 0; first < n; first += chunk) {
-    const size_t m = n - first < chunk ? n - first : chunk;
-    launch::tweak_front(st, order, mode, px + 4 * first, t_or_merkle ? t_or_merkle + 4 * first : nullptr, x, y, tt, valid, m);
-    if (big) launch::base_windowed_big(st, curve, tt, ctx->window16_table[curve], jx, jy, jz, m);
-    else launch::base_windowed_signed(st, curve, tt, ctx->window6_table[curve], jx, jy, jz, m, false);
-    launch::tweak_add(st, jx, jy, jz, x, y, m);
-    launch::to_affine_batched(st, curve, jx, jy, jz, x, y, m, true);                                   // the lifted P is spent: its place takes the affine Q
-    launch::tweak_accept(st, x, y, jz, valid, qx + 4 * first, parity + first, ok + first, m);
+  FOR_CHUNKS(first, m, n, L.chunk) {
+    launch::tweak_front(ctx->stream, O.words, mode, px + 4 * first, t_or_merkle ? t_or_merkle + 4 * first : nullptr, L.x, L.y, L.t, L.valid, m);
+    tweak_middle(ctx, n, L, m);
+    launch::tweak_accept(ctx->stream, L.x, L.y, L.j.z, L.valid, qx + 4 * first, parity + first, ok + first, m);
   }
   hipError_t err = hipGetLastError();
   return err == hipSuccess ? ECSIMD_HIP_OK : fail(ctx, err, what);
@@ -1950,59 +1974,49 @@ int xonly_tweak_chain(ecsimd_hip_ctx* ctx, const char* what, int mode, const uin
 int ecsimd_hip_xonly_tweak_add(ecsimd_hip_ctx* ctx, const uint64_t* px, const uint64_t* t, uint64_t* qx, uint8_t* parity, uint8_t* ok, size_t n) {
   REQUIRE_CTX(); REQUIRE_PTR(px); REQUIRE_PTR(t); REQUIRE_PTR(qx);
   if ((!parity || !ok) && n) return bad(ctx, "parity or ok is null");
-  if (n != 0 && (overlaps(qx, px) || overlaps(qx, t))) return bad(ctx, "qx must not alias an input");
+  if (n != 0 && any_alias({qx}, {px, t})) return bad(ctx, "qx must not alias an input");
   return xonly_tweak_chain(ctx, "xonly_tweak_add", launch::TWEAK_GIVEN, px, t, qx, parity, ok, n); }
 
 int ecsimd_hip_taproot_tweak_pubkey(ecsimd_hip_ctx* ctx, const uint64_t* px, const uint64_t* merkle_root, uint64_t* qx, uint8_t* parity, uint8_t* ok, size_t n) {
   REQUIRE_CTX(); REQUIRE_PTR(px); REQUIRE_PTR(qx);
   if (merkle_root && !aligned16(merkle_root)) return bad(ctx, "merkle_root is not 16-byte aligned");
   if ((!parity || !ok) && n) return bad(ctx, "parity or ok is null");
-  if (n != 0 && (overlaps(qx, px) || (merkle_root && overlaps(qx, merkle_root)))) return bad(ctx, "qx must not alias an input");
+  if (n != 0 && any_alias({qx}, {px, merkle_root})) return bad(ctx, "qx must not alias an input");
   return xonly_tweak_chain(ctx, "taproot_tweak_pubkey", merkle_root ? launch::TWEAK_MERKLE_ROOT : launch::TWEAK_KEY_PATH, px, merkle_root, qx, parity, ok, n); }
 
-// The secret key of the output key: d G on the constant-time comb with both coordinates through the simultaneous inversion (schnorr_sign's two launches for d G),
-// then k_taproot_seckey.  Per element of a chunk: the Jacobian product (96 B) and the affine d G (64 B) -- all zeroed behind the kernels (ecdsa_sign says why).
+// The secret key of the output key: d G on the constant-time comb with both coordinates through the simultaneous inversion (secret_base_product),
+// then k_taproot_seckey.  Per element of a chunk: the Jacobian product (96 B) and the affine d G (64 B) -- all zeroed behind the kernels (secret_base_product says why).
 int ecsimd_hip_taproot_tweak_seckey(ecsimd_hip_ctx* ctx, const uint64_t* d, const uint64_t* merkle_root, uint64_t* d_out, uint64_t* px, uint8_t* ok, size_t n) {
   REQUIRE_CTX(); REQUIRE_PTR(d); REQUIRE_PTR(d_out);
   if ((merkle_root && !aligned16(merkle_root)) || (px && !aligned16(px))) return bad(ctx, "merkle_root or px is not 16-byte aligned");
   if (!ok && n) return bad(ctx, "ok is null");
-  if (ctx->ref_square) return bad(ctx, "taproot_tweak_seckey is not the reference's algorithm: no ECSIMD_HIP_REF_SQUARE_COMPAT form");
-  gmod N; if (!lookup_modulus(ECSIMD_HIP_FIELD_SECP256K1_ORDER, &N)) return bad(ctx, "group order missing from the registry");
-  if (n != 0) {
-    if (overlaps(d_out, d) || (merkle_root && overlaps(d_out, merkle_root)) || (px && (overlaps(px, d) || overlaps(px, d_out) || (merkle_root && overlaps(px, merkle_root)))))
-      return bad(ctx, "d_out and px must not alias an input or each other");
-  }
-  if (n == 0) return ECSIMD_HIP_OK;
-  (void)hipSetDevice(ctx->device);
+  if (wants_compat(ctx)) return refuse_compat(ctx, "taproot_tweak_seckey");
+  group_order O; int rc = builtin_order(ctx, ECSIMD_HIP_SECP256K1, &O); if (rc != ECSIMD_HIP_OK) return rc;
+  if (n != 0 && any_alias({d_out, px}, {d, merkle_root})) return bad(ctx, "d_out and px must not alias an input or each other");
+  ENTER_ANY_SIZE();
   const int curve = ECSIMD_HIP_SECP256K1;
-  const size_t chunk = n < GC_CHUNK ? n : GC_CHUNK;
-  int rc = ensure_window_table(ctx, curve, CT_WBITS);
-  if (rc == ECSIMD_HIP_OK) rc = ensure_workspace(ctx, 5 * chunk * 32);
+  const size_t chunk = chunk_of(n, GC_CHUNK);
+  rc = ensure_window_table(ctx, curve, CT_WBITS);
+  if (rc == ECSIMD_HIP_OK) rc = ensure_workspace(ctx, sign_plan(nullptr, chunk, true).bytes);
   if (rc != ECSIMD_HIP_OK) return rc;
-  uint64_t* jx = ctx->workspace; uint64_t* jy = jx + 4 * chunk; uint64_t* jz = jy + 4 * chunk; uint64_t* xP = jz + 4 * chunk; uint64_t* yP = xP + 4 * chunk;
-  hipStream_t st = ctx->stream;
+  const sign_layout L = sign_plan(ctx->workspace, chunk, true);              // the Jacobian d G and both affine coordinates
   hipError_t err = hipSuccess;
-  for (size_t first = 0; first < n && err == hipSuccess; first += chunk) {
-    const size_t m = n - first < chunk ? n - first : chunk;
-    launch::base_windowed_signed(st, curve, d + 4 * first, ctx->windowct_table[curve], jx, jy, jz, m, true);      // d >= n is reduced by the comb; the lane is refused below
-    launch::to_affine_batched(st, curve, jx, jy, jz, xP, yP, m, true);
-    launch::taproot_seckey(st, N, d + 4 * first, merkle_root ? merkle_root + 4 * first : nullptr, xP, yP, d_out + 4 * first, px ? px + 4 * first : nullptr, ok + first, m);
-    err = hipGetLastError();
-    hipError_t wiped = hipMemsetAsync(ctx->workspace, 0, 5 * chunk * 32, st);                                     // whatever the launches said
-    if (err == hipSuccess) err = wiped;
+  FOR_CHUNKS(first, m, n, chunk) {
+    secret_base_product(ctx, curve, d + 4 * first, L.j, L.rx, L.ry, m);
+    launch::taproot_seckey(ctx->stream, O.N, d + 4 * first, merkle_root ? merkle_root + 4 * first : nullptr, L.rx, L.ry, d_out + 4 * first, px ? px + 4 * first : nullptr, ok + first, m);
+    err = wipe_workspace(ctx, L.bytes, hipGetLastError());
+    if (err != hipSuccess) break;
   }
   return err == hipSuccess ? ECSIMD_HIP_OK : fail(ctx, err, "taproot_tweak_seckey launch"); }
 
 // ---- BIP-340 Schnorr signatures on secp256k1 (k_schnorr.hip)
 namespace {
-int schnorr_common(ecsimd_hip_ctx* ctx, const char* what, const uint8_t* msg, size_t msg_bytes, size_t stride_bytes, size_t n, gmod* N, launch::words8* order) {
+int schnorr_common(ecsimd_hip_ctx* ctx, const char* what, const uint8_t* msg, size_t msg_bytes, size_t stride_bytes, size_t n, group_order* O) {
   if (!msg && n && msg_bytes) return bad(ctx, "msg is null");
   if (stride_bytes < msg_bytes) return bad(ctx, "schnorr: stride_bytes is smaller than msg_bytes");
   if (msg_bytes > ((size_t)1 << 40)) return bad(ctx, "schnorr: message too long");
-  if (ctx->ref_square) { snprintf(ctx->err, sizeof ctx->err, "bad argument: %s is not the reference's algorithm: no ECSIMD_HIP_REF_SQUARE_COMPAT form", what); return ECSIMD_HIP_ERR_BAD_ARG; }
-  if (!lookup_modulus(ECSIMD_HIP_FIELD_SECP256K1_ORDER, N)) return bad(ctx, "group order missing from the registry");
-  for (int i = 0; i < 8; ++i) order->w[i] = N->p[i];
-  return ECSIMD_HIP_OK;
+  if (wants_compat(ctx)) return refuse_compat(ctx, what);
+  return builtin_order(ctx, ECSIMD_HIP_SECP256K1, O);
 }
 }  // namespace
 
@@ -2013,70 +2027,58 @@ int ecsimd_hip_schnorr_verify(ecsimd_hip_ctx* ctx, const uint64_t* px, const uin
                               const uint64_t* r, const uint64_t* s_, uint8_t* ok, size_t n) {
   REQUIRE_CTX(); REQUIRE_PTR(px); REQUIRE_PTR(r); REQUIRE_PTR(s_);
   if (!ok && n) return bad(ctx, "ok is null");
-  gmod N; launch::words8 order;
-  int rc = schnorr_common(ctx, "schnorr_verify", msg, msg_bytes, stride_bytes, n, &N, &order); if (rc != ECSIMD_HIP_OK) return rc;
-  if (n == 0) return ECSIMD_HIP_OK;
-  (void)hipSetDevice(ctx->device);
+  group_order O;
+  int rc = schnorr_common(ctx, "schnorr_verify", msg, msg_bytes, stride_bytes, n, &O); if (rc != ECSIMD_HIP_OK) return rc;
+  ENTER_ANY_SIZE();
   const int curve = ECSIMD_HIP_SECP256K1;
-  const size_t chunk = n < VARWIN_CHUNK ? n : VARWIN_CHUNK, flag_bytes = ((chunk + 15) / 16) * 16;
-  const size_t front = verify_sizes(chunk).front, extra = 6 * chunk * 32 + 2 * flag_bytes;
+  const size_t chunk = chunk_of(n, VARWIN_CHUNK), front = dsm_plan(nullptr, chunk).bytes;
   // sizes the workspace (and builds the table) first, so that the pointers taken below stay valid
-  rc = ensure_window_table(ctx, curve, (ctx->window16_table[curve] != nullptr || n >= BIG_TABLE_WORTH_IT) ? launch::BIG_WINDOW_BITS : SIGNED_WBITS);
-  if (rc == ECSIMD_HIP_OK) rc = ensure_workspace(ctx, front + extra);
+  rc = public_base_product(ctx, curve, n);
+  if (rc == ECSIMD_HIP_OK) rc = ensure_workspace(ctx, front + recover_plan(nullptr, front, chunk, 2, true).extra);
   if (rc != ECSIMD_HIP_OK) return rc;
-  uint64_t* u1 = ctx->workspace + front / 8; uint64_t* u2 = u1 + 4 * chunk; uint64_t* qx = u2 + 4 * chunk; uint64_t* qy = qx + 4 * chunk;
-  uint64_t* rx = qy + 4 * chunk; uint64_t* ry = rx + 4 * chunk;
-  uint8_t* valid = reinterpret_cast<uint8_t*>(ry + 4 * chunk); uint8_t* fin = valid + flag_bytes;
-  for (size_t first = 0; first < n; first += chunk) {
-    const size_t m = n - first < chunk ? n - first : chunk;
-    launch::schnorr_verify_front(ctx->stream, order, px + 4 * first, r + 4 * first, s_ + 4 * first, msg ? msg + first * stride_bytes : nullptr, msg_bytes, stride_bytes, u1, u2, qx, qy, valid, m);
-    rc = double_scalar_mult_impl(ctx, curve, u1, u2, qx, qy, rx, ry, fin, m, extra, valid);
+  const recover_layout L = recover_plan(ctx->workspace, front, chunk, 2, true);      // px, py: the lifted P; more: R; more_flags: the sums' finite bytes
+  FOR_CHUNKS(first, m, n, chunk) {
+    launch::schnorr_verify_front(ctx->stream, O.words, px + 4 * first, r + 4 * first, s_ + 4 * first, msg ? msg + first * stride_bytes : nullptr, msg_bytes, stride_bytes, L.u1, L.u2, L.px, L.py, L.valid, m);
+    rc = double_scalar_mult_impl(ctx, curve, L.u1, L.u2, L.px, L.py, L.more[0], L.more[1], L.more_flags, m, L.extra, L.valid);
     if (rc != ECSIMD_HIP_OK) return rc;
-    launch::schnorr_accept(ctx->stream, rx, ry, fin, r + 4 * first, ok + first, m);
+    launch::schnorr_accept(ctx->stream, L.more[0], L.more[1], L.more_flags, r + 4 * first, ok + first, m);
   }
   hipError_t err = hipGetLastError();
   return err == hipSuccess ? ECSIMD_HIP_OK : fail(ctx, err, "schnorr_verify launch"); }
 
 // Signing: d G on the constant-time comb with both coordinates through the simultaneous inversion, k_schnorr_nonce, k0 G the same way, k_schnorr_finish.  Per
-// element of a chunk: the Jacobian product (96 B, used twice), the affine d G and k0 G (64 B each), k0 (32 B) -- all zeroed behind the kernels (ecdsa_sign says why).
+// element of a chunk: the Jacobian product (96 B, used twice), the affine d G and k0 G (64 B each), k0 (32 B) -- all zeroed behind the kernels (secret_base_product says why).
 int ecsimd_hip_schnorr_sign(ecsimd_hip_ctx* ctx, const uint64_t* d, const uint8_t* msg, size_t msg_bytes, size_t stride_bytes,
                             const uint64_t* aux, uint64_t* px, uint64_t* r, uint64_t* s_, uint8_t* ok, size_t n) {
   REQUIRE_CTX(); REQUIRE_PTR(d); REQUIRE_PTR(r); REQUIRE_PTR(s_);
   if ((aux && !aligned16(aux)) || (px && !aligned16(px))) return bad(ctx, "aux or px is not 16-byte aligned");
   if (!ok && n) return bad(ctx, "ok is null");
-  gmod N; launch::words8 order;
-  int rc = schnorr_common(ctx, "schnorr_sign", msg, msg_bytes, stride_bytes, n, &N, &order); if (rc != ECSIMD_HIP_OK) return rc;
-  if (n != 0) {
-    const void* in[3] = {d, aux, msg}; const void* out[3] = {r, s_, px};
-    for (int a = 0; a < 3; ++a) {
-      if (!out[a]) continue;
-      for (int b = 0; b < 3; ++b) if (in[b] && overlaps(out[a], in[b])) return bad(ctx, "r, s and px must not alias an input or each other");
-      for (int b = a + 1; b < 3; ++b) if (overlaps(out[a], out[b])) return bad(ctx, "r, s and px must not alias an input or each other");
-    }
-  }
-  if (n == 0) return ECSIMD_HIP_OK;
-  (void)hipSetDevice(ctx->device);
+  group_order O;
+  int rc = schnorr_common(ctx, "schnorr_sign", msg, msg_bytes, stride_bytes, n, &O); if (rc != ECSIMD_HIP_OK) return rc;
+  if (n != 0 && any_alias({r, s_, px}, {d, aux, msg})) return bad(ctx, "r, s and px must not alias an input or each other");
+  ENTER_ANY_SIZE();
   const int curve = ECSIMD_HIP_SECP256K1;
-  const size_t chunk = n < GC_CHUNK ? n : GC_CHUNK;
+  const size_t chunk = chunk_of(n, GC_CHUNK);
+  jacobian j; uint64_t *xP = nullptr, *yP = nullptr, *xR = nullptr, *yR = nullptr, *k0 = nullptr;
+  auto place = [&](void* base) {
+    carve c = carve_from(base);
+    j = carve_jacobian(c, chunk); xP = carve_limbs(c, chunk); yP = carve_limbs(c, chunk); xR = carve_limbs(c, chunk); yR = carve_limbs(c, chunk); k0 = carve_limbs(c, chunk);
+    return c;
+  };
   rc = ensure_window_table(ctx, curve, CT_WBITS);
-  if (rc == ECSIMD_HIP_OK) rc = ensure_workspace(ctx, 8 * chunk * 32);
+  if (rc == ECSIMD_HIP_OK) rc = ensure_workspace(ctx, place(nullptr).bytes);
   if (rc != ECSIMD_HIP_OK) return rc;
-  uint64_t* jx = ctx->workspace; uint64_t* jy = jx + 4 * chunk; uint64_t* jz = jy + 4 * chunk;
-  uint64_t* xP = jz + 4 * chunk; uint64_t* yP = xP + 4 * chunk; uint64_t* xR = yP + 4 * chunk; uint64_t* yR = xR + 4 * chunk; uint64_t* k0 = yR + 4 * chunk;
+  const carve ws = place(ctx->workspace);
   hipStream_t st = ctx->stream;
   hipError_t err = hipSuccess;
-  for (size_t first = 0; first < n && err == hipSuccess; first += chunk) {
-    const size_t m = n - first < chunk ? n - first : chunk;
+  FOR_CHUNKS(first, m, n, chunk) {
     const uint8_t* mp = msg ? msg + first * stride_bytes : nullptr;
-    launch::base_windowed_signed(st, curve, d + 4 * first, ctx->windowct_table[curve], jx, jy, jz, m, true);      // d >= n is reduced by the comb; the lane is refused below
-    launch::to_affine_batched(st, curve, jx, jy, jz, xP, yP, m, true);
-    launch::schnorr_nonce(st, order, d + 4 * first, aux ? aux + 4 * first : nullptr, xP, yP, mp, msg_bytes, stride_bytes, k0, m);
-    launch::base_windowed_signed(st, curve, k0, ctx->windowct_table[curve], jx, jy, jz, m, true);
-    launch::to_affine_batched(st, curve, jx, jy, jz, xR, yR, m, true);
-    launch::schnorr_finish(st, N, d + 4 * first, k0, xP, yP, xR, yR, mp, msg_bytes, stride_bytes, px ? px + 4 * first : nullptr, r + 4 * first, s_ + 4 * first, ok + first, m);
-    err = hipGetLastError();
-    hipError_t wiped = hipMemsetAsync(ctx->workspace, 0, 8 * chunk * 32, st);                                     // whatever the launches said
-    if (err == hipSuccess) err = wiped;
+    secret_base_product(ctx, curve, d + 4 * first, j, xP, yP, m);
+    launch::schnorr_nonce(st, O.words, d + 4 * first, aux ? aux + 4 * first : nullptr, xP, yP, mp, msg_bytes, stride_bytes, k0, m);
+    secret_base_product(ctx, curve, k0, j, xR, yR, m);
+    launch::schnorr_finish(st, O.N, d + 4 * first, k0, xP, yP, xR, yR, mp, msg_bytes, stride_bytes, px ? px + 4 * first : nullptr, r + 4 * first, s_ + 4 * first, ok + first, m);
+    err = wipe_workspace(ctx, ws.bytes, hipGetLastError());
+    if (err != hipSuccess) break;
   }
   return err == hipSuccess ? ECSIMD_HIP_OK : fail(ctx, err, "schnorr_sign launch"); }
 
@@ -2086,11 +2088,9 @@ int ecsimd_hip_fe29_raw(ecsimd_hip_ctx* ctx, int curve, int op, const int32_t* i
   gcurve GC; const bool registered = curve >= ECSIMD_HIP_FIRST_REGISTERED_CURVE;
   if (registered) { if (!lookup_curve(curve, &GC)) return bad(ctx, "unknown curve id"); }
   else REQUIRE_CURVE();
-  if (n == 0) return ECSIMD_HIP_OK;
-  if (n > (size_t)0x7fffffff * BLOCK) return bad(ctx, "batch too large");
-  hipError_t e = hipSetDevice(ctx->device); if (e != hipSuccess) return fail(ctx, e, "hipSetDevice");
+  ENTER();
   if (!launch::fe29_raw(ctx->stream, registered ? 2 : curve, registered ? &GC : nullptr, op, in, out, n, swap ? 0xffffffffu : 0u)) return bad(ctx, "fe29_raw: this function does not exist for this curve");
-  e = hipGetLastError();
+  hipError_t e = hipGetLastError();
   return e == hipSuccess ? ECSIMD_HIP_OK : fail(ctx, e, "fe29_raw launch"); }
 
 int ecsimd_hip_workspace_info(ecsimd_hip_ctx* ctx, const void** dptr, size_t* bytes) {
@@ -2139,19 +2139,10 @@ int ecsimd_hip_hmac_sha512(ecsimd_hip_ctx* ctx, const uint8_t* key, size_t key_b
 
 // ---- BIP-32 key derivation on secp256k1 (k_bip32.hip)
 namespace {
-int bip32_common(ecsimd_hip_ctx* ctx, const char* what, const uint32_t* index, gmod* N, launch::words8* order) {
+int bip32_common(ecsimd_hip_ctx* ctx, const char* what, const uint32_t* index, group_order* O) {
   if (reinterpret_cast<uintptr_t>(index) & 3u) return bad(ctx, "index is not 4-byte aligned");
-  if (ctx->ref_square) { snprintf(ctx->err, sizeof ctx->err, "bad argument: %s is not the reference's algorithm: no ECSIMD_HIP_REF_SQUARE_COMPAT form", what); return ECSIMD_HIP_ERR_BAD_ARG; }
-  if (!lookup_modulus(ECSIMD_HIP_FIELD_SECP256K1_ORDER, N)) return bad(ctx, "group order missing from the registry");
-  for (int i = 0; i < 8; ++i) order->w[i] = N->p[i];
-  return ECSIMD_HIP_OK;
-}
-bool any_alias(const void* const* out, int outs, const void* const* in, int ins) {
-  for (int a = 0; a < outs; ++a) {
-    for (int b = 0; b < ins; ++b) if (in[b] && overlaps(out[a], in[b])) return true;
-    for (int b = a + 1; b < outs; ++b) if (overlaps(out[a], out[b])) return true;
-  }
-  return false;
+  if (wants_compat(ctx)) return refuse_compat(ctx, what);
+  return builtin_order(ctx, ECSIMD_HIP_SECP256K1, O);
 }
 }  // namespace
 
@@ -2160,86 +2151,61 @@ int ecsimd_hip_bip32_master(ecsimd_hip_ctx* ctx, const uint8_t* seed, size_t see
   if ((!ok || !seed) && n) return bad(ctx, "seed or ok is null");
   if (seed_bytes < 16 || seed_bytes > 64) return bad(ctx, "bip32_master: seed_bytes is outside 16 .. 64");
   if (stride_bytes < seed_bytes) return bad(ctx, "bip32_master: stride_bytes is smaller than seed_bytes");
-  gmod N; launch::words8 order;
-  int rc = bip32_common(ctx, "bip32_master", nullptr, &N, &order); if (rc != ECSIMD_HIP_OK) return rc;
-  if (n != 0) { const void* out[3] = {k, c, ok}; const void* in[1] = {seed}; if (any_alias(out, 3, in, 1)) return bad(ctx, "k, c and ok must not alias an input or each other"); }
-  RUN(launch::bip32_master(s, order, seed, seed_bytes, stride_bytes, k, c, ok, n)); }
+  group_order O;
+  int rc = bip32_common(ctx, "bip32_master", nullptr, &O); if (rc != ECSIMD_HIP_OK) return rc;
+  if (n != 0 && any_alias({k, c, ok}, {seed})) return bad(ctx, "k, c and ok must not alias an input or each other");
+  RUN(launch::bip32_master(s, O.words, seed, seed_bytes, stride_bytes, k, c, ok, n)); }
 
 // Without the caller's promise, per chunk of 2^22: k_par G on the constant-time comb with both coordinates through the simultaneous inversion
-// (taproot_tweak_seckey's two launches), then k_bip32_ckd_priv<true>.  Per element of a chunk: the Jacobian product (96 B) and the affine k_par G (64 B) -- all
-// zeroed behind the kernels (ecdsa_sign says why).  With the promise (or index == NULL and a hardened index_all): k_bip32_ckd_priv<false> alone, no workspace.
+// (secret_base_product), then k_bip32_ckd_priv<true>.  Per element of a chunk: the Jacobian product (96 B) and the affine k_par G (64 B) -- all
+// zeroed behind the kernels (secret_base_product says why).  With the promise (or index == NULL and a hardened index_all): k_bip32_ckd_priv<false> alone, no workspace.
 int ecsimd_hip_bip32_ckd_priv(ecsimd_hip_ctx* ctx, const uint64_t* k_par, const uint64_t* c_par, const uint32_t* index, uint32_t index_all, uint64_t* k_child, uint64_t* c_child,
                               uint8_t* ok, size_t n, int flags) {
   REQUIRE_CTX(); REQUIRE_PTR(k_par); REQUIRE_PTR(c_par); REQUIRE_PTR(k_child); REQUIRE_PTR(c_child);
   if (!ok && n) return bad(ctx, "ok is null");
   if (flags & ~ECSIMD_HIP_BIP32_ALL_HARDENED) return bad(ctx, "bip32_ckd_priv: unknown flag");
-  gmod N; launch::words8 order;
-  int rc = bip32_common(ctx, "bip32_ckd_priv", index, &N, &order); if (rc != ECSIMD_HIP_OK) return rc;
-  if (n != 0) {
-    const void* out[3] = {k_child, c_child, ok}; const void* in[3] = {k_par, c_par, index};
-    if (any_alias(out, 3, in, 3)) return bad(ctx, "k_child, c_child and ok must not alias an input or each other");
-  }
-  if (n == 0) return ECSIMD_HIP_OK;
-  (void)hipSetDevice(ctx->device);
+  group_order O;
+  int rc = bip32_common(ctx, "bip32_ckd_priv", index, &O); if (rc != ECSIMD_HIP_OK) return rc;
+  if (n != 0 && any_alias({k_child, c_child, ok}, {k_par, c_par, index})) return bad(ctx, "k_child, c_child and ok must not alias an input or each other");
   const int curve = ECSIMD_HIP_SECP256K1;
-  const size_t chunk = n < GC_CHUNK ? n : GC_CHUNK;
-  const bool hardened_only = (flags & ECSIMD_HIP_BIP32_ALL_HARDENED) != 0 || (!index && (index_all >> 31) != 0);
-  hipStream_t st = ctx->stream;
   hipError_t err = hipSuccess;
-  if (hardened_only) {                                         // no workspace: nothing to chunk
-    if (n > (size_t)0x7fffffff * BLOCK) return bad(ctx, "batch too large");
-    launch::bip32_ckd_priv(st, N, k_par, c_par, index, index_all, nullptr, nullptr, k_child, c_child, ok, n);
+  if ((flags & ECSIMD_HIP_BIP32_ALL_HARDENED) != 0 || (!index && (index_all >> 31) != 0)) {      // hardened only -- no workspace: nothing to chunk
+    ENTER();
+    launch::bip32_ckd_priv(ctx->stream, O.N, k_par, c_par, index, index_all, nullptr, nullptr, k_child, c_child, ok, n);
     err = hipGetLastError();
     return err == hipSuccess ? ECSIMD_HIP_OK : fail(ctx, err, "bip32_ckd_priv launch");
   }
+  ENTER_ANY_SIZE();
+  const size_t chunk = chunk_of(n, GC_CHUNK);
   rc = ensure_window_table(ctx, curve, CT_WBITS);
-  if (rc == ECSIMD_HIP_OK) rc = ensure_workspace(ctx, 5 * chunk * 32);
+  if (rc == ECSIMD_HIP_OK) rc = ensure_workspace(ctx, sign_plan(nullptr, chunk, true).bytes);
   if (rc != ECSIMD_HIP_OK) return rc;
-  uint64_t* jx = ctx->workspace; uint64_t* jy = jx + 4 * chunk; uint64_t* jz = jy + 4 * chunk; uint64_t* xP = jz + 4 * chunk; uint64_t* yP = xP + 4 * chunk;
-  for (size_t first = 0; first < n && err == hipSuccess; first += chunk) {
-    const size_t m = n - first < chunk ? n - first : chunk;
-    launch::base_windowed_signed(st, curve, k_par + 4 * first, ctx->windowct_table[curve], jx, jy, jz, m, true);  // k_par >= n is reduced by the comb; the lane is refused below
-    launch::to_affine_batched(st, curve, jx, jy, jz, xP, yP, m, true);
-    launch::bip32_ckd_priv(st, N, k_par + 4 * first, c_par + 4 * first, index ? index + first : nullptr, index_all, xP, yP, k_child + 4 * first, c_child + 4 * first, ok + first, m);
-    err = hipGetLastError();
-    hipError_t wiped = hipMemsetAsync(ctx->workspace, 0, 5 * chunk * 32, st);                                     // whatever the launches said
-    if (err == hipSuccess) err = wiped;
+  const sign_layout L = sign_plan(ctx->workspace, chunk, true);              // the Jacobian k_par G and both affine coordinates
+  FOR_CHUNKS(first, m, n, chunk) {
+    secret_base_product(ctx, curve, k_par + 4 * first, L.j, L.rx, L.ry, m);
+    launch::bip32_ckd_priv(ctx->stream, O.N, k_par + 4 * first, c_par + 4 * first, index ? index + first : nullptr, index_all, L.rx, L.ry, k_child + 4 * first, c_child + 4 * first, ok + first, m);
+    err = wipe_workspace(ctx, L.bytes, hipGetLastError());
+    if (err != hipSuccess) break;
   }
   return err == hipSuccess ? ECSIMD_HIP_OK : fail(ctx, err, "bip32_ckd_priv launch"); }
 
-// (cx, cy) = IL G + K per chunk of 2^22: k_bip32_ckd_pub_front (the hash, the curve equation, the range checks), then xonly_tweak_chain's middle -- IL G on the
+// (cx, cy) = IL G + K per chunk of 2^22: k_bip32_ckd_pub_front (the hash, the curve equation, the range checks), then tweak_middle -- IL G on the
 // public comb, k_tweak_add, ONE simultaneous inversion that keeps y --, then k_bip32_ckd_pub_accept.  Per element of a chunk: K, later the affine sum (64 B),
 // IL (32 B), the Jacobian sum (96 B) and the validity byte.  The child chain code goes straight to its output.
 int ecsimd_hip_bip32_ckd_pub(ecsimd_hip_ctx* ctx, const uint64_t* qx, const uint64_t* qy, const uint64_t* c_par, const uint32_t* index, uint32_t index_all, uint64_t* cx, uint64_t* cy,
                              uint64_t* c_child, uint8_t* ok, size_t n) {
   REQUIRE_CTX(); REQUIRE_PTR(qx); REQUIRE_PTR(qy); REQUIRE_PTR(c_par); REQUIRE_PTR(cx); REQUIRE_PTR(cy); REQUIRE_PTR(c_child);
   if (!ok && n) return bad(ctx, "ok is null");
-  gmod N; launch::words8 order;
-  int rc = bip32_common(ctx, "bip32_ckd_pub", index, &N, &order); if (rc != ECSIMD_HIP_OK) return rc;
-  if (n != 0) {
-    const void* out[4] = {cx, cy, c_child, ok}; const void* in[4] = {qx, qy, c_par, index};
-    if (any_alias(out, 4, in, 4)) return bad(ctx, "cx, cy, c_child and ok must not alias an input or each other");
-  }
-  if (n == 0) return ECSIMD_HIP_OK;
-  (void)hipSetDevice(ctx->device);
-  const int curve = ECSIMD_HIP_SECP256K1;
-  const size_t chunk = n < GC_CHUNK ? n : GC_CHUNK, flag_bytes = ((chunk + 15) / 16) * 16;
-  const bool big = ctx->window16_table[curve] != nullptr || n >= BIG_TABLE_WORTH_IT;
-  rc = ensure_window_table(ctx, curve, big ? launch::BIG_WINDOW_BITS : SIGNED_WBITS);
-  if (rc == ECSIMD_HIP_OK) rc = ensure_workspace(ctx, 6 * chunk * 32 + flag_bytes);
+  group_order O;
+  int rc = bip32_common(ctx, "bip32_ckd_pub", index, &O); if (rc != ECSIMD_HIP_OK) return rc;
+  if (n != 0 && any_alias({cx, cy, c_child, ok}, {qx, qy, c_par, index})) return bad(ctx, "cx, cy, c_child and ok must not alias an input or each other");
+  ENTER_ANY_SIZE();
+  tweak_layout L; rc = tweak_prepare(ctx, n, &L);
   if (rc != ECSIMD_HIP_OK) return rc;
-  uint64_t* jx = ctx->workspace; uint64_t* jy = jx + 4 * chunk; uint64_t* jz = jy + 4 * chunk;
-  uint64_t* x = jz + 4 * chunk; uint64_t* y = x + 4 * chunk; uint64_t* tt = y + 4 * chunk;
-  uint8_t* valid = reinterpret_cast<uint8_t*>(tt + 4 * chunk);
-  hipStream_t st = ctx->stream;
-  for (size_t first = 0; first < n; first += chunk) {
-    const size_t m = n - first < chunk ? n - first : chunk;
-    launch::bip32_ckd_pub_front(st, order, qx + 4 * first, qy + 4 * first, c_par + 4 * first, index ? index + first : nullptr, index_all, x, y, tt, c_child + 4 * first, valid, m);
-    if (big) launch::base_windowed_big(st, curve, tt, ctx->window16_table[curve], jx, jy, jz, m);
-    else launch::base_windowed_signed(st, curve, tt, ctx->window6_table[curve], jx, jy, jz, m, false);
-    launch::tweak_add(st, jx, jy, jz, x, y, m);
-    launch::to_affine_batched(st, curve, jx, jy, jz, x, y, m, true);                                   // K is spent: its place takes the affine sum
-    launch::bip32_ckd_pub_accept(st, x, y, jz, valid, cx + 4 * first, cy + 4 * first, c_child + 4 * first, ok + first, m);
+  FOR_CHUNKS(first, m, n, L.chunk) {
+    launch::bip32_ckd_pub_front(ctx->stream, O.words, qx + 4 * first, qy + 4 * first, c_par + 4 * first, index ? index + first : nullptr, index_all, L.x, L.y, L.t, c_child + 4 * first, L.valid, m);
+    tweak_middle(ctx, n, L, m);
+    launch::bip32_ckd_pub_accept(ctx->stream, L.x, L.y, L.j.z, L.valid, cx + 4 * first, cy + 4 * first, c_child + 4 * first, ok + first, m);
   }
   hipError_t err = hipGetLastError();
   return err == hipSuccess ? ECSIMD_HIP_OK : fail(ctx, err, "bip32_ckd_pub launch"); }

@@ -18,6 +18,7 @@ import pytest
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, os.path.join(ROOT, "tools"))
 import bip32_model as model  # noqa: E402
+import capi_secret_shape     # noqa: E402
 import ct_check              # noqa: E402
 import keccak_listing        # noqa: E402  (the listing reader: any unit's path)
 
@@ -200,11 +201,19 @@ def test_the_secret_kernels_keep_the_secrets_out_of_control_flow_and_addresses(l
 
 
 def test_the_priv_call_runs_the_constant_time_comb_and_wipes_its_workspace():
-    src = open(os.path.join(CSRC, "capi.hip")).read()
-    body = src[src.index("int ecsimd_hip_bip32_ckd_priv("):src.index("int ecsimd_hip_bip32_ckd_pub(")]
-    assert body.count("launch::base_windowed_signed(st, curve,") == 1 and body.count("ctx->windowct_table[curve], jx, jy, jz, m, true)") == 1
-    assert body.count("launch::to_affine_batched(st, curve, jx, jy, jz, xP, yP, m, true)") == 1
-    assert "ensure_workspace(ctx, 5 * chunk * 32)" in body and "hipMemsetAsync(ctx->workspace, 0, 5 * chunk * 32, st)" in body
+    src = capi_secret_shape.source()
+    capi_secret_shape.check_shared_product(src)                 # the constant-time comb, the inversion, the unconditional wipe: one copy of each in capi.hip
+    head = "int ecsimd_hip_bip32_ckd_priv("
+    # the route with a point multiplication: the shared product once per chunk over sign_plan's five arrays (the Jacobian product, x, y), wiped by that total
+    route = capi_secret_shape.check_secret_entry(src, head, products=1, route="ENTER_ANY_SIZE();")
+    assert "sign_plan(ctx->workspace, chunk, true)" in route and "secret_base_product(ctx, curve, k_par + 4 * first, L.j, L.rx, L.ry, m)" in route
+    layout = capi_secret_shape.function(src, "sign_layout sign_plan(")
+    assert layout.count("carve_jacobian(c, n)") == 1 and layout.count("carve_limbs(c, n)") == 2 and "L.bytes = c.bytes" in layout     # 5 x 32 B per element, as before
+    # the hardened-only route: decided from the flags and the indices' pointer, one launch, no workspace
+    body = capi_secret_shape.function(src, head)
+    hardened = body[body.index("if ((flags & ECSIMD_HIP_BIP32_ALL_HARDENED) != 0"):body.index("ENTER_ANY_SIZE();")]
+    assert hardened.count("launch::") == 1 and "launch::bip32_ckd_priv(ctx->stream, O.N, k_par, c_par, index, index_all, nullptr, nullptr," in hardened and "return" in hardened
+    assert "workspace" not in hardened and "_plan(" not in hardened and "secret_base_product" not in hardened
     assert "hipMemcpy" not in body and "Synchronize" not in body                                        # nothing is read back to choose the route
 
 

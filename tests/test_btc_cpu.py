@@ -16,6 +16,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, os.path.join(ROOT, "tools"))
 import bip340_model        # noqa: E402
 import btc_model as model  # noqa: E402
+import capi_secret_shape   # noqa: E402
 import ct_check            # noqa: E402
 import keccak_listing      # noqa: E402  (the listing reader: any unit's path)
 
@@ -214,13 +215,15 @@ def test_the_seckey_kernel_keeps_the_secrets_out_of_control_flow_and_addresses(b
 
 
 def test_the_seckey_call_runs_the_constant_time_comb_and_wipes_its_workspace():
-    src = open(os.path.join(CSRC, "capi.hip")).read()
-    body = src[src.index("int ecsimd_hip_taproot_tweak_seckey("):src.index("// ---- BIP-340 Schnorr signatures")]
-    assert body.count("launch::base_windowed_signed(st, curve,") == 1 and body.count("ctx->windowct_table[curve], jx, jy, jz, m, true)") == 1
-    assert body.count("launch::to_affine_batched(st, curve, jx, jy, jz, xP, yP, m, true)") == 1
-    assert "ensure_workspace(ctx, 5 * chunk * 32)" in body and "hipMemsetAsync(ctx->workspace, 0, 5 * chunk * 32, st)" in body
-    sign = src[src.index("int ecsimd_hip_schnorr_sign("):src.index("int ecsimd_hip_fe29_raw(")]
-    assert "ctx->windowct_table[curve], jx, jy, jz, m, true)" in sign                                # the arguments schnorr_sign passes
+    src = capi_secret_shape.source()
+    capi_secret_shape.check_shared_product(src)                 # the constant-time comb, the inversion, the unconditional wipe: one copy of each in capi.hip
+    # the shared product once per chunk over sign_plan's five arrays (the Jacobian product, x, y), wiped by that total
+    body = capi_secret_shape.check_secret_entry(src, "int ecsimd_hip_taproot_tweak_seckey(", products=1)
+    assert "sign_plan(ctx->workspace, chunk, true)" in body and "secret_base_product(ctx, curve, d + 4 * first, L.j, L.rx, L.ry, m)" in body
+    layout = capi_secret_shape.function(src, "sign_layout sign_plan(")
+    assert layout.count("carve_jacobian(c, n)") == 1 and layout.count("carve_limbs(c, n)") == 2 and "L.bytes = c.bytes" in layout     # 5 x 32 B per element, as before
+    sign = capi_secret_shape.function(src, "int ecsimd_hip_schnorr_sign(")
+    assert "secret_base_product(ctx, curve, d + 4 * first, j, xP, yP, m)" in sign                    # the same product as schnorr_sign's for d G
 
 
 PLANTS = {

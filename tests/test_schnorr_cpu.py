@@ -15,6 +15,7 @@ import pytest
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, os.path.join(ROOT, "tools"))
 import bip340_model as model   # noqa: E402
+import capi_secret_shape       # noqa: E402
 import ct_check                # noqa: E402
 
 CSRC = os.path.join(ROOT, "ecsimd_amd", "csrc")
@@ -200,10 +201,26 @@ def test_the_comb_and_the_inversion_between_them_with_d_as_the_scalar(built):
     assert rep["secret_loads"] == 2 and not rep["secret_lds"]
     rep = ct_check.check_secret_flow(asm, "k_to_affine_batchedILb1E", secret_args=[0, 1, 2, 3, 4])
     assert rep["secret_loads"] >= 6
-    src = open(os.path.join(CSRC, "capi.hip")).read()
-    body = src[src.index("int ecsimd_hip_schnorr_sign("):src.index("int ecsimd_hip_fe29_raw(")]
-    assert body.count("launch::base_windowed_signed(st, curve,") == 2 and body.count("ctx->windowct_table[curve], jx, jy, jz, m, true)") == 2
-    assert body.count("launch::to_affine_batched(st, curve, jx, jy, jz,") == 2 and "hipMemsetAsync(ctx->workspace, 0, 8 * chunk * 32, st)" in body
+    src = capi_secret_shape.source()
+    capi_secret_shape.check_shared_product(src)                 # the constant-time comb, the inversion, the unconditional wipe: one copy of each in capi.hip
+    # schnorr_sign: the shared product twice (d G, then k0 G over the same Jacobian arrays) inside ONE wiped scope of eight arrays per element
+    body = capi_secret_shape.check_secret_entry(src, "int ecsimd_hip_schnorr_sign(", products=2)
+    assert "secret_base_product(ctx, curve, d + 4 * first, j, xP, yP, m)" in body and "secret_base_product(ctx, curve, k0, j, xR, yR, m)" in body
+    place = body[body.index("auto place = "):body.index("return c;")]
+    assert place.count("carve_jacobian(c, chunk)") == 1 and place.count("carve_limbs(c, chunk)") == 5                       # 8 x 32 B per element, as before
+    # ECDSA: both entry points go through the one signer per curve kind, and the built-in one through the shared product once: x only (4 arrays) for
+    # ecdsa_sign, with y (5 arrays) for ecdsa_sign_recoverable
+    for head in ("int ecsimd_hip_ecdsa_sign(", "int ecsimd_hip_ecdsa_sign_recoverable("):
+        entry = capi_secret_shape.function(src, head)
+        assert len(re.findall(r"\becdsa_sign_builtin\(", entry)) == 1 and len(re.findall(r"\becdsa_sign_registered\(", entry)) == 1, head
+        assert "launch::" not in entry and "workspace" not in entry and "hipMemcpy" not in entry and "Synchronize" not in entry, head
+    signer = capi_secret_shape.check_secret_entry(src, "int ecdsa_sign_builtin(", products=1)
+    assert "sign_plan(ctx->workspace, n, v != nullptr)" in signer and "secret_base_product(ctx, curve, k, L.j, L.rx, L.ry, n)" in signer
+    assert "L.ry = keep_y ? carve_limbs(c, n) : nullptr" in capi_secret_shape.function(src, "sign_layout sign_plan(")
+    registered = capi_secret_shape.function(src, "int ecdsa_sign_registered(")
+    assert "rc = ensure_workspace(ctx, L.bytes);" in registered and "L = gc_plan(ctx->workspace, n);" in registered
+    assert re.search(r"^\s*const hipError_t err = wipe_workspace\(ctx, L\.bytes, hipGetLastError\(\)\);", registered, re.M)   # the same unconditional wipe, over gc_plan's total
+    assert "hipMemcpy" not in registered and "Synchronize" not in registered
 
 
 PLANTS = {
