@@ -2209,4 +2209,92 @@ int ecsimd_hip_bip32_ckd_pub(ecsimd_hip_ctx* ctx, const uint64_t* qx, const uint
   }
   hipError_t err = hipGetLastError();
   return err == hipSuccess ? ECSIMD_HIP_OK : fail(ctx, err, "bip32_ckd_pub launch"); }
+
+// ---- PBKDF2-HMAC-SHA-512 and the BIP-39 seed (k_pbkdf2.hip); SECRET contents, PUBLIC lengths
+namespace {
+// How much one launch may do.  The loop body of k_pbkdf2 is 7 936 VALU instructions per iteration in the shipped listing (profiles/r11/bip39_listing.json) and the
+// device issues 35.5 T of them a second (39.3 T a priori, 35.2 .. 35.9 T read by ecsimd_hip_peak_mad32), which predicted 2^29 x 7 936 / 35.5 T =
+// 0.12 s for a launch of PBKDF2_UNIT_ITERATIONS = 2^29 (unit, iteration) pairs.  MEASURED on an MI355X (profiles/r11/bip39.txt): 109.7 ms for BIP-39's launch of 2^18
+// lanes x 2 048 iterations.  A unit is one 64-byte output block of one lane.  ECSIMD_HIP_PBKDF2_SLICE = 4 096 iterations bounds a launch of few units (65 lanes:
+// predicted 4 096 x 7 936 x 4 cycles at 2.4 GHz = 54 ms, measured 57.0 ms) and is twice BIP-39's count, so that c = 2 048 is ONE launch per chunk without the
+// workspace; PBKDF2_UNITS = 2^18 is 2^29 / 2 048, BIP-39's chunk, and two full residencies of the device at the kernel's two waves per SIMD (256 CUs x 4 SIMDs x
+// 2 waves x 64 lanes = 2^17).  From 4 096 iterations on a launch has 2^17 units: one residency.
+constexpr size_t PBKDF2_UNITS = (size_t)1 << 18;
+constexpr size_t PBKDF2_UNIT_ITERATIONS = (size_t)1 << 29;
+constexpr size_t PBKDF2_MAX_BYTES = (size_t)1 << 30;              // of a password, a salt, a derived key: lengths are 32-bit in the kernel
+static_assert(PBKDF2_UNIT_ITERATIONS / ECSIMD_HIP_PBKDF2_SLICE >= 1 && PBKDF2_UNIT_ITERATIONS / PBKDF2_UNITS <= ECSIMD_HIP_PBKDF2_SLICE, "the chunk is never empty and BIP-39's is PBKDF2_UNITS");
+struct pbkdf2_layout { void* state; size_t bytes; };              // inner midstate, outer midstate, U, T: 256 B per unit of a sliced derivation
+pbkdf2_layout pbkdf2_plan(void* base, size_t units) {
+  pbkdf2_layout L; carve c = carve_from(base);
+  L.state = carve_bytes(c, units * 256); L.bytes = c.bytes;
+  return L;
+}
+// n byte strings as the call takes its passwords and its salts: lane i's at p + i * stride, lens[i] bytes of it (at most stride), or `bytes` where lens == NULL
+struct byte_rows { const uint8_t* p; size_t bytes, stride; const uint32_t* lens; };
+int pbkdf2_rows(ecsimd_hip_ctx* ctx, const char* what, byte_rows& r, size_t n, bool one_for_all) {
+  if (r.lens) r.bytes = 0;                                                          // (ignored: every lane has its own length)
+  const bool shared = one_for_all && r.stride == 0;
+  const char* wrong = nullptr;
+  if (!r.p && n && (r.bytes || (r.lens && r.stride))) wrong = "is null";
+  else if (reinterpret_cast<uintptr_t>(r.lens) & 3u) wrong = "has lens that are not 4-byte aligned";
+  else if (shared && r.lens) wrong = "has stride 0 (one for the call) and lens";
+  else if (!shared && r.stride < r.bytes) wrong = "has a stride smaller than its length";
+  else if (r.bytes > PBKDF2_MAX_BYTES || (r.lens && r.stride > PBKDF2_MAX_BYTES)) wrong = "is too long (with lens, a lane may be as long as the stride)";
+  if (!wrong) return ECSIMD_HIP_OK;
+  snprintf(ctx->err, sizeof ctx->err, "bad argument: pbkdf2_hmac_sha512: the %s %s", what, wrong);
+  return ECSIMD_HIP_ERR_BAD_ARG;
+}
+byte_rows rows_from(const byte_rows& r, size_t first) { byte_rows q = r; if (q.p) q.p += first * q.stride; if (q.lens) q.lens += first; return q; }
+
+// The derivation behind both entry points.  pre: pre_bytes (0 or 8) bytes in front of every salt.  Lanes in chunks and output blocks in groups of at most
+// PBKDF2_UNITS units and PBKDF2_UNIT_ITERATIONS per launch; the iterations of a unit in slices of ECSIMD_HIP_PBKDF2_SLICE, between which its four states lie in
+// the workspace -- zeroed behind the last slice whatever the launches said.  iterations <= ECSIMD_HIP_PBKDF2_SLICE: one launch per chunk, no workspace.
+int pbkdf2_derive(ecsimd_hip_ctx* ctx, byte_rows pw, byte_rows salt, uint64_t pre, unsigned pre_bytes, uint32_t iterations, uint8_t* out, size_t dk_bytes, size_t out_stride_bytes, size_t n) {
+  int rc = pbkdf2_rows(ctx, "password", pw, n, false); if (rc != ECSIMD_HIP_OK) return rc;
+  rc = pbkdf2_rows(ctx, "salt", salt, n, true); if (rc != ECSIMD_HIP_OK) return rc;
+  if (iterations < 1 || dk_bytes < 1 || dk_bytes > PBKDF2_MAX_BYTES) return bad(ctx, "pbkdf2_hmac_sha512: iterations and dk_bytes are at least 1 (dk_bytes at most 2^30)");
+  if (out_stride_bytes < dk_bytes) return bad(ctx, "pbkdf2_hmac_sha512: out_stride_bytes is smaller than dk_bytes");
+  if (!out && n) return bad(ctx, "the output is null");
+  if (n != 0 && any_alias({out}, {pw.p, salt.p, pw.lens, salt.lens})) return bad(ctx, "out must not alias an input");
+  ENTER_ANY_SIZE();
+  const size_t slice = ECSIMD_HIP_PBKDF2_SLICE, blocks = (dk_bytes + 63) / 64;
+  const size_t most = chunk_of(PBKDF2_UNITS, PBKDF2_UNIT_ITERATIONS / chunk_of(iterations, slice));
+  const size_t chunk = chunk_of(n, most), group = chunk_of(blocks, chunk_of(most / chunk, 1u << 15));      // (a grid's y is below 2^16)
+  const bool sliced = iterations > slice;
+  pbkdf2_layout L = pbkdf2_plan(nullptr, 0);
+  if (sliced) {
+    rc = ensure_workspace(ctx, pbkdf2_plan(nullptr, chunk * group).bytes);
+    if (rc != ECSIMD_HIP_OK) return rc;
+    L = pbkdf2_plan(ctx->workspace, chunk * group);
+  }
+  hipError_t err = hipSuccess;
+  FOR_CHUNKS(first, m, n, chunk) {
+    const byte_rows P = rows_from(pw, first), S = rows_from(salt, first);
+    FOR_CHUNKS(block, nb, blocks, group) {
+      for (size_t done = 0, take; done < iterations; done += take) {
+        take = chunk_of(iterations - done, slice);
+        launch::pbkdf2_hmac_sha512(ctx->stream, done == 0, done + take == iterations, P.p, P.bytes, P.stride, P.lens, S.p, S.bytes, S.stride, S.lens, pre, pre_bytes, (unsigned)block,
+                                   (unsigned)nb, (unsigned)(done == 0 ? take - 1 : take), L.state, out + first * out_stride_bytes, dk_bytes, out_stride_bytes, m);
+      }
+      err = sliced ? wipe_workspace(ctx, L.bytes, hipGetLastError()) : hipGetLastError();
+      if (err != hipSuccess) break;
+    }
+    if (err != hipSuccess) break;
+  }
+  return err == hipSuccess ? ECSIMD_HIP_OK : fail(ctx, err, "pbkdf2_hmac_sha512 launch");
+}
+}  // namespace
+
+// (ECSIMD_HIP_REF_SQUARE_COMPAT concerns curve arithmetic: there is none here, so a context with that option is served like any other)
+int ecsimd_hip_pbkdf2_hmac_sha512(ecsimd_hip_ctx* ctx, const uint8_t* pw, size_t pw_bytes, size_t pw_stride_bytes, const uint32_t* pw_lens, const uint8_t* salt, size_t salt_bytes,
+                                  size_t salt_stride_bytes, const uint32_t* salt_lens, uint32_t iterations, uint8_t* out, size_t dk_bytes, size_t out_stride_bytes, size_t n) {
+  REQUIRE_CTX();
+  return pbkdf2_derive(ctx, {pw, pw_bytes, pw_stride_bytes, pw_lens}, {salt, salt_bytes, salt_stride_bytes, salt_lens}, 0u, 0u, iterations, out, dk_bytes, out_stride_bytes, n); }
+
+// salt = "mnemonic" || passphrase: the eight bytes are ONE block word, handed to the kernel by value
+int ecsimd_hip_bip39_seed(ecsimd_hip_ctx* ctx, const uint8_t* mnemonic, size_t mnemonic_bytes, size_t mnemonic_stride_bytes, const uint32_t* mnemonic_lens, const uint8_t* passphrase,
+                          size_t passphrase_bytes, size_t passphrase_stride_bytes, const uint32_t* passphrase_lens, uint8_t* seed64, size_t n) {
+  REQUIRE_CTX();
+  return pbkdf2_derive(ctx, {mnemonic, mnemonic_bytes, mnemonic_stride_bytes, mnemonic_lens}, {passphrase, passphrase_bytes, passphrase_stride_bytes, passphrase_lens},
+                       0x6d6e656d6f6e6963ull /* "mnemonic" */, 8u, 2048u, seed64, 64, 64, n); }
 }  // extern "C"

@@ -172,6 +172,14 @@ void bip32_ckd_pub_front(hipStream_t, const words8& order, const uint64_t* qx, c
 void bip32_ckd_pub_accept(hipStream_t, const uint64_t* ax, const uint64_t* ay, const uint64_t* jz, const uint8_t* valid, uint64_t* cx, uint64_t* cy, uint64_t* c_child, uint8_t* ok,
                           size_t n);
 
+// k_pbkdf2.hip: PBKDF2-HMAC-SHA-512, one (password, salt) pair per lane and `blocks` 64-byte output blocks block_first .. block_first + blocks - 1 (the grid's y) of
+// each.  SECRET contents, PUBLIC lengths: pw / salt as hmac_sha512's key (salt_stride_bytes == 0: one salt for the call), *_lens as keccak256's, any alignment.
+// pre: pre_bytes (0 or 8) bytes that stand in front of every salt (big-endian in the word).  first: the set-up and U_1 run (otherwise the n * blocks units of 256 B
+// at `state` are read); then `loops` times U = HMAC(P, U), T ^= U; last: T goes to out + i * out_stride_bytes + 64 block, dk_bytes in all (otherwise `state` is written).
+void pbkdf2_hmac_sha512(hipStream_t, bool first, bool last, const uint8_t* pw, size_t pw_bytes, size_t pw_stride_bytes, const uint32_t* pw_lens, const uint8_t* salt,
+                        size_t salt_bytes, size_t salt_stride_bytes, const uint32_t* salt_lens, uint64_t pre, unsigned pre_bytes, unsigned block_first, unsigned blocks,
+                        unsigned loops, void* state, uint8_t* out, size_t dk_bytes, size_t out_stride_bytes, size_t n);
+
 // k_fe29_raw.hip: one function of fe29.cuh on raw 9-limb operands (the diagnostic entry ecsimd_hip_fe29_raw)
 enum fe29_raw_op { RAW_ZDAU = 0, RAW_MADD = 1, RAW_JDBL = 2, RAW_DBL_ADD = 3, RAW_MADDV = 4, RAW_PDBL = 5, RAW_PADD = 6, RAW_MUL = 7, RAW_SQR = 8, RAW_GJDBL = 9, RAW_ZADDU = 10 };
 constexpr int fe29_raw_inputs(int op) { return op == RAW_ZDAU ? 6 : op == RAW_MUL ? 2 : op == RAW_SQR ? 1 : (op == RAW_JDBL || op == RAW_PDBL) ? 3 : op == RAW_GJDBL ? 4 : 5; }

@@ -605,6 +605,72 @@ class Engine:
             ok = ok & level_ok
         return k, c, ok
 
+    def _lens(self, lens, n, what):
+        """The pointer of a per-lane length argument: None, or an int32 / uint32 device tensor of n lengths."""
+        if lens is None:
+            return C.c_void_p(0)
+        torch = self.torch
+        assert lens.is_cuda and lens.device.index == self.device and lens.is_contiguous() and lens.dim() == 1, "lens: a contiguous 1-D tensor on the engine's device"
+        assert lens.dtype in (torch.int32, torch.uint32), lens.dtype
+        if int(lens.shape[0]) != n:
+            raise EcsimdHipError(f"{what}: operands disagree on the batch length: {sorted((n, int(lens.shape[0])))}")
+        return C.c_void_p(lens.data_ptr() if n else 0)
+
+    def _rows_or_one(self, t, n, what):
+        """(keep-alive, pointer, length, stride) of a 2-D uint8 device tensor with a row per lane, or of a 1-D one that serves the whole call (stride 0)."""
+        torch = self.torch
+        assert t.is_cuda and t.device.index == self.device and t.dtype == torch.uint8 and t.dim() in (1, 2), (t.dtype, t.shape)
+        if t.dim() == 1:
+            t = t.contiguous()
+            return t, C.c_void_p(t.data_ptr() if t.shape[0] else 0), C.c_size_t(int(t.shape[0])), C.c_size_t(0)
+        try:
+            return self._messages(t, n)
+        except EcsimdHipError as exc:
+            raise EcsimdHipError(f"{what}: {exc}") from None
+
+    def pbkdf2_hmac_sha512(self, passwords, salts, iterations, dk_bytes, pw_lens=None, salt_lens=None, out=None):
+        """ecsimd_hip_pbkdf2_hmac_sha512: (n, dk_bytes) uint8, PBKDF2-HMAC-SHA-512 of the rows of `passwords` (2-D uint8 device tensor, rows may be strided) under
+        `salts`: a 2-D tensor holds a salt per row, a 1-D one is ONE salt for the whole call.  pw_lens / salt_lens (optional int32 / uint32 device tensors of n
+        lengths, each at most the row length): lane i uses the first lens[i] bytes of its row.  out (optional): a 2-D uint8 device tensor of n rows of at least
+        dk_bytes columns whose rows are written in place (a column slice of a wider array keeps the bytes between the keys).  SECRET contents, public lengths."""
+        torch = self.torch
+        assert passwords.dim() == 2, passwords.shape
+        n = int(passwords.shape[0])
+        if out is None:
+            out = torch.empty((n, int(dk_bytes)), dtype=torch.uint8, device=self.tdev)
+        assert out.is_cuda and out.device.index == self.device and out.dtype == torch.uint8 and out.dim() == 2 and out.shape[1] >= dk_bytes and (out.stride(1) == 1 or out.shape[1] <= 1), (out.dtype, out.shape)
+        if int(out.shape[0]) != n:
+            raise EcsimdHipError(f"pbkdf2_hmac_sha512: operands disagree on the batch length: {sorted((n, int(out.shape[0])))}")
+        keep_p, pp, plen, pstride = self._rows_or_one(passwords, n, "pbkdf2_hmac_sha512")
+        keep_s, sp, slen, sstride = self._rows_or_one(salts, n, "pbkdf2_hmac_sha512")
+        if salts.dim() == 1 and salt_lens is not None:
+            raise EcsimdHipError("pbkdf2_hmac_sha512: one salt for the call takes no salt_lens")
+        stride = int(out.stride(0)) if n > 1 else max(int(out.shape[1]), int(dk_bytes))
+        self._call("pbkdf2_hmac_sha512", pp, plen, pstride, self._lens(pw_lens, n, "pbkdf2_hmac_sha512"), sp, slen, sstride, self._lens(salt_lens, n, "pbkdf2_hmac_sha512"),
+                   C.c_uint32(int(iterations)), C.c_void_p(out.data_ptr() if n else 0), C.c_size_t(int(dk_bytes)), C.c_size_t(stride), C.c_size_t(n))
+        return out[:, :dk_bytes] if out.shape[1] != dk_bytes else out
+
+    def bip39_seed(self, mnemonics, passphrases=None, mnemonic_lens=None, passphrase_lens=None):
+        """ecsimd_hip_bip39_seed: (n, 64) uint8, the BIP-39 seed of each SECRET sentence, a row of `mnemonics` (2-D uint8 device tensor; mnemonic_lens: the
+        sentences' own lengths where they differ).  passphrases: None = the empty passphrase, a 1-D tensor = one for the call, a 2-D one = a row per lane (with
+        passphrase_lens).  Bytes as given: NFKD, the word list and the checksum are the caller's."""
+        torch = self.torch
+        assert mnemonics.dim() == 2, mnemonics.shape
+        n = int(mnemonics.shape[0]); seed = torch.empty((n, 64), dtype=torch.uint8, device=self.tdev)
+        if passphrases is None:
+            passphrases = torch.empty((0,), dtype=torch.uint8, device=self.tdev)
+        keep_m, mp, mlen, mstride = self._rows_or_one(mnemonics, n, "bip39_seed")
+        keep_p, pp, plen, pstride = self._rows_or_one(passphrases, n, "bip39_seed")
+        if passphrases.dim() == 1 and passphrase_lens is not None:
+            raise EcsimdHipError("bip39_seed: one passphrase for the call takes no passphrase_lens")
+        self._call("bip39_seed", mp, mlen, mstride, self._lens(mnemonic_lens, n, "bip39_seed"), pp, plen, pstride, self._lens(passphrase_lens, n, "bip39_seed"),
+                   C.c_void_p(seed.data_ptr() if n else 0), C.c_size_t(n))
+        return seed
+
+    def bip39_master(self, mnemonics, passphrases=None, mnemonic_lens=None, passphrase_lens=None):
+        """(k, c, ok): the BIP-32 master key and chain code of each SECRET sentence -- bip39_seed, then bip32_master on the 64-byte seeds."""
+        return self.bip32_master(self.bip39_seed(mnemonics, passphrases, mnemonic_lens, passphrase_lens))
+
     def fe29_raw(self, curve, op, inputs, swap=0):
         """ecsimd_hip_fe29_raw: one function of the reduced-radix layer on raw int32 limbs; `inputs` is an int32 tensor (n, NIN, 9); returns (n, NOUT, 9)."""
         torch = self.torch

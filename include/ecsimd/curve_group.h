@@ -267,6 +267,14 @@ struct curve_group {
     hip::check(ecsimd_hip_bip32_master(hip::context(), seeds.data(), seeds.msg_bytes(), seeds.stride_bytes(), k.data(), c.data(), ok.data(), seeds.size()), "ecsimd_hip_bip32_master");
     return k;
   }
+  // The master key and chain code of the SECRET BIP-39 sentences (equal lengths; one passphrase each, or one for all): hip::bip39_seed, then bip32_master on the
+  // 64-byte seeds, which stay in device memory.
+  static WBN bip39_master(hip::messages const& mnemonics, hip::messages const& passphrases, WBN& c, hip::mask& ok) requires std::is_same_v<Curve, curve_secp256k1> {
+    const hip::derived_keys seeds = hip::bip39_seed(mnemonics, passphrases);
+    auto k = WBN::uninitialized(seeds.size()); c = WBN::uninitialized(seeds.size()); ok = hip::mask(seeds.size());
+    hip::check(ecsimd_hip_bip32_master(hip::context(), seeds.data(), 64, 64, k.data(), c.data(), ok.data(), seeds.size()), "ecsimd_hip_bip32_master");
+    return k;
+  }
   // CKDpriv of the SECRET nodes (k, c) at one index for every lane, or at index[i]; c_child is written, the child key returned.  ok[i] is false -- and both are
   // 0 -- where k is not in [1, n).  flags: ECSIMD_HIP_BIP32_ALL_HARDENED, the promise that every index is hardened (no point multiplication).  A hardened index for
   // every lane takes that route by itself.  k G runs on the constant-time comb; no branch or address depends on k, c or the results.

@@ -576,6 +576,35 @@ int ecsimd_hip_bip32_ckd_priv(ecsimd_hip_ctx*, const uint64_t* k_par, const uint
                               uint64_t* k_child, uint64_t* c_child, uint8_t* ok, size_t n, int flags);
 int ecsimd_hip_bip32_ckd_pub(ecsimd_hip_ctx*, const uint64_t* qx, const uint64_t* qy, const uint64_t* c_par, const uint32_t* index, uint32_t index_all,
                              uint64_t* cx, uint64_t* cy, uint64_t* c_child, uint8_t* ok, size_t n);
+/* PBKDF2 (RFC 8018 section 5.2) with HMAC-SHA-512 as the PRF over n (password, salt) pairs, one per lane, and BIP-39's seed, which is one such derivation.
+ * Lane i's password: pw + i * pw_stride_bytes, its salt: salt + i * salt_stride_bytes (device memory).  pw_lens / salt_lens as lens of ecsimd_hip_keccak256: NULL:
+ * every lane uses pw_bytes / salt_bytes (stride >= bytes); otherwise n x u32 of device memory, 4-byte aligned, lane i uses lens[i] <= stride bytes (a larger value
+ * is read as the stride), the stride is at most 2^30 and pw_bytes / salt_bytes is ignored.  Without lens, pw_bytes and salt_bytes are at most 2^30.  salt_stride_bytes == 0: ONE salt of salt_bytes bytes for the whole call, as the key of
+ * ecsimd_hip_hmac_sha512; salt_lens must then be NULL.  Any length including 0 (the pointer may then be NULL), any alignment (word loads where base and stride are
+ * multiples of 4, byte loads otherwise).  A password of at most 128 bytes is zero-padded to the key block, a longer one is hashed first.  iterations >= 1,
+ * 1 <= dk_bytes <= 2^30, out_stride_bytes >= dk_bytes: lane i's derived key at out + i * out_stride_bytes, its bytes in order, the bytes between two keys untouched; out
+ * must not alias an input.  Anything else: ERR_BAD_ARG.  n = 0 succeeds.  ECSIMD_HIP_REF_SQUARE_COMPAT does not concern this call (no curve arithmetic): accepted.
+ * SECRET: the passwords' and the salts' bytes, the HMAC midstates, every U and T and the derived key.  PUBLIC: the lengths, iterations and dk_bytes: they steer the
+ * loads and the block loops (per lane where lens is given), as seed_bytes does in ecsimd_hip_bip32_master.  No branch, address or lane mask in force at a memory
+ * access depends on a secret and no bit is declassified (tools/ct_check.py check_secret_flow on the shipped ISA: tests/test_bip39_cpu.py).
+ * Cost: 2 (iterations - 1) + 4 or so SHA-512 compressions per lane and 64-byte output block; the blocks of a long key run side by side (the grid's second
+ * dimension).  A launch runs at most ECSIMD_HIP_PBKDF2_SLICE iterations over a bounded number of lanes, so that no launch holds a shared
+ * device for long whatever the caller's count.  iterations <= ECSIMD_HIP_PBKDF2_SLICE: one launch per chunk of lanes and no workspace.  Beyond: the lane's two
+ * midstates, U and T lie in the context workspace between launches, 256 B per lane and block of a chunk, and every byte used is zeroed on the stream before the call
+ * returns, whatever the launches said.  Stream-ordered, nothing is read back.  Any n.
+ *
+ * bip39_seed: seed64[64 i ..] = PBKDF2-HMAC-SHA512(password = mnemonic i, salt = "mnemonic" || passphrase i, 2048 iterations, 64 bytes): one launch per chunk, no
+ * workspace; the eight bytes of the prefix reach the kernel by value, no salt is staged.  mnemonic / passphrase as pw / salt above (passphrase_stride_bytes == 0: one
+ * passphrase for the call; passphrase == NULL with passphrase_bytes == 0: the empty passphrase).  The sentence and the passphrase are taken as BYTES: Unicode
+ * normalisation (NFKD), the word list and the checksum are the caller's -- a sentence that BIP-39 would reject derives a seed like any other.  The seed is the
+ * `seed` of ecsimd_hip_bip32_master (seed_bytes = stride_bytes = 64). */
+enum { ECSIMD_HIP_PBKDF2_SLICE = 4096 };
+int ecsimd_hip_pbkdf2_hmac_sha512(ecsimd_hip_ctx*, const uint8_t* pw, size_t pw_bytes, size_t pw_stride_bytes, const uint32_t* pw_lens,
+                                  const uint8_t* salt, size_t salt_bytes, size_t salt_stride_bytes, const uint32_t* salt_lens,
+                                  uint32_t iterations, uint8_t* out, size_t dk_bytes, size_t out_stride_bytes, size_t n);
+int ecsimd_hip_bip39_seed(ecsimd_hip_ctx*, const uint8_t* mnemonic, size_t mnemonic_bytes, size_t mnemonic_stride_bytes, const uint32_t* mnemonic_lens,
+                          const uint8_t* passphrase, size_t passphrase_bytes, size_t passphrase_stride_bytes, const uint32_t* passphrase_lens,
+                          uint8_t* seed64, size_t n);
 /* Diagnostic (r5): ONE function of the reduced-radix layer the multiplication-bound loops run on (fe29.cuh: nine signed 29-bit limbs in 32-bit words,
  * Montgomery radix 2^261, lazy carries) on RAW operands -- int32 limbs exactly as a loop holds them between two operations: element e's coordinate c, limb l at
  * in[(e * NIN + c) * 9 + l] (device memory).  What tests use to hand the device the states and operand pairs at which the interval proofs of

@@ -415,7 +415,8 @@ def check_secret_flow(text, want, secret_args, public_loads_from=()):
     S = "S"
     report = {"kernel": want, "instructions": sum(1 for b in blocks for i in b[2] if not i.startswith(".implicit_def")), "secret_loads": 0, "public_branches": 0, "lane_mask_updates": 0,
               "secret_scratch": False, "secret_lds": False, "kernarg_sgpr": kptr}
-    kp = {("s", kptr), ("s", kptr + 1)}
+    KP = "K"                                                    # the tag of the kernarg segment pointer: it follows the pointer through copies and spills
+    entry = {("s", kptr): frozenset({KP}), ("s", kptr + 1): frozenset({KP})}
 
     def transfer(n, state, final):
         """state: {reg: frozenset(tags)} plus the pseudo-registers 'scratch' / 'lds'.  Runs block n; with `final` set it raises on a violation."""
@@ -438,15 +439,34 @@ def check_secret_flow(text, want, secret_args, public_loads_from=()):
             if _IMPLICIT_SCC_READ.match(op):
                 src.append("scc")
             t = frozenset().union(*[tags(r) for r in src]) if src else frozenset()
+            if op not in ("s_mov_b32", "s_mov_b64"):
+                t = t - {KP}                                     # a value COMPUTED from the kernarg pointer is not the kernarg pointer
+            if not op.startswith("v_writelane"):                 # anything else that writes a VGPR overwrites the SGPRs spilled to its lanes
+                for r in dst:
+                    for lane in st.pop(("lanes", r), ()):
+                        st.pop(("lane", r, lane), None)
             bad = lambda what: (_ for _ in ()).throw(Violation(f"{lab}: a secret reaches {what} of `{inst}`")) if final else None
             masked = S in tags("exec")                           # the set of active lanes depends on a secret: moves under EXEC are fine (same issue
             if masked and op.startswith(("global_", "scratch_", "ds_", "s_load", "v_readfirstlane", "v_readlane", "v_writelane", "s_cbranch_exec")):
                 bad("the lane mask (EXEC) in force at")          # slot whatever the mask), anything whose cost or address set depends on it is not
             if masked and op.startswith("v_"):
                 t = t | tags("exec") | frozenset().union(*[tags(r) for r in dst if isinstance(r, tuple)])    # inactive lanes keep the old value
+            if op in ("v_writelane_b32", "v_readlane_b32") and re.fullmatch(r"\d+", ops[2].split()[0]):
+                # an SGPR spilled to ONE lane of a VGPR and read back from it: tracked per (register, lane), as the scratch slots below, so that a spilled
+                # pointer (the kernarg pointer among them) comes back as what it was and not as the union of everything that register holds
+                vreg = _operand_regs(ops[0] if op.startswith("v_writelane") else ops[1])[0]
+                slot = ("lane", vreg, int(ops[2].split()[0]))
+                if op.startswith("v_writelane"):
+                    st[slot] = frozenset().union(*[tags(r) for r in _operand_regs(ops[1])]) if _operand_regs(ops[1]) else frozenset()
+                    st[("lanes", vreg)] = st.get(("lanes", vreg), frozenset()) | {slot[2]}      # (lane numbers, not tags: which slots of this register are live)
+                    st[vreg] = tags(vreg) | (st[slot] - {KP})
+                else:
+                    for r in dst:
+                        st[r] = tags(slot) if slot in st else tags(vreg)
+                continue
             if op.startswith("s_load_dword"):
-                base = set(_operand_regs(ops[1]))
-                if base == kp and re.fullmatch(r"(0x[0-9a-f]+|\d+)", ops[2].split()[0]):
+                base = _operand_regs(ops[1])
+                if len(base) == 2 and all(KP in tags(r) for r in base) and re.fullmatch(r"(0x[0-9a-f]+|\d+)", ops[2].split()[0]):
                     first = int(ops[2].split()[0], 0)
                     for j, r in enumerate(dst):
                         b = first + 4 * j
@@ -562,7 +582,7 @@ def check_secret_flow(text, want, secret_args, public_loads_from=()):
                 else:
                     sh, val = (ops[1], ops[2]) if op.startswith("v_lshlrev") else (ops[2], ops[1])
                     lo = un(_operand_regs(sh)) | un(pair(val)[0])
-                st[dst[0]] = lo
+                st[dst[0]] = lo - {KP}
                 for r in dst[1:]:
                     st[r] = t
                 if op.startswith("s_"):
@@ -579,6 +599,10 @@ def check_secret_flow(text, want, secret_args, public_loads_from=()):
         for s_ in states:
             for r, t in s_.items():
                 out[r] = out.get(r, frozenset()) | t
+        for r in [r for r in out if isinstance(r, tuple) and r[0] == "lane"]:      # a spill slot that one path does not hold: there the lane is whatever the register is
+            for s_ in states:
+                if r not in s_:
+                    out[r] = out[r] | s_.get(r[1], frozenset())
         return out
 
     outs = [None] * len(blocks)
@@ -588,7 +612,7 @@ def check_secret_flow(text, want, secret_args, public_loads_from=()):
         changed = False
         rounds += 1
         for n in range(len(blocks)):
-            ins = join([outs[m] for m in preds[n] if outs[m] is not None])
+            ins = join([outs[m] for m in preds[n] if outs[m] is not None] + ([entry] if n == 0 else []))
             o = transfer(n, ins, False)
             if o != outs[n]:
                 outs[n] = o
@@ -596,7 +620,7 @@ def check_secret_flow(text, want, secret_args, public_loads_from=()):
         if rounds > 200:
             raise Violation("the analysis did not converge")
     for n in range(len(blocks)):
-        o = transfer(n, join([outs[m] for m in preds[n] if outs[m] is not None]), True)
+        o = transfer(n, join([outs[m] for m in preds[n] if outs[m] is not None] + ([entry] if n == 0 else [])), True)
         report["secret_scratch"] |= any(S in t_ for k_, t_ in o.items() if isinstance(k_, str) and k_.startswith("scratch"))
         report["secret_lds"] |= S in o.get("lds", frozenset())
     if report["secret_loads"] == 0:
