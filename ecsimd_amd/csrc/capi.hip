@@ -91,6 +91,8 @@ struct ecsimd_hip_ctx {
                                     // three degenerate scalars with its affine results for them on G (as base_special); built on first use
   ecsimd_hip_ctx* helper;      // ecsimd_hip_scalar_mult_host: the second stream's context (created on first use, destroyed with this one)
   uint64_t* hstage; size_t hstage_bytes;    // ... and this context's staging block for one chunk (grow-only)
+  uint64_t* pinned; size_t pinned_bytes;    // btc_merkle_root: the pinned host block its node offsets are uploaded from (grow-only) ...
+  hipEvent_t pinned_copied;                 // ... and the event behind the last upload: the next one waits for it before it overwrites the block
   char err[256];
 };
 
@@ -680,6 +682,7 @@ int ecsimd_hip_init(int device, ecsimd_hip_ctx** out) {
   if (!ctx) return ECSIMD_HIP_ERR_HIP;
   ctx->device = device; ctx->cus = prop.multiProcessorCount; ctx->err[0] = 0; ctx->sink = nullptr;
   ctx->window_table[0] = ctx->window_table[1] = nullptr; ctx->window6_table[0] = ctx->window6_table[1] = nullptr; ctx->windowct_table[0] = ctx->windowct_table[1] = nullptr; ctx->window16_table[0] = ctx->window16_table[1] = nullptr; ctx->workspace = nullptr; ctx->workspace_bytes = 0; ctx->ref_square = 0; ctx->valid = nullptr; ctx->valid_bytes = 0; ctx->base_special[0] = ctx->base_special[1] = nullptr; ctx->helper = nullptr; ctx->hstage = nullptr; ctx->hstage_bytes = 0;
+  ctx->pinned = nullptr; ctx->pinned_bytes = 0; ctx->pinned_copied = nullptr;
   if (hipSetDevice(device) != hipSuccess || hipStreamCreateWithFlags(&ctx->own_stream, hipStreamNonBlocking) != hipSuccess) { delete ctx; return ECSIMD_HIP_ERR_HIP; }
   ctx->stream = ctx->own_stream;
   if (hipEventCreateWithFlags(&ctx->handoff, hipEventDisableTiming) != hipSuccess) { (void)hipStreamDestroy(ctx->own_stream); delete ctx; return ECSIMD_HIP_ERR_HIP; }
@@ -695,6 +698,8 @@ int ecsimd_hip_destroy(ecsimd_hip_ctx* ctx) {
   (void)hipFree(ctx->window_table[0]); (void)hipFree(ctx->window_table[1]); (void)hipFree(ctx->window6_table[0]); (void)hipFree(ctx->window6_table[1]); (void)hipFree(ctx->windowct_table[0]); (void)hipFree(ctx->windowct_table[1]); (void)hipFree(ctx->window16_table[0]); (void)hipFree(ctx->window16_table[1]); (void)hipFree(ctx->workspace); (void)hipFree(ctx->valid); (void)hipFree(ctx->base_special[0]); (void)hipFree(ctx->base_special[1]);
   for (auto& t : ctx->gcomb) { (void)hipFree(t.table); (void)hipFree(t.special); (void)hipFree(t.table7); (void)hipFree(t.table5); (void)hipFree(t.table20); }
   (void)hipFree(ctx->hstage);
+  if (ctx->pinned) (void)hipHostFree(ctx->pinned);
+  if (ctx->pinned_copied) (void)hipEventDestroy(ctx->pinned_copied);
   if (ctx->helper) (void)ecsimd_hip_destroy(ctx->helper);
   (void)hipEventDestroy(ctx->handoff);
   (void)hipStreamDestroy(ctx->own_stream);
@@ -2008,6 +2013,152 @@ int ecsimd_hip_taproot_tweak_seckey(ecsimd_hip_ctx* ctx, const uint64_t* d, cons
     if (err != hipSuccess) break;
   }
   return err == hipSuccess ? ECSIMD_HIP_OK : fail(ctx, err, "taproot_tweak_seckey launch"); }
+
+// ---- Bitcoin: one length per lane, Merkle roots, BIP-341 script paths (k_btc_tree.hip); public data throughout
+namespace {
+// btc_hash_args for a call with lens: msg_bytes does not count, the rows do
+int btc_lens_args(ecsimd_hip_ctx* ctx, const char* what, const uint8_t* msg, size_t stride_bytes, const uint32_t* lens, const void* out, size_t n) {
+  int rc = btc_hash_args(ctx, what, msg, 0, stride_bytes, out, n); if (rc != ECSIMD_HIP_OK) return rc;
+  if (reinterpret_cast<uintptr_t>(lens) & 3u) return bad(ctx, "lens is not 4-byte aligned");
+  if (!msg && n && stride_bytes) return bad(ctx, "msg is null");
+  if (!stride_bytes && n > 1) return bad(ctx, "stride_bytes is 0 with lens: every lane would read the first row");
+  return ECSIMD_HIP_OK;
+}
+}  // namespace
+
+int ecsimd_hip_sha256_lens(ecsimd_hip_ctx* ctx, const uint8_t* msg, size_t msg_bytes, size_t stride_bytes, const uint32_t* lens, uint64_t* e, size_t n) {
+  if (!lens) return ecsimd_hip_sha256(ctx, msg, msg_bytes, stride_bytes, e, n);
+  REQUIRE_CTX(); REQUIRE_PTR(e);
+  int rc = btc_lens_args(ctx, "sha256_lens", msg, stride_bytes, lens, e, n); if (rc != ECSIMD_HIP_OK) return rc;
+  RUN(launch::sha256_lens(s, msg, stride_bytes, lens, e, n)); }
+
+int ecsimd_hip_sha256d_lens(ecsimd_hip_ctx* ctx, const uint8_t* msg, size_t msg_bytes, size_t stride_bytes, const uint32_t* lens, uint64_t* e, size_t n) {
+  if (!lens) return ecsimd_hip_sha256d(ctx, msg, msg_bytes, stride_bytes, e, n);
+  REQUIRE_CTX(); REQUIRE_PTR(e);
+  int rc = btc_lens_args(ctx, "sha256d_lens", msg, stride_bytes, lens, e, n); if (rc != ECSIMD_HIP_OK) return rc;
+  RUN(launch::sha256d_lens(s, msg, stride_bytes, lens, e, n)); }
+
+int ecsimd_hip_hash160_lens(ecsimd_hip_ctx* ctx, const uint8_t* msg, size_t msg_bytes, size_t stride_bytes, const uint32_t* lens, uint8_t* out20, size_t n) {
+  if (!lens) return ecsimd_hip_hash160(ctx, msg, msg_bytes, stride_bytes, out20, n);
+  REQUIRE_CTX();
+  int rc = btc_lens_args(ctx, "hash160_lens", msg, stride_bytes, lens, out20, n); if (rc != ECSIMD_HIP_OK) return rc;
+  if (reinterpret_cast<uintptr_t>(out20) & 3u) return bad(ctx, "out20 is not 4-byte aligned");
+  RUN(launch::hash160_lens(s, msg, stride_bytes, lens, out20, n)); }
+
+int ecsimd_hip_ripemd160_lens(ecsimd_hip_ctx* ctx, const uint8_t* msg, size_t msg_bytes, size_t stride_bytes, const uint32_t* lens, uint8_t* out20, size_t n) {
+  if (!lens) return ecsimd_hip_ripemd160(ctx, msg, msg_bytes, stride_bytes, out20, n);
+  REQUIRE_CTX();
+  int rc = btc_lens_args(ctx, "ripemd160_lens", msg, stride_bytes, lens, out20, n); if (rc != ECSIMD_HIP_OK) return rc;
+  if (reinterpret_cast<uintptr_t>(out20) & 3u) return bad(ctx, "out20 is not 4-byte aligned");
+  RUN(launch::ripemd160_lens(s, msg, stride_bytes, lens, out20, n)); }
+
+namespace {
+// A chunk of whole trees: `trees` of them from tree `first`, `levels` launches; its node offsets are (levels + 1) rows of trees + 1 values from offsets[at] --
+// row 0 the leaves' (into the caller's array), row l the nodes' behind l launches (from 0) -- and row `levels` has every tree at one node.
+struct merkle_chunk { size_t first, trees, levels, at; };
+// The chunks of a call and all their rows; p1 / p2 = the most nodes a chunk has behind its first / second launch.  Nothing may throw across the C ABI.
+int merkle_plan(ecsimd_hip_ctx* ctx, const uint64_t* tree_offsets, size_t m, std::vector<merkle_chunk>& chunks, std::vector<uint64_t>& offsets, size_t* p1, size_t* p2) {
+  *p1 = *p2 = 0;
+  try {
+    for (size_t t = 0; t < m;) {
+      merkle_chunk c = {t, 0, 0, offsets.size()};
+      uint64_t parents = 0, most = 0;
+      for (; t < m; ++t, ++c.trees) {
+        const uint64_t count = tree_offsets[t + 1] - tree_offsets[t];
+        if (c.trees && parents + (count + 1) / 2 > GC_CHUNK) break;       // a tree larger than a chunk gets a chunk of its own
+        parents += (count + 1) / 2;
+        if (count > most) most = count;
+      }
+      for (uint64_t v = most; v > 1; v = (v + 1) / 2) ++c.levels;
+      if (!c.levels) c.levels = 1;                                         // single leaves: one launch passes them through
+      const size_t row = c.trees + 1;
+      offsets.resize(c.at + (c.levels + 1) * row);
+      uint64_t* o = &offsets[c.at];
+      for (size_t q = 0; q < row; ++q) o[q] = tree_offsets[c.first + q];
+      for (size_t l = 1; l <= c.levels; ++l) {
+        const uint64_t* prev = o + (l - 1) * row; uint64_t* cur = o + l * row;
+        cur[0] = 0;
+        for (size_t q = 0; q < c.trees; ++q) cur[q + 1] = cur[q] + (prev[q + 1] - prev[q] + 1) / 2;
+      }
+      if (o[row + c.trees] > *p1) *p1 = o[row + c.trees];
+      if (c.levels > 1 && o[2 * row + c.trees] > *p2) *p2 = o[2 * row + c.trees];
+      chunks.push_back(c);
+    }
+  } catch (...) { return bad(ctx, "btc_merkle_root: out of host memory"); }
+  return ECSIMD_HIP_OK;
+}
+// The pinned host block the rows are uploaded from: the copy is stream-ordered, so the block is the context's and the next upload waits for this one's event.
+int merkle_stage(ecsimd_hip_ctx* ctx, const std::vector<uint64_t>& offsets, uint64_t* device) {
+  const size_t bytes = offsets.size() * 8;
+  hipError_t e = hipSuccess;
+  if (!ctx->pinned_copied) e = hipEventCreateWithFlags(&ctx->pinned_copied, hipEventDisableTiming);
+  else e = hipEventSynchronize(ctx->pinned_copied);
+  if (e == hipSuccess && ctx->pinned_bytes < bytes) {
+    if (ctx->pinned) (void)hipHostFree(ctx->pinned);
+    ctx->pinned = nullptr; ctx->pinned_bytes = 0;
+    e = hipHostMalloc(reinterpret_cast<void**>(&ctx->pinned), bytes, hipHostMallocDefault);
+    if (e == hipSuccess) ctx->pinned_bytes = bytes;
+  }
+  if (e != hipSuccess) return fail(ctx, e, "btc_merkle_root: the pinned block of the node offsets");
+  memcpy(ctx->pinned, offsets.data(), bytes);
+  e = hipMemcpyAsync(device, ctx->pinned, bytes, hipMemcpyHostToDevice, ctx->stream);
+  if (e == hipSuccess) e = hipEventRecord(ctx->pinned_copied, ctx->stream);
+  return e == hipSuccess ? ECSIMD_HIP_OK : fail(ctx, e, "btc_merkle_root: uploading the node offsets");
+}
+}  // namespace
+
+// Per chunk of whole trees: one launch per level.  Level 1 reads the caller's leaves, the levels between ping-pong in the workspace (odd levels in the first
+// array, even ones in the second: every level is at most half the one two launches before it, rounded up per tree), the last one writes the caller's roots.
+int ecsimd_hip_btc_merkle_root(ecsimd_hip_ctx* ctx, const uint64_t* leaves, const uint64_t* tree_offsets, size_t m, uint64_t* roots, uint8_t* mutated) {
+  const size_t n = m;
+  REQUIRE_CTX(); REQUIRE_PTR(leaves); REQUIRE_PTR(roots);
+  if (!tree_offsets && n) return bad(ctx, "tree_offsets is null");
+  for (size_t t = 0; t < m; ++t) {
+    if (tree_offsets[t + 1] < tree_offsets[t]) return bad(ctx, "btc_merkle_root: tree_offsets decrease");
+    if (tree_offsets[t + 1] == tree_offsets[t]) return bad(ctx, "btc_merkle_root: an empty tree");
+  }
+  if (n != 0 && any_alias({roots}, {leaves})) return bad(ctx, "roots must not alias leaves");
+  ENTER_ANY_SIZE();
+  if (capturing(ctx)) return bad(ctx, "btc_merkle_root stages its node offsets from host memory: not for a stream under capture");
+  std::vector<merkle_chunk> chunks; std::vector<uint64_t> offsets; size_t p1, p2;
+  int rc = merkle_plan(ctx, tree_offsets, m, chunks, offsets, &p1, &p2); if (rc != ECSIMD_HIP_OK) return rc;
+  carve c = carve_from(nullptr);
+  (void)carve_limbs(c, p1); (void)carve_limbs(c, p2); (void)carve_bytes(c, offsets.size() * 8);
+  rc = ensure_workspace(ctx, c.bytes); if (rc != ECSIMD_HIP_OK) return rc;
+  c = carve_from(ctx->workspace);
+  uint64_t* level[2] = {carve_limbs(c, p1), carve_limbs(c, p2)};
+  uint64_t* rows = static_cast<uint64_t*>(carve_bytes(c, offsets.size() * 8));
+  rc = merkle_stage(ctx, offsets, rows); if (rc != ECSIMD_HIP_OK) return rc;
+  hipError_t err = mutated ? hipMemsetAsync(mutated, 0, m, ctx->stream) : hipSuccess;
+  if (err != hipSuccess) return fail(ctx, err, "btc_merkle_root: zeroing mutated");
+  for (const merkle_chunk& k : chunks) {
+    const size_t row = k.trees + 1;
+    const uint64_t* in = leaves;
+    for (size_t l = 1; l <= k.levels; ++l) {
+      uint64_t* out = l == k.levels ? roots + 4 * k.first : level[(l - 1) & 1];
+      launch::merkle_level(ctx->stream, in, rows + k.at + (l - 1) * row, rows + k.at + l * row, k.trees, out, mutated ? mutated + k.first : nullptr, offsets[k.at + l * row + k.trees]);
+      in = out;
+    }
+  }
+  err = hipGetLastError();
+  return err == hipSuccess ? ECSIMD_HIP_OK : fail(ctx, err, "btc_merkle_root launch"); }
+
+int ecsimd_hip_tapleaf_hash(ecsimd_hip_ctx* ctx, const uint8_t* script, size_t script_bytes, size_t stride_bytes, const uint32_t* lens, const uint8_t* leaf_version,
+                            uint32_t leaf_version_all, uint64_t* e, size_t n) {
+  REQUIRE_CTX(); REQUIRE_PTR(e);
+  int rc = lens ? btc_lens_args(ctx, "tapleaf_hash", script, stride_bytes, lens, e, n) : btc_hash_args(ctx, "tapleaf_hash", script, script_bytes, stride_bytes, e, n);
+  if (rc != ECSIMD_HIP_OK) return rc;
+  if (!lens && script_bytes > 0xffffffffull) return bad(ctx, "tapleaf_hash: a script's length is below 2^32");
+  if (!leaf_version && leaf_version_all > 0xffu) return bad(ctx, "tapleaf_hash: leaf_version_all is one byte");
+  RUN(launch::tapleaf_hash(s, script, lens ? 0 : script_bytes, stride_bytes, lens, leaf_version, leaf_version_all, e, n)); }
+
+int ecsimd_hip_taproot_merkle_path(ecsimd_hip_ctx* ctx, const uint64_t* leaf, const uint8_t* path, size_t path_stride_bytes, const uint8_t* depth, uint32_t depth_all,
+                                   uint64_t* root, uint8_t* ok, size_t n) {
+  REQUIRE_CTX(); REQUIRE_PTR(leaf); REQUIRE_PTR(root);
+  if (!ok && n) return bad(ctx, "ok is null");
+  if (!path && n && (depth || (depth_all != 0 && depth_all <= 128u))) return bad(ctx, "path is null");
+  if (n != 0 && any_alias({root}, {leaf})) return bad(ctx, "root must not alias leaf");
+  RUN(launch::taproot_merkle_path(s, leaf, path, path_stride_bytes, depth, depth_all, root, ok, n)); }
 
 // ---- BIP-340 Schnorr signatures on secp256k1 (k_schnorr.hip)
 namespace {

@@ -154,6 +154,22 @@ void tweak_accept(hipStream_t, const uint64_t* ax, const uint64_t* ay, const uin
 void taproot_seckey(hipStream_t, const gmod& order, const uint64_t* d, const uint64_t* merkle, const uint64_t* xP, const uint64_t* yP, uint64_t* d_out, uint64_t* px,
                     uint8_t* ok, size_t n);
 
+// k_btc_tree.hip (PUBLIC data).  *_lens: the hashes above with lens[i] bytes of message i (lens != NULL, n x u32; a value above stride_bytes is read as
+// stride_bytes); no byte at or behind a lane's message is loaded.  merkle_level: one level of `trees` Merkle trees -- off_in / off_out are the trees + 1 node
+// offsets of the level read and the level written (device memory), n = off_out[trees] parents; mutated (may be NULL) gets a 1 per tree with a real pair of equal
+// nodes.  tapleaf_hash: e = H_TapLeaf(version || compact_size(len) || script), scripts addressed as messages (lens may be NULL: script_bytes each), version
+// n x u8 or NULL for version_all.  taproot_merkle_path: root = the TapBranch walk from leaf over depth[i] (NULL: depth_all) nodes of 32 bytes at
+// path + i * path_stride_bytes; ok = 0 and root = 0 where the depth is above 128.
+void sha256_lens(hipStream_t, const uint8_t* msg, size_t stride_bytes, const uint32_t* lens, uint64_t* e, size_t n);
+void sha256d_lens(hipStream_t, const uint8_t* msg, size_t stride_bytes, const uint32_t* lens, uint64_t* e, size_t n);
+void hash160_lens(hipStream_t, const uint8_t* msg, size_t stride_bytes, const uint32_t* lens, uint8_t* out20, size_t n);
+void ripemd160_lens(hipStream_t, const uint8_t* msg, size_t stride_bytes, const uint32_t* lens, uint8_t* out20, size_t n);
+void merkle_level(hipStream_t, const uint64_t* in, const uint64_t* off_in, const uint64_t* off_out, size_t trees, uint64_t* out, uint8_t* mutated, size_t n);
+void tapleaf_hash(hipStream_t, const uint8_t* script, size_t script_bytes, size_t stride_bytes, const uint32_t* lens, const uint8_t* version, uint32_t version_all, uint64_t* e,
+                  size_t n);
+void taproot_merkle_path(hipStream_t, const uint64_t* leaf, const uint8_t* path, size_t path_stride_bytes, const uint8_t* depth, uint32_t depth_all, uint64_t* root, uint8_t* ok,
+                         size_t n);
+
 // k_sha512.hip: SHA-512 and HMAC-SHA-512 of n equal-length messages (PUBLIC data; messages as for sha256); 64 digest bytes per lane at out64 + 64 i (16-byte
 // aligned).  hmac_sha512: lane i's key at key + i * key_stride_bytes (0: one key for the call), zero-padded to a block or, beyond 128 bytes, hashed first.
 void sha512(hipStream_t, const uint8_t* msg, size_t msg_bytes, size_t stride_bytes, uint8_t* out64, size_t n);

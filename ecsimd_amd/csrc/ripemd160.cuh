@@ -116,6 +116,29 @@ template <bool ALIGNED> ECS_DEV void rmd160_absorb_message(rmd160_state& s, cons
   if (two) rmd160_compress(s, rmd160_tail_block(p, msg_bytes, 64 * full + 64, true));
 }
 
+// The same for a length of the lane's own (PUBLIC: the loop's trip count is the lane's), in the shape of sha256_absorb_message_lens: len / 64 whole blocks, the
+// tail block from msg_tail_words_le -- no byte at or behind p + len is loaded, `spare` takes those loads --, a block of zeros behind it where fewer than 9
+// bytes are free, the bit length (little-endian) in the last.
+template <bool ALIGNED> ECS_DEV void rmd160_absorb_message_lens(rmd160_state& s, const uint8_t* p, uint32_t len, const uint8_t* spare) {
+  const uint32_t full = len >> 6, rem = len & 63u;
+  rmd160_block m;
+#pragma unroll 1
+  for (uint32_t b = 0; b < full; ++b) {
+    msg_words_le<ALIGNED>(p, m.w);
+    rmd160_compress(s, m);
+    p += 64;
+  }
+  msg_tail_words_le<ALIGNED>(p, rem, spare, m.w);
+  const uint32_t tails = rem >= 56u ? 2u : 1u;
+#pragma unroll 1
+  for (uint32_t t = 0; t < tails; ++t) {
+    if (t + 1 == tails) { m.w[14] = len << 3; m.w[15] = len >> 29; }
+    rmd160_compress(s, m);
+#pragma unroll
+    for (int j = 0; j < 16; ++j) m.w[j] = 0u;
+  }
+}
+
 // RIPEMD160 of a 32-byte SHA-256 digest, straight from the state: one compression (HASH160's second half)
 ECS_DEV rmd160_state rmd160_of_sha256(const sha256_state& d) {
   rmd160_block m;

@@ -101,6 +101,95 @@ ECS_DEV void sha256_absorb_message(sha256_state& s, const uint8_t* __restrict__ 
   }
 }
 
+// ---- one length per lane.  PUBLIC lengths: the block loop's trip count and the shape of the tail are the lane's own, so a wave runs until its longest lane
+// is done.  ALIGNED as above, a template argument here.
+// a where mask is all ones, b where it is zero -- as arithmetic on the address (keccak.cuh's keccak_pick says why)
+ECS_DEV const uint8_t* msg_pick(uint32_t mask, const uint8_t* a, const uint8_t* b) {
+  const uintptr_t ia = reinterpret_cast<uintptr_t>(a), ib = reinterpret_cast<uintptr_t>(b);
+  return reinterpret_cast<const uint8_t*>(ib + ((ia - ib) & (uintptr_t)(int64_t)(int32_t)mask));
+}
+// the 64 message bytes at q as sixteen little-endian words
+template <bool ALIGNED> ECS_DEV void msg_words_le(const uint8_t* q, uint32_t (&w)[16]) {
+  if constexpr (ALIGNED) {
+    const uint32_t* p = reinterpret_cast<const uint32_t*>(q);
+#pragma unroll
+    for (int j = 0; j < 16; ++j) w[j] = p[j];
+  } else {
+#pragma unroll
+    for (int j = 0; j < 16; ++j) w[j] = (uint32_t)q[4 * j] | ((uint32_t)q[4 * j + 1] << 8) | ((uint32_t)q[4 * j + 2] << 16) | ((uint32_t)q[4 * j + 3] << 24);
+  }
+}
+// The last rem (0 .. 63) message bytes at q as little-endian words, the byte 0x80 right behind them, zeros.  No branch, and no byte at or behind q + rem is
+// loaded (a row's tail need not be allocated): such a load is pointed at `spare` instead -- any readable, 4-byte aligned address: the lane's own output slot --
+// and its value dropped, as in keccak_absorb_last.
+template <bool ALIGNED> ECS_DEV void msg_tail_words_le(const uint8_t* q, uint32_t rem, const uint8_t* spare, uint32_t (&w)[16]) {
+  const uint32_t whole = rem >> 2, part = rem & 3u;            // words that are message bytes only; bytes of the one that is not
+  uint32_t edge = 0x80u << (8 * part);                         // that word: `part` message bytes, then the padding's first byte
+  if constexpr (ALIGNED) {
+#pragma unroll
+    for (uint32_t t = 0; t < 3; ++t) {
+      const uint32_t have = 0u - (uint32_t)(t < part);
+      const uint32_t b = *msg_pick(have, q + 4 * whole + t, spare);
+      edge |= (b & have) << (8 * t);
+    }
+#pragma unroll
+    for (uint32_t k = 0; k < 16; ++k) {
+      const uint32_t have = 0u - (uint32_t)(k < whole);
+      w[k] = *reinterpret_cast<const uint32_t*>(msg_pick(have, q + 4 * k, spare)) & have;
+    }
+  } else {
+#pragma unroll
+    for (uint32_t k = 0; k < 16; ++k) {
+      uint32_t v = 0;
+#pragma unroll
+      for (uint32_t t = 0; t < 4; ++t) {
+        const uint32_t have = 0u - (uint32_t)(4 * k + t < rem);
+        const uint32_t b = *msg_pick(have, q + 4 * k + t, spare);
+        v |= (b & have) << (8 * t);
+      }
+      w[k] = v;                                                // (the edge word holds its message bytes already: the 0x80 joins them below)
+    }
+  }
+#pragma unroll
+  for (uint32_t k = 0; k < 16; ++k) w[k] |= edge & (0u - (uint32_t)(k == whole));
+}
+template <bool ALIGNED> ECS_DEV sha256_block sha256_load_block(const uint8_t* q) {
+  uint32_t w[16];
+  msg_words_le<ALIGNED>(q, w);
+  sha256_block m;
+#pragma unroll
+  for (int j = 0; j < 16; ++j) m.w[j] = __builtin_bswap32(w[j]);
+  return m;
+}
+template <bool ALIGNED> ECS_DEV sha256_block sha256_load_tail(const uint8_t* q, uint32_t rem, const uint8_t* spare) {
+  uint32_t w[16];
+  msg_tail_words_le<ALIGNED>(q, rem, spare, w);
+  sha256_block m;
+#pragma unroll
+  for (int j = 0; j < 16; ++j) m.w[j] = __builtin_bswap32(w[j]);
+  return m;
+}
+// sha256_absorb_message for a length of the lane's own: the len bytes at p, the padding and the bit length.  Whole blocks go through THE loop of this function,
+// len / 64 trips; the tail block comes from sha256_load_tail, and where fewer than 9 bytes are free behind the message a block of zeros follows it: the
+// second loop's one or two trips, the bit length in the last.
+template <bool ALIGNED> ECS_DEV void sha256_absorb_message_lens(sha256_state& s, const uint8_t* p, uint32_t len, const uint8_t* spare) {
+  const uint32_t full = len >> 6, rem = len & 63u;
+#pragma unroll 1
+  for (uint32_t b = 0; b < full; ++b) {
+    sha256_compress(s, sha256_load_block<ALIGNED>(p));
+    p += 64;
+  }
+  sha256_block m = sha256_load_tail<ALIGNED>(p, rem, spare);
+  const uint32_t tails = rem >= 56u ? 2u : 1u;
+#pragma unroll 1
+  for (uint32_t t = 0; t < tails; ++t) {
+    if (t + 1 == tails) { m.w[14] = len >> 29; m.w[15] = len << 3; }
+    sha256_compress(s, m);
+#pragma unroll
+    for (int j = 0; j < 16; ++j) m.w[j] = 0u;
+  }
+}
+
 // ---- 256-bit integers <-> big-endian words
 ECS_DEV void sha_words_of(const fe& x, uint32_t (&be)[8]) {
 #pragma unroll

@@ -399,9 +399,12 @@ class Engine:
                    C.c_int(ECDSA_LOW_S if low_s else 0))
         return r, s, v, ok
 
-    def sha256(self, msgs):
+    def sha256(self, msgs, lens=None):
         """ecsimd_hip_sha256: the digests of the rows of `msgs` (2-D uint8 device tensor, one message per row; rows may be strided, e.g. a column slice of a
-        wider record array) as (n, 4) integers, ready to be the `e` of the ECDSA calls."""
+        wider record array) as (n, 4) integers, ready to be the `e` of the ECDSA calls.  lens (optional, as keccak256's): lane i hashes the first lens[i] bytes
+        of its row (ecsimd_hip_sha256_lens)."""
+        if lens is not None:
+            return self._digest_lens("sha256_lens", msgs, lens, None)
         torch = self.torch
         assert msgs.is_cuda and msgs.device.index == self.device, "tensor on the wrong device"
         assert msgs.dtype == torch.uint8 and msgs.dim() == 2, (msgs.dtype, msgs.shape)
@@ -462,16 +465,19 @@ class Engine:
         first lens[i] bytes of its row."""
         n = int(msgs.shape[0]); e = self.empty(n)
         keep, mp, length, stride = self._messages(msgs, n)
-        lp = C.c_void_p(0)
-        if lens is not None:
-            torch = self.torch
-            assert lens.is_cuda and lens.device.index == self.device and lens.is_contiguous() and lens.dim() == 1, "lens: a contiguous 1-D tensor on the engine's device"
-            assert lens.dtype in (torch.int32, torch.uint32), lens.dtype
-            if int(lens.shape[0]) != n:
-                raise EcsimdHipError(f"keccak256: operands disagree on the batch length: {sorted((n, int(lens.shape[0])))}")
-            lp = C.c_void_p(lens.data_ptr())
-        self._call("keccak256", mp, length, stride, lp, self._ptr(e), C.c_size_t(n))
+        self._call("keccak256", mp, length, stride, self._lens_ptr("keccak256", lens, n), self._ptr(e), C.c_size_t(n))
         return e
+
+    def _lens_ptr(self, what, lens, n):
+        """The pointer of an optional int32 / uint32 device tensor of n lengths (None: NULL), as ecsimd_hip_keccak256 and the *_lens calls take it."""
+        if lens is None:
+            return C.c_void_p(0)
+        torch = self.torch
+        assert lens.is_cuda and lens.device.index == self.device and lens.is_contiguous() and lens.dim() == 1, "lens: a contiguous 1-D tensor on the engine's device"
+        assert lens.dtype in (torch.int32, torch.uint32), lens.dtype
+        if int(lens.shape[0]) != n:
+            raise EcsimdHipError(f"{what}: operands disagree on the batch length: {sorted((n, int(lens.shape[0])))}")
+        return C.c_void_p(lens.data_ptr())
 
     def eth_address(self, qx, qy):
         """ecsimd_hip_eth_address: (n, 20) uint8, the Ethereum address of each public key (qx, qy) -- the last 20 bytes of Keccak-256 over its 64 big-endian bytes."""
@@ -489,22 +495,36 @@ class Engine:
                    C.c_int(ETH_REQUIRE_LOW_S if require_low_s else 0))
         return (addr, qx, qy, ok) if want_key else (addr, ok)
 
-    def _digest20(self, name, msgs):
+    def _digest_lens(self, name, msgs, lens, out20):
+        """One of the four *_lens calls: lane i hashes the first lens[i] bytes of its row; the result is (n, 4) integers, or the (n, 20) uint8 tensor out20."""
+        n = int(msgs.shape[0]); out = self.empty(n) if out20 is None else out20
+        keep, mp, length, stride = self._messages(msgs, n)
+        lp = self._lens_ptr(name, lens if length.value else None, n)          # rows of no bytes: every message is empty
+        self._call(name, mp, length, stride, lp, self._ptr(out) if out20 is None else self._bytes_ptr(out), C.c_size_t(n))
+        return out
+
+    def _digest20(self, name, msgs, lens=None):
         n = int(msgs.shape[0]); out = self.torch.empty((n, 20), dtype=self.torch.uint8, device=self.tdev)
+        if lens is not None:
+            return self._digest_lens(name + "_lens", msgs, lens, out)
         keep, mp, length, stride = self._messages(msgs, n)
         self._call(name, mp, length, stride, self._bytes_ptr(out), C.c_size_t(n))
         return out
 
-    def ripemd160(self, msgs):
-        """ecsimd_hip_ripemd160: (n, 20) uint8, RIPEMD-160 of the rows of `msgs` (2-D uint8 device tensor, rows may be strided).  Public data."""
-        return self._digest20("ripemd160", msgs)
+    def ripemd160(self, msgs, lens=None):
+        """ecsimd_hip_ripemd160: (n, 20) uint8, RIPEMD-160 of the rows of `msgs` (2-D uint8 device tensor, rows may be strided).  Public data.  lens (optional, as
+        keccak256's): the first lens[i] bytes of row i (ecsimd_hip_ripemd160_lens)."""
+        return self._digest20("ripemd160", msgs, lens)
 
-    def hash160(self, msgs):
-        """ecsimd_hip_hash160: (n, 20) uint8, RIPEMD-160(SHA-256(row)) of the rows of `msgs`.  Public data."""
-        return self._digest20("hash160", msgs)
+    def hash160(self, msgs, lens=None):
+        """ecsimd_hip_hash160: (n, 20) uint8, RIPEMD-160(SHA-256(row)) of the rows of `msgs`.  Public data.  lens as ripemd160's (ecsimd_hip_hash160_lens)."""
+        return self._digest20("hash160", msgs, lens)
 
-    def sha256d(self, msgs):
-        """ecsimd_hip_sha256d: SHA-256(SHA-256(row)) of the rows of `msgs` as (n, 4) integers, as sha256 returns its digests.  Public data."""
+    def sha256d(self, msgs, lens=None):
+        """ecsimd_hip_sha256d: SHA-256(SHA-256(row)) of the rows of `msgs` as (n, 4) integers, as sha256 returns its digests.  Public data.  lens as ripemd160's
+        (ecsimd_hip_sha256d_lens): a batch of transactions to their txids."""
+        if lens is not None:
+            return self._digest_lens("sha256d_lens", msgs, lens, None)
         n = int(msgs.shape[0]); e = self.empty(n)
         keep, mp, length, stride = self._messages(msgs, n)
         self._call("sha256d", mp, length, stride, self._ptr(e), C.c_size_t(n))
@@ -533,6 +553,63 @@ class Engine:
         n = d.shape[0]; d_out, ok = self.empty(n), self.flags(n); px = self.empty(n) if want_px else None
         self._call("taproot_tweak_seckey", self._ptr(d), self._ptr(merkle_root), self._ptr(d_out), self._ptr(px), self._ptr(ok, 0), C.c_size_t(n))
         return d_out, px, ok
+
+    def btc_merkle_root(self, leaves, counts, want_mutated=False):
+        """ecsimd_hip_btc_merkle_root: the Merkle roots of len(counts) trees of txids, Bitcoin's rule (the last node paired with itself where a level is odd).
+        leaves: (sum(counts), 4) integers as sha256d returns them, tree after tree; counts: any host sequence of the trees' sizes, each at least 1.  Returns the
+        (m, 4) roots, or (roots, mutated) with want_mutated: one byte per tree, 1 where some level holds a real pair of equal nodes (CVE-2012-2459)."""
+        counts = [int(c) for c in counts]
+        m = len(counts)
+        offsets = (C.c_uint64 * (m + 1))()
+        for t, c in enumerate(counts):
+            if c < 0:
+                raise EcsimdHipError("btc_merkle_root: a negative count")
+            offsets[t + 1] = offsets[t] + c
+        if int(leaves.shape[0]) != int(offsets[m]):
+            raise EcsimdHipError(f"btc_merkle_root: {int(leaves.shape[0])} leaves for counts that add up to {int(offsets[m])}")
+        roots = self.empty(m); mutated = self.flags(m) if want_mutated else None
+        lp = self._ptr(leaves); self._rows.clear()              # leaves and roots have their own lengths
+        self._call("btc_merkle_root", lp, offsets, C.c_size_t(m), C.c_void_p(roots.data_ptr()), C.c_void_p(mutated.data_ptr() if want_mutated else 0))
+        return (roots, mutated) if want_mutated else roots
+
+    def tapleaf_hash(self, scripts, lens=None, leaf_version=0xc0):
+        """ecsimd_hip_tapleaf_hash: (n, 4) integers, the BIP-341 leaf hash H_TapLeaf(version || compact_size(len) || script) of the rows of `scripts` (2-D uint8
+        device tensor, rows may be strided; lens as keccak256's).  leaf_version: one int for every lane, or a uint8 device tensor of n versions."""
+        n = int(scripts.shape[0]); e = self.empty(n)
+        keep, mp, length, stride = self._messages(scripts, n)
+        per_lane = not isinstance(leaf_version, int)
+        vp = self._ptr(leaf_version, 0) if per_lane else C.c_void_p(0)
+        self._call("tapleaf_hash", mp, length, stride, self._lens_ptr("tapleaf_hash", lens if length.value else None, n), vp, C.c_uint32(0 if per_lane else leaf_version), self._ptr(e), C.c_size_t(n))
+        return e
+
+    def taproot_merkle_path(self, leaf, path, depth):
+        """ecsimd_hip_taproot_merkle_path: (root, ok), the TapBranch walk from each leaf hash over its control block's path.  path: 2-D uint8 device tensor, row i
+        holding lane i's nodes of 32 bytes, the leaf's sibling first (rows may be strided: the tail of a control block); depth: one int for every lane, or a uint8
+        device tensor of n depths.  ok = 0 and root = 0 where a depth is above 128.  A row must hold 32 x depth bytes (checked for an int depth only); rows of no bytes mean depth 0."""
+        n = int(leaf.shape[0]); root, ok = self.empty(n), self.flags(n)
+        keep, pp, width, stride = self._messages(path, n)
+        per_lane = not isinstance(depth, int)
+        if per_lane and width.value == 0:
+            per_lane, depth = False, 0                          # rows of no bytes hold no node
+        if not per_lane and depth <= 128 and 32 * depth > width.value:
+            raise EcsimdHipError(f"taproot_merkle_path: rows of {width.value} bytes for a depth of {depth}")
+        dp = self._ptr(depth, 0) if per_lane else C.c_void_p(0)
+        self._call("taproot_merkle_path", self._ptr(leaf), pp, stride, dp, C.c_uint32(0 if per_lane else depth), self._ptr(root), self._ptr(ok, 0), C.c_size_t(n))
+        return root, ok
+
+    def taproot_script_path_ok(self, qx, control_blocks, depths, scripts, lens=None):
+        """BIP-341's script-path check on the device, from existing calls: a uint8 verdict per lane, 1 where the control block and the script commit to the
+        output key qx.  control_blocks: (n, 33 + 32 d) uint8 device tensor -- the control byte (leaf version | the output key's parity), the internal key, the
+        path; depths: uint8 device tensor, the number of path nodes of each lane (the rest of its row is not read); scripts / lens as tapleaf_hash's.
+        tapleaf_hash -> taproot_merkle_path -> taproot_tweak_pubkey -> the comparison of qx and the parity."""
+        control = control_blocks[:, 0]
+        keys = self.torch.empty((int(control_blocks.shape[0]), 32), dtype=self.torch.uint8, device=self.tdev)      # a copy of its own: from_bytes_be wants 16-byte alignment
+        keys.copy_(control_blocks[:, 1:33])
+        px = self.from_bytes_be(keys)
+        leaf = self.tapleaf_hash(scripts, lens, (control & 0xfe).contiguous())
+        root, in_bound = self.taproot_merkle_path(leaf, control_blocks[:, 33:], depths)
+        q, parity, ok = self.taproot_tweak_pubkey(px, root)
+        return ok & in_bound & self.cmp_eq(q, qx) & (parity == (control & 1)).to(self.torch.uint8)
 
     def sha512(self, msgs):
         """ecsimd_hip_sha512: (n, 64) uint8, SHA-512 of the rows of `msgs` (2-D uint8 device tensor, rows may be strided).  Public data."""

@@ -260,6 +260,42 @@ struct curve_group {
                "ecsimd_hip_taproot_tweak_seckey");
     return out;
   }
+  // ---- Bitcoin's trees: Merkle roots of txids and BIP-341 script paths.  Public data.
+  // The Merkle roots of counts.size() trees of txids (as hip::sha256d returns them), tree after tree in `leaves`; Bitcoin's rule.  mutated (optional): one flag
+  // per tree, set where some level holds a real pair of equal nodes (CVE-2012-2459).
+  static WBN btc_merkle_root(WBN const& leaves, std::vector<uint64_t> const& counts, hip::mask* mutated = nullptr) requires std::is_same_v<Curve, curve_secp256k1> {
+    std::vector<uint64_t> offsets(counts.size() + 1, 0);
+    for (size_t t = 0; t < counts.size(); ++t) offsets[t + 1] = offsets[t] + counts[t];
+    same_length(leaves.size(), offsets.back(), "btc_merkle_root");
+    auto roots = WBN::uninitialized(counts.size());
+    if (mutated) *mutated = hip::mask(counts.size());
+    hip::check(ecsimd_hip_btc_merkle_root(hip::context(), leaves.data(), offsets.data(), counts.size(), roots.data(), mutated ? mutated->data() : nullptr), "ecsimd_hip_btc_merkle_root");
+    return roots;
+  }
+  // BIP-341: the leaf hashes H_TapLeaf(leaf_version || compact_size(len) || script) of the scripts (lens = nullptr: of one length).
+  static WBN tapleaf_hash(hip::messages const& scripts, hip::lengths const* lens = nullptr, uint8_t leaf_version = 0xc0) requires std::is_same_v<Curve, curve_secp256k1> {
+    if (lens) hip::same_rows(scripts, *lens);
+    auto e = WBN::uninitialized(scripts.size());
+    hip::check(ecsimd_hip_tapleaf_hash(hip::context(), scripts.data(), scripts.msg_bytes(), scripts.stride_bytes(), lens ? lens->data() : nullptr, nullptr, leaf_version, e.data(),
+                                       scripts.size()), "ecsimd_hip_tapleaf_hash");
+    return e;
+  }
+  // BIP-341: the merkle root each leaf hash reaches over the first `depth` nodes (32 bytes each, the leaf's sibling first) of its row of `path` -- or over
+  // depths[i] of them; ok[i] is false, and the root 0, where a depth is above 128.  The root feeds taproot_tweak_pubkey.
+  static WBN taproot_merkle_path(WBN const& leaf, hip::messages const& path, uint32_t depth, hip::mask& ok, std::vector<uint8_t> const* depths = nullptr)
+      requires std::is_same_v<Curve, curve_secp256k1> {
+    same_length(leaf.size(), path.size(), "taproot_merkle_path");
+    hip::mask per_lane;
+    if (depths) {
+      same_length(leaf.size(), depths->size(), "taproot_merkle_path");
+      per_lane = hip::mask(depths->size());
+      if (!depths->empty()) hip::check(ecsimd_hip_memcpy_h2d(hip::context(), per_lane.data(), depths->data(), depths->size()), "h2d");
+    }
+    auto root = WBN::uninitialized(leaf.size()); ok = hip::mask(leaf.size());
+    hip::check(ecsimd_hip_taproot_merkle_path(hip::context(), leaf.data(), path.data(), path.stride_bytes(), depths ? per_lane.data() : nullptr, depth, root.data(), ok.data(),
+                                              leaf.size()), "ecsimd_hip_taproot_merkle_path");
+    return root;
+  }
   // ---- BIP-32 key derivation: secp256k1 only.  Keys and chain codes are the integers whose 32 big-endian bytes the BIP writes; an index >= 2^31 is hardened.
   // The master key and chain code of the SECRET seeds (16 .. 64 bytes each, one length); ok[i] is false -- and both are 0 -- where the key would be 0 or >= n.
   static WBN bip32_master(hip::messages const& seeds, WBN& c, hip::mask& ok) requires std::is_same_v<Curve, curve_secp256k1> {

@@ -26,6 +26,25 @@ inline wide_bignum<bignum_256> sha256d(messages const& m) {
   check(ecsimd_hip_sha256d(context(), m.data(), m.msg_bytes(), m.stride_bytes(), e.data(), m.size()), "ecsimd_hip_sha256d");
   return e;
 }
+// The same three of the first lens[i] bytes of message i (ecsimd_hip_ripemd160_lens, _hash160_lens, _sha256d_lens): transactions, scripts, witness items
+inline digests20 ripemd160(messages const& m, lengths const& lens) {
+  same_rows(m, lens);
+  digests20 out(m.size());
+  check(ecsimd_hip_ripemd160_lens(context(), m.data(), m.msg_bytes(), m.stride_bytes(), lens.data(), out.data(), m.size()), "ecsimd_hip_ripemd160_lens");
+  return out;
+}
+inline digests20 hash160(messages const& m, lengths const& lens) {
+  same_rows(m, lens);
+  digests20 out(m.size());
+  check(ecsimd_hip_hash160_lens(context(), m.data(), m.msg_bytes(), m.stride_bytes(), lens.data(), out.data(), m.size()), "ecsimd_hip_hash160_lens");
+  return out;
+}
+inline wide_bignum<bignum_256> sha256d(messages const& m, lengths const& lens) {
+  same_rows(m, lens);
+  auto e = wide_bignum<bignum_256>::uninitialized(m.size());
+  check(ecsimd_hip_sha256d_lens(context(), m.data(), m.msg_bytes(), m.stride_bytes(), lens.data(), e.data(), m.size()), "ecsimd_hip_sha256d_lens");
+  return e;
+}
 }  // namespace hip
 }  // namespace ecsimd
 #endif

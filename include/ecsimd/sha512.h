@@ -82,18 +82,7 @@ inline derived_keys bip39_seed(messages const& mnemonics, messages const& passph
 }
 
 // n BIP-32 child indices in device memory (i >= 2^31: hardened), copied from the host
-class indices {
- public:
-  indices() = default;
-  explicit indices(std::vector<uint32_t> const& host) : mem_((host.size() + 1) / 2), n_(host.size()) {
-    if (n_) check(ecsimd_hip_memcpy_h2d(context(), mem_.data(), host.data(), 4 * n_), "h2d");
-  }
-  const uint32_t* data() const { return reinterpret_cast<const uint32_t*>(mem_.data()); }
-  size_t size() const { return n_; }
- private:
-  buffer mem_;
-  size_t n_ = 0;
-};
+using indices = lengths;
 }  // namespace hip
 }  // namespace ecsimd
 #endif

@@ -414,7 +414,7 @@ int ecsimd_hip_ecdsa_sign_recoverable(ecsimd_hip_ctx*, int curve, const uint64_t
 /* SHA-256 (FIPS 180-4) of n messages of msg_bytes bytes each, message i at msg + i * stride_bytes (stride_bytes >= msg_bytes; device memory, any alignment --
  * a base and a stride that are multiples of 4 are read a word at a time).  e[i] = SHA-256(message i) as the integer the ECDSA calls take: 4 x u64 little-endian
  * limbs of the digest read as a big-endian number.  Public data.  msg_bytes = 0 is allowed (msg may then be NULL).  One message per lane, the state and the
- * message schedule in registers; equal lengths only. */
+ * message schedule in registers; equal lengths only (one length per lane: ecsimd_hip_sha256_lens, with Bitcoin's hashes below). */
 int ecsimd_hip_sha256(ecsimd_hip_ctx*, const uint8_t* msg, size_t msg_bytes, size_t stride_bytes, uint64_t* e, size_t n);
 /* The deterministic nonce of RFC 6979 section 3.2 with H = SHA-256 (HMAC-SHA-256), bit for bit: k[i] for digest e[i] and private key d[i].  Supported where
  * qlen = 256, i.e. the group order n >= 2^255: the two built-in curves and every registered curve with the ECDSA capability and such an order (brainpoolP256r1,
@@ -499,6 +499,47 @@ int ecsimd_hip_eth_recover(ecsimd_hip_ctx*, const uint64_t* e, const uint64_t* r
 int ecsimd_hip_ripemd160(ecsimd_hip_ctx*, const uint8_t* msg, size_t msg_bytes, size_t stride_bytes, uint8_t* out20, size_t n);
 int ecsimd_hip_hash160(ecsimd_hip_ctx*, const uint8_t* msg, size_t msg_bytes, size_t stride_bytes, uint8_t* out20, size_t n);
 int ecsimd_hip_sha256d(ecsimd_hip_ctx*, const uint8_t* msg, size_t msg_bytes, size_t stride_bytes, uint64_t* e, size_t n);
+/* The same four hashes -- ecsimd_hip_sha256 and the three above -- with one length per lane, for transactions, scripts and witness items, which never share one:
+ * lens as in ecsimd_hip_keccak256.  lens != NULL (n x u32, device memory, 4-byte aligned): lane i hashes the first min(lens[i], stride_bytes) bytes of its row,
+ * msg_bytes is ignored and the block loop runs per lane, so a wave runs until its longest lane is done.  lens == NULL: exactly the equal-length call, which is
+ * called.  No byte at or behind a lane's message is loaded: the last row need only be lens[n - 1] bytes long.  stride_bytes = 0 with n > 1 is refused (every lane
+ * would read lane 0's row).  Word loads where base and stride are multiples of 4, byte loads otherwise; the last one or two blocks are padded in registers.
+ * ECSIMD_HIP_REF_SQUARE_COMPAT does not concern these calls (no curve arithmetic).  PUBLIC data.  Stream-ordered; no workspace. */
+int ecsimd_hip_sha256_lens(ecsimd_hip_ctx*, const uint8_t* msg, size_t msg_bytes, size_t stride_bytes, const uint32_t* lens, uint64_t* e, size_t n);
+int ecsimd_hip_sha256d_lens(ecsimd_hip_ctx*, const uint8_t* msg, size_t msg_bytes, size_t stride_bytes, const uint32_t* lens, uint64_t* e, size_t n);
+int ecsimd_hip_hash160_lens(ecsimd_hip_ctx*, const uint8_t* msg, size_t msg_bytes, size_t stride_bytes, const uint32_t* lens, uint8_t* out20, size_t n);
+int ecsimd_hip_ripemd160_lens(ecsimd_hip_ctx*, const uint8_t* msg, size_t msg_bytes, size_t stride_bytes, const uint32_t* lens, uint8_t* out20, size_t n);
+/* The Merkle roots of m trees of txids (or wtxids) in one call, by Bitcoin Core's ComputeMerkleRoot: level by level, node j = SHA256d(be32(L[2j]) || be32(L[2j + 1])),
+ * the last node paired with itself where the level's count is odd; a tree of one leaf is that leaf.  Tree t's leaves are leaves[tree_offsets[t] ..
+ * tree_offsets[t + 1]) in device memory (4 x u64 limbs each, as ecsimd_hip_sha256d returns txids, 16-byte aligned); tree_offsets: m + 1 non-decreasing u64 in
+ * HOST memory (the counts are public, and the host sizes every level with them), read before the call returns.  An empty tree is ECSIMD_HIP_ERR_BAD_ARG; m = 0
+ * succeeds.  roots: m x 4 limbs.  mutated (m bytes of device memory, or NULL): mutated[t] = 1 iff on any level a REAL pair (2j + 1 < count) holds two equal
+ * values, else 0 -- Bitcoin Core's flag for CVE-2012-2459, evaluated before the last node is duplicated.  One launch per level, one lane per parent node
+ * across all trees: the lane finds its tree by bisection over the level's node offsets, which the host computes for all levels at once and uploads in one
+ * stream-ordered copy from a pinned block of the context (a second call waits for the first one's copy, not for its kernels' results).  Three compressions per
+ * parent; the padding block's schedule is a constant.  Trees are taken in chunks of whole trees with at most 2^22 first-level parents (a larger tree is a chunk
+ * of its own).  PUBLIC data.  Stream-ordered, nothing read back.  Workspace, per chunk: 32 B per parent of the first level and of the second (the levels
+ * ping-pong) -- 24 B per leaf for large trees, at most 64 B per leaf --, and 8 B x (trees + 1) x (levels + 1) of offsets for every chunk of the call. */
+int ecsimd_hip_btc_merkle_root(ecsimd_hip_ctx*, const uint64_t* leaves, const uint64_t* tree_offsets, size_t m, uint64_t* roots, uint8_t* mutated);
+/* BIP-341 script paths, PUBLIC data.  With them and ecsimd_hip_taproot_tweak_pubkey a script-path spend is checked without leaving the device: the leaf hash of
+ * the script, the walk up the control block's path to the merkle root, the tweak of the internal key by it, and the comparison of qx and parity with the
+ * output key and the control byte's low bit (ecsimd_hip_cmp_eq).  Stream-ordered; no workspace; nothing read back.
+ *
+ * tapleaf_hash: e[i] = SHA256(tag || tag || version || compact_size(len) || script), tag = SHA256("TapLeaf"), from the tag block's midstate.  Scripts are
+ * addressed as the messages of the *_lens calls: script i at script + i * stride_bytes, min(lens[i], stride_bytes) bytes of it, or script_bytes (< 2^32) with
+ * lens = NULL.  leaf_version: n x u8 of device memory, or NULL for leaf_version_all (<= 255) on every lane.  The compact size is 1, 3 or 5 bytes (< 0xfd; <= 0xffff:
+ * fd and u16 little-endian; else fe and u32 little-endian); the 2 to 6 prefix bytes are built in registers and the script follows them shifted against the word
+ * grid: nothing is staged in memory, and no byte at or behind a script is loaded.
+ *
+ * taproot_merkle_path: lane i starts with k = leaf[i] and, for j < depth, takes node e_j = the 32 bytes at path + i * path_stride_bytes + 32 j, in the order a
+ * control block holds them, to k = SHA256(tag || tag || min(k, e_j) || max(k, e_j)), tag = SHA256("TapBranch") -- the order is that of the 32 bytes, the
+ * integers'.  root[i] = the final k; depth 0 gives the leaf (path may then be NULL).  depth: n x u8, or NULL for depth_all.  A depth above 128 (BIP-341's bound)
+ * gives ok[i] = 0 and root = 0, else ok[i] = 1.  Two compressions a step, the second a constant padding block; the loop runs per lane.  Any alignment of path
+ * (word loads where base and stride are multiples of 4).  root must not alias leaf. */
+int ecsimd_hip_tapleaf_hash(ecsimd_hip_ctx*, const uint8_t* script, size_t script_bytes, size_t stride_bytes, const uint32_t* lens, const uint8_t* leaf_version,
+                            uint32_t leaf_version_all, uint64_t* e, size_t n);
+int ecsimd_hip_taproot_merkle_path(ecsimd_hip_ctx*, const uint64_t* leaf, const uint8_t* path, size_t path_stride_bytes, const uint8_t* depth, uint32_t depth_all,
+                                   uint64_t* root, uint8_t* ok, size_t n);
 /* HASH160 of the SEC1 encoding of n public keys (qx, qy), 4 x u64 limbs each: compressed != 0: (02 | parity of qy) || be32(qx), 33 bytes, one SHA-256 and one
  * RIPEMD-160 compression; compressed == 0: 04 || be32(qx) || be32(qy), 65 bytes, two and one.  The encoding is built in registers and never reaches memory.  No
  * validation: the call hashes the encoding of the integers it is given ((0, 0) hashes as 02 || 32 zero bytes does).  out20 as above.  PUBLIC data.
