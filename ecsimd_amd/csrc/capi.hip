@@ -175,6 +175,10 @@ bool capturing(ecsimd_hip_ctx* ctx) {
   if (hipStreamIsCapturing(ctx->stream, &st) != hipSuccess) { (void)hipGetLastError(); return false; }
   return st != hipStreamCaptureStatusNone;
 }
+// The entry points that need the host -- they hand a value back, copy from or to memory that may be pageable, wait for the stream, allocate or time with
+// events -- cannot be part of a capture, and a synchronisation on a capturing stream invalidates the whole capture.  They refuse BEFORE they touch the stream
+// (include/ecsimd_hip.h, above ecsimd_hip_set_stream, lists them): nothing is enqueued and the caller's capture stays valid.
+#define REFUSE_IN_CAPTURE(why) do { if (capturing(ctx)) return bad(ctx, why ": not inside a stream capture"); } while (0)
 template <class T>
 int ensure_block(ecsimd_hip_ctx* ctx, T*& block, size_t& have, size_t bytes, const char* during_capture, const char* what) {
   if (have >= bytes) return ECSIMD_HIP_OK;
@@ -730,29 +734,37 @@ int ecsimd_hip_set_ref_square_compat(ecsimd_hip_ctx* ctx, int on) { REQUIRE_CTX(
 int ecsimd_hip_get_ref_square_compat(const ecsimd_hip_ctx* ctx) { return ctx ? ctx->ref_square : ECSIMD_HIP_ERR_BAD_ARG; }
 int ecsimd_hip_sync(ecsimd_hip_ctx* ctx) {
   REQUIRE_CTX();
+  REFUSE_IN_CAPTURE("sync waits for the stream");
   hipError_t e = hipStreamSynchronize(ctx->stream);
   return e == hipSuccess ? ECSIMD_HIP_OK : fail(ctx, e, "hipStreamSynchronize");
 }
 const char* ecsimd_hip_last_error(const ecsimd_hip_ctx* ctx) { return ctx ? ctx->err : "null context"; }
 int ecsimd_hip_malloc(ecsimd_hip_ctx* ctx, void** p, size_t bytes) {
   REQUIRE_CTX(); if (!p) return bad(ctx, "dptr is null");
+  REFUSE_IN_CAPTURE("malloc allocates device memory");
   (void)hipSetDevice(ctx->device);
   hipError_t e = hipMalloc(p, bytes ? bytes : 16);
   return e == hipSuccess ? ECSIMD_HIP_OK : fail(ctx, e, "hipMalloc");
 }
 int ecsimd_hip_free(ecsimd_hip_ctx* ctx, void* p) {
-  REQUIRE_CTX(); (void)hipSetDevice(ctx->device);
+  REQUIRE_CTX();
+  REFUSE_IN_CAPTURE("free releases device memory, which waits for the device");
+  (void)hipSetDevice(ctx->device);
   hipError_t e = hipFree(p);
   return e == hipSuccess ? ECSIMD_HIP_OK : fail(ctx, e, "hipFree");
 }
 int ecsimd_hip_memcpy_h2d(ecsimd_hip_ctx* ctx, void* dst, const void* src, size_t bytes) {
-  REQUIRE_CTX(); (void)hipSetDevice(ctx->device);
+  REQUIRE_CTX();
+  REFUSE_IN_CAPTURE("memcpy_h2d copies from host memory and waits for the copy");
+  (void)hipSetDevice(ctx->device);
   hipError_t e = hipMemcpyAsync(dst, src, bytes, hipMemcpyHostToDevice, ctx->stream);
   if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);     // src may be pageable: complete before returning
   return e == hipSuccess ? ECSIMD_HIP_OK : fail(ctx, e, "hipMemcpy h2d");
 }
 int ecsimd_hip_memcpy_d2h(ecsimd_hip_ctx* ctx, void* dst, const void* src, size_t bytes) {
-  REQUIRE_CTX(); (void)hipSetDevice(ctx->device);
+  REQUIRE_CTX();
+  REFUSE_IN_CAPTURE("memcpy_d2h copies to host memory and waits for the copy");
+  (void)hipSetDevice(ctx->device);
   hipError_t e = hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToHost, ctx->stream);
   if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
   return e == hipSuccess ? ECSIMD_HIP_OK : fail(ctx, e, "hipMemcpy d2h");
@@ -957,6 +969,7 @@ int ecsimd_hip_mask_count(ecsimd_hip_ctx* ctx, const uint8_t* a, size_t n, size_
   REQUIRE_CTX(); if (!count) return bad(ctx, "count is null");
   *count = 0;
   if (!a && n) return bad(ctx, "mask pointer is null");
+  REFUSE_IN_CAPTURE("mask_count returns the count to the host");      // before the empty batch's early return: one answer whatever n is
   ENTER_ANY_SIZE();
   unsigned long long* slot = reinterpret_cast<unsigned long long*>(ctx->sink + 1024 - 16);     // 8-byte slot next to the shared scalar
   hipError_t e = hipMemsetAsync(slot, 0, sizeof *slot, ctx->stream);
@@ -2257,6 +2270,7 @@ int ecsimd_hip_fill_random(ecsimd_hip_ctx* ctx, uint64_t* out, size_t n, uint64_
 
 int ecsimd_hip_peak_mad32(ecsimd_hip_ctx* ctx, int iters, double* mads, double* ms) {
   REQUIRE_CTX(); if (iters < 1 || !mads || !ms) return bad(ctx, "peak_mad32 arguments");
+  REFUSE_IN_CAPTURE("peak_mad32 times its launches with events and waits for them");
   (void)hipSetDevice(ctx->device);
   const int blocks = ctx->cus * 8;          // 8 workgroups of 4 waves per CU = 8 waves per SIMD
   hipEvent_t e0, e1; (void)hipEventCreate(&e0); (void)hipEventCreate(&e1);

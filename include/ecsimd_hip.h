@@ -130,18 +130,34 @@ enum {
 
 /* ---- context, stream and memory ------------------------------------------------------- */
 int ecsimd_hip_init(int device, ecsimd_hip_ctx** ctx);
+/* Waits for the context's stream, then frees everything the context owns.  Not while that stream is being captured (see STREAM CAPTURE below). */
 int ecsimd_hip_destroy(ecsimd_hip_ctx* ctx);
 /* Run on a caller-owned hipStream_t (e.g. torch's current stream).  NULL is HIP's default (null)
  * stream -- which is what torch's default stream is -- not "none".  The context's scratch memory is ordered
  * by its stream: switching makes the new stream wait (by event, no host synchronisation) for the work this
  * context enqueued on the previous one, which must still exist at that moment.  Streams under hipGraph capture are
- * selected without that hand-off; every compute entry point is capturable once its first call has sized the
- * context workspace and built its tables (those steps allocate and synchronise).  A call that would have to grow the
- * workspace or build a table WHILE its stream is being captured returns ECSIMD_HIP_ERR_BAD_ARG instead (growing frees the
- * old block, which an earlier capture may still point into): warm up at the largest batch size, then capture. */
+ * selected without that hand-off (the caller brackets the capture: synchronise, capture, synchronise).
+ *
+ * STREAM CAPTURE.  Every entry point is in one of three classes (tests/capture_matrix.py holds the list to this header):
+ *   - it only ENQUEUES on the context's stream -- kernel launches, the hipMemsetAsync wipes of secret workspace, device-to-device copies -- and is
+ *     capturable once its first call at the capture's batch size has sized the context workspace and built the tables it uses (those steps allocate and
+ *     synchronise).  Every compute entry point not listed below is of this kind, and so are set_stream, use_own_stream and memcpy_d2d.  Host scalars and
+ *     the few-word host arrays (mgry_pow's exponent, scalar_mult_1s's k1) are kernel arguments: a graph replays the values it was captured with.  The
+ *     wipes are nodes of the graph: a replay leaves the workspace as clean as the eager call does.  A call that would have to grow the workspace or build a
+ *     table WHILE its stream is being captured returns ECSIMD_HIP_ERR_BAD_ARG instead (growing frees the old block, which an earlier capture may still
+ *     point into): warm up at the largest batch size, then capture;
+ *   - it NEEDS THE HOST -- hands a value back, copies from or to memory that may be pageable, waits for the stream, allocates or frees, times with events --
+ *     and REFUSES while the context's stream is being captured: ECSIMD_HIP_ERR_BAD_ARG with "capture" in ecsimd_hip_last_error, decided BEFORE the
+ *     stream is touched, so nothing is enqueued and the caller's capture stays valid (a synchronisation on a capturing stream would invalidate it).  These
+ *     are sync, malloc, free, memcpy_h2d, memcpy_d2h, mask_count, scalar_mult_host, btc_merkle_root and peak_mad32;
+ *   - it is no part of a stream's work and enqueues nothing on the context's stream: init, set / get_ref_square_compat, last_error, version, get_constant,
+ *     register_modulus, register_curve, curve_capabilities, workspace_info, shard_range and the group_* family, whose groups own their contexts and
+ *     streams -- and destroy, which WAITS for the context's stream before it frees what the context owns: it must not be called while that stream is
+ *     being captured (the wait would invalidate the capture); end or abandon the capture first. */
 int ecsimd_hip_set_stream(ecsimd_hip_ctx* ctx, void* hip_stream);
 /* Go back to the non-blocking stream the context created in ecsimd_hip_init (the default). */
 int ecsimd_hip_use_own_stream(ecsimd_hip_ctx* ctx);
+/* Waits for the context's stream.  Refuses under stream capture (above). */
 int ecsimd_hip_sync(ecsimd_hip_ctx* ctx);
 /* Reference-square compatibility for every entry point that evaluates the reference's own expression DAG and contains a
  * squaring (square, mgry_sqr, mgry_pow, gfp_inverse, gfp_sqrt, compute_y, to_affine, DBLU ... TRPLU, the ladder):
@@ -153,6 +169,8 @@ int ecsimd_hip_set_ref_square_compat(ecsimd_hip_ctx* ctx, int on);
 int ecsimd_hip_get_ref_square_compat(const ecsimd_hip_ctx* ctx);
 const char* ecsimd_hip_last_error(const ecsimd_hip_ctx* ctx);
 const char* ecsimd_hip_version(void);
+/* Device memory on the context's device, and synchronous copies between it and host memory (pageable is fine: each copy has completed when the call
+ * returns).  All four refuse under stream capture (above): allocate, fill and read back outside the capture. */
 int ecsimd_hip_malloc(ecsimd_hip_ctx* ctx, void** dptr, size_t bytes);
 int ecsimd_hip_free(ecsimd_hip_ctx* ctx, void* dptr);
 int ecsimd_hip_memcpy_h2d(ecsimd_hip_ctx* ctx, void* dst, const void* src, size_t bytes);
@@ -229,7 +247,7 @@ int ecsimd_hip_sub_if_above(ecsimd_hip_ctx*, const uint64_t* a, const uint64_t* 
 /* Lane masks on the device (the reference's eve::logical<wide>, bignum.h:136-137, with eve::all / eve::any):
  * cmp_eq: flag[i] = (a[i] == b[i]) over the low `limbs` (1..8) limbs of each element (element stride 4 limbs,
  * 8 for limbs > 4: a 128-bit value occupies the low half of a 256-bit element); mask_op: NOT (b ignored), AND, OR, EQ of
- * 0/1 byte masks; mask_count: number of non-zero flags (synchronises the stream: all = count == n, any = count > 0). */
+ * 0/1 byte masks; mask_count: number of non-zero flags (synchronises the stream: all = count == n, any = count > 0; refuses under stream capture). */
 enum { ECSIMD_HIP_MASK_NOT = 0, ECSIMD_HIP_MASK_AND = 1, ECSIMD_HIP_MASK_OR = 2, ECSIMD_HIP_MASK_EQ = 3 };
 int ecsimd_hip_cmp_eq(ecsimd_hip_ctx*, const uint64_t* a, const uint64_t* b, int limbs, uint8_t* flag, size_t n);
 int ecsimd_hip_mask_op(ecsimd_hip_ctx*, int op, const uint8_t* a, const uint8_t* b, uint8_t* out, size_t n);
@@ -516,7 +534,8 @@ int ecsimd_hip_ripemd160_lens(ecsimd_hip_ctx*, const uint8_t* msg, size_t msg_by
  * succeeds.  roots: m x 4 limbs.  mutated (m bytes of device memory, or NULL): mutated[t] = 1 iff on any level a REAL pair (2j + 1 < count) holds two equal
  * values, else 0 -- Bitcoin Core's flag for CVE-2012-2459, evaluated before the last node is duplicated.  One launch per level, one lane per parent node
  * across all trees: the lane finds its tree by bisection over the level's node offsets, which the host computes for all levels at once and uploads in one
- * stream-ordered copy from a pinned block of the context (a second call waits for the first one's copy, not for its kernels' results).  Three compressions per
+ * stream-ordered copy from a pinned block of the context (a second call waits for the first one's copy, not for its kernels' results; the host work makes
+ * the call refuse under stream capture).  Three compressions per
  * parent; the padding block's schedule is a constant.  Trees are taken in chunks of whole trees with at most 2^22 first-level parents (a larger tree is a chunk
  * of its own).  PUBLIC data.  Stream-ordered, nothing read back.  Workspace, per chunk: 32 B per parent of the first level and of the second (the levels
  * ping-pong) -- 24 B per leaf for large trees, at most 64 B per leaf --, and 8 B x (trees + 1) x (levels + 1) of offsets for every chunk of the call. */
@@ -664,7 +683,7 @@ int ecsimd_hip_workspace_info(ecsimd_hip_ctx* ctx, const void** dptr, size_t* by
 /* scalar_mult with every array in HOST memory (n elements each; pageable is fine): the PCIe-inclusive form of the hot path.  Same curve ids, flags and
  * meaning as ecsimd_hip_scalar_mult (x = y = NULL with ECSIMD_HIP_BASE_GENERATOR: k G; OUT_AFFINE: oz unused, oy optional).  Chunks of 2^19 elements
  * alternate between the context and a helper context it creates on first use (a second stream): the copies of one chunk overlap the ladder of its
- * neighbour.  Synchronous -- returns with the results in place; not capturable.  One MI355X, 2^22 elements of pageable memory: 56 M scalar mults/s against
+ * neighbour.  Synchronous -- returns with the results in place; refuses under stream capture.  One MI355X, 2^22 elements of pageable memory: 56 M scalar mults/s against
  * 58 with the arrays resident in HBM (reuse the output arrays: fresh pages are first touched inside the call).  The reference's own types instead of arrays: integration/scalar_mult_p256_adapter.cpp. */
 int ecsimd_hip_scalar_mult_host(ecsimd_hip_ctx*, int curve, const uint64_t* k, const uint64_t* x, const uint64_t* y,
                                 uint64_t* ox, uint64_t* oy, uint64_t* oz, size_t n, int flags);
@@ -678,7 +697,7 @@ int ecsimd_hip_scalar_mult_p256(ecsimd_hip_ctx*, const uint64_t* k, const uint64
  * clear_top_bits > 0 clears that many top bits of limb 3 (field elements < 2^255 < p). */
 int ecsimd_hip_fill_random(ecsimd_hip_ctx*, uint64_t* out, size_t n, uint64_t seed, uint64_t stream, uint64_t first_index, int clear_top_bits);
 /* Dependency-free v_mad_u64_u32 stream: the integer-multiply roofline denominator.  Returns the
- * number of mad32 executed in *mads; elapsed device time in *ms (HIP events on the ctx stream). */
+ * number of mad32 executed in *mads; elapsed device time in *ms (HIP events on the ctx stream, waited for: refuses under stream capture). */
 int ecsimd_hip_peak_mad32(ecsimd_hip_ctx*, int iters, double* mads, double* ms);
 
 /* ---- device groups: one batch over several GPUs -------------------------------
