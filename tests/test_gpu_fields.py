@@ -286,6 +286,33 @@ def test_ecdsa_sign_vs_big_ints_and_libcrypto(engine, openssl, cv):
 
 
 @pytest.mark.parametrize("cv", CURVES)
+def test_ecdsa_sign_refuses_the_key_that_makes_s_zero(engine, cv):
+    """r = x(k G) mod n comes from k alone, so d = -e / r mod n makes s = (e + r d) / k = 0: that lane is refused with r = s = 0, and its two neighbours
+    d + 1, d - 1 are signed -- (r, s) of the textbook formulas with k G from the big-int curve model, and accepted by ecdsa_verify under d G."""
+    from helpers import ec_mul
+    c = CURVE_PARAMS[cv]; order = c["n"]; G = (c["gx"], c["gy"])
+    rng = np.random.default_rng(40 + cv)
+    draw = lambda: to_int(rng.integers(0, 2**64, size=4, dtype=np.uint64))
+    e, d, k, want, pub = [], [], [], [], []
+    for trip in range(6):
+        ei, ki = draw(), draw() % (order - 1) + 1
+        ri = ec_mul(cv, ki, G)[0] % order
+        d0 = -ei * pow(ri, -1, order) % order
+        assert ri != 0 and 2 <= d0 < order - 1 and (ei + ri * d0) % order == 0
+        for di in (d0, d0 + 1, d0 - 1):
+            si = pow(ki, -1, order) * (ei + ri * di) % order
+            e.append(ei); d.append(di); k.append(ki); want.append((ri, si, 1) if si else (0, 0, 0)); pub.append(ec_mul(cv, di, G))
+    assert [w[2] for w in want] == [0, 1, 1] * 6
+    up = lambda values: engine.to_device(ints_to_arr(values))
+    r, s, ok = (engine.to_numpy(t) for t in engine.ecdsa_sign(cv, up(e), up(d), up(k)))
+    assert [(to_int(r[i]), to_int(s[i]), int(ok[i])) for i in range(len(want))] == want
+    served = [i for i, w in enumerate(want) if w[2]]
+    take = lambda values: up([values[i] for i in served])
+    verdict = engine.ecdsa_verify(cv, take(e), take([w[0] for w in want]), take([w[1] for w in want]), take([q[0] for q in pub]), take([q[1] for q in pub]))
+    assert engine.to_numpy(verdict).all()
+
+
+@pytest.mark.parametrize("cv", CURVES)
 def test_scalar_field_arithmetic_against_big_ints(gpu, cv):
     """u1 = e / s, u2 = r / s mod n by the public field entry points on the group-order field id: what ecdsa_verify computes inside."""
     from ecsimd_amd.engine import ORDER_FIELD
