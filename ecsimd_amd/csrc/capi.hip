@@ -16,6 +16,7 @@
 #include <vector>
 
 #include "../../include/ecsimd_hip.h"
+#include "../../include/ecsimd_ed25519.h"
 #include "kernels.h"
 #include "point.cuh"   // curve constants for ecsimd_hip_get_constant (host-side constexpr use only)
 #include "gfield.cuh"  // gmod: a run-time modulus as the generic field kernels take it
@@ -2245,6 +2246,124 @@ int ecsimd_hip_schnorr_sign(ecsimd_hip_ctx* ctx, const uint64_t* d, const uint8_
     if (err != hipSuccess) break;
   }
   return err == hipSuccess ? ECSIMD_HIP_OK : fail(ctx, err, "schnorr_sign launch"); }
+
+// ---- Ed25519 (include/ecsimd_ed25519.h; k_ed25519.hip).  Bytes in, bytes out; the multiples of B are constants of the library, so nothing is built at run time
+// and the only thing a capture can refuse is a workspace that would have to grow.  ECSIMD_HIP_REF_SQUARE_COMPAT contexts are accepted: none of the reference's
+// arithmetic is involved.
+namespace {
+// L = 2^252 + 27742317777372353535851937790883648493 as the scalar kernels take it
+const gmod* ed25519_order() {
+  static const uint64_t l[4] = {0x5812631a5cf5d3edull, 0x14def9dea2f79cd6ull, 0x0000000000000000ull, 0x1000000000000000ull};
+  static const gmod M = make_gmod(l, GMOD_PRIME);
+  return &M;
+}
+// keccak256's message arguments, checked the same way; msg_bytes comes back as 0 where lens rules
+int ed25519_messages(ecsimd_hip_ctx* ctx, const uint8_t* msg, size_t* msg_bytes, size_t stride_bytes, const uint32_t* lens, size_t n) {
+  if (lens) *msg_bytes = 0;
+  if (!msg && n && (*msg_bytes || (lens && stride_bytes))) return bad(ctx, "msg is null");
+  if (lens && (reinterpret_cast<uintptr_t>(lens) & 3u)) return bad(ctx, "lens is not 4-byte aligned");
+  if (stride_bytes < *msg_bytes) return bad(ctx, "ed25519: stride_bytes is smaller than msg_bytes");
+  if (*msg_bytes > ((size_t)1 << 40)) return bad(ctx, "ed25519: message too long");
+  return ECSIMD_HIP_OK;
+}
+// Per lane of a chunk: the scalars a and r side by side (one comb launch takes both), then their encodings the same way.  pubkey needs a alone.
+struct ed25519_secret_layout { uint64_t *a, *r; uint8_t *encA, *encR; size_t bytes; };
+ed25519_secret_layout ed25519_secret_plan(void* base, size_t chunk, bool sign) {
+  ed25519_secret_layout L; carve c = carve_from(base);
+  L.a = carve_limbs(c, chunk); L.r = sign ? carve_limbs(c, chunk) : nullptr;
+  L.encA = sign ? static_cast<uint8_t*>(carve_bytes(c, 32 * chunk)) : nullptr; L.encR = sign ? static_cast<uint8_t*>(carve_bytes(c, 32 * chunk)) : nullptr;
+  L.bytes = c.bytes;
+  return L;
+}
+// The longest launch is the verification loop's: 2^20 lanes of it stay within what DESIGN.md section 4d allows a launch on a shared device, and 1 KiB of
+// table per lane keeps the workspace at 1.1 GB.
+constexpr size_t ED25519_VERIFY_CHUNK = (size_t)1 << 20;
+struct ed25519_verify_layout { uint64_t *s, *h; void* table; uint8_t* valid; size_t bytes; };
+ed25519_verify_layout ed25519_verify_plan(void* base, size_t chunk) {
+  ed25519_verify_layout L; carve c = carve_from(base);
+  L.s = carve_limbs(c, chunk); L.h = carve_limbs(c, chunk); L.table = carve_bytes(c, launch::ed25519_table_bytes(chunk)); L.valid = carve_flags(c, chunk);
+  L.bytes = c.bytes;
+  return L;
+}
+}  // namespace
+
+int ecsimd_ed25519_pubkey(ecsimd_hip_ctx* ctx, const uint8_t* seed, uint8_t* pk, size_t n) {
+  REQUIRE_CTX(); if ((!seed || !pk) && n) return bad(ctx, "ed25519_pubkey: seed or pk is null");
+  if (n != 0 && overlaps(seed, pk)) return bad(ctx, "ed25519_pubkey: pk must not alias seed");
+  ENTER_ANY_SIZE();
+  const size_t chunk = chunk_of(n, GC_CHUNK);
+  int rc = ensure_workspace(ctx, ed25519_secret_plan(nullptr, chunk, false).bytes);
+  if (rc != ECSIMD_HIP_OK) return rc;
+  const ed25519_secret_layout L = ed25519_secret_plan(ctx->workspace, chunk, false);
+  hipError_t err = hipSuccess;
+  FOR_CHUNKS(first, m, n, chunk) {
+    launch::ed25519_secret_front(ctx->stream, *ed25519_order(), seed + 32 * first, nullptr, 0, 0, nullptr, false, L.a, nullptr, m);
+    launch::ed25519_base_ct(ctx->stream, L.a, pk + 32 * first, m);
+    err = wipe_workspace(ctx, L.bytes, hipGetLastError());
+    if (err != hipSuccess) break;
+  }
+  return err == hipSuccess ? ECSIMD_HIP_OK : fail(ctx, err, "ed25519_pubkey launch"); }
+
+int ecsimd_ed25519_sign(ecsimd_hip_ctx* ctx, const uint8_t* seed, const uint8_t* msg, size_t msg_bytes, size_t stride_bytes, const uint32_t* lens,
+                        uint8_t* sig, uint8_t* pk, size_t n) {
+  REQUIRE_CTX(); if ((!seed || !sig) && n) return bad(ctx, "ed25519_sign: seed or sig is null");
+  int rc = ed25519_messages(ctx, msg, &msg_bytes, stride_bytes, lens, n); if (rc != ECSIMD_HIP_OK) return rc;
+  if (n != 0 && (pk ? any_alias({sig, pk}, {seed, msg, lens}) : any_alias({sig}, {seed, msg, lens}))) return bad(ctx, "ed25519_sign: sig and pk must not alias an input or each other");
+  ENTER_ANY_SIZE();
+  const size_t chunk = chunk_of(n, GC_CHUNK);
+  rc = ensure_workspace(ctx, ed25519_secret_plan(nullptr, chunk, true).bytes);
+  if (rc != ECSIMD_HIP_OK) return rc;
+  const ed25519_secret_layout L = ed25519_secret_plan(ctx->workspace, chunk, true);
+  hipError_t err = hipSuccess;
+  FOR_CHUNKS(first, m, n, chunk) {
+    const uint8_t* mp = msg ? msg + first * stride_bytes : nullptr;
+    const uint32_t* lp = lens ? lens + first : nullptr;
+    launch::ed25519_secret_front(ctx->stream, *ed25519_order(), seed + 32 * first, mp, msg_bytes, stride_bytes, lp, true, L.a, L.r, m);
+    // a and r lie `chunk` lanes apart, and so do their encodings: a full chunk takes one comb launch of 2 m lanes, a shorter one two
+    if (m == chunk) launch::ed25519_base_ct(ctx->stream, L.a, L.encA, 2 * m);
+    else { launch::ed25519_base_ct(ctx->stream, L.a, L.encA, m); launch::ed25519_base_ct(ctx->stream, L.r, L.encR, m); }
+    launch::ed25519_sign_finish(ctx->stream, *ed25519_order(), L.a, L.r, L.encA, L.encR, mp, msg_bytes, stride_bytes, lp, sig + 64 * first, pk ? pk + 32 * first : nullptr, m);
+    err = wipe_workspace(ctx, L.bytes, hipGetLastError());
+    if (err != hipSuccess) break;
+  }
+  return err == hipSuccess ? ECSIMD_HIP_OK : fail(ctx, err, "ed25519_sign launch"); }
+
+int ecsimd_ed25519_verify(ecsimd_hip_ctx* ctx, const uint8_t* pk, const uint8_t* msg, size_t msg_bytes, size_t stride_bytes, const uint32_t* lens,
+                          const uint8_t* sig, uint8_t* ok, size_t n, int flags) {
+  REQUIRE_CTX(); if ((!pk || !sig || !ok) && n) return bad(ctx, "ed25519_verify: pk, sig or ok is null");
+  if (flags & ~ECSIMD_ED25519_REJECT_SMALL_ORDER) return bad(ctx, "ed25519_verify: unknown flag");
+  int rc = ed25519_messages(ctx, msg, &msg_bytes, stride_bytes, lens, n); if (rc != ECSIMD_HIP_OK) return rc;
+  if (n != 0 && any_alias({ok}, {pk, msg, sig, lens})) return bad(ctx, "ed25519_verify: ok must not alias an input");
+  ENTER_ANY_SIZE();
+  const size_t chunk = chunk_of(n, ED25519_VERIFY_CHUNK);
+  rc = ensure_workspace(ctx, ed25519_verify_plan(nullptr, chunk).bytes);
+  if (rc != ECSIMD_HIP_OK) return rc;
+  const ed25519_verify_layout L = ed25519_verify_plan(ctx->workspace, chunk);
+  FOR_CHUNKS(first, m, n, chunk) {
+    launch::ed25519_verify_front(ctx->stream, *ed25519_order(), pk + 32 * first, sig + 64 * first, msg ? msg + first * stride_bytes : nullptr, msg_bytes, stride_bytes,
+                                 lens ? lens + first : nullptr, (flags & ECSIMD_ED25519_REJECT_SMALL_ORDER) != 0, L.s, L.h, L.table, L.valid, m);
+    launch::ed25519_verify_loop(ctx->stream, L.s, L.h, L.table, L.valid, sig + 64 * first, ok + first, m);
+  }
+  const hipError_t err = hipGetLastError();
+  return err == hipSuccess ? ECSIMD_HIP_OK : fail(ctx, err, "ed25519_verify launch"); }
+
+int ecsimd_ed25519_raw_inputs(int op) { return (op < 0 || op > launch::ED_RAW_DOUBLE_MULT) ? 0 : launch::ed_raw_inputs(op); }
+int ecsimd_ed25519_raw_outputs(int op) { return (op < 0 || op > launch::ED_RAW_DOUBLE_MULT) ? 0 : launch::ed_raw_outputs(op); }
+int ecsimd_ed25519_raw(ecsimd_hip_ctx* ctx, int op, const uint8_t* in, uint8_t* out, size_t n) {
+  REQUIRE_CTX(); if ((!in || !out) && n) return bad(ctx, "ed25519_raw: null pointer");
+  if (op < 0 || op > launch::ED_RAW_DOUBLE_MULT) return bad(ctx, "ed25519_raw: unknown function");
+  if (n != 0 && overlaps(in, out)) return bad(ctx, "ed25519_raw: out must not alias in");
+  ENTER();
+  void* table = nullptr;
+  if (op == launch::ED_RAW_DOUBLE_MULT) {
+    if (n > ED25519_VERIFY_CHUNK) return bad(ctx, "ed25519_raw: at most 2^20 lanes of DOUBLE_MULT");
+    const int rc = ensure_workspace(ctx, launch::ed25519_table_bytes(n));
+    if (rc != ECSIMD_HIP_OK) return rc;
+    table = ctx->workspace;
+  }
+  launch::ed25519_raw(ctx->stream, *ed25519_order(), op, in, out, table, n);
+  const hipError_t e = hipGetLastError();
+  return e == hipSuccess ? ECSIMD_HIP_OK : fail(ctx, e, "ed25519_raw launch"); }
 
 int ecsimd_hip_fe29_raw(ecsimd_hip_ctx* ctx, int curve, int op, const int32_t* in, int32_t* out, size_t n, int swap) {
   REQUIRE_CTX(); if ((!in || !out) && n) return bad(ctx, "fe29_raw: null pointer");

@@ -202,6 +202,27 @@ constexpr int fe29_raw_inputs(int op) { return op == RAW_ZDAU ? 6 : op == RAW_MU
 constexpr int fe29_raw_outputs(int op) { return (op == RAW_ZDAU || op == RAW_ZADDU) ? 6 : (op == RAW_MUL || op == RAW_SQR) ? 1 : op == RAW_GJDBL ? 4 : 3; }
 bool fe29_raw(hipStream_t, int curve, const gcurve* G, int op, const int32_t* in, int32_t* out, size_t n, uint32_t swap);
 
+// k_ed25519.hip: Ed25519 (RFC 8032, pure).  L = the group order's gmod.  Keys, signatures and seeds are BYTES (32 / 64 / 32 per lane, any alignment: word
+// accesses where the base is a multiple of 4); messages as keccak256's (lens may be NULL).  SECRET (selects only): ed25519_secret_front writes a = the clamped
+// half of SHA-512(seed), reduced modulo L, and with sign = true r = SHA-512(prefix || M) mod L; ed25519_base_ct the 32-byte encodings of [k]B for n scalars below
+// L; ed25519_sign_finish R || s with s = r + SHA-512(R || A || M) a mod L, and A at pk (may be NULL).  PUBLIC: ed25519_verify_front writes valid = s < L && A
+// decodes (&& no small-order A or R), s, h = SHA-512(R || A || M) mod L and the lanes' tables of 1 .. 8 times -A (ed25519_table_bytes(n) bytes, 16-byte aligned);
+// ed25519_verify_loop ok = valid && encode([s]B + [h](-A)) == R.  ed25519_raw: one function of the layers on 32-byte records (ED_RAW_DOUBLE_MULT needs the table).
+enum ed25519_raw_op { ED_RAW_FE_MUL = 0, ED_RAW_FE_SQR = 1, ED_RAW_FE_ADD = 2, ED_RAW_FE_SUB = 3, ED_RAW_FE_NEG = 4, ED_RAW_FE_INVERT = 5, ED_RAW_FE_CANON = 6, ED_RAW_SQRT_RATIO = 7,
+                      ED_RAW_DECODE_ENCODE = 8, ED_RAW_POINT_ADD = 9, ED_RAW_POINT_DBL = 10, ED_RAW_SC_REDUCE = 11, ED_RAW_BASE_MULT = 12, ED_RAW_DOUBLE_MULT = 13 };
+constexpr int ed_raw_inputs(int op) { return op == ED_RAW_DOUBLE_MULT ? 3 : (op == ED_RAW_FE_MUL || op == ED_RAW_FE_ADD || op == ED_RAW_FE_SUB || op == ED_RAW_SQRT_RATIO || op == ED_RAW_POINT_ADD || op == ED_RAW_SC_REDUCE) ? 2 : 1; }
+constexpr int ed_raw_outputs(int op) { return (op == ED_RAW_SQRT_RATIO || op == ED_RAW_DECODE_ENCODE || op == ED_RAW_POINT_ADD || op == ED_RAW_POINT_DBL || op == ED_RAW_DOUBLE_MULT) ? 2 : 1; }
+inline size_t ed25519_table_bytes(size_t n) { return n * 8 * 128; }
+void ed25519_secret_front(hipStream_t, const gmod& L, const uint8_t* seed, const uint8_t* msg, size_t msg_bytes, size_t stride_bytes, const uint32_t* lens, bool sign,
+                          uint64_t* a, uint64_t* r, size_t n);
+void ed25519_base_ct(hipStream_t, const uint64_t* k, uint8_t* out32, size_t n);
+void ed25519_sign_finish(hipStream_t, const gmod& L, const uint64_t* a, const uint64_t* r, const uint8_t* encA, const uint8_t* encR, const uint8_t* msg, size_t msg_bytes,
+                         size_t stride_bytes, const uint32_t* lens, uint8_t* sig, uint8_t* pk, size_t n);
+void ed25519_verify_front(hipStream_t, const gmod& L, const uint8_t* pk, const uint8_t* sig, const uint8_t* msg, size_t msg_bytes, size_t stride_bytes, const uint32_t* lens,
+                          bool reject_small_order, uint64_t* s, uint64_t* h, void* table, uint8_t* valid, size_t n);
+void ed25519_verify_loop(hipStream_t, const uint64_t* s, const uint64_t* h, const void* table, const uint8_t* valid, const uint8_t* sig, uint8_t* ok, size_t n);
+void ed25519_raw(hipStream_t, const gmod& L, int op, const uint8_t* in, uint8_t* out, void* table, size_t n);
+
 // k_point_<curve>.hip
 void from_affine(hipStream_t, int curve, const uint64_t* x, const uint64_t* y, uint64_t* jx, uint64_t* jy, uint64_t* jz, size_t n);
 void to_affine(hipStream_t, int curve, const uint64_t* jx, const uint64_t* jy, const uint64_t* jz, uint64_t* x, uint64_t* y, size_t n);

@@ -11,7 +11,7 @@ import os
 
 import numpy as np
 
-from .flags import BIP32_ALL_HARDENED, ECDSA_LOW_S, ETH_REQUIRE_LOW_S
+from .flags import BIP32_ALL_HARDENED, ECDSA_LOW_S, ED25519_REJECT_SMALL_ORDER, ETH_REQUIRE_LOW_S
 
 P256, SECP256K1 = 0, 1
 CURVES = {"p256": P256, "secp256k1": SECP256K1}
@@ -467,6 +467,59 @@ class Engine:
         keep, mp, length, stride = self._messages(msgs, n)
         self._call("keccak256", mp, length, stride, self._lens_ptr("keccak256", lens, n), self._ptr(e), C.c_size_t(n))
         return e
+
+    # ---- Ed25519 (include/ecsimd_ed25519.h): keys and signatures are bytes
+    def _rows_u8(self, t, width, what):
+        """The pointer and the row count of a contiguous (n, width) uint8 device tensor (a view at any byte offset will do)."""
+        assert t.is_cuda and t.device.index == self.device, "tensor on the wrong device"
+        assert t.dtype == self.torch.uint8 and t.dim() == 2 and int(t.shape[1]) == width and t.is_contiguous(), (what, t.dtype, tuple(t.shape))
+        return C.c_void_p(t.data_ptr() if t.shape[0] else 0), int(t.shape[0])
+
+    def ed25519_pubkey(self, seeds):
+        """ecsimd_ed25519_pubkey: (n, 32) uint8 public keys of the (n, 32) uint8 SECRET seeds (RFC 8032 5.1.5)."""
+        sp, n = self._rows_u8(seeds, 32, "seeds")
+        pk = self.torch.empty((n, 32), dtype=self.torch.uint8, device=self.tdev)
+        self._bind_stream()
+        self._check(self.lib.ecsimd_ed25519_pubkey(self.ctx, sp, C.c_void_p(pk.data_ptr()), C.c_size_t(n)), "ed25519_pubkey")
+        return pk
+
+    def ed25519_sign(self, seeds, msgs, lens=None, want_pk=True):
+        """ecsimd_ed25519_sign: (sig, pk), the (n, 64) uint8 signatures R || s of the rows of `msgs` (as keccak256's: 2-D uint8, rows may be strided; lens: lane i
+        signs the first lens[i] bytes of its row) under the SECRET seeds, and the public keys derived from them (None with want_pk=False)."""
+        sp, n = self._rows_u8(seeds, 32, "seeds")
+        keep, mp, length, stride = self._messages(msgs, n)
+        sig = self.torch.empty((n, 64), dtype=self.torch.uint8, device=self.tdev)
+        pk = self.torch.empty((n, 32), dtype=self.torch.uint8, device=self.tdev) if want_pk else None
+        lp = self._lens_ptr("ed25519_sign", lens if length.value else None, n)
+        self._bind_stream()
+        self._check(self.lib.ecsimd_ed25519_sign(self.ctx, sp, mp, length, stride, lp, C.c_void_p(sig.data_ptr()), C.c_void_p(pk.data_ptr() if want_pk else 0), C.c_size_t(n)), "ed25519_sign")
+        return sig, pk
+
+    def ed25519_verify(self, pk, msgs, sig, lens=None, reject_small_order=False):
+        """ecsimd_ed25519_verify: ok, one byte per lane: s < L, A decodes strictly, and the canonical encoding of [s]B - [k]A is the signature's R (cofactorless);
+        reject_small_order also refuses the eight small-order encodings as A or R.  Public data only."""
+        pp, n = self._rows_u8(pk, 32, "pk")
+        gp, n2 = self._rows_u8(sig, 64, "sig")
+        if n2 != n:
+            raise EcsimdHipError(f"ed25519_verify: operands disagree on the batch length: {sorted((n, n2))}")
+        keep, mp, length, stride = self._messages(msgs, n)
+        ok = self.flags(n)
+        lp = self._lens_ptr("ed25519_verify", lens if length.value else None, n)
+        self._bind_stream()
+        self._check(self.lib.ecsimd_ed25519_verify(self.ctx, pp, mp, length, stride, lp, gp, C.c_void_p(ok.data_ptr()), C.c_size_t(n),
+                                                   C.c_int(ED25519_REJECT_SMALL_ORDER if reject_small_order else 0)), "ed25519_verify")
+        return ok
+
+    def ed25519_raw(self, op, records):
+        """ecsimd_ed25519_raw: one function of the layers below on (n, 32 * inputs) uint8 records; returns (n, 32 * outputs) uint8 (see the header's table)."""
+        ni, no = int(self.lib.ecsimd_ed25519_raw_inputs(C.c_int(op))), int(self.lib.ecsimd_ed25519_raw_outputs(C.c_int(op)))
+        if ni == 0:
+            raise EcsimdHipError(f"ed25519_raw: unknown function {op}")
+        ip, n = self._rows_u8(records, 32 * ni, "records")
+        out = self.torch.empty((n, 32 * no), dtype=self.torch.uint8, device=self.tdev)
+        self._bind_stream()
+        self._check(self.lib.ecsimd_ed25519_raw(self.ctx, C.c_int(op), ip, C.c_void_p(out.data_ptr()), C.c_size_t(n)), "ed25519_raw")
+        return out
 
     def _lens_ptr(self, what, lens, n):
         """The pointer of an optional int32 / uint32 device tensor of n lengths (None: NULL), as ecsimd_hip_keccak256 and the *_lens calls take it."""

@@ -15,3 +15,4 @@ GROUP_NO_GATHER = 0x10000    # ecsimd_hip_group_scalar_mult only: compute withou
 ECDSA_LOW_S = 1               # ecsimd_hip_ecdsa_sign_recoverable only: s > n / 2 is returned as n - s (and bit 0 of v flipped)
 ETH_REQUIRE_LOW_S = 1         # ecsimd_hip_eth_recover only: s > n / 2 is refused (EIP-2)
 BIP32_ALL_HARDENED = 1        # ecsimd_hip_bip32_ckd_priv only: every index has bit 31 set (no point multiplication; a lane that breaks the promise is refused)
+ED25519_REJECT_SMALL_ORDER = 1   # ecsimd_ed25519_verify only: a small-order A or R is refused as well
