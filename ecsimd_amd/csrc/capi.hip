@@ -17,6 +17,7 @@
 
 #include "../../include/ecsimd_hip.h"
 #include "../../include/ecsimd_ed25519.h"
+#include "../../include/ecsimd_x25519.h"
 #include "kernels.h"
 #include "point.cuh"   // curve constants for ecsimd_hip_get_constant (host-side constexpr use only)
 #include "gfield.cuh"  // gmod: a run-time modulus as the generic field kernels take it
@@ -2364,6 +2365,57 @@ int ecsimd_ed25519_raw(ecsimd_hip_ctx* ctx, int op, const uint8_t* in, uint8_t* 
   launch::ed25519_raw(ctx->stream, *ed25519_order(), op, in, out, table, n);
   const hipError_t e = hipGetLastError();
   return e == hipSuccess ? ECSIMD_HIP_OK : fail(ctx, e, "ed25519_raw launch"); }
+
+// ---- X25519 and the Ed25519 key conversions (include/ecsimd_x25519.h; k_x25519.hip).  Bytes in, bytes out, one kernel per call and no workspace: nothing to
+// size, nothing to wipe, nothing a capture can refuse.  ECSIMD_HIP_REF_SQUARE_COMPAT contexts are accepted: none of the reference's arithmetic is involved.
+namespace {
+// One launch covers at most 2^20 lanes (ed25519_verify's figure): the ladder is the longest kernel here, and DESIGN.md section 4g has what a launch of it takes.
+constexpr size_t X25519_CHUNK = (size_t)1 << 20;
+}  // namespace
+
+int ecsimd_x25519(ecsimd_hip_ctx* ctx, const uint8_t* scalar, const uint8_t* u, uint8_t* out, uint8_t* ok, size_t n) {
+  REQUIRE_CTX(); if ((!scalar || !u || !out) && n) return bad(ctx, "x25519: scalar, u or out is null");
+  if (n != 0 && (ok ? any_alias({out, ok}, {scalar, u}) : any_alias({out}, {scalar, u}))) return bad(ctx, "x25519: out and ok must not alias an input or each other");
+  ENTER_ANY_SIZE();
+  FOR_CHUNKS(first, m, n, X25519_CHUNK) launch::x25519(ctx->stream, scalar + 32 * first, u + 32 * first, out + 32 * first, ok ? ok + first : nullptr, m);
+  const hipError_t err = hipGetLastError();
+  return err == hipSuccess ? ECSIMD_HIP_OK : fail(ctx, err, "x25519 launch"); }
+
+int ecsimd_x25519_base(ecsimd_hip_ctx* ctx, const uint8_t* scalar, uint8_t* out, size_t n) {
+  REQUIRE_CTX(); if ((!scalar || !out) && n) return bad(ctx, "x25519_base: scalar or out is null");
+  if (n != 0 && overlaps(scalar, out)) return bad(ctx, "x25519_base: out must not alias scalar");
+  ENTER_ANY_SIZE();
+  FOR_CHUNKS(first, m, n, X25519_CHUNK) launch::x25519_base(ctx->stream, *ed25519_order(), scalar + 32 * first, out + 32 * first, m);
+  const hipError_t err = hipGetLastError();
+  return err == hipSuccess ? ECSIMD_HIP_OK : fail(ctx, err, "x25519_base launch"); }
+
+int ecsimd_x25519_from_ed25519_pk(ecsimd_hip_ctx* ctx, const uint8_t* pk, uint8_t* u, uint8_t* ok, size_t n) {
+  REQUIRE_CTX(); if ((!pk || !u || !ok) && n) return bad(ctx, "x25519_from_ed25519_pk: pk, u or ok is null");
+  if (n != 0 && any_alias({u, ok}, {pk})) return bad(ctx, "x25519_from_ed25519_pk: u and ok must not alias an input or each other");
+  ENTER_ANY_SIZE();
+  FOR_CHUNKS(first, m, n, X25519_CHUNK) launch::x25519_from_ed_pk(ctx->stream, pk + 32 * first, u + 32 * first, ok + first, m);
+  const hipError_t err = hipGetLastError();
+  return err == hipSuccess ? ECSIMD_HIP_OK : fail(ctx, err, "x25519_from_ed25519_pk launch"); }
+
+int ecsimd_x25519_from_ed25519_seed(ecsimd_hip_ctx* ctx, const uint8_t* seed, uint8_t* scalar, size_t n) {
+  REQUIRE_CTX(); if ((!seed || !scalar) && n) return bad(ctx, "x25519_from_ed25519_seed: seed or scalar is null");
+  if (n != 0 && overlaps(seed, scalar)) return bad(ctx, "x25519_from_ed25519_seed: scalar must not alias seed");
+  ENTER_ANY_SIZE();
+  FOR_CHUNKS(first, m, n, X25519_CHUNK) launch::x25519_from_ed_seed(ctx->stream, seed + 32 * first, scalar + 32 * first, m);
+  const hipError_t err = hipGetLastError();
+  return err == hipSuccess ? ECSIMD_HIP_OK : fail(ctx, err, "x25519_from_ed25519_seed launch"); }
+
+int ecsimd_x25519_raw_inputs(int op) { return (op < 0 || op > launch::X25519_RAW_ED_TO_MONT) ? 0 : launch::x25519_raw_inputs(op); }
+int ecsimd_x25519_raw_outputs(int op) { return (op < 0 || op > launch::X25519_RAW_ED_TO_MONT) ? 0 : launch::x25519_raw_outputs(op); }
+int ecsimd_x25519_raw(ecsimd_hip_ctx* ctx, int op, const uint8_t* in, uint8_t* out, size_t n) {
+  REQUIRE_CTX(); if ((!in || !out) && n) return bad(ctx, "x25519_raw: null pointer");
+  if (op < 0 || op > launch::X25519_RAW_ED_TO_MONT) return bad(ctx, "x25519_raw: unknown function");
+  if (n != 0 && overlaps(in, out)) return bad(ctx, "x25519_raw: out must not alias in");
+  ENTER_ANY_SIZE();
+  const size_t ni = launch::x25519_raw_inputs(op), no = launch::x25519_raw_outputs(op);
+  FOR_CHUNKS(first, m, n, X25519_CHUNK) launch::x25519_raw(ctx->stream, op, in + 32 * ni * first, out + 32 * no * first, m);
+  const hipError_t e = hipGetLastError();
+  return e == hipSuccess ? ECSIMD_HIP_OK : fail(ctx, e, "x25519_raw launch"); }
 
 int ecsimd_hip_fe29_raw(ecsimd_hip_ctx* ctx, int curve, int op, const int32_t* in, int32_t* out, size_t n, int swap) {
   REQUIRE_CTX(); if ((!in || !out) && n) return bad(ctx, "fe29_raw: null pointer");

@@ -223,6 +223,20 @@ void ed25519_verify_front(hipStream_t, const gmod& L, const uint8_t* pk, const u
 void ed25519_verify_loop(hipStream_t, const uint64_t* s, const uint64_t* h, const void* table, const uint8_t* valid, const uint8_t* sig, uint8_t* ok, size_t n);
 void ed25519_raw(hipStream_t, const gmod& L, int op, const uint8_t* in, uint8_t* out, void* table, size_t n);
 
+// k_x25519.hip: X25519 (RFC 7748) and the Ed25519 key conversions.  Every array is n records of 32 little-endian bytes at any alignment; nothing uses a
+// workspace.  SECRET (selects only): x25519 writes X25519(scalar, u) (clamped scalar, bit 255 of u dropped, 0 at infinity) and, where ok is given, ok = the
+// output is not all zero; x25519_base X25519(scalar, 9) through the comb over the multiples of B (L = the group order's gmod); x25519_from_ed_seed the clamped
+// low half of SHA-512(seed).  PUBLIC: x25519_from_ed_pk writes u = (1 + y) / (1 - y) and ok = the key decodes strictly and is no small-order encoding
+// (u = 0 where not).  x25519_raw: one function of the layers on 32-byte records.
+enum x25519_raw_op { X25519_RAW_FE_MUL_SMALL = 0, X25519_RAW_LADDER = 1, X25519_RAW_ED_TO_MONT = 2 };
+constexpr int x25519_raw_inputs(int op) { return op == X25519_RAW_LADDER ? 2 : 1; }
+constexpr int x25519_raw_outputs(int op) { return op == X25519_RAW_ED_TO_MONT ? 2 : 1; }
+void x25519(hipStream_t, const uint8_t* scalar, const uint8_t* u, uint8_t* out, uint8_t* ok, size_t n);
+void x25519_base(hipStream_t, const gmod& L, const uint8_t* scalar, uint8_t* out, size_t n);
+void x25519_from_ed_pk(hipStream_t, const uint8_t* pk, uint8_t* u, uint8_t* ok, size_t n);
+void x25519_from_ed_seed(hipStream_t, const uint8_t* seed, uint8_t* scalar, size_t n);
+void x25519_raw(hipStream_t, int op, const uint8_t* in, uint8_t* out, size_t n);
+
 // k_point_<curve>.hip
 void from_affine(hipStream_t, int curve, const uint64_t* x, const uint64_t* y, uint64_t* jx, uint64_t* jy, uint64_t* jz, size_t n);
 void to_affine(hipStream_t, int curve, const uint64_t* jx, const uint64_t* jy, const uint64_t* jz, uint64_t* x, uint64_t* y, size_t n);

@@ -521,6 +521,59 @@ class Engine:
         self._check(self.lib.ecsimd_ed25519_raw(self.ctx, C.c_int(op), ip, C.c_void_p(out.data_ptr()), C.c_size_t(n)), "ed25519_raw")
         return out
 
+    # ---- X25519 (include/ecsimd_x25519.h): scalars, u-coordinates and shared secrets are 32-byte little-endian records
+    def _u8_out(self, n, width=32):
+        return self.torch.empty((n, width), dtype=self.torch.uint8, device=self.tdev)
+
+    def x25519(self, scalars, us, want_ok=False):
+        """ecsimd_x25519: the (n, 32) uint8 shared secrets X25519(scalar, u) of the SECRET (n, 32) uint8 scalars and the peers' (n, 32) uint8 u (RFC 7748
+        section 5: clamped scalar, bit 255 of u ignored, zeros at infinity).  want_ok: (out, ok), ok one byte per lane, 0 where the output is all zero."""
+        sp, n = self._rows_u8(scalars, 32, "scalars")
+        up, n2 = self._rows_u8(us, 32, "us")
+        if n2 != n:
+            raise EcsimdHipError(f"x25519: operands disagree on the batch length: {sorted((n, n2))}")
+        out = self._u8_out(n)
+        ok = self.flags(n) if want_ok else None
+        self._bind_stream()
+        self._check(self.lib.ecsimd_x25519(self.ctx, sp, up, C.c_void_p(out.data_ptr()), C.c_void_p(ok.data_ptr() if want_ok else 0), C.c_size_t(n)), "x25519")
+        return (out, ok) if want_ok else out
+
+    def x25519_base(self, scalars):
+        """ecsimd_x25519_base: the (n, 32) uint8 public keys X25519(scalar, 9) of the SECRET (n, 32) uint8 private keys."""
+        sp, n = self._rows_u8(scalars, 32, "scalars")
+        out = self._u8_out(n)
+        self._bind_stream()
+        self._check(self.lib.ecsimd_x25519_base(self.ctx, sp, C.c_void_p(out.data_ptr()), C.c_size_t(n)), "x25519_base")
+        return out
+
+    def x25519_from_ed25519_pk(self, pk):
+        """ecsimd_x25519_from_ed25519_pk: (u, ok), the X25519 public keys of (n, 32) uint8 Ed25519 public keys; ok is 0 (and u zero) where a key does not
+        decode strictly or is a small-order encoding.  Public data only; no prime-subgroup check."""
+        pp, n = self._rows_u8(pk, 32, "pk")
+        u, ok = self._u8_out(n), self.flags(n)
+        self._bind_stream()
+        self._check(self.lib.ecsimd_x25519_from_ed25519_pk(self.ctx, pp, C.c_void_p(u.data_ptr()), C.c_void_p(ok.data_ptr()), C.c_size_t(n)), "x25519_from_ed25519_pk")
+        return u, ok
+
+    def x25519_from_ed25519_seed(self, seeds):
+        """ecsimd_x25519_from_ed25519_seed: the (n, 32) uint8 X25519 private keys of the SECRET (n, 32) uint8 Ed25519 seeds (the clamped low half of SHA-512)."""
+        sp, n = self._rows_u8(seeds, 32, "seeds")
+        out = self._u8_out(n)
+        self._bind_stream()
+        self._check(self.lib.ecsimd_x25519_from_ed25519_seed(self.ctx, sp, C.c_void_p(out.data_ptr()), C.c_size_t(n)), "x25519_from_ed25519_seed")
+        return out
+
+    def x25519_raw(self, op, records):
+        """ecsimd_x25519_raw: one function of the layers below on (n, 32 * inputs) uint8 records; returns (n, 32 * outputs) uint8 (see the header's table)."""
+        ni, no = int(self.lib.ecsimd_x25519_raw_inputs(C.c_int(op))), int(self.lib.ecsimd_x25519_raw_outputs(C.c_int(op)))
+        if ni == 0:
+            raise EcsimdHipError(f"x25519_raw: unknown function {op}")
+        ip, n = self._rows_u8(records, 32 * ni, "records")
+        out = self._u8_out(n, 32 * no)
+        self._bind_stream()
+        self._check(self.lib.ecsimd_x25519_raw(self.ctx, C.c_int(op), ip, C.c_void_p(out.data_ptr()), C.c_size_t(n)), "x25519_raw")
+        return out
+
     def _lens_ptr(self, what, lens, n):
         """The pointer of an optional int32 / uint32 device tensor of n lengths (None: NULL), as ecsimd_hip_keccak256 and the *_lens calls take it."""
         if lens is None:
