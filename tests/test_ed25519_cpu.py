@@ -1,6 +1,7 @@
 """Ed25519, the part that needs no GPU: the entry points are declared in a header of their own, exported beside (not among) the ecsimd_hip_* set, and callable
 from C99; the host model the GPU tests take their expected values from (tools/ed25519_model.py) gives the fixture bit for bit, rejects every one-bit change
-of each known answer and the rule set's edge encodings, and agrees with libcrypto where libcrypto loads; the new kernels exist in the shipped gfx950 listing,
+of each known answer and the rule set's edge encodings, and agrees with libcrypto where libcrypto loads; tests/golden/ed25519_verdicts.json (refused and
+accepted lanes of every kind, keys and R with a small-order component among them) is reproduced by the model and by libcrypto, record for record; the new kernels exist in the shipped gfx950 listing,
 the secret ones without scratch memory or LDS; those keep the seed, a, r and the products out of every branch condition, address and lane mask
 (tools/ct_check.py check_secret_flow), and the analysis refuses a planted branch on one bit of a; the host functions wipe through wipe_workspace over their
 own carve's total."""
@@ -182,6 +183,78 @@ def test_the_model_refuses_the_edge_encodings():
         assert pt is not None and model.encode(pt) == e and model.pt_eq(model.pt_mul(8, pt), model.IDENTITY)
     assert model.sc_reduce(le32(L) + bytes(32)) == 0 and model.base_mult(L) == ident and model.base_mult(1) == le32(model.BY)
     assert model.expand(bytes(32))[0] % 8 == 0 and model.expand(bytes(32))[0] >> 254 == 1
+
+
+# ---- the verdict fixture
+def verdict_records():
+    return json.load(open(model.VERDICTS_PATH))["records"]
+
+
+def test_the_model_reproduces_every_verdict_of_the_fixture():
+    recs = verdict_records()
+    golden = os.path.dirname(model.VERDICTS_PATH)
+    assert 1000 <= len(recs) <= 1500                                                                  # one batch on the device
+    assert os.path.getsize(model.VERDICTS_PATH) < max(os.path.getsize(os.path.join(golden, f)) for f in os.listdir(golden) if f != os.path.basename(model.VERDICTS_PATH))
+    for r in recs:
+        pk, msg, sig = bytes.fromhex(r["public_key"]), bytes.fromhex(r["message"]), bytes.fromhex(r["signature"])
+        assert len(msg) <= 16 and len(pk) == 32 and len(sig) == 64
+        assert int(model.verify(pk, msg, sig)) == r["model"], r
+        assert int(model.verify(pk, msg, sig, True)) == r["model_strict"], r
+
+
+def test_libcrypto_reproduces_every_verdict_of_the_fixture():
+    ossl = model.libcrypto()
+    if ossl is None:
+        return                                                                                        # (the comparison exists only where libcrypto loads)
+    for r in verdict_records():
+        assert int(ossl.verify(bytes.fromhex(r["public_key"]), bytes.fromhex(r["message"]), bytes.fromhex(r["signature"]))) == r["libcrypto"], r
+
+
+def test_the_fixtures_classes_divergences_and_mixed_order_predicate():
+    recs = verdict_records()
+    kinds = model.check_verdicts(recs)                                                                # model == libcrypto off the divergent kind, both verdicts per class
+    divergent = [r for r in recs if r.get("divergent")]
+    assert [r["kind"] for r in divergent] == [model.DIVERGENT_KIND] * 2 == [r["kind"] for r in recs if r["kind"] == model.DIVERGENT_KIND]
+    assert all((r["libcrypto"], r["model"], r["model_strict"]) == (1, 0, 0) for r in divergent)       # the header's stated difference, and nothing else
+    assert all(r["libcrypto"] == r["model"] for r in recs if not r.get("divergent"))
+    assert kinds["small order"] == 512 and sum(r["model"] for r in recs if r["kind"] == "small order") == 60
+    # the classes (order of t_a, order of t_r), counted here without check_verdicts: accepted and refused
+    count = {}
+    for r in recs:
+        if r["kind"] in model.MIXED_KINDS:
+            count.setdefault(tuple(r["orders"]), [0, 0])[r["model"]] += 1
+            assert r["model"] == r["holds"] == r["libcrypto"] == r["model_strict"], r
+    assert set(count) == {(a, b) for a in (1, 2, 4, 8) for b in (1, 2, 4, 8)} - {(1, 1)}
+    for (a, b), (refused, accepted) in count.items():
+        assert refused >= 8 and (accepted >= 8 if a % b == 0 else accepted == 0), (a, b, refused, accepted)
+    # the predicate from the parts, on torsion points alone: t_r + [h]t_a = O has a solution exactly where the order of t_r divides that of t_a
+    tors = model.torsion()
+    assert [n for _, _, n in tors] == [1, 2, 4, 4, 8, 8, 8, 8]
+    for _, ta, na in tors:
+        for _, tr, nr in tors:
+            assert any(model.pt_eq(model.pt_add(tr, model.pt_mul(h, ta)), model.IDENTITY) for h in range(8)) == (na % nr == 0)
+    # a mixed-order key is no small-order encoding, decodes, and has order 8 L at most: [L]A is the torsion part times L mod 8 = 5
+    rng = random.Random(8)
+    for _, t, n in tors[1:]:
+        a = rng.randrange(1, L)
+        pt = model.mixed(model.base_point_mul(a), t)
+        enc = model.encode(pt)
+        assert enc not in model.SMALL_ORDER and model.pt_eq(model.decode(enc), pt)
+        assert model.pt_eq(model.pt_mul(L, pt), model.pt_mul(5, t)) and not model.pt_eq(model.pt_mul(L, pt), model.IDENTITY)
+        assert model.pt_eq(model.pt_mul(8 * L, pt), model.IDENTITY)
+
+
+def test_sign_mixed_states_the_verdict_the_model_and_libcrypto_reach():
+    ossl = model.libcrypto()
+    tors = model.torsion()
+    rng = random.Random(2280)
+    seen = set()
+    for j in range(48):
+        (_, ta, na), (_, tr, nr) = tors[rng.randrange(8)], tors[rng.randrange(8)]
+        pk, sig, holds = model.sign_mixed(rng.randrange(1, L), rng.randrange(1, L), ta, tr, b"%d" % j)
+        assert model.verify(pk, b"%d" % j, sig) == holds and (ossl is None or ossl.verify(pk, b"%d" % j, sig) == holds), (j, na, nr)
+        seen.add(holds)
+    assert seen == {True, False}
 
 
 def test_the_small_order_words_in_the_device_source_are_the_models():

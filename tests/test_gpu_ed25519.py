@@ -1,7 +1,10 @@
 """GPU suite for Ed25519 (include/ecsimd_ed25519.h).  Every expected value comes from tools/ed25519_model.py (plain Python integers, hashlib) or from
 tests/golden/ed25519_vectors.json (RFC 8032 7.1 TEST 1-3 and records minted from libcrypto).  Layer by layer through ecsimd_ed25519_raw -- the field against
 Python integers AND against Engine.mod_mul etc. on register_modulus(2^255 - 19), a second device path that shares no code with fe25519.cuh --, then the three
-calls: the fixture bit for bit, the padding boundaries of both hashes, unaligned arrays, the chunk boundary, graph replay, and the wiped workspace."""
+calls: the fixture bit for bit, the padding boundaries of both hashes, unaligned arrays, the chunk boundary, graph replay, and the wiped workspace.
+tests/golden/ed25519_verdicts.json carries the verdict of every refused and accepted kind of lane as libcrypto and the model gave it when the file was minted
+(tests/test_ed25519_cpu.py holds both to it): the tests that read it run no model on the host.  Points with a small-order component -- [k]B + T -- go
+through every layer and through verification, where the cofactorless equation is decided by (h mod L) mod 8."""
 import ctypes as C
 import functools
 import json
@@ -33,6 +36,17 @@ def dev_rows(engine, rows, width):
     import torch
     a = np.frombuffer(b"".join(rows), dtype=np.uint8).reshape(len(rows), width).copy()
     return torch.from_numpy(a).to(engine.tdev)
+
+
+def at_offset(engine, rows, width, offset):
+    """rows as an (n, width) device view `offset` bytes into its allocation"""
+    import torch
+    n = len(rows)
+    buf = torch.zeros(width * n + 8, dtype=torch.uint8, device=engine.tdev)
+    view = buf[offset:offset + width * n].view(n, width)
+    view.copy_(dev_rows(engine, rows, width))
+    assert view.data_ptr() % 4 == offset % 4
+    return view
 
 
 def host_rows(t):
@@ -190,6 +204,71 @@ def test_double_multiplication(engine):
     assert raw(engine, "DOUBLE_MULT", [le32(1)], [le32(1)], [le32(2)]) == [[ZERO32, le32(0)]]
 
 
+# ---- points outside the prime-order subgroup: [k]B + T, T one of the seven non-zero torsion points
+@functools.lru_cache(maxsize=None)
+def mixed_points():
+    """8 prime-order points times the 7 torsion points: (k, index of T, the point [k]B + T)"""
+    rng = random.Random(56)
+    tors = model.torsion()
+    ks = [rng.randrange(1, L) for _ in range(8)]
+    return tuple((k, j, model.mixed(model.base_point_mul(k), tors[j][1])) for k in ks for j in range(1, 8))
+
+
+def from_parts(k, t):
+    """the encoding of [k]B + t"""
+    return model.encode(model.pt_add(model.base_point_mul(k), t))
+
+
+def test_mixed_order_points_decode_add_and_double(engine):
+    tors = model.torsion()
+    mp = mixed_points()
+    enc = [model.encode(m) for _, _, m in mp]
+    assert len(set(enc)) == 56 and not set(enc) & set(model.SMALL_ORDER)
+    assert raw(engine, "DECODE_ENCODE", enc) == [[e, le32(1)] for e in enc]
+    rng = random.Random(57)
+    a, b, want = [], [], []
+    for i, (k, j, m) in enumerate(mp):
+        k2 = rng.randrange(1, L)                                                                    # mixed + prime order
+        a.append(enc[i]); b.append(model.base_mult(k2)); want.append(from_parts(k + k2, tors[j][1]))
+        k3, j3, m3 = mp[(i + 9) % 56]                                                               # mixed + mixed: another k, another T
+        a.append(enc[i]); b.append(enc[(i + 9) % 56]); want.append(from_parts(k + k3, model.pt_add(tors[j][1], tors[j3][1])))
+        a.append(enc[i]); b.append(enc[i]); want.append(from_parts(2 * k, model.pt_dbl(tors[j][1])))  # mixed + itself, by the unified addition
+        a.append(enc[i]); b.append(model.encode(model.pt_neg(m))); want.append(le32(1))             # mixed + its negative
+        for e, t, _ in tors:                                                                        # mixed + torsion: -T among them, which leaves [k]B
+            a.append(enc[i]); b.append(e); want.append(from_parts(k, model.pt_add(tors[j][1], t)))
+            a.append(e); b.append(enc[i]); want.append(want[-1])
+    out = raw(engine, "POINT_ADD", a, b)
+    for x, y, w, o in zip(a, b, want, out):
+        assert o == [w, le32(1)], (x.hex(), y.hex())
+    assert want == [model.encode(model.pt_add(model.decode(x), model.decode(y))) for x, y in zip(a, b)]      # the parts and the points agree on the host
+    assert all(want[20 * i:20 * i + 20].count(model.base_mult(k)) == 2 for i, (k, _, _) in enumerate(mp))    # adding -T, from either side, leaves [k]B
+    out = raw(engine, "POINT_DBL", enc)
+    for (k, j, m), o in zip(mp, out):
+        assert o == [from_parts(2 * k, model.pt_dbl(tors[j][1])), le32(1)] and o[0] == model.encode(model.pt_dbl(m)), (k, j)
+
+
+def test_double_multiplication_with_a_mixed_order_point(engine):
+    """[s]B + [h mod L]([k]B + T) = [s + (h mod L) k]B + [(h mod L) mod 8]T: the expected value is made from the parts, the torsion part by the residue alone."""
+    tors = model.torsion()
+    rng = random.Random(58)
+    cases = []
+    for k, j, m in mixed_points():
+        e = model.encode(m)
+        sh = [(rng.randrange(L), (rng.randrange(L - 8) & ~7) + r) for r in range(8)]               # h congruent to each residue modulo 8
+        sh += [(0, rng.randrange(1, L)), (rng.randrange(L), 8), (rng.randrange(L), L - 8)]         # s = 0; the table's last entry, [8]P, and its negative's residue
+        sh += [(rng.randrange(L), int("7" * 40 + "8", 16)), (rng.randrange(L), int("7" * 62, 16))]  # 41 digits of -8; 62 digits of 7: both ends of the digit range
+        sh += [(L + rng.randrange(L), L + rng.randrange(L)), (2**256 - 1, 2**256 - 1), (rng.randrange(15 * L, 2**256), rng.randrange(15 * L, 2**256)),
+               (rng.randrange(L), L)]                                                              # scalars in [L, 2^256); h = L is h = 0
+        cases += [(s, h, e, k, j) for s, h in sh]
+    assert len(cases) == 56 * 17 and {c[1] % L % 8 for c in cases} == set(range(8))
+    out = raw(engine, "DOUBLE_MULT", [le32(c[0]) for c in cases], [le32(c[1]) for c in cases], [c[2] for c in cases])
+    for (s, h, e, k, j), o in zip(cases, out):
+        hr = h % L
+        assert o == [from_parts(s + hr * k, model.pt_mul(hr % 8, tors[j][1])), le32(1)], (s, h, e.hex())
+    for c, o in list(zip(cases, out))[::41]:                                                        # ... and the model's plain double-and-add on the point itself
+        assert o[0] == model.double_mult(c[0], c[1], c[2]), c[:3]
+
+
 # ---- pubkey and sign
 def sign_on_device(engine, seeds, msgs, stride=None, lens=False, want_pk=True, offset=0):
     """Signs msgs (a list of byte strings) with seeds; with lens the rows are `stride` wide and the lengths travel per lane; offset: the byte offset of the
@@ -245,6 +324,31 @@ def test_batch_sizes(engine, n):
     assert sig == [w[0] for w in want] and pk == [w[1] for w in want]
     assert host_rows(engine.ed25519_pubkey(st)) == pk
     assert engine.ed25519_verify(dev_rows(engine, pk, 32), mt, dev_rows(engine, sig, 64), lens=lt).cpu().tolist() == [1] * n
+
+
+@functools.lru_cache(maxsize=None)
+def every_length():
+    """(seeds, messages, the model's (signature, public key)) for the lengths 0 .. 272, one lane each, 16 seeds in turn: both heads' block boundaries (the
+    32-byte head's at 79 / 80, 207 / 208, the 64-byte head's at 47 / 48, 175 / 176), the word boundaries between them, and one block more."""
+    rng = random.Random(272)
+    pool = [rng.randbytes(32) for _ in range(16)]
+    seeds = tuple(pool[i % 16] for i in range(273))
+    msgs = tuple(rng.randbytes(i) for i in range(273))
+    return seeds, msgs, tuple(model_sign(s, m) for s, m in zip(seeds, msgs))
+
+
+@pytest.mark.parametrize("stride,offset", [(272, 0), (273, 1)])
+def test_every_message_length_up_to_272_in_one_batch(engine, stride, offset):
+    import torch
+    seeds, msgs, want = every_length()
+    sig, pk, (st, mt, lt) = sign_on_device(engine, list(seeds), list(msgs), stride=stride, lens=True, offset=offset)
+    assert mt.data_ptr() % 4 == offset and lt.cpu().tolist() == list(range(273))
+    wrong = [i for i in range(273) if (sig[i], pk[i]) != want[i]]
+    assert not wrong, wrong
+    gt, kt = at_offset(engine, sig, 64, offset), at_offset(engine, pk, 32, offset)
+    assert engine.ed25519_verify(kt, mt, gt, lens=lt).cpu().tolist() == [1] * 273
+    # one byte fewer is another message: every lane but the empty one is refused (the length is read per lane, exactly)
+    assert engine.ed25519_verify(kt, mt, gt, lens=torch.clamp(lt - 1, min=0)).cpu().tolist() == [1] + [0] * 272
 
 
 # ---- verify
@@ -306,6 +410,44 @@ def test_one_batch_of_every_kind_in_both_flag_settings(engine):
             assert by_kind[k] == {0}, k
         assert by_kind["small order"] == ({0} if strict else {0, 1})                                  # the default rule set accepts the ones whose equation holds
     assert model.verify(model.SMALL_ORDER[0], b"anything", model.SMALL_ORDER[0] + le32(0)) and not model.verify(model.SMALL_ORDER[0], b"anything", model.SMALL_ORDER[0] + le32(0), True)
+
+
+# ---- the verdict fixture: what libcrypto and the model said of every lane when it was minted; no model runs here
+@functools.lru_cache(maxsize=None)
+def verdicts():
+    return tuple(json.load(open(model.VERDICTS_PATH))["records"])
+
+
+@pytest.mark.parametrize("stride,offset", [(16, 0), (17, 1)])
+def test_the_verdict_fixture_in_one_batch_in_both_flag_settings(engine, stride, offset):
+    """offset 1, stride 17: the keys, the signatures, the messages and the verdicts all start at an odd address (the lengths stay word aligned, as the
+    header asks), and the messages' rows fall on every residue modulo 4."""
+    import torch
+    recs = verdicts()
+    n = len(recs)
+    assert 1000 <= n <= 1500
+    msgs = [bytes.fromhex(r["message"]) for r in recs]
+    assert max(len(m) for m in msgs) == 16 and min(len(m) for m in msgs) == 0
+    pk = at_offset(engine, [bytes.fromhex(r["public_key"]) for r in recs], 32, offset)
+    sig = at_offset(engine, [bytes.fromhex(r["signature"]) for r in recs], 64, offset)
+    mt = at_offset(engine, padded(msgs, stride), stride, offset)
+    lens = torch.tensor([len(m) for m in msgs], dtype=torch.int32, device=engine.tdev)
+    for flags, column in ((0, "model"), (1, "model_strict")):
+        buf = torch.full((n + 8,), 0xA5, dtype=torch.uint8, device=engine.tdev)
+        ok = buf[offset:offset + n]
+        engine._bind_stream()
+        engine._check(engine.lib.ecsimd_ed25519_verify(engine.ctx, C.c_void_p(pk.data_ptr()), C.c_void_p(mt.data_ptr()), C.c_size_t(stride), C.c_size_t(stride),
+                                                      C.c_void_p(lens.data_ptr()), C.c_void_p(sig.data_ptr()), C.c_void_p(ok.data_ptr()), C.c_size_t(n), C.c_int(flags)),
+                      "ed25519_verify")
+        got = ok.cpu().tolist()
+        wrong = [(i, recs[i]["kind"], recs[i].get("orders"), got[i]) for i in range(n) if got[i] != recs[i][column]]
+        assert not wrong, (column, len(wrong), wrong[:10])
+        assert set(buf[:offset].cpu().tolist()) <= {0xA5} and set(buf[offset + n:].cpu().tolist()) == {0xA5}      # nothing outside the n verdicts was written
+        if flags == 0:
+            assert all(g == r["libcrypto"] for g, r in zip(got, recs) if not r.get("divergent"))                  # libcrypto's verdict, where the header claims it
+            assert [r["kind"] for g, r in zip(got, recs) if g != r["libcrypto"]] == [model.DIVERGENT_KIND] * 2
+        for kind in model.MIXED_KINDS[::2] + ("small order",) * (1 - flags):
+            assert {g for g, r in zip(got, recs) if r["kind"] == kind} == {0, 1}, kind                            # both verdicts came out of the device
 
 
 def test_one_launch_sequence_across_the_chunk_boundary(engine):

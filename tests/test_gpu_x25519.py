@@ -1,7 +1,7 @@
 """GPU suite for X25519 (include/ecsimd_x25519.h).  Every expected value comes from tools/x25519_model.py (plain Python integers; its Edwards route from
 tools/ed25519_model.py) or from tests/golden/x25519_vectors.json (RFC 7748 5.2 and 6.1 and records minted from libcrypto).  Layer by layer through
 ecsimd_x25519_raw, then the four calls: the fixture bit for bit, RFC 7748's 1000-fold iteration, unaligned arrays, the small-order and non-canonical u, both
-routes to a public key against each other, the chunk boundary, graph capture on a fresh context, and the untouched workspace."""
+routes to a public key against each other, Ed25519 keys with a small-order component, the chunk boundary, graph capture on a fresh context, and the untouched workspace."""
 import ctypes as C
 import functools
 import json
@@ -226,6 +226,38 @@ def test_both_conversions_and_the_seed_pk_property(engine):
     u, ok = engine.x25519_from_ed25519_pk(dev_rows(engine, keys, 32, 1))
     assert ok.cpu().tolist() == [0] * len(bad) + [1] * 5
     assert host_rows(u) == [model.from_ed25519_pk(e)[0] for e in keys] and host_rows(u)[:len(bad)] == [ZERO32] * len(bad)
+
+
+def test_ed25519_keys_with_a_small_order_component(engine):
+    """A + T for 8 prime-order A = [a]B and the 7 non-zero torsion points T.  Every expected value is made on the Edwards curve and mapped by
+    u = (1 + y) / (1 - y): the conversion checks no subgroup, the raw ladder sees the torsion, and the clamp (a multiple of 8) removes it."""
+    rng = random.Random(56)
+    tors = ed.torsion()
+    keys = model.mixed_keys([rng.randrange(1, L) for _ in range(8)])
+    encs = [ed.encode(m) for _, _, _, m in keys]
+    u_mixed = [model.u_of_encoding(e) for e in encs]
+    u_pure = [model.u_of_encoding(ed.encode(pt)) for _, _, pt, _ in keys]
+    assert len(keys) == 56 and not set(encs) & set(ed.SMALL_ORDER) and all(x != y for x, y in zip(u_mixed, u_pure))
+    u, ok = engine.x25519_from_ed25519_pk(dev_rows(engine, encs))
+    assert ok.cpu().tolist() == [1] * 56
+    assert host_rows(u) == [le32(x) for x in u_mixed] == [model.from_ed25519_pk(e)[0] for e in encs]
+    # x25519 under 16 scalars: the same shared secret as the prime-order key's, [clamp(k) a]B on the Edwards curve
+    ks = [rng.randbytes(32) for _ in range(16)]
+    assert all(any(k[0] >> bit & 1 for k in ks) for bit in range(3))                                # the clamp has each of the three bits to clear
+    lanes = [(k, i) for i in range(56) for k in ks]
+    shared = {(k, a): le32(model.edwards_base(model.clamp(int.from_bytes(k, "little")) * a)) for k in ks for a in {key[0] for key in keys}}
+    want = [shared[(k, keys[i][0])] for k, i in lanes]
+    got_mixed, ok_mixed = run_x25519(engine, [k for k, _ in lanes], [le32(u_mixed[i]) for _, i in lanes])
+    got_pure, ok_pure = run_x25519(engine, [k for k, _ in lanes], [le32(u_pure[i]) for _, i in lanes])
+    assert got_mixed == want and got_pure == want and ok_mixed == ok_pure == [1] * len(lanes)
+    assert got_mixed[:32] == [model_x25519(k, le32(u_mixed[i])) for k, i in lanes[:32]]               # ... and the ladder model's
+    # the ladder itself, unclamped: k = 1 gives u back; k = L + 1 (6 modulo 8) leaves A + [6]T, which is A only where T has order 2
+    one = raw(engine, "LADDER", [le32(1)] * 112, [le32(x) for x in u_mixed + u_pure])
+    assert [int.from_bytes(o[0], "little") for o in one] == u_mixed + u_pure
+    more = [int.from_bytes(o[0], "little") for o in raw(engine, "LADDER", [le32(L + 1)] * 112, [le32(x) for x in u_mixed + u_pure])]
+    assert more[56:] == u_pure
+    assert more[:56] == [model.ed_point_to_u(ed.pt_add(pt, ed.pt_mul((L + 1) % 8, tors[j][1]))) for _, j, pt, _ in keys]
+    assert [x != y for x, y in zip(more[:56], more[56:])] == [tors[j][2] != 2 for _, j, _, _ in keys]
 
 
 # ---- the chunk boundary

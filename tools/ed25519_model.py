@@ -9,6 +9,8 @@ The rule set is the one include/ecsimd_ed25519.h states:
 Points are in extended coordinates (X, Y, Z, T) with the formulas of ed25519.cuh, so a few hundred lanes take seconds.
 
   python tools/ed25519_model.py --mint    writes tests/golden/ed25519_vectors.json (RFC 8032 7.1 TEST 1-3 and records minted from libcrypto)
+  python tools/ed25519_model.py --mint-verdicts   writes tests/golden/ed25519_verdicts.json (refused and accepted lanes of every kind, mixed-order keys
+                                                  among them, each adjudicated by libcrypto; refuses to write where libcrypto and this model differ)
   python tools/ed25519_model.py --table   writes ecsimd_amd/csrc/ed25519_base.inc (the comb's multiples of B and the field constants)
 """
 import hashlib
@@ -265,6 +267,243 @@ def mint(path):
     return len(cases)
 
 
+# ---- points outside the prime-order subgroup
+def order_of(pt):
+    """The order of a point of the torsion subgroup: 1, 2, 4 or 8."""
+    for n in (1, 2, 4, 8):
+        if pt_eq(pt_mul(n, pt), IDENTITY):
+            return n
+    raise ValueError("not a torsion point")
+
+
+def torsion():
+    """((encoding, point, order), ...) for the eight encodings of SMALL_ORDER, in that order: the identity first."""
+    return tuple((e, decode(e), order_of(decode(e))) for e in SMALL_ORDER)
+
+
+def mixed(point, tors):
+    """point + tors: with point in the prime-order subgroup and tors a non-zero torsion point, a point of order 2 L, 4 L or 8 L."""
+    return pt_add(point, tors)
+
+
+def sign_mixed(a, r, t_a, t_r, msg):
+    """(pk, sig, holds) for A = [a]B + t_a, R = [r]B + t_r, s = r + h a with h = SHA-512(R || A || M) mod L.  [s]B - [h]A = [r]B - [h]t_a, so the
+    cofactorless equation holds iff t_r + [h]t_a is the identity: `holds`, computed from the torsion parts alone, h reduced modulo L first."""
+    pk = encode(mixed(base_point_mul(a), t_a))
+    rb = encode(mixed(base_point_mul(r), t_r))
+    h = sc_reduce(hashlib.sha512(rb + pk + msg).digest())
+    return pk, rb + ((r + h * a) % L).to_bytes(32, "little"), pt_eq(pt_add(t_r, pt_mul(h, t_a)), IDENTITY)
+
+
+# ---- the verdict fixture: refused and accepted lanes of every kind, each adjudicated by libcrypto
+VERDICTS_PATH = os.path.join(ROOT, "tests", "golden", "ed25519_verdicts.json")
+DIVERGENT_KIND = "A non-canonical"
+MIXED_KINDS = ("mixed A, honest R", "honest A, mixed R", "mixed A, mixed R")
+MIXED_MINIMUM = 8          # accepted and refused lanes per class (order of t_a, order of t_r) that can accept; refused lanes per class that cannot
+
+
+def refused_encodings():
+    """Encodings of A that strict decoding refuses: y = p .. p + 18, x = 0 with the sign bit set, y without a point.  (Under a signature made for another
+    key libcrypto refuses them all as well; p + 1 and 01 00 .. 00 80, which it reads as the identity, part from this rule set in the kind DIVERGENT_KIND.)"""
+    le = lambda v: v.to_bytes(32, "little")
+    out = [le(P + i) for i in range(19)] + [le(1 | (1 << 255)), le((P - 1) | (1 << 255)), le(2), le(2 | (1 << 255)), le(7), le((1 << 255) - 1), bytes([0xff]) * 32]
+    assert all(decode(e) is None for e in out)
+    return out
+
+
+def _tag(text, *numbers):
+    return (text + "".join(" %d" % n for n in numbers)).encode()
+
+
+def _scalar(text, *numbers):
+    return sc_reduce(hashlib.sha512(_tag(text, *numbers)).digest())
+
+
+def _message(text, *numbers, length):
+    return hashlib.shake_128(_tag(text, *numbers)).digest(length)
+
+
+def can_accept(order_a, order_r):
+    """t_r + [h]t_a = O has a solution h iff t_r lies in the group t_a generates; the torsion subgroup is cyclic of order 8, so iff order_r divides order_a."""
+    return order_a % order_r == 0
+
+
+def verdict_lanes():
+    """[(kind, pk, msg, sig, extra)], extra = {} or what the mixed-order records carry: orders = [order of t_a, order of t_r] and holds, the predicate of
+    sign_mixed.  Messages are at most 16 bytes; seeds, nonces and messages come from fixed strings."""
+    le = lambda v: int(v).to_bytes(32, "little")
+    flip = lambda b, bit: (int.from_bytes(b, "little") ^ (1 << bit)).to_bytes(len(b), "little")
+    lanes = []
+    add = lambda kind, pk, msg, sig, **extra: lanes.append((kind, pk, msg, sig, extra))
+    # -- every length 0 .. 16, valid
+    signed = []
+    for length in range(17):
+        seed = hashlib.sha256(_tag("ed25519 verdict seed", length)).digest()
+        msg = _message("ed25519 verdict message", length, length=length)
+        sig, pk = sign(seed, msg)
+        signed.append((pk, msg, sig))
+        add("valid", pk, msg, sig)
+    # -- one signature per kind of damage, a few positions each
+    for j, kind in enumerate(("flip pk", "flip R", "flip s", "flip message", "message shorter", "message longer", "s + k L", "s = L", "A refused",
+                              "small-order A, honest R", "small-order R, honest A")):
+        pk, msg, sig = signed[5 + j]
+        s = int.from_bytes(sig[32:], "little")
+        for t in range(4):
+            bit = _scalar("ed25519 verdict bit", j, t)
+            if kind == "flip pk":
+                add(kind, flip(pk, bit % 256), msg, sig)
+            elif kind == "flip R":
+                add(kind, pk, msg, flip(sig[:32], bit % 256) + sig[32:])
+            elif kind == "flip s":
+                add(kind, pk, msg, sig[:32] + flip(sig[32:], bit % 252))
+            elif kind == "flip message":
+                add(kind, pk, flip(msg, bit % (8 * len(msg))), sig)
+        if kind == "message shorter":
+            add(kind, pk, msg[:-1], sig); add(kind, pk, b"", sig)
+        elif kind == "message longer":
+            add(kind, pk, msg + b"\x00", sig); add(kind, pk, msg + msg[:1], sig)
+        elif kind == "s + k L":                               # the same residue written k L higher: every k that fits 256 bits; k = 14, 15 set the top three bits
+            for k in range(1, 17):
+                if s + k * L < 2**256:
+                    add(kind, pk, msg, sig[:32] + le(s + k * L))
+            assert (s + 14 * L) >> 253 == 7
+        elif kind == "s = L":
+            add(kind, pk, msg, sig[:32] + le(L))
+        elif kind == "A refused":
+            for e in refused_encodings():
+                add(kind, e, msg, sig)
+        elif kind == "small-order A, honest R":
+            for e in SMALL_ORDER:
+                add(kind, e, msg, sig)
+        elif kind == "small-order R, honest A":
+            for e in SMALL_ORDER:
+                add(kind, pk, msg, e + sig[32:])
+    # -- s at the edge of L, where the equation can be made to hold for any s: A = the identity, R = [s]B
+    ident = SMALL_ORDER[0]
+    for s in (L - 1, L, L + 1, 2 * L - 1, 15 * L + 1, 2**256 - 1, 2**255, 7 << 253):
+        add("s around L under A = identity", ident, b"edge", base_mult(s) + le(s))                  # only s = L - 1 is below L
+    # -- R non-canonical: y + p for y < 19.  y = 1 (the identity) under A = identity; y = 0 (order 4, either sign) under the A of order 4 with a message for
+    # which -[h]A is that point, so that the canonical encoding beside it is accepted
+    for i in range(19):
+        add("R non-canonical", ident, b"m", le(P + i) + le(0))
+    add("R canonical beside them", ident, b"m", ident + le(0))
+    four = [e for e, _, n in torsion() if n == 4]
+    for a in four:
+        for r in four:
+            j = 0
+            while not verify(a, _tag("order four", j), r + le(0)):
+                j += 1
+            m = _tag("order four", j)
+            add("R canonical beside them", a, m, r + le(0))
+            add("R non-canonical", a, m, le(int.from_bytes(r, "little") + P) + le(0))
+    # -- A non-canonical: libcrypto accepts, this rule set refuses
+    for e in (le(P + 1), le(1 | (1 << 255))):
+        add(DIVERGENT_KIND, e, b"", ident + le(0))
+    # -- all 8 x 8 small-order pairs, s = 0, 8 messages
+    for a in SMALL_ORDER:
+        for r in SMALL_ORDER:
+            for t in range(8):
+                add("small order", a, bytes([t]), r + le(0))
+    # -- mixed order
+    tors = torsion()
+    first_accepted = {}
+
+    def search(kind, ia, ir):
+        (_, t_a, order_a), (_, t_r, order_r) = tors[ia], tors[ir]
+        pairs = sum(1 for _, _, x in tors for _, _, y in tors if (x, y) == (order_a, order_r))
+        quota = max(2, -(-MIXED_MINIMUM // pairs)) if ia and ir else MIXED_MINIMUM       # per pair of torsion points; the classes' minimum follows
+        want = {True: quota if can_accept(order_a, order_r) else 0, False: quota}
+        a = expand(hashlib.sha256(_tag("ed25519 verdict mixed seed", ia, ir)).digest())[0]
+        have, j = {True: 0, False: 0}, 0
+        while have != want:
+            r = _scalar("ed25519 verdict mixed nonce", ia, ir, j)
+            msg = _message("ed25519 verdict mixed message", ia, ir, j, length=1 + j % 16)
+            j += 1
+            pk, sig, holds = sign_mixed(a, r, t_a, t_r, msg)
+            if have[holds] == want[holds]:
+                continue
+            have[holds] += 1
+            add(kind, pk, msg, sig, orders=[order_a, order_r], holds=int(holds))
+            if holds and kind == MIXED_KINDS[0]:
+                first_accepted.setdefault(ia, (pk, msg, sig))
+    for ia in range(1, 8):
+        search(MIXED_KINDS[0], ia, 0)
+    for ir in range(1, 8):
+        search(MIXED_KINDS[1], 0, ir)
+    for ia in range(1, 8):
+        for ir in range(1, 8):
+            search(MIXED_KINDS[2], ia, ir)
+    for ia in range(1, 8):                                     # an accepted mixed-order lane, damaged
+        pk, msg, sig = first_accepted[ia]
+        add("mixed A, flipped message", pk, flip(msg, ia % (8 * len(msg))), sig)
+        add("mixed A, s + 1", pk, msg, sig[:32] + le((int.from_bytes(sig[32:], "little") + 1) % L))
+    return lanes
+
+
+def check_verdicts(records):
+    """The conditions under which the fixture may exist; raises AssertionError.  Returns {kind: count}."""
+    kinds = {}
+    for rec in records:
+        kinds[rec["kind"]] = kinds.get(rec["kind"], 0) + 1
+        assert len(rec["message"]) <= 32, rec
+        assert bool(rec.get("divergent")) == (rec["kind"] == DIVERGENT_KIND), rec
+        if rec.get("divergent"):
+            assert (rec["libcrypto"], rec["model"], rec["model_strict"]) == (1, 0, 0), rec
+        else:
+            assert rec["model"] == rec["libcrypto"], rec
+        assert rec["model_strict"] <= rec["model"], rec
+        if rec["kind"] in MIXED_KINDS:
+            assert rec["model"] == rec["model_strict"] == rec["holds"], rec
+            assert rec["public_key"] not in [e.hex() for e in SMALL_ORDER] and rec["signature"][:64] not in [e.hex() for e in SMALL_ORDER], rec
+    verdicts = lambda kind: {r["model"] for r in records if r["kind"] == kind}
+    assert verdicts("valid") == {1} and verdicts("R canonical beside them") == {1}
+    assert verdicts("small order") == {0, 1} and verdicts("s around L under A = identity") == {0, 1}
+    for kind in kinds:
+        if kind not in MIXED_KINDS + ("valid", "R canonical beside them", "small order", "s around L under A = identity"):
+            assert verdicts(kind) == {0}, kind
+    assert kinds["small order"] == 512 and {r["model_strict"] for r in records if r["kind"] == "small order"} == {0}
+    classes = {}
+    for rec in records:
+        if rec["kind"] in MIXED_KINDS:
+            classes.setdefault((rec["kind"],) + tuple(rec["orders"]), [0, 0])[rec["model"]] += 1
+    expected = {(MIXED_KINDS[0], n, 1) for n in (2, 4, 8)} | {(MIXED_KINDS[1], 1, n) for n in (2, 4, 8)} | {(MIXED_KINDS[2], m, n) for m in (2, 4, 8) for n in (2, 4, 8)}
+    assert set(classes) == expected, sorted(classes)
+    for (kind, order_a, order_r), (refused, accepted) in classes.items():
+        assert refused >= MIXED_MINIMUM, (kind, order_a, order_r, refused)
+        assert accepted >= MIXED_MINIMUM if can_accept(order_a, order_r) else accepted == 0, (kind, order_a, order_r, accepted)
+    return kinds
+
+
+def verdicts_text(records):
+    head = dict(comment="Ed25519 verdicts: lanes of every kind tests/test_gpu_ed25519.py verifies, refused and accepted, each adjudicated by libcrypto's "
+                        "EVP_DigestVerify (NID 1087) and by tools/ed25519_model.py (model: the default rule set, model_strict: with the small-order flag); "
+                        "written by mint_verdicts, which refuses to write where the two differ on a record not marked divergent.  Mixed-order records: "
+                        "A = [a]B + t_a, R = [r]B + t_r, s = r + h a; orders = [order of t_a, order of t_r]; holds = (t_r + [h mod L]t_a is the identity)")
+    lines = ",\n".join(json.dumps(r, separators=(",", ":")) for r in records)
+    return "{\"comment\":%s,\n\"records\":[\n%s\n]}\n" % (json.dumps(head["comment"]), lines)
+
+
+def mint_verdicts(path):
+    ossl = libcrypto()
+    assert ossl is not None, "libcrypto does not load here"
+    records = []
+    for kind, pk, msg, sig, extra in verdict_lanes():
+        rec = dict(kind=kind, public_key=pk.hex(), message=msg.hex(), signature=sig.hex(), libcrypto=int(ossl.verify(pk, msg, sig)),
+                   model=int(verify(pk, msg, sig)), model_strict=int(verify(pk, msg, sig, True)))
+        if kind == DIVERGENT_KIND:
+            rec["divergent"] = True
+        rec.update(extra)
+        records.append(rec)
+    kinds = check_verdicts(records)
+    text = verdicts_text(records)
+    golden = os.path.dirname(VERDICTS_PATH)
+    largest = max(os.path.getsize(os.path.join(golden, f)) for f in os.listdir(golden) if f != os.path.basename(VERDICTS_PATH))
+    assert len(text) < largest, (len(text), largest)
+    with open(path, "w") as f:
+        f.write(text)
+    return kinds, len(text)
+
+
 # ---- the device constants
 def words(v):
     return ", ".join("0x%08xu" % ((v >> (32 * i)) & 0xffffffff) for i in range(8))
@@ -297,7 +536,10 @@ def table_text():
 
 
 if __name__ == "__main__":
-    if "--mint" in sys.argv:
+    if "--mint-verdicts" in sys.argv:
+        kinds, size = mint_verdicts(VERDICTS_PATH)
+        print(json.dumps(kinds, indent=1), sum(kinds.values()), "records,", size, "bytes")
+    elif "--mint" in sys.argv:
         print(mint(os.path.join(ROOT, "tests", "golden", "ed25519_vectors.json")), "records")
     elif "--table" in sys.argv:
         with open(os.path.join(ROOT, "ecsimd_amd", "csrc", "ed25519_base.inc"), "w") as f:

@@ -6,7 +6,7 @@ The rule set is the one include/ecsimd_x25519.h states:
     canonical x-coordinate, 32 zero bytes at infinity (no exception: the caller reads `ok`).
   * x25519_base(k): the same on u = 9, computed the way the device computes it -- [clamp(k) mod L]B on the Edwards curve (tools/ed25519_model.py), mapped by
     u = (1 + y) / (1 - y).
-  * from_ed25519_pk: strict decoding, the eight small-order encodings refused, no prime-subgroup check.  from_ed25519_seed: the clamped low half of SHA-512.
+  * from_ed25519_pk: strict decoding, the eight small-order encodings refused, no prime-subgroup check (mixed_keys: keys that show it).  from_ed25519_seed: the clamped low half of SHA-512.
 
   python tools/x25519_model.py --mint    writes tests/golden/x25519_vectors.json (RFC 7748's values and records minted from libcrypto)
 """
@@ -72,6 +72,23 @@ def ok_of(out):
 def ed_point_to_u(pt):
     """(Z + Y) / (Z - Y); 0 for the identity"""
     return (pt[2] + pt[1]) * ed.inv((pt[2] - pt[1]) % P) % P
+
+
+def u_of_encoding(enc):
+    """u = (1 + y) / (1 - y) on the y an Edwards encoding carries, whatever subgroup the point lies in: 0 for y = 1"""
+    y = int.from_bytes(enc, "little") & ((1 << 255) - 1)
+    return (1 + y) * ed.inv((1 - y) % P) % P
+
+
+def mixed_keys(scalars):
+    """[(a, index of T, [a]B, [a]B + T)] for each a and each of the seven non-zero torsion points T of ed.torsion(): Ed25519 public keys outside the prime-order
+    subgroup, which from_ed25519_pk accepts (it checks no subgroup) and whose torsion part X25519's clamped scalar, a multiple of 8, removes."""
+    tors = ed.torsion()
+    out = []
+    for a in scalars:
+        pt = ed.base_point_mul(a)
+        out += [(a, j, pt, ed.mixed(pt, tors[j][1])) for j in range(1, 8)]
+    return out
 
 
 def edwards_base(k):
