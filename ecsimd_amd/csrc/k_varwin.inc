@@ -539,8 +539,11 @@ __global__ void __launch_bounds__(BLOCK) k_add_mixed_complete(const uint64_t* __
 }
 
 // ---------------------------------------------------------------- secp256k1: the GLV split in constant time
-// ALG_WINDOWED | ALG_CONSTANT_TIME on secp256k1.  The split's digits include zero and the interleaved sum can meet R = +-T, which the
-// default loop handles behind a branch (add_checked); a constant-time loop cannot.  So this loop runs on the COMPLETE addition law of a
+// ALG_WINDOWED | ALG_CONSTANT_TIME on secp256k1.  The split's digits include zero, and the accumulator is the point at infinity until the first
+// non-zero digit (k = 0 mod n: to the end) -- cases the default loop leaves behind a branch (add_checked); a constant-time loop cannot.  A finite
+// accumulator never meets R = +-T for a valid point: the split stays inside the lattice's cell (tests/test_recoding_models.py walks every prefix,
+// tests/scalar_catalogue.py's aimed scalars included); what does occur is O + T, 2 O, and the sum a zero digit forms with the window's first entry
+// and drops, which may be anything.  So this loop runs on the COMPLETE addition law of a
 // prime-order curve with a = 0 (Bosma-Lenstra as arranged by Renes, Costello and Batina, "Complete addition formulas for prime order
 // elliptic curves", 2016: homogeneous projective (X : Y : Z), x = X/Z, y = Y/Z, O = (0 : 1 : 0)) -- one formula for every pair of
 // inputs, a doubling that maps O to O:

@@ -109,7 +109,8 @@ def test_glv_split_of_secp256k1():
     def signed256(v):
         v &= M256
         return v - (1 << 256) if v >> 255 else v
-    for k in scalars(7, 5000) + [lam, lam + 1, n - lam, a1, mb1, a2, (a1 * lam) % n, n - 1]:
+    from scalar_catalogue import catalogue
+    for k in scalars(7, 5000) + [lam, lam + 1, n - lam, a1, mb1, a2, (a1 * lam) % n, n - 1] + [k for k, _ in catalogue(SECP256K1)]:
         k = (k & M256) % n
         c1 = ((k * g1) >> 384) + (((k * g1) >> 383) & 1)
         c2 = ((k * g2) >> 384) + (((k * g2) >> 383) & 1)
@@ -143,3 +144,57 @@ def test_glv_split_of_secp256k1():
                         assert (acc - t) % n and (acc + t) % n
                     acc = (acc + t) % n
             assert acc == k % n
+
+
+def test_scalar_catalogue_reaches_every_link_of_the_glv_split():
+    """tests/scalar_catalogue.py: the scalars tests/test_gpu_scalar_routes.py runs through every route.  Building the catalogue already holds the word-level
+    model of the split to the integer formula on each of them; here: every feature class has a scalar, the lists stay small, and the model is SENSITIVE to
+    the fault the carry_* scalars are aimed at -- with the rounding's carry cut after word 0 it disagrees with the integer formula on every one of them
+    and on none of 10 000 random scalars (2^-33 each)."""
+    import scalar_catalogue as sc
+    n = CURVE_PARAMS[SECP256K1]["n"]
+    for cv in (P256, SECP256K1):
+        cat = sc.catalogue(cv)
+        assert len(cat) <= 400 and len({k for k, _ in cat}) == len(cat) and all(0 <= k <= M256 for k, _ in cat)
+        have = set().union(*(f for _, f in cat))
+        assert {"edge", "comb_exceptional", "digit_pattern", "ladder_degenerate", "zero_mod_n"} <= have
+        assert sum("ladder_degenerate" in f for _, f in cat) == 3 and {k for k, f in cat if "zero_mod_n" in f} == {0, CURVE_PARAMS[cv]["n"]}
+        listed = {k for k, _ in cat}
+        assert set(sc.edge_scalars(cv)) | set(sc.comb_exceptional_scalars(cv)) | set(sc.digit_pattern_sample()) <= listed
+    cat = sc.catalogue(SECP256K1)
+    have = set().union(*(f for _, f in cat))
+    carries = ["carry_g%d_w%d" % (g, w) for g in (1, 2) for w in (1, 2, 3)]
+    wanted = carries + ["k1_zero", "k2_zero", "sign_pp", "sign_pn", "sign_np", "sign_nn", "top1_half1", "top1_half2", "neg_borrow_w1", "neg_borrow_w2",
+                        "neg_borrow_w3", "lattice"] + ["digit_%d_everywhere" % d for d in range(-8, 8)]
+    assert not [name for name in wanted if name not in have]
+    assert all(sum(name in f for _, f in cat) == len(sc.CARRY_HIGH) for name in carries)             # every (constant, words, high part) exists below n
+    assert 0x546840c7b2f5edcc74c6af67a76f28a65d5b44440 in sc.with_feature(SECP256K1, "carry_g1_w1")   # c1 rounds from ffffffff to 1 00000000
+    assert set(sc.lattice_scalars()) <= {k for k, f in cat if "lattice" in f}
+    # top1_both: no scalar has it, and none can.  With (x, y) the split's rounding remainders, |x|, |y| <= 1/2 + e: k1 = x a1 + y a2, k2 = x b1 + y b2
+    # (b1 < 0 < a1 = b2 < a2).  Say k2 >= T = 0x7777..78 (else negate k): x <= (y b2 - T) / |b1| and x >= -h force y >= (T - h |b1|) / b2 > 0, so
+    # 0 < k1 <= h a2 - a1 (T - h b2) / |b1| -- which is below T.  e: g_i approximates 2^384 b / n to half a unit, |k g_i / 2^384 - k b / n| < 2^-128.
+    from fractions import Fraction
+    assert "top1_both" not in have
+    a1, b1, a2, b2, T = sc.A1, -sc.MB1, sc.A2, sc.A1, sc.TOP1
+    h = Fraction(1, 2) + Fraction(1, 1 << 64)
+    assert (T - h * -b1) / b2 > 0 and -h * a1 + (T - h * -b1) / b2 * a2 > 0 and h * a2 - a1 * (T - h * b2) / -b1 < T
+    for g, b in ((sc.G1, b2), (sc.G2, -b1)):
+        assert abs(Fraction(g, 1 << 384) - Fraction(b, n)) * n < Fraction(1, 1 << 128)
+    # the fault in question, in the model
+    cut = sc.GlvWordModel(cut_carry=True)
+    for k in sc.with_feature(SECP256K1, "carry_"):
+        assert cut.split(k)[:2] != sc.glv_split_integers(k % n), hex(k)
+        k1, k2, _ = cut.split(k)
+        assert not (abs(k1) < 1 << 128 and abs(k2) < 1 << 128), hex(k)                           # off by 2^32 a1 (or more): outside the 160 bits the loops read
+    rng = random.Random(2033)
+    for _ in range(10000):
+        k = rng.getrandbits(256)
+        assert cut.split(k)[:2] == sc.WORD_MODEL.split(k)[:2] == sc.glv_split_integers(k % n if k >= n else k), hex(k)
+
+
+def test_scalar_catalogue_restates_the_digit_pattern_family():
+    """digit_pattern_sample() is rows 0, 70 000, .. of test_oracle.digit_pattern_operands(): every 700th of the every-100th sample the windowed GPU tests run."""
+    import scalar_catalogue as sc
+    from helpers import arr_to_ints
+    from test_oracle import digit_pattern_operands
+    assert arr_to_ints(digit_pattern_operands()[::100][::700]) == sc.digit_pattern_sample()
