@@ -18,6 +18,7 @@
 #include "../../include/ecsimd_hip.h"
 #include "../../include/ecsimd_ed25519.h"
 #include "../../include/ecsimd_x25519.h"
+#include "../../include/ecsimd_msm.h"
 #include "kernels.h"
 #include "point.cuh"   // curve constants for ecsimd_hip_get_constant (host-side constexpr use only)
 #include "gfield.cuh"  // gmod: a run-time modulus as the generic field kernels take it
@@ -2416,6 +2417,175 @@ int ecsimd_x25519_raw(ecsimd_hip_ctx* ctx, int op, const uint8_t* in, uint8_t* o
   FOR_CHUNKS(first, m, n, X25519_CHUNK) launch::x25519_raw(ctx->stream, op, in + 32 * ni * first, out + 32 * no * first, m);
   const hipError_t e = hipGetLastError();
   return e == hipSuccess ? ECSIMD_HIP_OK : fail(ctx, e, "x25519_raw launch"); }
+
+// ---- Multi-scalar multiplication and the point sum (include/ecsimd_msm.h; k_msm.inc has the stages).  PUBLIC data.  msm_schedule_of is the ONE place that turns
+// (n, bits, flags) into sizes: ecsimd_msm_plan reports it, ecsimd_msm enqueues from it, tools/msm_model.py restates it.  Nothing here looks at the data.
+namespace {
+int floor_log2(size_t v) { int r = 0; while (v >>= 1) ++r; return r; }
+int ceil_log2(size_t v) { return v <= 1 ? 0 : floor_log2(v - 1) + 1; }
+int tree_passes(size_t count) { int p = 0; while (count > 1) { count = (count + launch::MSM_TREE_FAN - 1) / launch::MSM_TREE_FAN; ++p; } return p; }
+size_t round16(size_t b) { return (b + 15) / 16 * 16; }
+struct msm_schedule {
+  ecsimd_msm_plan_t plan;
+  size_t T, K, slices, per_window, chunk_lanes, front_lanes;      // BUCKETS: entries, keys, slice lanes, chunks per window, their product with the windows; LANES: the affine tree's lanes
+};
+// The workspace of a call, carved from `base` (nullptr: sizes only).
+struct msm_blocks {
+  uint32_t *counter, *hist, *start, *cursor, *sorted;   // counter (invalid points, broken invariants) and hist are ONE block, zeroed by one kernel
+  uint64_t *kk, *px, *py, *buckets, *partial, *tree;    // LANES: kk, px, py = the sanitized scalars and points, buckets / partial = the affine products (ox, oy)
+  size_t zero_bytes, reserve;                           // the length of that block; LANES: what run_varwin leaves alone at the start of the workspace
+};
+msm_blocks msm_carve(const msm_schedule& S, size_t n, void* base, size_t* bytes) {
+  msm_blocks B = {};
+  carve c = carve_from(base);
+  if (S.plan.route == ECSIMD_MSM_ALG_BUCKETS) {
+    B.zero_bytes = round16(16 + 4 * S.K);
+    B.counter = static_cast<uint32_t*>(carve_bytes(c, B.zero_bytes)); B.hist = B.counter ? B.counter + 4 : nullptr;
+    B.start = static_cast<uint32_t*>(carve_bytes(c, round16(4 * (S.K + 1))));
+    B.cursor = static_cast<uint32_t*>(carve_bytes(c, round16(4 * S.K)));
+    B.sorted = static_cast<uint32_t*>(carve_bytes(c, round16(4 * S.T)));
+    B.kk = carve_limbs(c, n); B.px = carve_limbs(c, n); B.py = carve_limbs(c, n);
+    B.buckets = carve_limbs(c, 3 * S.K); B.partial = carve_limbs(c, 3 * 2 * S.slices); B.tree = carve_limbs(c, 3 * S.chunk_lanes);
+  } else {
+    B.zero_bytes = 32;                                  // (32: run_varwin's scratch behind `reserve` stays 32-byte aligned)
+    B.counter = static_cast<uint32_t*>(carve_bytes(c, 32));
+    B.kk = carve_limbs(c, n); B.px = carve_limbs(c, n); B.py = carve_limbs(c, n);
+    B.buckets = carve_limbs(c, n); B.partial = carve_limbs(c, n); B.tree = carve_limbs(c, 3 * S.front_lanes);
+    B.reserve = c.bytes;
+    (void)carve_bytes(c, launch::varwin_scratch_bytes(chunk_of(n, VARWIN_CHUNK)));
+  }
+  *bytes = c.bytes;
+  return B;
+}
+bool msm_schedule_of(size_t n, int bits, int flags, msm_schedule* S) {
+  if (bits < 1 || bits > 256 || n > ECSIMD_MSM_MAX_N) return false;
+  if (flags != ECSIMD_MSM_ALG_AUTO && flags != ECSIMD_MSM_ALG_BUCKETS && flags != ECSIMD_MSM_ALG_LANES) return false;
+  *S = msm_schedule();
+  ecsimd_msm_plan_t& P = S->plan;
+  P.route = flags != ECSIMD_MSM_ALG_AUTO ? flags : n >= ECSIMD_MSM_AUTO_THRESHOLD ? ECSIMD_MSM_ALG_BUCKETS : ECSIMD_MSM_ALG_LANES;
+  if (n == 0) { P.launches = 1; P.max_chain = 0; return true; }                  // the last kernel alone writes the empty sum
+  const int fan = launch::MSM_TREE_FAN;
+  if (P.route == ECSIMD_MSM_ALG_BUCKETS) {
+    int c = floor_log2(n) - 4; if (c < 2) c = 2; if (c > 16) c = 16; if (c > bits) c = bits;
+    P.windows = (bits + c - 1) / c;
+    c = (bits + P.windows - 1) / P.windows;             // the same number of windows, evenly wide: no narrow top window whose few buckets hold every term
+    P.c = c; P.buckets = 1u << c;
+    const uint32_t L = (1u << ((ceil_log2(n) + 1) / 2)) / 4; P.L = L < 4 ? 4 : L;
+    uint32_t m = 1u << ((c + 1) / 2); if (m > 32) m = 32; if (m < 2) m = 2; if (m > P.buckets) m = P.buckets; P.m = m;
+    S->T = n * (size_t)P.windows; S->K = (size_t)P.windows << c; S->slices = (S->T + P.L - 1) / P.L;
+    S->per_window = P.buckets / m; S->chunk_lanes = S->per_window * P.windows;
+    const size_t chain[] = {P.L, (n + P.L - 1) / P.L + 1, 2 * (size_t)m + 2 * (size_t)c, (size_t)fan, (size_t)P.windows * (c + 1)};
+    for (size_t v : chain) if (v > P.max_chain) P.max_chain = (uint32_t)v;
+    P.launches = 8 + tree_passes(S->per_window);        // zero, digits, scan, scatter, slices, combine, chunks, the tree's passes, the last kernel
+  } else {
+    S->front_lanes = (n + fan - 1) / fan;
+    P.max_chain = fan;
+    P.launches = 4 + 5 * (int)((n + VARWIN_CHUNK - 1) / VARWIN_CHUNK) + tree_passes(S->front_lanes);   // zero, sanitize, the products (five kernels on P-256, three on secp256k1: the plan has no curve and reports the larger), the affine tree, the tree, the last kernel
+  }
+  (void)msm_carve(*S, n, nullptr, &P.workspace_bytes);
+  return true;
+}
+extern "C++" template <int CV> int msm_run(ecsimd_hip_ctx* ctx, const msm_schedule& S, const uint64_t* k, const uint64_t* x, const uint64_t* y, uint64_t* rx, uint64_t* ry, uint8_t* finite,
+                              uint32_t* invalid, size_t n, int bits) {
+  using ML = launch::msm_launch<CV>;
+  const ecsimd_msm_plan_t& P = S.plan;
+  hipStream_t s = ctx->stream;
+  const int fan = launch::MSM_TREE_FAN;
+  if (n == 0) { ML::finish(s, nullptr, 0, 0, 0, 0, nullptr, rx, ry, finite, invalid); const hipError_t e0 = hipGetLastError(); return e0 == hipSuccess ? ECSIMD_HIP_OK : fail(ctx, e0, "msm launch"); }
+  int rc = ensure_workspace(ctx, P.workspace_bytes);
+  if (rc != ECSIMD_HIP_OK) return rc;
+  size_t bytes = 0;
+  const msm_blocks B = msm_carve(S, n, ctx->workspace, &bytes);
+  hipError_t e;
+  ML::zero(s, B.counter, B.zero_bytes);
+  size_t count, stride; int windows;
+  if (P.route == ECSIMD_MSM_ALG_BUCKETS) {
+    ML::digits(s, k, x, y, B.kk, B.px, B.py, B.hist, B.counter, n, bits, P.c, P.windows);
+    ML::scan(s, B.hist, B.start, B.cursor, S.K);
+    ML::scatter(s, B.kk, B.cursor, B.sorted, B.counter + 1, n, S.T, P.c, P.windows);
+    ML::slices(s, B.sorted, B.kk, B.px, B.py, B.start, B.buckets, B.partial, B.counter + 1, n, S.T, P.L, S.slices, P.c, S.K);
+    ML::combine(s, B.start, B.buckets, B.partial, B.counter + 1, P.L, S.slices, P.c, S.K);
+    ML::chunks(s, B.buckets, B.tree, S.chunk_lanes, S.per_window, P.c, (int)P.m, S.K);
+    count = S.per_window; stride = S.per_window; windows = P.windows;
+  } else {
+    ML::sanitize(s, k, x, y, B.kk, B.px, B.py, B.counter, n, bits);
+    rc = run_varwin(ctx, CV, B.kk, 4, B.px, B.py, B.buckets, B.partial, n, ECSIMD_HIP_OUT_AFFINE | ECSIMD_HIP_ALG_WINDOWED, B.reserve);   // the workspace is large enough: nothing moves
+    if (rc != ECSIMD_HIP_OK) return rc;
+    ML::tree_affine(s, B.buckets, B.partial, false, B.counter, B.tree, n, S.front_lanes, fan);
+    count = S.front_lanes; stride = 0; windows = 1;
+  }
+  const size_t total = P.route == ECSIMD_MSM_ALG_BUCKETS ? S.chunk_lanes : S.front_lanes;
+  while (count > 1) {
+    const size_t lanes = (count + fan - 1) / fan;
+    ML::tree(s, B.tree, total, count, stride, (size_t)windows, lanes, fan);
+    count = lanes;
+  }
+  ML::finish(s, B.tree, total, stride, windows, P.route == ECSIMD_MSM_ALG_BUCKETS ? P.c : 0, B.counter, rx, ry, finite, invalid);
+  e = hipGetLastError();
+  return e == hipSuccess ? ECSIMD_HIP_OK : fail(ctx, e, "msm launch");
+}
+extern "C++" template <int CV> int point_sum_run(ecsimd_hip_ctx* ctx, const uint64_t* x, const uint64_t* y, uint64_t* rx, uint64_t* ry, uint8_t* finite, uint32_t* invalid, size_t n) {
+  using ML = launch::msm_launch<CV>;
+  hipStream_t s = ctx->stream;
+  const int fan = launch::MSM_TREE_FAN;
+  if (n == 0) { ML::finish(s, nullptr, 0, 0, 0, 0, nullptr, rx, ry, finite, invalid); const hipError_t e0 = hipGetLastError(); return e0 == hipSuccess ? ECSIMD_HIP_OK : fail(ctx, e0, "msm launch"); }
+  const size_t front = (n + fan - 1) / fan;
+  carve c = carve_from(nullptr); (void)carve_bytes(c, 16); (void)carve_limbs(c, 3 * front);
+  int rc = ensure_workspace(ctx, c.bytes);
+  if (rc != ECSIMD_HIP_OK) return rc;
+  c = carve_from(ctx->workspace);
+  uint32_t* counter = static_cast<uint32_t*>(carve_bytes(c, 16)); uint64_t* tree = carve_limbs(c, 3 * front);
+  hipError_t e;
+  ML::zero(s, counter, 16);
+  ML::tree_affine(s, x, y, true, counter, tree, n, front, fan);
+  for (size_t count = front; count > 1;) {
+    const size_t lanes = (count + fan - 1) / fan;
+    ML::tree(s, tree, front, count, 0, 1, lanes, fan);
+    count = lanes;
+  }
+  ML::finish(s, tree, front, 0, 1, 0, counter, rx, ry, finite, invalid);
+  e = hipGetLastError();
+  return e == hipSuccess ? ECSIMD_HIP_OK : fail(ctx, e, "point_sum launch");
+}
+int msm_check_common(ecsimd_hip_ctx* ctx, int curve, const uint64_t* x, const uint64_t* y, uint64_t* rx, uint64_t* ry, uint8_t* finite, uint32_t* invalid, size_t n) {
+  if (curve >= ECSIMD_HIP_FIRST_REGISTERED_CURVE) return bad(ctx, "registered curves have no multi-scalar multiplication: ECSIMD_HIP_P256 and ECSIMD_HIP_SECP256K1 only");
+  REQUIRE_CURVE();
+  REQUIRE_PTR(x); REQUIRE_PTR(y);
+  if (!rx || !ry || !finite) return bad(ctx, "msm: rx, ry or finite is null");
+  if (!aligned16(rx) || !aligned16(ry)) return bad(ctx, "msm: rx or ry is not 16-byte aligned");
+  if (invalid && (reinterpret_cast<uintptr_t>(invalid) & 3u)) return bad(ctx, "msm: invalid is not 4-byte aligned");
+  if (invalid ? any_alias({rx, ry, finite, invalid}, {x, y}) : any_alias({rx, ry, finite}, {x, y})) return bad(ctx, "msm: an output must not alias an input or another output");
+  return ECSIMD_HIP_OK;
+}
+}  // namespace
+
+int ecsimd_msm_plan(size_t n, int bits, int flags, ecsimd_msm_plan_t* out) {
+  msm_schedule S;
+  if (!out || !msm_schedule_of(n, bits, flags, &S)) return ECSIMD_HIP_ERR_BAD_ARG;
+  *out = S.plan;
+  return ECSIMD_HIP_OK; }
+
+int ecsimd_msm(ecsimd_hip_ctx* ctx, int curve, const uint64_t* k, const uint64_t* x, const uint64_t* y, uint64_t* rx, uint64_t* ry, uint8_t* finite, uint32_t* invalid,
+               size_t n, int bits, int flags) {
+  REQUIRE_CTX();
+  int rc = msm_check_common(ctx, curve, x, y, rx, ry, finite, invalid, n);
+  if (rc != ECSIMD_HIP_OK) return rc;
+  REQUIRE_PTR(k);
+  if (n && (overlaps(k, rx) || overlaps(k, ry) || overlaps(k, finite) || overlaps(k, invalid))) return bad(ctx, "msm: an output must not alias an input or another output");
+  if (bits < 1 || bits > 256) return bad(ctx, "msm: bits must be 1 .. 256");
+  if (n > ECSIMD_MSM_MAX_N) return bad(ctx, "msm: n is above ECSIMD_MSM_MAX_N: chain chunks through ecsimd_msm_point_sum");
+  msm_schedule S;
+  if (!msm_schedule_of(n, bits, flags, &S)) return bad(ctx, "msm: flags must be ECSIMD_MSM_ALG_AUTO, ECSIMD_MSM_ALG_BUCKETS or ECSIMD_MSM_ALG_LANES");
+  const hipError_t e0 = hipSetDevice(ctx->device); if (e0 != hipSuccess) return fail(ctx, e0, "hipSetDevice");
+  return curve == ECSIMD_HIP_P256 ? msm_run<CURVE_P256>(ctx, S, k, x, y, rx, ry, finite, invalid, n, bits) : msm_run<CURVE_SECP256K1>(ctx, S, k, x, y, rx, ry, finite, invalid, n, bits); }
+
+int ecsimd_msm_point_sum(ecsimd_hip_ctx* ctx, int curve, const uint64_t* x, const uint64_t* y, uint64_t* rx, uint64_t* ry, uint8_t* finite, uint32_t* invalid, size_t n) {
+  REQUIRE_CTX();
+  int rc = msm_check_common(ctx, curve, x, y, rx, ry, finite, invalid, n);
+  if (rc != ECSIMD_HIP_OK) return rc;
+  if ((n + launch::MSM_TREE_FAN - 1) / launch::MSM_TREE_FAN > MAX_LAUNCH) return bad(ctx, "batch too large");
+  const hipError_t e0 = hipSetDevice(ctx->device); if (e0 != hipSuccess) return fail(ctx, e0, "hipSetDevice");
+  return curve == ECSIMD_HIP_P256 ? point_sum_run<CURVE_P256>(ctx, x, y, rx, ry, finite, invalid, n) : point_sum_run<CURVE_SECP256K1>(ctx, x, y, rx, ry, finite, invalid, n); }
 
 int ecsimd_hip_fe29_raw(ecsimd_hip_ctx* ctx, int curve, int op, const int32_t* in, int32_t* out, size_t n, int swap) {
   REQUIRE_CTX(); if ((!in || !out) && n) return bad(ctx, "fe29_raw: null pointer");

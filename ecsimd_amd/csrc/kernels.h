@@ -314,6 +314,25 @@ template <int C> struct point_launch {
   static void add_mixed_complete(hipStream_t, const uint64_t*, const uint64_t*, const uint64_t*, const uint64_t*, const uint64_t*, uint64_t*, uint64_t*, uint64_t*, size_t);
   static void varwin_scalar_mult(hipStream_t, const uint64_t* k, int k_stride, const uint64_t* x, const uint64_t* y, int flags, uint64_t* scratch, uint64_t* ox, uint64_t* oy, size_t n);
 };
+// k_msm_<curve>.hip: R = sum k_i P_i by the bucket method and the point sum over lanes (k_msm.inc has the stages; PUBLIC data).  Jacobian arrays are three planes
+// of `total` elements in the fast domain, Z = 0 at infinity.  Every launcher enqueues ONE kernel; capi.hip's msm_schedule_of decides the sizes from (n, bits, flags).
+constexpr int MSM_TREE_FAN = 16;                 // elements a lane of the tree sum adds per launch
+template <int C> struct msm_launch {
+  static void zero(hipStream_t, void* words, size_t bytes);          // bytes: a multiple of 16
+  static void digits(hipStream_t, const uint64_t* k, const uint64_t* x, const uint64_t* y, uint64_t* kk, uint64_t* px, uint64_t* py, uint32_t* hist, uint32_t* counter, size_t n,
+                     int bits, int c, int windows);
+  static void scan(hipStream_t, const uint32_t* hist, uint32_t* start, uint32_t* cursor, size_t K);
+  static void scatter(hipStream_t, const uint64_t* kk, uint32_t* cursor, uint32_t* sorted, uint32_t* broken, size_t n, size_t T, int c, int windows);
+  static void slices(hipStream_t, const uint32_t* sorted, const uint64_t* kk, const uint64_t* px, const uint64_t* py, const uint32_t* start, uint64_t* buckets, uint64_t* partial,
+                     uint32_t* broken, size_t n, size_t T, size_t L, size_t slices, int c, size_t K);
+  static void combine(hipStream_t, const uint32_t* start, uint64_t* buckets, const uint64_t* partial, uint32_t* broken, size_t L, size_t slices, int c, size_t K);
+  static void chunks(hipStream_t, const uint64_t* buckets, uint64_t* out, size_t lanes, size_t per_window, int c, int m, size_t K);
+  static void tree(hipStream_t, uint64_t* arr, size_t total, size_t count, size_t stride, size_t groups, size_t lanes, int fan);
+  static void tree_affine(hipStream_t, const uint64_t* x, const uint64_t* y, bool validate, uint32_t* counter, uint64_t* out, size_t n, size_t lanes, int fan);
+  static void sanitize(hipStream_t, const uint64_t* k, const uint64_t* x, const uint64_t* y, uint64_t* kk, uint64_t* sx, uint64_t* sy, uint32_t* counter, size_t n, int bits);
+  static void finish(hipStream_t, const uint64_t* arr, size_t total, size_t stride, int windows, int c, const uint32_t* counter, uint64_t* rx, uint64_t* ry, uint8_t* finite,
+                     uint32_t* invalid);
+};
 inline size_t scalar_mult_x_scratch_bytes(size_t n) { return 4 * n * 32 + ((n + 31) & ~(size_t)31); }   // odd scalars, num, den, 1/den, zero flags
 // The 4-bit fixed-base table in LDS (BASELINE configs[2]): odd digits only (round 3) -- the regular recoding of the odd one of k mod n, n - k, as in
 // the big-window kernel: 64 windows x 8 odd multiples (2d + 1) 16^w G = 32 KiB, 63 mixed additions, no zero digit and therefore no "skip" / "infinity"

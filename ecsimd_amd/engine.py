@@ -61,6 +61,12 @@ def _u64(v):
     return C.c_uint64(int(v) & 0xFFFFFFFFFFFFFFFF)
 
 
+class MsmPlan(C.Structure):
+    """ecsimd_msm_plan_t (include/ecsimd_msm.h)."""
+    _fields_ = [("route", C.c_int), ("c", C.c_int), ("windows", C.c_int), ("buckets", C.c_uint32), ("L", C.c_uint32), ("m", C.c_uint32), ("max_chain", C.c_uint32),
+                ("launches", C.c_int), ("workspace_bytes", C.c_size_t)]
+
+
 class Engine:
     """One context (HIP stream owner) on one GPU."""
 
@@ -573,6 +579,55 @@ class Engine:
         self._bind_stream()
         self._check(self.lib.ecsimd_x25519_raw(self.ctx, C.c_int(op), ip, C.c_void_p(out.data_ptr()), C.c_size_t(n)), "x25519_raw")
         return out
+
+    # ---- multi-scalar multiplication (include/ecsimd_msm.h): ONE point out of a batch.  PUBLIC data only.
+    MSM_ALG_AUTO, MSM_ALG_BUCKETS, MSM_ALG_LANES = 0, 1, 2
+
+    @staticmethod
+    def msm_plan(n, bits=256, alg=0):
+        """ecsimd_msm_plan: what msm(n terms, bits, alg) will do, as a dict (route, c, windows, buckets, L, m, max_chain, launches, workspace_bytes).
+        Host only: needs the library, no GPU and no Engine."""
+        plan = MsmPlan()
+        lib = load_library()
+        rc = lib.ecsimd_msm_plan(C.c_size_t(n), C.c_int(bits), C.c_int(alg), C.byref(plan))
+        if rc != 0:
+            raise EcsimdHipError(f"msm_plan(n={n}, bits={bits}, alg={alg}) failed ({rc}): bits must be 1 .. 256, n at most 2^24, alg 0, 1 or 2")
+        return {name: int(getattr(plan, name)) for name, _ in MsmPlan._fields_}
+
+    def _msm_out(self, want_invalid):
+        torch = self.torch
+        rx, ry = self.empty(1), self.empty(1)
+        finite = torch.zeros((1,), dtype=torch.uint8, device=self.tdev)
+        invalid = torch.zeros((1,), dtype=torch.int32, device=self.tdev) if want_invalid else None
+        return rx, ry, finite, invalid
+
+    def msm(self, curve, k, x, y, bits=256, alg=0, want_invalid=False):
+        """ecsimd_msm: (rx, ry, finite) = the sum of (k[i] mod 2^bits) * (x[i], y[i]) as ONE affine point ((1, 4) tensors, (0, 0) and finite = 0 at infinity).
+        Points are validated; an invalid one counts as infinity.  want_invalid: a fourth tensor, the (1,) int32 number of invalid points.  PUBLIC data only.
+        Capturable after one warm-up call at the same (n, bits, alg): see CAPTURE in the header."""
+        n = int(k.shape[0])
+        if int(x.shape[0]) != n or int(y.shape[0]) != n:
+            raise EcsimdHipError(f"msm: operands disagree on the batch length: {sorted({n, int(x.shape[0]), int(y.shape[0])})}")
+        rx, ry, finite, invalid = self._msm_out(want_invalid)
+        kp, xp, yp = self._ptr(k), self._ptr(x), self._ptr(y)
+        self._rows.clear()
+        self._bind_stream()
+        self._check(self.lib.ecsimd_msm(self.ctx, C.c_int(curve), kp, xp, yp, C.c_void_p(rx.data_ptr()), C.c_void_p(ry.data_ptr()), C.c_void_p(finite.data_ptr()),
+                                        C.c_void_p(invalid.data_ptr() if want_invalid else 0), C.c_size_t(n), C.c_int(bits), C.c_int(alg)), "msm")
+        return (rx, ry, finite, invalid) if want_invalid else (rx, ry, finite)
+
+    def point_sum(self, curve, x, y, want_invalid=False):
+        """ecsimd_msm_point_sum: (rx, ry, finite) = the sum of the points (x[i], y[i]) as ONE affine point; validation and want_invalid as for msm."""
+        n = int(x.shape[0])
+        if int(y.shape[0]) != n:
+            raise EcsimdHipError(f"point_sum: operands disagree on the batch length: {sorted({n, int(y.shape[0])})}")
+        rx, ry, finite, invalid = self._msm_out(want_invalid)
+        xp, yp = self._ptr(x), self._ptr(y)
+        self._rows.clear()
+        self._bind_stream()
+        self._check(self.lib.ecsimd_msm_point_sum(self.ctx, C.c_int(curve), xp, yp, C.c_void_p(rx.data_ptr()), C.c_void_p(ry.data_ptr()), C.c_void_p(finite.data_ptr()),
+                                                  C.c_void_p(invalid.data_ptr() if want_invalid else 0), C.c_size_t(n)), "point_sum")
+        return (rx, ry, finite, invalid) if want_invalid else (rx, ry, finite)
 
     def _lens_ptr(self, what, lens, n):
         """The pointer of an optional int32 / uint32 device tensor of n lengths (None: NULL), as ecsimd_hip_keccak256 and the *_lens calls take it."""
