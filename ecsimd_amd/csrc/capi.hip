@@ -19,6 +19,7 @@
 #include "../../include/ecsimd_ed25519.h"
 #include "../../include/ecsimd_x25519.h"
 #include "../../include/ecsimd_msm.h"
+#include "../../include/ecsimd_schnorr_batch.h"
 #include "kernels.h"
 #include "point.cuh"   // curve constants for ecsimd_hip_get_constant (host-side constexpr use only)
 #include "gfield.cuh"  // gmod: a run-time modulus as the generic field kernels take it
@@ -2185,24 +2186,27 @@ int schnorr_common(ecsimd_hip_ctx* ctx, const char* what, const uint8_t* msg, si
   if (wants_compat(ctx)) return refuse_compat(ctx, what);
   return builtin_order(ctx, ECSIMD_HIP_SECP256K1, O);
 }
-}  // namespace
-
-// Verification: k_schnorr_verify_front (the challenge, the lift, the range checks), then u1 G + u2 P through double_scalar_mult's window loops with the front end's
-// validity byte (P was just built from the curve equation: no second validation pass), then k_schnorr_accept.  One chunk of 2^22 at a time, all in the workspace
-// behind the window loops' own part: u1, u2, P, R (six arrays), the validity and the finite bytes.
-int ecsimd_hip_schnorr_verify(ecsimd_hip_ctx* ctx, const uint64_t* px, const uint8_t* msg, size_t msg_bytes, size_t stride_bytes,
-                              const uint64_t* r, const uint64_t* s_, uint8_t* ok, size_t n) {
-  REQUIRE_CTX(); REQUIRE_PTR(px); REQUIRE_PTR(r); REQUIRE_PTR(s_);
-  if (!ok && n) return bad(ctx, "ok is null");
-  group_order O;
-  int rc = schnorr_common(ctx, "schnorr_verify", msg, msg_bytes, stride_bytes, n, &O); if (rc != ECSIMD_HIP_OK) return rc;
-  ENTER_ANY_SIZE();
+// The workspace of schnorr_verify_run for n signatures; verdicts_at: where the n verdict bytes of its ok == nullptr form begin (16-byte aligned), the last block.
+size_t schnorr_verify_bytes(size_t n, bool verdicts_inside, size_t* verdicts_at = nullptr) {
+  const size_t chunk = chunk_of(n, VARWIN_CHUNK), front = dsm_plan(nullptr, chunk).bytes;
+  const size_t own = front + recover_plan(nullptr, front, chunk, 2, true).extra, aligned = (own + 15) / 16 * 16;
+  if (verdicts_at) *verdicts_at = aligned;
+  return verdicts_inside ? aligned + flag_bytes(n) : own;
+}
+// Verification of n >= 1 signatures, behind the argument checks and ENTER: k_schnorr_verify_front (the challenge, the lift, the range checks), then u1 G + u2 P
+// through double_scalar_mult's window loops with the front end's validity byte (P was just built from the curve equation: no second validation pass), then
+// k_schnorr_accept.  One chunk of 2^22 at a time, all in the workspace behind the window loops' own part: u1, u2, P, R (six arrays), the validity and the finite
+// bytes.  ok == nullptr (schnorr_verify_batch's per-lane route): the verdict bytes go to the workspace, behind all of that, and *in_workspace is where.
+int schnorr_verify_run(ecsimd_hip_ctx* ctx, const group_order& O, const uint64_t* px, const uint8_t* msg, size_t msg_bytes, size_t stride_bytes,
+                       const uint64_t* r, const uint64_t* s_, uint8_t* ok, size_t n, uint8_t** in_workspace = nullptr) {
   const int curve = ECSIMD_HIP_SECP256K1;
   const size_t chunk = chunk_of(n, VARWIN_CHUNK), front = dsm_plan(nullptr, chunk).bytes;
+  size_t verdicts_at = 0;
   // sizes the workspace (and builds the table) first, so that the pointers taken below stay valid
-  rc = public_base_product(ctx, curve, n);
-  if (rc == ECSIMD_HIP_OK) rc = ensure_workspace(ctx, front + recover_plan(nullptr, front, chunk, 2, true).extra);
+  int rc = public_base_product(ctx, curve, n);
+  if (rc == ECSIMD_HIP_OK) rc = ensure_workspace(ctx, schnorr_verify_bytes(n, ok == nullptr, &verdicts_at));
   if (rc != ECSIMD_HIP_OK) return rc;
+  if (!ok) ok = *in_workspace = reinterpret_cast<uint8_t*>(ctx->workspace) + verdicts_at;
   const recover_layout L = recover_plan(ctx->workspace, front, chunk, 2, true);      // px, py: the lifted P; more: R; more_flags: the sums' finite bytes
   FOR_CHUNKS(first, m, n, chunk) {
     launch::schnorr_verify_front(ctx->stream, O.words, px + 4 * first, r + 4 * first, s_ + 4 * first, msg ? msg + first * stride_bytes : nullptr, msg_bytes, stride_bytes, L.u1, L.u2, L.px, L.py, L.valid, m);
@@ -2212,6 +2216,16 @@ int ecsimd_hip_schnorr_verify(ecsimd_hip_ctx* ctx, const uint64_t* px, const uin
   }
   hipError_t err = hipGetLastError();
   return err == hipSuccess ? ECSIMD_HIP_OK : fail(ctx, err, "schnorr_verify launch"); }
+}  // namespace
+
+int ecsimd_hip_schnorr_verify(ecsimd_hip_ctx* ctx, const uint64_t* px, const uint8_t* msg, size_t msg_bytes, size_t stride_bytes,
+                              const uint64_t* r, const uint64_t* s_, uint8_t* ok, size_t n) {
+  REQUIRE_CTX(); REQUIRE_PTR(px); REQUIRE_PTR(r); REQUIRE_PTR(s_);
+  if (!ok && n) return bad(ctx, "ok is null");
+  group_order O;
+  int rc = schnorr_common(ctx, "schnorr_verify", msg, msg_bytes, stride_bytes, n, &O); if (rc != ECSIMD_HIP_OK) return rc;
+  ENTER_ANY_SIZE();
+  return schnorr_verify_run(ctx, O, px, msg, msg_bytes, stride_bytes, r, s_, ok, n); }
 
 // Signing: d G on the constant-time comb with both coordinates through the simultaneous inversion, k_schnorr_nonce, k0 G the same way, k_schnorr_finish.  Per
 // element of a chunk: the Jacobian product (96 B, used twice), the affine d G and k0 G (64 B each), k0 (32 B) -- all zeroed behind the kernels (secret_base_product says why).
@@ -2486,16 +2500,17 @@ bool msm_schedule_of(size_t n, int bits, int flags, msm_schedule* S) {
   return true;
 }
 extern "C++" template <int CV> int msm_run(ecsimd_hip_ctx* ctx, const msm_schedule& S, const uint64_t* k, const uint64_t* x, const uint64_t* y, uint64_t* rx, uint64_t* ry, uint8_t* finite,
-                              uint32_t* invalid, size_t n, int bits) {
+                              uint32_t* invalid, size_t n, int bits, size_t offset = 0) {
+  // offset: the bytes at the start of the workspace that are the caller's (schnorr_verify_batch keeps its own arrays there); the blocks are carved behind them
   using ML = launch::msm_launch<CV>;
   const ecsimd_msm_plan_t& P = S.plan;
   hipStream_t s = ctx->stream;
   const int fan = launch::MSM_TREE_FAN;
   if (n == 0) { ML::finish(s, nullptr, 0, 0, 0, 0, nullptr, rx, ry, finite, invalid); const hipError_t e0 = hipGetLastError(); return e0 == hipSuccess ? ECSIMD_HIP_OK : fail(ctx, e0, "msm launch"); }
-  int rc = ensure_workspace(ctx, P.workspace_bytes);
+  int rc = ensure_workspace(ctx, offset + P.workspace_bytes);
   if (rc != ECSIMD_HIP_OK) return rc;
   size_t bytes = 0;
-  const msm_blocks B = msm_carve(S, n, ctx->workspace, &bytes);
+  const msm_blocks B = msm_carve(S, n, reinterpret_cast<uint8_t*>(ctx->workspace) + offset, &bytes);
   hipError_t e;
   ML::zero(s, B.counter, B.zero_bytes);
   size_t count, stride; int windows;
@@ -2509,7 +2524,7 @@ extern "C++" template <int CV> int msm_run(ecsimd_hip_ctx* ctx, const msm_schedu
     count = S.per_window; stride = S.per_window; windows = P.windows;
   } else {
     ML::sanitize(s, k, x, y, B.kk, B.px, B.py, B.counter, n, bits);
-    rc = run_varwin(ctx, CV, B.kk, 4, B.px, B.py, B.buckets, B.partial, n, ECSIMD_HIP_OUT_AFFINE | ECSIMD_HIP_ALG_WINDOWED, B.reserve);   // the workspace is large enough: nothing moves
+    rc = run_varwin(ctx, CV, B.kk, 4, B.px, B.py, B.buckets, B.partial, n, ECSIMD_HIP_OUT_AFFINE | ECSIMD_HIP_ALG_WINDOWED, offset + B.reserve);   // the workspace is large enough: nothing moves
     if (rc != ECSIMD_HIP_OK) return rc;
     ML::tree_affine(s, B.buckets, B.partial, false, B.counter, B.tree, n, S.front_lanes, fan);
     count = S.front_lanes; stride = 0; windows = 1;
@@ -2586,6 +2601,149 @@ int ecsimd_msm_point_sum(ecsimd_hip_ctx* ctx, int curve, const uint64_t* x, cons
   if ((n + launch::MSM_TREE_FAN - 1) / launch::MSM_TREE_FAN > MAX_LAUNCH) return bad(ctx, "batch too large");
   const hipError_t e0 = hipSetDevice(ctx->device); if (e0 != hipSuccess) return fail(ctx, e0, "hipSetDevice");
   return curve == ECSIMD_HIP_P256 ? point_sum_run<CURVE_P256>(ctx, x, y, rx, ry, finite, invalid, n) : point_sum_run<CURVE_SECP256K1>(ctx, x, y, rx, ry, finite, invalid, n); }
+
+// ---- BIP-340 batch verification (include/ecsimd_schnorr_batch.h; k_schnorr_batch.hip has the stages, tools/schnorr_batch_model.py the definition).  PUBLIC data.
+// sb_schedule_of is the ONE place that turns (n, msg_bytes, flags) into sizes: ecsimd_schnorr_batch_plan reports it, the calls enqueue from it.  The MSM route's
+// workspace: the call's own arrays first (sb_carve), then the blocks of the two bucket sums, which run one after the other and share their bytes.
+namespace {
+size_t fan_lanes(size_t count) { return (count + launch::SCHNORR_BATCH_FAN - 1) / launch::SCHNORR_BATCH_FAN; }
+int fan_passes(size_t count) { int p = 0; while (count > 1) { count = fan_lanes(count); ++p; } return p; }
+size_t fan_elements(size_t count) { size_t t = 0; while (count > 1) { count = fan_lanes(count); t += count; } return t; }      // every level below the leaves
+struct sb_blocks {
+  launch::schnorr_batch_head* head;
+  uint64_t *E, *leaf, *nodes, *a, *ae, *as, *sums, *Px, *Py, *Rx, *Ry;      // ae, Px, Py: n + 1 elements, the last one the G term; nodes, sums: the trees' levels, one behind the other
+  uint8_t* valid;
+};
+sb_blocks sb_carve(size_t n, void* base, size_t* bytes) {
+  sb_blocks B; carve c = carve_from(base);
+  B.head = static_cast<launch::schnorr_batch_head*>(carve_bytes(c, sizeof(launch::schnorr_batch_head)));
+  B.E = carve_limbs(c, n); B.leaf = carve_limbs(c, n); B.nodes = carve_limbs(c, fan_elements(n));
+  B.a = carve_limbs(c, n); B.ae = carve_limbs(c, n + 1); B.as = carve_limbs(c, n); B.sums = carve_limbs(c, fan_elements(n));
+  B.Px = carve_limbs(c, n + 1); B.Py = carve_limbs(c, n + 1); B.Rx = carve_limbs(c, n); B.Ry = carve_limbs(c, n);
+  B.valid = carve_flags(c, n);
+  (void)carve_bytes(c, (32 - c.bytes % 32) % 32);      // the sums' blocks start on 32 bytes
+  *bytes = c.bytes;
+  return B;
+}
+struct sb_schedule { ecsimd_schnorr_batch_plan_t plan; msm_schedule sum_r, sum_p; };
+// The MSM route's bytes for exactly n >= 1 signatures: its own arrays, then the larger of the two sums' blocks.
+size_t sb_msm_bytes(size_t n) {
+  msm_schedule r, p; size_t own = 0;
+  if (!msm_schedule_of(n, 128, ECSIMD_MSM_ALG_BUCKETS, &r) || !msm_schedule_of(n + 1, 256, ECSIMD_MSM_ALG_BUCKETS, &p)) return 0;
+  (void)sb_carve(n, nullptr, &own);
+  return own + (r.plan.workspace_bytes > p.plan.workspace_bytes ? r.plan.workspace_bytes : p.plan.workspace_bytes);
+}
+bool sb_route_ok(int flags) { return flags == ECSIMD_SCHNORR_BATCH_AUTO || flags == ECSIMD_SCHNORR_BATCH_MSM || flags == ECSIMD_SCHNORR_BATCH_LANES; }
+bool sb_schedule_of(size_t n, size_t msg_bytes, int flags, sb_schedule* S) {
+  if (n > ECSIMD_MSM_MAX_N - 1 || msg_bytes > ((size_t)1 << 40) || !sb_route_ok(flags)) return false;
+  *S = sb_schedule();
+  ecsimd_schnorr_batch_plan_t& P = S->plan;
+  P.route = flags != ECSIMD_SCHNORR_BATCH_AUTO ? flags : n >= ECSIMD_SCHNORR_BATCH_AUTO_THRESHOLD ? ECSIMD_SCHNORR_BATCH_MSM : ECSIMD_SCHNORR_BATCH_LANES;
+  if (n == 0) { P.launches = 1; return true; }                                   // the reduction kernel alone writes the empty batch's verdict
+  if (P.route == ECSIMD_SCHNORR_BATCH_MSM) {
+    if (!msm_schedule_of(n, 128, ECSIMD_MSM_ALG_BUCKETS, &S->sum_r) || !msm_schedule_of(n + 1, 256, ECSIMD_MSM_ALG_BUCKETS, &S->sum_p)) return false;
+    // What this batch needs, and what every smaller batch would: the bucket sums' blocks are not monotone in the number of terms (a wider window means fewer
+    // sorted entries), but between powers of two they are -- the window width, the bucket count and the segment split are fixed there and only the entries
+    // grow --, so the largest need below n is met at n itself or next to a power of two.  A context warmed up at n then serves every smaller batch in a capture.
+    P.workspace_bytes = sb_msm_bytes(n);
+    for (size_t p = 2; p <= n + 2; p <<= 1)
+      for (size_t m = p - 2; m <= p && m <= n; ++m)
+        if (m >= 1 && sb_msm_bytes(m) > P.workspace_bytes) P.workspace_bytes = sb_msm_bytes(m);
+    const int levels = fan_passes(n);
+    P.launches = 5 + levels + (levels > 1 ? levels : 1) + S->sum_r.plan.launches + S->sum_p.plan.launches;   // zero, front, seed, scalars, accept; the two trees; the two sums
+  } else {
+    P.workspace_bytes = schnorr_verify_bytes(n, true);
+    P.launches = 1 + 9 * (int)((n + VARWIN_CHUNK - 1) / VARWIN_CHUNK);
+  }
+  return true;
+}
+// Two byte ranges that share a byte (an empty or a null one shares none).
+bool ranges_overlap(const void* a, size_t abytes, const void* b, size_t bbytes) {
+  if (!a || !b || !abytes || !bbytes) return false;
+  const uintptr_t pa = reinterpret_cast<uintptr_t>(a), pb = reinterpret_cast<uintptr_t>(b);
+  return pa < pb + bbytes && pb < pa + abytes;
+}
+// What the two calls check alike, `out` being the `out_bytes` bytes either writes; fills O.
+int sb_check(ecsimd_hip_ctx* ctx, const char* what, const uint64_t* px, const uint8_t* msg, size_t msg_bytes, size_t stride_bytes, const uint64_t* r, const uint64_t* s_,
+             const void* out, size_t out_bytes, size_t n, group_order* O) {
+  REQUIRE_PTR(px); REQUIRE_PTR(r); REQUIRE_PTR(s_);
+  if (n > ECSIMD_MSM_MAX_N - 1) return bad(ctx, "schnorr batch: n is above ECSIMD_MSM_MAX_N - 1: verify chunks and AND their verdicts");
+  int rc = schnorr_common(ctx, what, msg, msg_bytes, stride_bytes, n, O); if (rc != ECSIMD_HIP_OK) return rc;
+  const size_t msg_extent = n ? (n - 1) * stride_bytes + msg_bytes : 0;
+  if (ranges_overlap(out, out_bytes, px, 32 * n) || ranges_overlap(out, out_bytes, r, 32 * n) || ranges_overlap(out, out_bytes, s_, 32 * n) ||
+      ranges_overlap(out, out_bytes, msg, msg_extent)) return bad(ctx, "schnorr batch: the output must not overlap an input");
+  return ECSIMD_HIP_OK;
+}
+// Stages 1 to 3 for n >= 1: the front, the hash tree, the seed, the scalars.  `a`: where the randomizers go (B.a, or the caller's array).
+void sb_randomizers(ecsimd_hip_ctx* ctx, const group_order& O, const sb_blocks& B, const uint64_t* px, const uint8_t* msg, size_t msg_bytes, size_t stride_bytes,
+                    const uint64_t* r, const uint64_t* s_, uint64_t* a, size_t n) {
+  hipStream_t s = ctx->stream;
+  launch::msm_launch<CURVE_SECP256K1>::zero(s, B.head, sizeof(launch::schnorr_batch_head));
+  launch::schnorr_batch_front(s, O.words, px, r, s_, msg, msg_bytes, stride_bytes, B.E, B.leaf, B.Px, B.Py, B.Rx, B.Ry, B.valid, B.head, n);
+  const uint64_t* level = B.leaf; uint64_t* out = B.nodes;
+  for (size_t count = n; count > 1;) {
+    launch::schnorr_batch_node(s, level, count, out);
+    count = fan_lanes(count); level = out; out += 4 * count;
+  }
+  launch::schnorr_batch_seed(s, level, n, B.head);
+  launch::schnorr_batch_scalars(s, O.N, B.head, B.E, s_, B.valid, a, B.ae, B.as, n);
+}
+}  // namespace
+
+int ecsimd_schnorr_batch_plan(size_t n, size_t msg_bytes, int flags, ecsimd_schnorr_batch_plan_t* out) {
+  sb_schedule S;
+  if (!out || !sb_schedule_of(n, msg_bytes, flags, &S)) return ECSIMD_HIP_ERR_BAD_ARG;
+  *out = S.plan;
+  return ECSIMD_HIP_OK; }
+
+int ecsimd_schnorr_verify_batch(ecsimd_hip_ctx* ctx, const uint64_t* px, const uint8_t* msg, size_t msg_bytes, size_t stride_bytes,
+                                const uint64_t* r, const uint64_t* s_, uint8_t* ok, size_t n, int flags) {
+  REQUIRE_CTX();
+  if (!ok) return bad(ctx, "schnorr_verify_batch: ok is null");
+  if (!sb_route_ok(flags)) return bad(ctx, "schnorr_verify_batch: flags must be ECSIMD_SCHNORR_BATCH_AUTO, ECSIMD_SCHNORR_BATCH_MSM or ECSIMD_SCHNORR_BATCH_LANES");
+  group_order O;
+  int rc = sb_check(ctx, "schnorr_verify_batch", px, msg, msg_bytes, stride_bytes, r, s_, ok, 1, n, &O); if (rc != ECSIMD_HIP_OK) return rc;
+  sb_schedule S;
+  if (!sb_schedule_of(n, msg_bytes, flags, &S)) return bad(ctx, "schnorr_verify_batch: no schedule for these arguments");
+  const hipError_t e0 = hipSetDevice(ctx->device); if (e0 != hipSuccess) return fail(ctx, e0, "hipSetDevice");
+  hipStream_t s = ctx->stream;
+  if (n == 0) launch::schnorr_batch_all(s, nullptr, 0, ok);
+  else if (S.plan.route == ECSIMD_SCHNORR_BATCH_LANES) {
+    uint8_t* verdicts = nullptr;
+    rc = schnorr_verify_run(ctx, O, px, msg, msg_bytes, stride_bytes, r, s_, nullptr, n, &verdicts); if (rc != ECSIMD_HIP_OK) return rc;
+    launch::schnorr_batch_all(s, verdicts, n, ok);
+  } else {
+    rc = ensure_workspace(ctx, S.plan.workspace_bytes); if (rc != ECSIMD_HIP_OK) return rc;      // all of it now: the sums below find it large enough, nothing moves
+    size_t own = 0;
+    const sb_blocks B = sb_carve(n, ctx->workspace, &own);
+    sb_randomizers(ctx, O, B, px, msg, msg_bytes, stride_bytes, r, s_, B.a, n);
+    const uint64_t* in = B.as; uint64_t* out = B.sums;
+    for (size_t count = n, lanes = 0; lanes != 1; count = lanes) {                                  // sum a s: the last level writes term n of the key sum
+      lanes = fan_lanes(count);
+      const bool last = lanes == 1;
+      launch::schnorr_batch_sum(s, O.N, in, count, last ? B.ae + 4 * n : out, last ? B.Px + 4 * n : nullptr, last ? B.Py + 4 * n : nullptr);
+      in = out; out += 4 * lanes;
+    }
+    rc = msm_run<CURVE_SECP256K1>(ctx, S.sum_r, B.a, B.Rx, B.Ry, B.head->rx[0], B.head->ry[0], &B.head->finite[0], &B.head->invalid[0], n, 128, own);
+    if (rc == ECSIMD_HIP_OK) rc = msm_run<CURVE_SECP256K1>(ctx, S.sum_p, B.ae, B.Px, B.Py, B.head->rx[1], B.head->ry[1], &B.head->finite[1], &B.head->invalid[1], n + 1, 256, own);
+    if (rc != ECSIMD_HIP_OK) return rc;
+    launch::schnorr_batch_accept(s, B.head, ok);
+  }
+  const hipError_t e = hipGetLastError();
+  return e == hipSuccess ? ECSIMD_HIP_OK : fail(ctx, e, "schnorr_verify_batch launch"); }
+
+int ecsimd_schnorr_batch_randomizers(ecsimd_hip_ctx* ctx, const uint64_t* px, const uint8_t* msg, size_t msg_bytes, size_t stride_bytes,
+                                     const uint64_t* r, const uint64_t* s_, uint64_t* a, size_t n) {
+  REQUIRE_CTX(); REQUIRE_PTR(a);
+  group_order O;
+  int rc = sb_check(ctx, "schnorr_batch_randomizers", px, msg, msg_bytes, stride_bytes, r, s_, a, 32 * n, n, &O); if (rc != ECSIMD_HIP_OK) return rc;
+  ENTER_ANY_SIZE();
+  size_t own = 0;
+  (void)sb_carve(n, nullptr, &own);
+  rc = ensure_workspace(ctx, own); if (rc != ECSIMD_HIP_OK) return rc;
+  sb_randomizers(ctx, O, sb_carve(n, ctx->workspace, &own), px, msg, msg_bytes, stride_bytes, r, s_, a, n);
+  const hipError_t e = hipGetLastError();
+  return e == hipSuccess ? ECSIMD_HIP_OK : fail(ctx, e, "schnorr_batch_randomizers launch"); }
 
 int ecsimd_hip_fe29_raw(ecsimd_hip_ctx* ctx, int curve, int op, const int32_t* in, int32_t* out, size_t n, int swap) {
   REQUIRE_CTX(); if ((!in || !out) && n) return bad(ctx, "fe29_raw: null pointer");

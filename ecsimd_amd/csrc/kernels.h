@@ -333,6 +333,24 @@ template <int C> struct msm_launch {
   static void finish(hipStream_t, const uint64_t* arr, size_t total, size_t stride, int windows, int c, const uint32_t* counter, uint64_t* rx, uint64_t* ry, uint8_t* finite,
                      uint32_t* invalid);
 };
+// k_schnorr_batch.hip: BIP-340 batch verification (include/ecsimd_schnorr_batch.h; PUBLIC data).  Every launcher enqueues ONE kernel.  The call's header block in
+// the workspace: the seed, the two sums as msm_launch::finish writes them (0: sum a R, 1: the key sum with the G term), the malformed lanes' counter.  192 bytes,
+// zeroed by msm_launch::zero.
+constexpr int SCHNORR_BATCH_FAN = 16;            // children per node of the hash tree, terms per lane of the tree of additions modulo n
+struct schnorr_batch_head { uint64_t seed[4], rx[2][4], ry[2][4]; uint32_t malformed, invalid[2]; uint8_t finite[2], unused[18]; };
+// front: E = the challenge digest, leaf, (Px, Py) and (Rx, Ry) = the even-y lifts ((0, 0) on a malformed lane, which is counted in head->malformed), valid.
+// node: out[j] = H_node(in[16 j ..]) for j < ceil(count / 16).  seed: head->seed from the root and n.  scalars: a, a e mod n, a s mod n (0 where not valid).
+// sum: out[j] = sum of in[16 j ..] mod n; with gx (count <= 16): out[0] = n - sum (0 stays 0) and (gx, gy)[0] = G.  accept: ok[0] from head.
+// all: ok[0] = every one of the n bytes of flags (16-byte aligned) is 1; n = 0: 1.
+void schnorr_batch_front(hipStream_t, const words8& order, const uint64_t* px, const uint64_t* r, const uint64_t* s, const uint8_t* msg, size_t msg_bytes, size_t stride_bytes,
+                         uint64_t* E, uint64_t* leaf, uint64_t* Px, uint64_t* Py, uint64_t* Rx, uint64_t* Ry, uint8_t* valid, schnorr_batch_head* head, size_t n);
+void schnorr_batch_node(hipStream_t, const uint64_t* in, size_t count, uint64_t* out);
+void schnorr_batch_seed(hipStream_t, const uint64_t* root, size_t n, schnorr_batch_head* head);
+void schnorr_batch_scalars(hipStream_t, const gmod& order, const schnorr_batch_head* head, const uint64_t* E, const uint64_t* s, const uint8_t* valid, uint64_t* a, uint64_t* ae,
+                           uint64_t* as, size_t n);
+void schnorr_batch_sum(hipStream_t, const gmod& order, const uint64_t* in, size_t count, uint64_t* out, uint64_t* gx, uint64_t* gy);
+void schnorr_batch_accept(hipStream_t, const schnorr_batch_head* head, uint8_t* ok);
+void schnorr_batch_all(hipStream_t, const uint8_t* flags, size_t n, uint8_t* ok);
 inline size_t scalar_mult_x_scratch_bytes(size_t n) { return 4 * n * 32 + ((n + 31) & ~(size_t)31); }   // odd scalars, num, den, 1/den, zero flags
 // The 4-bit fixed-base table in LDS (BASELINE configs[2]): odd digits only (round 3) -- the regular recoding of the odd one of k mod n, n - k, as in
 // the big-window kernel: 64 windows x 8 odd multiples (2d + 1) 16^w G = 32 KiB, 63 mixed additions, no zero digit and therefore no "skip" / "infinity"

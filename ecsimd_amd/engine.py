@@ -67,6 +67,11 @@ class MsmPlan(C.Structure):
                 ("launches", C.c_int), ("workspace_bytes", C.c_size_t)]
 
 
+class SchnorrBatchPlan(C.Structure):
+    """ecsimd_schnorr_batch_plan_t (include/ecsimd_schnorr_batch.h)."""
+    _fields_ = [("route", C.c_int), ("launches", C.c_int), ("workspace_bytes", C.c_size_t)]
+
+
 class Engine:
     """One context (HIP stream owner) on one GPU."""
 
@@ -628,6 +633,45 @@ class Engine:
         self._check(self.lib.ecsimd_msm_point_sum(self.ctx, C.c_int(curve), xp, yp, C.c_void_p(rx.data_ptr()), C.c_void_p(ry.data_ptr()), C.c_void_p(finite.data_ptr()),
                                                   C.c_void_p(invalid.data_ptr() if want_invalid else 0), C.c_size_t(n)), "point_sum")
         return (rx, ry, finite, invalid) if want_invalid else (rx, ry, finite)
+
+    # ---- BIP-340 batch verification (include/ecsimd_schnorr_batch.h): ONE verdict out of a batch.  PUBLIC data only.
+    @staticmethod
+    def schnorr_batch_plan(n, msg_bytes, route=0):
+        """ecsimd_schnorr_batch_plan: what schnorr_verify_batch(n signatures, messages of msg_bytes bytes, route) will do, as a dict (route, launches,
+        workspace_bytes).  Host only: needs the library, no GPU and no Engine."""
+        plan = SchnorrBatchPlan()
+        rc = load_library().ecsimd_schnorr_batch_plan(C.c_size_t(n), C.c_size_t(msg_bytes), C.c_int(route), C.byref(plan))
+        if rc != 0:
+            raise EcsimdHipError(f"schnorr_batch_plan(n={n}, msg_bytes={msg_bytes}, route={route}) failed ({rc}): n at most 2^24 - 1, msg_bytes at most 2^40, route 0, 1 or 2")
+        return {name: int(getattr(plan, name)) for name, _ in SchnorrBatchPlan._fields_}
+
+    def _schnorr_batch_args(self, what, px, msgs, r, s):
+        n = int(px.shape[0])
+        if int(r.shape[0]) != n or int(s.shape[0]) != n:
+            raise EcsimdHipError(f"{what}: operands disagree on the batch length: {sorted({n, int(r.shape[0]), int(s.shape[0])})}")
+        keep, mp, length, stride = self._messages(msgs, n)
+        args = (self._ptr(px), mp, length, stride, self._ptr(r), self._ptr(s))
+        self._rows.clear()
+        self._bind_stream()
+        return n, keep, args
+
+    def schnorr_verify_batch(self, px, msgs, r, s, route=0, out=None):
+        """ecsimd_schnorr_verify_batch: a (1,) uint8 tensor, 1 iff EVERY BIP-340 signature (r, s) of the rows of `msgs` under the x-only keys px is valid (a batch
+        with an invalid one passes with probability at most 2^-127 on the MSM route); an empty batch gives 1.  route: flags.SCHNORR_BATCH_*.  Which lane is at fault
+        is schnorr_verify's to say.  out: a (1,) uint8 device tensor to write instead of a new one.  Capturable after one warm-up call at the same (n, message
+        length, route)."""
+        n, keep, args = self._schnorr_batch_args("schnorr_verify_batch", px, msgs, r, s)
+        ok = self.torch.zeros((1,), dtype=self.torch.uint8, device=self.tdev) if out is None else out
+        assert ok.is_cuda and ok.device.index == self.device and ok.dtype == self.torch.uint8 and ok.numel() == 1, "out: one uint8 on the engine's device"
+        self._check(self.lib.ecsimd_schnorr_verify_batch(self.ctx, *args, C.c_void_p(ok.data_ptr()), C.c_size_t(n), C.c_int(route)), "schnorr_verify_batch")
+        return ok
+
+    def schnorr_batch_randomizers(self, px, msgs, r, s):
+        """ecsimd_schnorr_batch_randomizers: the (n, 4) randomizers a_i the MSM route of schnorr_verify_batch weighs the lanes with (odd, below 2^128)."""
+        n, keep, args = self._schnorr_batch_args("schnorr_batch_randomizers", px, msgs, r, s)
+        a = self.empty(n)
+        self._check(self.lib.ecsimd_schnorr_batch_randomizers(self.ctx, *args, C.c_void_p(a.data_ptr() if n else 0), C.c_size_t(n)), "schnorr_batch_randomizers")
+        return a
 
     def _lens_ptr(self, what, lens, n):
         """The pointer of an optional int32 / uint32 device tensor of n lengths (None: NULL), as ecsimd_hip_keccak256 and the *_lens calls take it."""

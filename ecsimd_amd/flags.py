@@ -16,3 +16,6 @@ ECDSA_LOW_S = 1               # ecsimd_hip_ecdsa_sign_recoverable only: s > n / 
 ETH_REQUIRE_LOW_S = 1         # ecsimd_hip_eth_recover only: s > n / 2 is refused (EIP-2)
 BIP32_ALL_HARDENED = 1        # ecsimd_hip_bip32_ckd_priv only: every index has bit 31 set (no point multiplication; a lane that breaks the promise is refused)
 ED25519_REJECT_SMALL_ORDER = 1   # ecsimd_ed25519_verify only: a small-order A or R is refused as well
+SCHNORR_BATCH_AUTO = 0        # ecsimd_schnorr_verify_batch only (include/ecsimd_schnorr_batch.h): LANES below ECSIMD_SCHNORR_BATCH_AUTO_THRESHOLD signatures, MSM from there on
+SCHNORR_BATCH_MSM = 1         # ... the randomized sum: two bucket multi-scalar multiplications and one verdict
+SCHNORR_BATCH_LANES = 2       # ... schnorr_verify's own path and one reduction

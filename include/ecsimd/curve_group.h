@@ -10,6 +10,7 @@
 #include <ecsimd/hash160.h>
 #include <ecsimd/sha256.h>
 #include <ecsimd/sha512.h>
+#include <ecsimd_schnorr_batch.h>
 #include <optional>
 #include <type_traits>
 
@@ -201,6 +202,15 @@ struct curve_group {
     hip::mask ok(m.size());
     hip::check(ecsimd_hip_schnorr_verify(hip::context(), px.data(), m.data(), m.msg_bytes(), m.stride_bytes(), r.data(), s.data(), ok.data(), m.size()), "ecsimd_hip_schnorr_verify");
     return ok;
+  }
+  // ONE verdict for the whole batch: true iff every signature is valid (ecsimd_schnorr_batch.h: a batch with an invalid one passes with probability at most
+  // 2^-127 on the MSM route; an empty batch is accepted).  route: ECSIMD_SCHNORR_BATCH_AUTO, _MSM or _LANES.  Waits for the stream to read the byte;
+  // hip::schnorr_verify_batch (ecsimd/schnorr_batch.h) leaves it on the device.  Which lane is at fault is schnorr_verify's to say.
+  static bool schnorr_verify_batch(WBN const& px, hip::messages const& m, WBN const& r, WBN const& s, int route = ECSIMD_SCHNORR_BATCH_AUTO) requires std::is_same_v<Curve, curve_secp256k1> {
+    same_length(px.size(), m.size(), "schnorr_verify_batch"); same_length(r.size(), m.size(), "schnorr_verify_batch"); same_length(s.size(), m.size(), "schnorr_verify_batch");
+    hip::mask ok(1);
+    hip::check(ecsimd_schnorr_verify_batch(hip::context(), px.data(), m.data(), m.msg_bytes(), m.stride_bytes(), r.data(), s.data(), ok.data(), m.size(), route), "ecsimd_schnorr_verify_batch");
+    return ok.get(0);
   }
   // Default signing with the SECRET keys d and the auxiliary randomness aux (nullptr: 32 zero bytes): returns (r, s), px = the x-only public keys.  ok[i] is
   // false -- and r = s = px = 0 -- where d is not in [1, n).  Both products run on the constant-time comb; no branch or address depends on d, aux or the nonce.
