@@ -20,6 +20,7 @@
 #include "../../include/ecsimd_x25519.h"
 #include "../../include/ecsimd_msm.h"
 #include "../../include/ecsimd_schnorr_batch.h"
+#include "../../include/ecsimd_ed25519_batch.h"
 #include "kernels.h"
 #include "point.cuh"   // curve constants for ecsimd_hip_get_constant (host-side constexpr use only)
 #include "gfield.cuh"  // gmod: a run-time modulus as the generic field kernels take it
@@ -2744,6 +2745,265 @@ int ecsimd_schnorr_batch_randomizers(ecsimd_hip_ctx* ctx, const uint64_t* px, co
   sb_randomizers(ctx, O, sb_carve(n, ctx->workspace, &own), px, msg, msg_bytes, stride_bytes, r, s_, a, n);
   const hipError_t e = hipGetLastError();
   return e == hipSuccess ? ECSIMD_HIP_OK : fail(ctx, e, "schnorr_batch_randomizers launch"); }
+
+// ---- The bucket method on the Edwards curve and Ed25519 batch verification (include/ecsimd_ed25519_batch.h; k_msm_ed25519.hip has the stages,
+// tools/ed25519_batch_model.py the definition).  PUBLIC data.  The sum's schedule is msm_schedule_of's BUCKETS route, field for field; its workspace is its own
+// (edm_carve).  edb_schedule_of is the ONE place that turns (n, msg_bytes, flags) into the batch's sizes.
+namespace {
+struct edm_blocks {
+  uint32_t *counter, *hist, *start, *cursor, *sorted;   // counter (refused encodings, broken invariants) and hist are ONE block, zeroed by one kernel
+  uint64_t *kk, *pre, *buckets, *partial, *tree;        // pre: three planes of n; buckets, partial, tree: four planes
+  size_t zero_bytes;
+};
+edm_blocks edm_carve(const msm_schedule& S, size_t n, void* base, size_t* bytes) {
+  edm_blocks B = {};
+  carve c = carve_from(base);
+  B.zero_bytes = round16(16 + 4 * S.K);
+  B.counter = static_cast<uint32_t*>(carve_bytes(c, B.zero_bytes)); B.hist = B.counter ? B.counter + 4 : nullptr;
+  B.start = static_cast<uint32_t*>(carve_bytes(c, round16(4 * (S.K + 1))));
+  B.cursor = static_cast<uint32_t*>(carve_bytes(c, round16(4 * S.K)));
+  B.sorted = static_cast<uint32_t*>(carve_bytes(c, round16(4 * S.T)));
+  B.kk = carve_limbs(c, n); B.pre = carve_limbs(c, 3 * n);
+  B.buckets = carve_limbs(c, 4 * S.K); B.partial = carve_limbs(c, 4 * 2 * S.slices); B.tree = carve_limbs(c, 4 * S.chunk_lanes);
+  *bytes = c.bytes;
+  return B;
+}
+bool edm_schedule_of(size_t n, int bits, int flags, msm_schedule* S) {
+  if (flags != ECSIMD_MSM_ALG_AUTO && flags != ECSIMD_MSM_ALG_BUCKETS) return false;                 // the bucket route only
+  if (!msm_schedule_of(n, bits, ECSIMD_MSM_ALG_BUCKETS, S)) return false;
+  S->plan.workspace_bytes = 0;
+  if (n) (void)edm_carve(*S, n, nullptr, &S->plan.workspace_bytes);
+  return true;
+}
+// out: the encoding (raw == nullptr) or raw: the extended point.  offset: the bytes at the start of the workspace that are the caller's.
+int edm_run(ecsimd_hip_ctx* ctx, const msm_schedule& S, const uint8_t* k, const uint8_t* pts, uint8_t* out, uint64_t* raw, uint8_t* finite, uint32_t* invalid, size_t n, int bits,
+            size_t offset = 0) {
+  using ML = launch::msm_launch<CURVE_SECP256K1>;       // zero, scan and scatter do not depend on the curve
+  const ecsimd_msm_plan_t& P = S.plan;
+  hipStream_t s = ctx->stream;
+  const int fan = launch::MSM_TREE_FAN;
+  if (n == 0) { launch::ed25519_msm_finish(s, nullptr, 0, 0, 0, 0, nullptr, out, raw, finite, invalid); const hipError_t e0 = hipGetLastError(); return e0 == hipSuccess ? ECSIMD_HIP_OK : fail(ctx, e0, "ed25519_msm launch"); }
+  int rc = ensure_workspace(ctx, offset + P.workspace_bytes);
+  if (rc != ECSIMD_HIP_OK) return rc;
+  size_t bytes = 0;
+  const edm_blocks B = edm_carve(S, n, reinterpret_cast<uint8_t*>(ctx->workspace) + offset, &bytes);
+  ML::zero(s, B.counter, B.zero_bytes);
+  launch::ed25519_msm_digits(s, k, pts, B.kk, B.pre, B.hist, B.counter, n, bits, P.c, P.windows);
+  ML::scan(s, B.hist, B.start, B.cursor, S.K);
+  ML::scatter(s, B.kk, B.cursor, B.sorted, B.counter + 1, n, S.T, P.c, P.windows);
+  launch::ed25519_msm_slices(s, B.sorted, B.kk, B.pre, B.start, B.buckets, B.partial, B.counter + 1, n, S.T, P.L, S.slices, P.c, S.K);
+  launch::ed25519_msm_combine(s, B.start, B.buckets, B.partial, B.counter + 1, P.L, S.slices, P.c, S.K);
+  launch::ed25519_msm_chunks(s, B.buckets, B.tree, S.chunk_lanes, S.per_window, P.c, (int)P.m, S.K);
+  for (size_t count = S.per_window; count > 1;) {
+    const size_t lanes = (count + fan - 1) / fan;
+    launch::ed25519_msm_tree(s, B.tree, S.chunk_lanes, count, S.per_window, (size_t)P.windows, lanes, fan);
+    count = lanes;
+  }
+  launch::ed25519_msm_finish(s, B.tree, S.chunk_lanes, S.per_window, P.windows, P.c, B.counter, out, raw, finite, invalid);
+  const hipError_t e = hipGetLastError();
+  return e == hipSuccess ? ECSIMD_HIP_OK : fail(ctx, e, "ed25519_msm launch");
+}
+
+// The per-lane cofactored rule, a chunk at a time: s, h, R's (x, y), the table of -A, valid.
+struct edc_layout { uint64_t *s, *h, *rxy; void* table; uint8_t* valid; size_t bytes; };
+edc_layout edc_plan(void* base, size_t chunk) {
+  edc_layout L; carve c = carve_from(base);
+  L.s = carve_limbs(c, chunk); L.h = carve_limbs(c, chunk); L.rxy = carve_limbs(c, 2 * chunk); L.table = carve_bytes(c, launch::ed25519_table_bytes(chunk)); L.valid = carve_flags(c, chunk);
+  L.bytes = c.bytes;
+  return L;
+}
+size_t round32(size_t b) { return (b + 31) / 32 * 32; }
+size_t edc_bytes(size_t n, bool own_verdicts) { return (own_verdicts ? round32(flag_bytes(n)) : 0) + edc_plan(nullptr, chunk_of(n, ED25519_VERIFY_CHUNK)).bytes; }
+// ok == nullptr: the verdicts go to the first bytes of the workspace (*verdicts), the chunk's arrays behind them.  n >= 1.
+int edc_run(ecsimd_hip_ctx* ctx, const uint8_t* pk, const uint8_t* msg, size_t msg_bytes, size_t stride_bytes, const uint32_t* lens, const uint8_t* sig, uint8_t* ok, size_t n,
+            bool reject_small, uint8_t** verdicts) {
+  const size_t own = ok ? 0 : round32(flag_bytes(n)), chunk = chunk_of(n, ED25519_VERIFY_CHUNK);
+  const int rc = ensure_workspace(ctx, edc_bytes(n, !ok));
+  if (rc != ECSIMD_HIP_OK) return rc;
+  uint8_t* base = reinterpret_cast<uint8_t*>(ctx->workspace);
+  if (!ok) ok = base;
+  if (verdicts) *verdicts = ok;
+  const edc_layout L = edc_plan(base + own, chunk);
+  FOR_CHUNKS(first, m, n, chunk) {
+    launch::ed25519_cofactored_front(ctx->stream, *ed25519_order(), pk + 32 * first, sig + 64 * first, msg ? msg + first * stride_bytes : nullptr, msg_bytes, stride_bytes,
+                                     lens ? lens + first : nullptr, reject_small, L.s, L.h, L.rxy, L.table, L.valid, m);
+    launch::ed25519_cofactored_loop(ctx->stream, L.s, L.h, L.rxy, L.table, L.valid, ok + first, m);
+  }
+  return ECSIMD_HIP_OK;
+}
+
+size_t edb_fan_lanes(size_t count) { return (count + launch::ED25519_BATCH_FAN - 1) / launch::ED25519_BATCH_FAN; }
+int edb_fan_passes(size_t count) { int p = 0; while (count > 1) { count = edb_fan_lanes(count); ++p; } return p; }
+size_t edb_fan_elements(size_t count) { size_t t = 0; while (count > 1) { count = edb_fan_lanes(count); t += count; } return t; }      // every level below the leaves
+struct edb_blocks {
+  launch::ed25519_batch_head* head;
+  uint64_t *h, *leaf, *nodes, *z, *zh, *zs, *sums, *Aenc, *Renc;      // zh, Aenc: n + 1 elements, the last one the B term; nodes, sums: the trees' levels, one behind the other
+  uint8_t* valid;
+};
+edb_blocks edb_carve(size_t n, void* base, size_t* bytes) {
+  edb_blocks B; carve c = carve_from(base);
+  B.head = static_cast<launch::ed25519_batch_head*>(carve_bytes(c, sizeof(launch::ed25519_batch_head)));
+  B.h = carve_limbs(c, n); B.leaf = carve_limbs(c, n); B.nodes = carve_limbs(c, edb_fan_elements(n));
+  B.z = carve_limbs(c, n); B.zh = carve_limbs(c, n + 1); B.zs = carve_limbs(c, n); B.sums = carve_limbs(c, edb_fan_elements(n));
+  B.Aenc = carve_limbs(c, n + 1); B.Renc = carve_limbs(c, n);
+  B.valid = carve_flags(c, n);
+  (void)carve_bytes(c, (32 - c.bytes % 32) % 32);      // the sums' blocks start on 32 bytes
+  *bytes = c.bytes;
+  return B;
+}
+constexpr int EDB_KEY_BITS = 253;                       // z h mod L and L - sum z s are below L < 2^253
+struct edb_schedule { ecsimd_ed25519_batch_plan_t plan; msm_schedule sum_r, sum_a; bool reject_small; };
+// The MSM route's bytes for exactly n >= 1 signatures: its own arrays, then the larger of the two sums' blocks (they run one after the other).
+size_t edb_msm_bytes(size_t n) {
+  msm_schedule r, a; size_t own = 0;
+  if (!edm_schedule_of(n, 128, ECSIMD_MSM_ALG_BUCKETS, &r) || !edm_schedule_of(n + 1, EDB_KEY_BITS, ECSIMD_MSM_ALG_BUCKETS, &a)) return 0;
+  (void)edb_carve(n, nullptr, &own);
+  return own + (r.plan.workspace_bytes > a.plan.workspace_bytes ? r.plan.workspace_bytes : a.plan.workspace_bytes);
+}
+bool edb_flags_ok(int flags) {
+  const int route = flags & ~ECSIMD_ED25519_REJECT_SMALL_ORDER;
+  return flags >= 0 && (route == ECSIMD_ED25519_BATCH_AUTO || route == ECSIMD_ED25519_BATCH_MSM || route == ECSIMD_ED25519_BATCH_LANES);
+}
+bool edb_schedule_of(size_t n, size_t msg_bytes, int flags, edb_schedule* S) {
+  if (n > ECSIMD_MSM_MAX_N - 1 || msg_bytes > ((size_t)1 << 40) || !edb_flags_ok(flags)) return false;
+  *S = edb_schedule();
+  ecsimd_ed25519_batch_plan_t& P = S->plan;
+  const int route = flags & ~ECSIMD_ED25519_REJECT_SMALL_ORDER;
+  S->reject_small = (flags & ECSIMD_ED25519_REJECT_SMALL_ORDER) != 0;
+  P.route = route != ECSIMD_ED25519_BATCH_AUTO ? route : n >= ECSIMD_ED25519_BATCH_AUTO_THRESHOLD ? ECSIMD_ED25519_BATCH_MSM : ECSIMD_ED25519_BATCH_LANES;
+  if (n == 0) { P.launches = 1; return true; }                                   // the reduction kernel alone writes the empty batch's verdict
+  if (P.route == ECSIMD_ED25519_BATCH_MSM) {
+    if (!edm_schedule_of(n, 128, ECSIMD_MSM_ALG_BUCKETS, &S->sum_r) || !edm_schedule_of(n + 1, EDB_KEY_BITS, ECSIMD_MSM_ALG_BUCKETS, &S->sum_a)) return false;
+    // What this batch needs, and what every smaller batch would: as in sb_schedule_of, the sums' blocks are monotone in the number of terms between powers of
+    // two only, so the largest need below n is met at n itself or next to a power of two.
+    P.workspace_bytes = edb_msm_bytes(n);
+    for (size_t p = 2; p <= n + 2; p <<= 1)
+      for (size_t m = p - 2; m <= p && m <= n; ++m)
+        if (m >= 1 && edb_msm_bytes(m) > P.workspace_bytes) P.workspace_bytes = edb_msm_bytes(m);
+    const int levels = edb_fan_passes(n);
+    P.launches = 5 + levels + (levels > 1 ? levels : 1) + S->sum_r.plan.launches + S->sum_a.plan.launches;   // zero, front, seed, scalars, accept; the two trees; the two sums
+  } else {
+    P.workspace_bytes = edc_bytes(n, true);
+    P.launches = 1 + 2 * (int)((n + ED25519_VERIFY_CHUNK - 1) / ED25519_VERIFY_CHUNK);
+  }
+  return true;
+}
+// What the batch calls check alike, `out` being the `out_bytes` bytes either writes; msg_bytes comes back as 0 where lens rules.
+int edb_check(ecsimd_hip_ctx* ctx, const uint8_t* pk, const uint8_t* msg, size_t* msg_bytes, size_t stride_bytes, const uint32_t* lens, const uint8_t* sig, const void* out,
+              size_t out_bytes, size_t n) {
+  if ((!pk || !sig) && n) return bad(ctx, "ed25519 batch: pk or sig is null");
+  if (n > ECSIMD_MSM_MAX_N - 1) return bad(ctx, "ed25519 batch: n is above ECSIMD_MSM_MAX_N - 1: verify chunks and AND their verdicts");
+  const int rc = ed25519_messages(ctx, msg, msg_bytes, stride_bytes, lens, n); if (rc != ECSIMD_HIP_OK) return rc;
+  const size_t msg_extent = n ? (n - 1) * stride_bytes + (lens ? stride_bytes : *msg_bytes) : 0;
+  if (ranges_overlap(out, out_bytes, pk, 32 * n) || ranges_overlap(out, out_bytes, sig, 64 * n) || ranges_overlap(out, out_bytes, msg, msg_extent) ||
+      ranges_overlap(out, out_bytes, lens, 4 * n)) return bad(ctx, "ed25519 batch: the output must not overlap an input");
+  return ECSIMD_HIP_OK;
+}
+// The front, the hash tree, the seed, the scalars for n >= 1.  z: where the randomizers go; products: also z h and z s (B.zh, B.zs).
+void edb_randomizers(ecsimd_hip_ctx* ctx, const edb_blocks& B, const uint8_t* pk, const uint8_t* msg, size_t msg_bytes, size_t stride_bytes, const uint32_t* lens,
+                     const uint8_t* sig, bool reject_small, uint64_t* z, bool products, size_t n) {
+  hipStream_t s = ctx->stream;
+  launch::msm_launch<CURVE_SECP256K1>::zero(s, B.head, sizeof(launch::ed25519_batch_head));
+  launch::ed25519_batch_front(s, *ed25519_order(), pk, sig, msg, msg_bytes, stride_bytes, lens, reject_small, B.h, B.leaf, B.Aenc, B.Renc, B.valid, B.head, n);
+  const uint64_t* level = B.leaf; uint64_t* out = B.nodes;
+  for (size_t count = n; count > 1;) {
+    launch::ed25519_batch_node(s, level, count, out);
+    count = edb_fan_lanes(count); level = out; out += 4 * count;
+  }
+  launch::ed25519_batch_seed(s, level, n, B.head);
+  launch::ed25519_batch_scalars(s, *ed25519_order(), B.head, B.h, sig, B.valid, z, products ? B.zh : nullptr, products ? B.zs : nullptr, n);
+}
+}  // namespace
+
+int ecsimd_ed25519_msm_plan(size_t n, int bits, int flags, ecsimd_msm_plan_t* out) {
+  msm_schedule S;
+  if (!out || !edm_schedule_of(n, bits, flags, &S)) return ECSIMD_HIP_ERR_BAD_ARG;
+  *out = S.plan;
+  return ECSIMD_HIP_OK; }
+
+int ecsimd_ed25519_msm(ecsimd_hip_ctx* ctx, const uint8_t* k, const uint8_t* pts, uint8_t* out, uint8_t* finite, uint32_t* invalid, size_t n, int bits, int flags) {
+  REQUIRE_CTX();
+  if ((!k || !pts) && n) return bad(ctx, "ed25519_msm: k or pts is null");
+  if (!out || !finite) return bad(ctx, "ed25519_msm: out or finite is null");
+  if (invalid && (reinterpret_cast<uintptr_t>(invalid) & 3u)) return bad(ctx, "ed25519_msm: invalid is not 4-byte aligned");
+  if (bits < 1 || bits > 256) return bad(ctx, "ed25519_msm: bits must be 1 .. 256");
+  if (n > ECSIMD_MSM_MAX_N) return bad(ctx, "ed25519_msm: n is above ECSIMD_MSM_MAX_N");
+  msm_schedule S;
+  if (!edm_schedule_of(n, bits, flags, &S)) return bad(ctx, "ed25519_msm: flags must be 0 or ECSIMD_MSM_ALG_BUCKETS: the bucket route only");
+  const void* outs[3] = {out, finite, invalid}; const size_t out_bytes[3] = {32, 1, 4};
+  for (int a = 0; a < 3; ++a) {
+    if (ranges_overlap(outs[a], out_bytes[a], k, 32 * n) || ranges_overlap(outs[a], out_bytes[a], pts, 32 * n)) return bad(ctx, "ed25519_msm: an output must not overlap an input or another output");
+    for (int b = a + 1; b < 3; ++b) if (ranges_overlap(outs[a], out_bytes[a], outs[b], out_bytes[b])) return bad(ctx, "ed25519_msm: an output must not overlap an input or another output");
+  }
+  const hipError_t e0 = hipSetDevice(ctx->device); if (e0 != hipSuccess) return fail(ctx, e0, "hipSetDevice");
+  return edm_run(ctx, S, k, pts, out, nullptr, finite, invalid, n, bits); }
+
+int ecsimd_ed25519_verify_cofactored(ecsimd_hip_ctx* ctx, const uint8_t* pk, const uint8_t* msg, size_t msg_bytes, size_t stride_bytes, const uint32_t* lens,
+                                     const uint8_t* sig, uint8_t* ok, size_t n, int flags) {
+  REQUIRE_CTX(); if ((!pk || !sig || !ok) && n) return bad(ctx, "ed25519_verify_cofactored: pk, sig or ok is null");
+  if (flags & ~ECSIMD_ED25519_REJECT_SMALL_ORDER) return bad(ctx, "ed25519_verify_cofactored: unknown flag");
+  int rc = ed25519_messages(ctx, msg, &msg_bytes, stride_bytes, lens, n); if (rc != ECSIMD_HIP_OK) return rc;
+  if (n != 0 && any_alias({ok}, {pk, msg, sig, lens})) return bad(ctx, "ed25519_verify_cofactored: ok must not alias an input");
+  ENTER_ANY_SIZE();
+  rc = edc_run(ctx, pk, msg, msg_bytes, stride_bytes, lens, sig, ok, n, (flags & ECSIMD_ED25519_REJECT_SMALL_ORDER) != 0, nullptr); if (rc != ECSIMD_HIP_OK) return rc;
+  const hipError_t err = hipGetLastError();
+  return err == hipSuccess ? ECSIMD_HIP_OK : fail(ctx, err, "ed25519_verify_cofactored launch"); }
+
+int ecsimd_ed25519_batch_plan(size_t n, size_t msg_bytes, int flags, ecsimd_ed25519_batch_plan_t* out) {
+  edb_schedule S;
+  if (!out || !edb_schedule_of(n, msg_bytes, flags, &S)) return ECSIMD_HIP_ERR_BAD_ARG;
+  *out = S.plan;
+  return ECSIMD_HIP_OK; }
+
+int ecsimd_ed25519_verify_batch(ecsimd_hip_ctx* ctx, const uint8_t* pk, const uint8_t* msg, size_t msg_bytes, size_t stride_bytes, const uint32_t* lens,
+                                const uint8_t* sig, uint8_t* ok, size_t n, int flags) {
+  REQUIRE_CTX();
+  if (!ok) return bad(ctx, "ed25519_verify_batch: ok is null");
+  if (!edb_flags_ok(flags)) return bad(ctx, "ed25519_verify_batch: flags must be ECSIMD_ED25519_BATCH_AUTO, _MSM or _LANES, or-able with ECSIMD_ED25519_REJECT_SMALL_ORDER");
+  int rc = edb_check(ctx, pk, msg, &msg_bytes, stride_bytes, lens, sig, ok, 1, n); if (rc != ECSIMD_HIP_OK) return rc;
+  edb_schedule S;
+  if (!edb_schedule_of(n, lens ? stride_bytes : msg_bytes, flags, &S)) return bad(ctx, "ed25519_verify_batch: no schedule for these arguments");
+  const hipError_t e0 = hipSetDevice(ctx->device); if (e0 != hipSuccess) return fail(ctx, e0, "hipSetDevice");
+  hipStream_t s = ctx->stream;
+  if (n == 0) launch::schnorr_batch_all(s, nullptr, 0, ok);
+  else if (S.plan.route == ECSIMD_ED25519_BATCH_LANES) {
+    uint8_t* verdicts = nullptr;
+    rc = edc_run(ctx, pk, msg, msg_bytes, stride_bytes, lens, sig, nullptr, n, S.reject_small, &verdicts); if (rc != ECSIMD_HIP_OK) return rc;
+    launch::schnorr_batch_all(s, verdicts, n, ok);      // k_schnorr_batch.hip's reduction: the AND of n bytes has no curve
+  } else {
+    rc = ensure_workspace(ctx, S.plan.workspace_bytes); if (rc != ECSIMD_HIP_OK) return rc;      // all of it now: the sums below find it large enough, nothing moves
+    size_t own = 0;
+    const edb_blocks B = edb_carve(n, ctx->workspace, &own);
+    edb_randomizers(ctx, B, pk, msg, msg_bytes, stride_bytes, lens, sig, S.reject_small, B.z, true, n);
+    const uint64_t* in = B.zs; uint64_t* out = B.sums;
+    for (size_t count = n, lanes = 0; lanes != 1; count = lanes) {                                  // sum z s: the last level writes term n of the key sum
+      lanes = edb_fan_lanes(count);
+      const bool last = lanes == 1;
+      launch::ed25519_batch_sum(s, *ed25519_order(), in, count, last ? B.zh + 4 * n : out, last ? B.Aenc + 4 * n : nullptr);
+      in = out; out += 4 * lanes;
+    }
+    rc = edm_run(ctx, S.sum_r, reinterpret_cast<const uint8_t*>(B.z), reinterpret_cast<const uint8_t*>(B.Renc), nullptr, B.head->sum[0], &B.head->finite[0], &B.head->invalid[0], n, 128, own);
+    if (rc == ECSIMD_HIP_OK) rc = edm_run(ctx, S.sum_a, reinterpret_cast<const uint8_t*>(B.zh), reinterpret_cast<const uint8_t*>(B.Aenc), nullptr, B.head->sum[1], &B.head->finite[1],
+                                          &B.head->invalid[1], n + 1, EDB_KEY_BITS, own);
+    if (rc != ECSIMD_HIP_OK) return rc;
+    launch::ed25519_batch_accept(s, B.head, ok);
+  }
+  const hipError_t e = hipGetLastError();
+  return e == hipSuccess ? ECSIMD_HIP_OK : fail(ctx, e, "ed25519_verify_batch launch"); }
+
+int ecsimd_ed25519_batch_randomizers(ecsimd_hip_ctx* ctx, const uint8_t* pk, const uint8_t* msg, size_t msg_bytes, size_t stride_bytes, const uint32_t* lens,
+                                     const uint8_t* sig, uint8_t* z, size_t n) {
+  REQUIRE_CTX();
+  if (!z && n) return bad(ctx, "ed25519_batch_randomizers: z is null");
+  if (!aligned16(z)) return bad(ctx, "ed25519_batch_randomizers: z is not 16-byte aligned");
+  int rc = edb_check(ctx, pk, msg, &msg_bytes, stride_bytes, lens, sig, z, 32 * n, n); if (rc != ECSIMD_HIP_OK) return rc;
+  ENTER_ANY_SIZE();
+  size_t own = 0;
+  (void)edb_carve(n, nullptr, &own);
+  rc = ensure_workspace(ctx, own); if (rc != ECSIMD_HIP_OK) return rc;
+  edb_randomizers(ctx, edb_carve(n, ctx->workspace, &own), pk, msg, msg_bytes, stride_bytes, lens, sig, false, reinterpret_cast<uint64_t*>(z), false, n);
+  const hipError_t e = hipGetLastError();
+  return e == hipSuccess ? ECSIMD_HIP_OK : fail(ctx, e, "ed25519_batch_randomizers launch"); }
 
 int ecsimd_hip_fe29_raw(ecsimd_hip_ctx* ctx, int curve, int op, const int32_t* in, int32_t* out, size_t n, int swap) {
   REQUIRE_CTX(); if ((!in || !out) && n) return bad(ctx, "fe29_raw: null pointer");

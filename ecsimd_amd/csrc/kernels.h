@@ -351,6 +351,39 @@ void schnorr_batch_scalars(hipStream_t, const gmod& order, const schnorr_batch_h
 void schnorr_batch_sum(hipStream_t, const gmod& order, const uint64_t* in, size_t count, uint64_t* out, uint64_t* gx, uint64_t* gy);
 void schnorr_batch_accept(hipStream_t, const schnorr_batch_head* head, uint8_t* ok);
 void schnorr_batch_all(hipStream_t, const uint8_t* flags, size_t n, uint8_t* ok);
+// k_msm_ed25519.hip: the bucket method on the twisted Edwards curve and Ed25519 batch verification (include/ecsimd_ed25519_batch.h; PUBLIC data).  Every launcher
+// enqueues ONE kernel.  The sum's stages are k_msm.inc's on ed25519.cuh's arithmetic; zero, scan and scatter are msm_launch<CURVE_SECP256K1>'s (they do not depend
+// on the curve).  Terms: k = n x 32 little-endian bytes, pts = n x 32-byte encodings, both at any alignment; kk = the masked scalars, pre = the decoded terms as
+// three planes of n (y + x, y - x, 2 d x y); buckets, partial and the tree are FOUR planes (X, Y, Z, T), the identity (0, 1, 1, 0).  finish: out = the 32-byte
+// encoding, or with raw != nullptr the extended point as 16 words at raw and no encoding.
+// The batch's header block in the workspace: the seed, the two sums as finish writes them raw (0: sum z R, 1: the key sum with the B term), the malformed lanes'
+// counter.  304 bytes, zeroed by msm_launch::zero.
+constexpr int ED25519_BATCH_FAN = 16;            // children per node of the hash tree, terms per lane of the tree of additions modulo L
+struct ed25519_batch_head { uint64_t seed[4], sum[2][16]; uint32_t malformed, invalid[2]; uint8_t finite[2], unused[2]; };
+void ed25519_msm_digits(hipStream_t, const uint8_t* k, const uint8_t* pts, uint64_t* kk, uint64_t* pre, uint32_t* hist, uint32_t* counter, size_t n, int bits, int c, int windows);
+void ed25519_msm_slices(hipStream_t, const uint32_t* sorted, const uint64_t* kk, const uint64_t* pre, const uint32_t* start, uint64_t* buckets, uint64_t* partial, uint32_t* broken,
+                        size_t n, size_t T, size_t L, size_t slices, int c, size_t K);
+void ed25519_msm_combine(hipStream_t, const uint32_t* start, uint64_t* buckets, const uint64_t* partial, uint32_t* broken, size_t L, size_t slices, int c, size_t K);
+void ed25519_msm_chunks(hipStream_t, const uint64_t* buckets, uint64_t* out, size_t lanes, size_t per_window, int c, int m, size_t K);
+void ed25519_msm_tree(hipStream_t, uint64_t* arr, size_t total, size_t count, size_t stride, size_t groups, size_t lanes, int fan);
+void ed25519_msm_finish(hipStream_t, const uint64_t* arr, size_t total, size_t stride, int windows, int c, const uint32_t* counter, uint8_t* out, uint64_t* raw, uint8_t* finite,
+                        uint32_t* invalid);
+// front: h = SHA-512(R || A || M) mod L, leaf, A and R copied to Aenc / Renc, valid = s < L (&& no small-order A or R); a lane that is not valid counts in
+// head->malformed.  node / seed: schnorr_batch's shapes under this call's tags.  scalars: z, and where zh is given z h mod L and z s mod L (0 where not valid).
+// sum: out[j] = sum of in[16 j ..] mod L; with benc (count <= 16): out[0] = L - sum (0 stays 0) and benc[0] = B's encoding.  accept: ok[0] from head.
+void ed25519_batch_front(hipStream_t, const gmod& L, const uint8_t* pk, const uint8_t* sig, const uint8_t* msg, size_t msg_bytes, size_t stride_bytes, const uint32_t* lens,
+                         bool reject_small_order, uint64_t* h, uint64_t* leaf, uint64_t* Aenc, uint64_t* Renc, uint8_t* valid, ed25519_batch_head* head, size_t n);
+void ed25519_batch_node(hipStream_t, const uint64_t* in, size_t count, uint64_t* out);
+void ed25519_batch_seed(hipStream_t, const uint64_t* root, size_t n, ed25519_batch_head* head);
+void ed25519_batch_scalars(hipStream_t, const gmod& L, const ed25519_batch_head* head, const uint64_t* h, const uint8_t* sig, const uint8_t* valid, uint64_t* z, uint64_t* zh,
+                           uint64_t* zs, size_t n);
+void ed25519_batch_sum(hipStream_t, const gmod& L, const uint64_t* in, size_t count, uint64_t* out, uint64_t* benc);
+void ed25519_batch_accept(hipStream_t, const ed25519_batch_head* head, uint8_t* ok);
+// The per-lane cofactored rule: front writes valid = s < L && A and R decode (&& no small-order A or R), s, h, R's affine (x, y) as two planes of n and the table
+// of 1 .. 8 times -A (ed25519_table_bytes(n) bytes); loop ok = valid && [8]([s]B - [h]A - R) is the identity.
+void ed25519_cofactored_front(hipStream_t, const gmod& L, const uint8_t* pk, const uint8_t* sig, const uint8_t* msg, size_t msg_bytes, size_t stride_bytes, const uint32_t* lens,
+                              bool reject_small_order, uint64_t* s, uint64_t* h, uint64_t* rxy, void* table, uint8_t* valid, size_t n);
+void ed25519_cofactored_loop(hipStream_t, const uint64_t* s, const uint64_t* h, const uint64_t* rxy, const void* table, const uint8_t* valid, uint8_t* ok, size_t n);
 inline size_t scalar_mult_x_scratch_bytes(size_t n) { return 4 * n * 32 + ((n + 31) & ~(size_t)31); }   // odd scalars, num, den, 1/den, zero flags
 // The 4-bit fixed-base table in LDS (BASELINE configs[2]): odd digits only (round 3) -- the regular recoding of the odd one of k mod n, n - k, as in
 // the big-window kernel: 64 windows x 8 odd multiples (2d + 1) 16^w G = 32 KiB, 63 mixed additions, no zero digit and therefore no "skip" / "infinity"

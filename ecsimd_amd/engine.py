@@ -72,6 +72,11 @@ class SchnorrBatchPlan(C.Structure):
     _fields_ = [("route", C.c_int), ("launches", C.c_int), ("workspace_bytes", C.c_size_t)]
 
 
+class Ed25519BatchPlan(C.Structure):
+    """ecsimd_ed25519_batch_plan_t (include/ecsimd_ed25519_batch.h)."""
+    _fields_ = [("route", C.c_int), ("launches", C.c_int), ("workspace_bytes", C.c_size_t)]
+
+
 class Engine:
     """One context (HIP stream owner) on one GPU."""
 
@@ -672,6 +677,81 @@ class Engine:
         a = self.empty(n)
         self._check(self.lib.ecsimd_schnorr_batch_randomizers(self.ctx, *args, C.c_void_p(a.data_ptr() if n else 0), C.c_size_t(n)), "schnorr_batch_randomizers")
         return a
+
+    # ---- Ed25519 batch verification and the Edwards bucket sum (include/ecsimd_ed25519_batch.h).  PUBLIC data only.
+    @staticmethod
+    def ed25519_msm_plan(n, bits=256, alg=0):
+        """ecsimd_ed25519_msm_plan: msm_plan's dict for the bucket sum on the Edwards curve (the same schedule, its own workspace_bytes).  Host only."""
+        plan = MsmPlan()
+        rc = load_library().ecsimd_ed25519_msm_plan(C.c_size_t(n), C.c_int(bits), C.c_int(alg), C.byref(plan))
+        if rc != 0:
+            raise EcsimdHipError(f"ed25519_msm_plan(n={n}, bits={bits}, alg={alg}) failed ({rc}): bits must be 1 .. 256, n at most 2^24, alg 0 or 1 (the bucket route only)")
+        return {name: int(getattr(plan, name)) for name, _ in MsmPlan._fields_}
+
+    def ed25519_msm(self, k, pts, bits=256, alg=0, want_invalid=False):
+        """ecsimd_ed25519_msm: (out, finite) = the (32,) uint8 encoding of the sum of (k[i] mod 2^bits) * P[i] and a (1,) uint8 flag (0 and the identity's
+        encoding for the neutral result); k: (n, 32) uint8 little-endian INTEGERS (not residues modulo L), pts: (n, 32) uint8 encodings.  An encoding that does
+        not decode strictly contributes nothing; want_invalid: a third tensor, the (1,) int32 number of them.  Capturable after one warm-up call."""
+        torch = self.torch
+        kp, n = self._rows_u8(k, 32, "k")
+        pp, n2 = self._rows_u8(pts, 32, "pts")
+        if n2 != n:
+            raise EcsimdHipError(f"ed25519_msm: operands disagree on the batch length: {sorted((n, n2))}")
+        out = torch.zeros((32,), dtype=torch.uint8, device=self.tdev)
+        finite = torch.zeros((1,), dtype=torch.uint8, device=self.tdev)
+        invalid = torch.zeros((1,), dtype=torch.int32, device=self.tdev) if want_invalid else None
+        self._bind_stream()
+        self._check(self.lib.ecsimd_ed25519_msm(self.ctx, kp, pp, C.c_void_p(out.data_ptr()), C.c_void_p(finite.data_ptr()), C.c_void_p(invalid.data_ptr() if want_invalid else 0),
+                                                C.c_size_t(n), C.c_int(bits), C.c_int(alg)), "ed25519_msm")
+        return (out, finite, invalid) if want_invalid else (out, finite)
+
+    def _ed25519_batch_args(self, what, pk, msgs, sig, lens):
+        pp, n = self._rows_u8(pk, 32, "pk")
+        gp, n2 = self._rows_u8(sig, 64, "sig")
+        if n2 != n:
+            raise EcsimdHipError(f"{what}: operands disagree on the batch length: {sorted((n, n2))}")
+        keep, mp, length, stride = self._messages(msgs, n)
+        lp = self._lens_ptr(what, lens if length.value else None, n)
+        self._bind_stream()
+        return n, keep, (pp, mp, length, stride, lp, gp)
+
+    def ed25519_verify_cofactored(self, pk, msgs, sig, lens=None, reject_small_order=False):
+        """ecsimd_ed25519_verify_cofactored: ok, one byte per lane: s < L, A AND R decode strictly, and [8]([s]B - [h]A - R) is the identity (strict encodings
+        with the cofactored equation; not ZIP-215).  The per-lane rule of ed25519_verify_batch: it names the culprits of a refused batch."""
+        n, keep, args = self._ed25519_batch_args("ed25519_verify_cofactored", pk, msgs, sig, lens)
+        ok = self.flags(n)
+        self._check(self.lib.ecsimd_ed25519_verify_cofactored(self.ctx, *args, C.c_void_p(ok.data_ptr()), C.c_size_t(n),
+                                                              C.c_int(ED25519_REJECT_SMALL_ORDER if reject_small_order else 0)), "ed25519_verify_cofactored")
+        return ok
+
+    @staticmethod
+    def ed25519_batch_plan(n, msg_bytes, flags=0):
+        """ecsimd_ed25519_batch_plan: what ed25519_verify_batch(n signatures, messages of at most msg_bytes bytes, flags) will do, as a dict (route, launches,
+        workspace_bytes).  Host only: needs the library, no GPU and no Engine."""
+        plan = Ed25519BatchPlan()
+        rc = load_library().ecsimd_ed25519_batch_plan(C.c_size_t(n), C.c_size_t(msg_bytes), C.c_int(flags), C.byref(plan))
+        if rc != 0:
+            raise EcsimdHipError(f"ed25519_batch_plan(n={n}, msg_bytes={msg_bytes}, flags={flags}) failed ({rc}): n at most 2^24 - 1, msg_bytes at most 2^40, "
+                                 "flags one of flags.ED25519_BATCH_* or-able with ED25519_REJECT_SMALL_ORDER")
+        return {name: int(getattr(plan, name)) for name, _ in Ed25519BatchPlan._fields_}
+
+    def ed25519_verify_batch(self, pk, msgs, sig, lens=None, flags=0, out=None):
+        """ecsimd_ed25519_verify_batch: a (1,) uint8 tensor, 1 iff EVERY lane passes ed25519_verify_cofactored's rule (a batch with a failing lane passes with
+        probability at most 2^-127 on the MSM route); an empty batch gives 1.  flags: flags.ED25519_BATCH_AUTO / _MSM / _LANES, or-able with
+        flags.ED25519_REJECT_SMALL_ORDER.  out: a (1,) uint8 device tensor to write instead of a new one.  Capturable after one warm-up at the same arguments."""
+        n, keep, args = self._ed25519_batch_args("ed25519_verify_batch", pk, msgs, sig, lens)
+        ok = self.torch.zeros((1,), dtype=self.torch.uint8, device=self.tdev) if out is None else out
+        assert ok.is_cuda and ok.device.index == self.device and ok.dtype == self.torch.uint8 and ok.numel() == 1, "out: one uint8 on the engine's device"
+        self._check(self.lib.ecsimd_ed25519_verify_batch(self.ctx, *args, C.c_void_p(ok.data_ptr()), C.c_size_t(n), C.c_int(flags)), "ed25519_verify_batch")
+        return ok
+
+    def ed25519_batch_randomizers(self, pk, msgs, sig, lens=None):
+        """ecsimd_ed25519_batch_randomizers: the (n, 32) uint8 little-endian randomizers z_i the MSM route of ed25519_verify_batch weighs the lanes with (odd,
+        below 2^128)."""
+        n, keep, args = self._ed25519_batch_args("ed25519_batch_randomizers", pk, msgs, sig, lens)
+        z = self.torch.zeros((n, 32), dtype=self.torch.uint8, device=self.tdev)
+        self._check(self.lib.ecsimd_ed25519_batch_randomizers(self.ctx, *args, C.c_void_p(z.data_ptr() if n else 0), C.c_size_t(n)), "ed25519_batch_randomizers")
+        return z
 
     def _lens_ptr(self, what, lens, n):
         """The pointer of an optional int32 / uint32 device tensor of n lengths (None: NULL), as ecsimd_hip_keccak256 and the *_lens calls take it."""

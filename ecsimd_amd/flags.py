@@ -19,3 +19,6 @@ ED25519_REJECT_SMALL_ORDER = 1   # ecsimd_ed25519_verify only: a small-order A o
 SCHNORR_BATCH_AUTO = 0        # ecsimd_schnorr_verify_batch only (include/ecsimd_schnorr_batch.h): LANES below ECSIMD_SCHNORR_BATCH_AUTO_THRESHOLD signatures, MSM from there on
 SCHNORR_BATCH_MSM = 1         # ... the randomized sum: two bucket multi-scalar multiplications and one verdict
 SCHNORR_BATCH_LANES = 2       # ... schnorr_verify's own path and one reduction
+ED25519_BATCH_AUTO = 0        # ecsimd_ed25519_verify_batch / _batch_plan only (include/ecsimd_ed25519_batch.h): LANES below ECSIMD_ED25519_BATCH_AUTO_THRESHOLD signatures, MSM from there on
+ED25519_BATCH_MSM = 2         # ... the randomized cofactored sum: two bucket multi-scalar multiplications on the Edwards curve and one verdict
+ED25519_BATCH_LANES = 4       # ... ed25519_verify_cofactored's own path and one reduction; all three or-able with ED25519_REJECT_SMALL_ORDER

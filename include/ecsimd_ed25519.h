@@ -31,7 +31,9 @@
  * R is never decompressed: a non-canonical or off-curve R cannot equal a canonical encoding.  With ECSIMD_ED25519_REJECT_SMALL_ORDER a lane whose A or R is
  * one of the eight small-order encodings (01 00..00, ec ff..ff 7f, 00..00, 00..00 80, c7176a70..037a and ..03fa, 26e8958f..fc05 and ..fc85) is refused as
  * well, as `verify_strict` implementations do.  DIFFERENCE FROM libcrypto (checked against OpenSSL 3.0.2): libcrypto accepts some non-canonical A, such as
- * y = p + 1 and 01 00..00 80; this call refuses them.  A cofactored (ZIP-215) mode does not exist here.  k is reduced modulo L before [k]A, as libcrypto
+ * y = p + 1 and 01 00..00 80; this call refuses them.  The cofactored equation (strict encodings; not ZIP-215) is ecsimd_ed25519_batch.h's: ecsimd_ed25519_verify_cofactored() per lane,
+ * ecsimd_ed25519_verify_batch() for one verdict per batch with ecsimd_ed25519_batch_plan() and ecsimd_ed25519_batch_randomizers(), on the bucket sum
+ * ecsimd_ed25519_msm() / ecsimd_ed25519_msm_plan().  k is reduced modulo L before [k]A, as libcrypto
  * reduces it, and there is no subgroup check: a key (or an R) with a small-order component is accepted or refused by that equation alone, so for
  * A = [a]B + T_A, R = [r]B + T_R, s = r + k a the verdict is whether T_R + [k mod L]T_A is the identity (tests/golden/ed25519_verdicts.json).
  */
