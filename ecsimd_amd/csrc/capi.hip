@@ -18,6 +18,7 @@
 #include "../../include/ecsimd_hip.h"
 #include "../../include/ecsimd_ed25519.h"
 #include "../../include/ecsimd_x25519.h"
+#include "../../include/ecsimd_p384.h"
 #include "../../include/ecsimd_msm.h"
 #include "../../include/ecsimd_schnorr_batch.h"
 #include "../../include/ecsimd_ed25519_batch.h"
@@ -2432,6 +2433,111 @@ int ecsimd_x25519_raw(ecsimd_hip_ctx* ctx, int op, const uint8_t* in, uint8_t* o
   FOR_CHUNKS(first, m, n, X25519_CHUNK) launch::x25519_raw(ctx->stream, op, in + 32 * ni * first, out + 32 * no * first, m);
   const hipError_t e = hipGetLastError();
   return e == hipSuccess ? ECSIMD_HIP_OK : fail(ctx, e, "x25519_raw launch"); }
+
+// ---- NIST P-384 (include/ecsimd_p384.h; k_p384.hip).  Bytes in, bytes out; the multiples of G are constants of the library, so nothing is built at run time
+// and the only thing a capture can refuse is a workspace that would have to grow.  ECSIMD_HIP_REF_SQUARE_COMPAT contexts are accepted: none of the reference's
+// arithmetic is involved.
+namespace {
+// One launch covers at most 2^16 lanes: the kernels hold a twelve-word point law in registers and run one wave per SIMD, so 2^16 lanes are one full round of
+// the device, a launch of the longest of them (verification) stays short on a shared device, and the lanes' tables take 75 MB of workspace.
+constexpr size_t P384_CHUNK = (size_t)1 << 16;
+struct p384_table_layout { uint32_t* table; size_t bytes; };
+p384_table_layout p384_table_plan(void* base, size_t chunk) {
+  p384_table_layout L; carve c = carve_from(base);
+  L.table = static_cast<uint32_t*>(carve_bytes(c, launch::p384_table_bytes(chunk)));
+  L.bytes = c.bytes;
+  return L;
+}
+struct p384_sign_layout { uint32_t* kws; size_t bytes; };
+p384_sign_layout p384_sign_plan(void* base, size_t chunk) {
+  p384_sign_layout L; carve c = carve_from(base);
+  L.kws = static_cast<uint32_t*>(carve_bytes(c, launch::p384_nonce_bytes(chunk)));
+  L.bytes = c.bytes;
+  return L;
+}
+}  // namespace
+
+int ecsimd_p384_sha384(ecsimd_hip_ctx* ctx, const uint8_t* msg, size_t msg_bytes, size_t stride_bytes, const uint32_t* lens, uint8_t* digest, size_t n) {
+  REQUIRE_CTX(); if (!digest && n) return bad(ctx, "p384_sha384: digest is null");
+  int rc = ed25519_messages(ctx, msg, &msg_bytes, stride_bytes, lens, n); if (rc != ECSIMD_HIP_OK) return rc;
+  if (n != 0 && any_alias({digest}, {msg, lens})) return bad(ctx, "p384_sha384: digest must not alias an input");
+  ENTER_ANY_SIZE();
+  FOR_CHUNKS(first, m, n, P384_CHUNK)
+    launch::p384_sha384(ctx->stream, msg ? msg + first * stride_bytes : nullptr, msg_bytes, stride_bytes, lens ? lens + first : nullptr, digest + 48 * first, m);
+  const hipError_t err = hipGetLastError();
+  return err == hipSuccess ? ECSIMD_HIP_OK : fail(ctx, err, "p384_sha384 launch"); }
+
+int ecsimd_p384_pubkey(ecsimd_hip_ctx* ctx, const uint8_t* d, uint8_t* pub, uint8_t* ok, size_t n) {
+  REQUIRE_CTX(); if ((!d || !pub || !ok) && n) return bad(ctx, "p384_pubkey: d, pub or ok is null");
+  if (n != 0 && any_alias({pub, ok}, {d})) return bad(ctx, "p384_pubkey: pub and ok must not alias an input or each other");
+  ENTER_ANY_SIZE();
+  FOR_CHUNKS(first, m, n, P384_CHUNK) launch::p384_pubkey(ctx->stream, d + 48 * first, pub + 96 * first, ok + first, m);
+  const hipError_t err = hipGetLastError();
+  return err == hipSuccess ? ECSIMD_HIP_OK : fail(ctx, err, "p384_pubkey launch"); }
+
+int ecsimd_p384_ecdh(ecsimd_hip_ctx* ctx, const uint8_t* d, const uint8_t* peer, uint8_t* z, uint8_t* ok, size_t n) {
+  REQUIRE_CTX(); if ((!d || !peer || !z || !ok) && n) return bad(ctx, "p384_ecdh: d, peer, z or ok is null");
+  if (n != 0 && any_alias({z, ok}, {d, peer})) return bad(ctx, "p384_ecdh: z and ok must not alias an input or each other");
+  ENTER_ANY_SIZE();
+  const size_t chunk = chunk_of(n, P384_CHUNK);
+  const int rc = ensure_workspace(ctx, p384_table_plan(nullptr, chunk).bytes);
+  if (rc != ECSIMD_HIP_OK) return rc;
+  const p384_table_layout L = p384_table_plan(ctx->workspace, chunk);
+  hipError_t err = hipSuccess;
+  FOR_CHUNKS(first, m, n, chunk) {
+    launch::p384_ecdh(ctx->stream, d + 48 * first, peer + 96 * first, L.table, z + 48 * first, ok + first, m);
+    err = wipe_workspace(ctx, L.bytes, hipGetLastError());        // multiples of the public peer: wiped all the same, no value of a secret call stays behind
+    if (err != hipSuccess) break;
+  }
+  return err == hipSuccess ? ECSIMD_HIP_OK : fail(ctx, err, "p384_ecdh launch"); }
+
+int ecsimd_p384_ecdsa_verify(ecsimd_hip_ctx* ctx, const uint8_t* pub, const uint8_t* digest, const uint8_t* sig, uint8_t* ok, size_t n) {
+  REQUIRE_CTX(); if ((!pub || !digest || !sig || !ok) && n) return bad(ctx, "p384_ecdsa_verify: pub, digest, sig or ok is null");
+  if (n != 0 && any_alias({ok}, {pub, digest, sig})) return bad(ctx, "p384_ecdsa_verify: ok must not alias an input");
+  ENTER_ANY_SIZE();
+  const size_t chunk = chunk_of(n, P384_CHUNK);
+  const int rc = ensure_workspace(ctx, p384_table_plan(nullptr, chunk).bytes);
+  if (rc != ECSIMD_HIP_OK) return rc;
+  const p384_table_layout L = p384_table_plan(ctx->workspace, chunk);
+  FOR_CHUNKS(first, m, n, chunk) launch::p384_verify(ctx->stream, pub + 96 * first, digest + 48 * first, sig + 96 * first, L.table, ok + first, m);
+  const hipError_t err = hipGetLastError();
+  return err == hipSuccess ? ECSIMD_HIP_OK : fail(ctx, err, "p384_ecdsa_verify launch"); }
+
+int ecsimd_p384_ecdsa_sign(ecsimd_hip_ctx* ctx, const uint8_t* d, const uint8_t* digest, uint8_t* sig, uint8_t* ok, size_t n, int flags) {
+  REQUIRE_CTX(); if ((!d || !digest || !sig || !ok) && n) return bad(ctx, "p384_ecdsa_sign: d, digest, sig or ok is null");
+  if (flags != 0) return bad(ctx, "p384_ecdsa_sign: flags must be 0");
+  if (n != 0 && any_alias({sig, ok}, {d, digest})) return bad(ctx, "p384_ecdsa_sign: sig and ok must not alias an input or each other");
+  ENTER_ANY_SIZE();
+  const size_t chunk = chunk_of(n, P384_CHUNK);
+  const int rc = ensure_workspace(ctx, p384_sign_plan(nullptr, chunk).bytes);
+  if (rc != ECSIMD_HIP_OK) return rc;
+  const p384_sign_layout L = p384_sign_plan(ctx->workspace, chunk);
+  hipError_t err = hipSuccess;
+  FOR_CHUNKS(first, m, n, chunk) {
+    launch::p384_sign_nonce(ctx->stream, d + 48 * first, digest + 48 * first, L.kws, m);
+    launch::p384_sign_finish(ctx->stream, d + 48 * first, digest + 48 * first, L.kws, sig + 96 * first, ok + first, m);
+    err = wipe_workspace(ctx, L.bytes, hipGetLastError());        // k and its validity; K, V, k G and its inverse never leave the registers
+    if (err != hipSuccess) break;
+  }
+  return err == hipSuccess ? ECSIMD_HIP_OK : fail(ctx, err, "p384_ecdsa_sign launch"); }
+
+int ecsimd_p384_raw_inputs(int op) { return (op < 0 || op > launch::P384_RAW_DOUBLE_MULT) ? 0 : launch::p384_raw_inputs(op); }
+int ecsimd_p384_raw_outputs(int op) { return (op < 0 || op > launch::P384_RAW_DOUBLE_MULT) ? 0 : launch::p384_raw_outputs(op); }
+int ecsimd_p384_raw(ecsimd_hip_ctx* ctx, int op, const uint8_t* in, uint8_t* out, size_t n) {
+  REQUIRE_CTX(); if ((!in || !out) && n) return bad(ctx, "p384_raw: null pointer");
+  if (op < 0 || op > launch::P384_RAW_DOUBLE_MULT) return bad(ctx, "p384_raw: unknown function");
+  if (n != 0 && overlaps(in, out)) return bad(ctx, "p384_raw: out must not alias in");
+  ENTER();
+  uint32_t* table = nullptr;
+  if (op == launch::P384_RAW_VAR_MULT || op == launch::P384_RAW_DOUBLE_MULT) {
+    if (n > P384_CHUNK) return bad(ctx, "p384_raw: at most 2^16 lanes of VAR_MULT and DOUBLE_MULT");
+    const int rc = ensure_workspace(ctx, p384_table_plan(nullptr, n).bytes);
+    if (rc != ECSIMD_HIP_OK) return rc;
+    table = p384_table_plan(ctx->workspace, n).table;
+  }
+  launch::p384_raw(ctx->stream, op, in, out, table, n);
+  const hipError_t e = hipGetLastError();
+  return e == hipSuccess ? ECSIMD_HIP_OK : fail(ctx, e, "p384_raw launch"); }
 
 // ---- Multi-scalar multiplication and the point sum (include/ecsimd_msm.h; k_msm.inc has the stages).  PUBLIC data.  msm_schedule_of is the ONE place that turns
 // (n, bits, flags) into sizes: ecsimd_msm_plan reports it, ecsimd_msm enqueues from it, tools/msm_model.py restates it.  Nothing here looks at the data.

@@ -237,6 +237,29 @@ void x25519_from_ed_pk(hipStream_t, const uint8_t* pk, uint8_t* u, uint8_t* ok, 
 void x25519_from_ed_seed(hipStream_t, const uint8_t* seed, uint8_t* scalar, size_t n);
 void x25519_raw(hipStream_t, int op, const uint8_t* in, uint8_t* out, size_t n);
 
+// k_p384.hip: NIST P-384 (include/ecsimd_p384.h).  Integers are 48 big-endian bytes, keys and signatures 96, at any alignment; messages as keccak256's.
+// table: the lanes' multiples 1 .. 8 of their point, p384_table_bytes(n) bytes, 4-byte aligned; kws: p384_nonce_bytes(n) bytes for k and its validity.
+// SECRET (selects only): p384_pubkey writes d G and ok = 1 <= d < n; p384_ecdh x(d peer) and ok = 1 <= d < n && the peer decodes; p384_sign_nonce the first
+// RFC 6979 candidate (HMAC-SHA-384) and valid = 1 <= d, k < n into kws; p384_sign_finish r || s from kws and ok.  PUBLIC: p384_sha384; p384_verify
+// ok = 1 <= r, s < n && pub decodes && u1 G + u2 Q is not the identity && x(R) mod n = r.  p384_raw: one function of the layers on 48-byte records.
+enum p384_raw_op { P384_RAW_FE_MUL = 0, P384_RAW_FE_SQR = 1, P384_RAW_FE_ADD = 2, P384_RAW_FE_SUB = 3, P384_RAW_FE_NEG = 4, P384_RAW_FE_INVERT = 5, P384_RAW_FE_CANON = 6,
+                   P384_RAW_SC_MUL = 7, P384_RAW_SC_INVERT = 8, P384_RAW_DECODE_ENCODE = 9, P384_RAW_POINT_ADD = 10, P384_RAW_POINT_DBL = 11, P384_RAW_BASE_MULT = 12,
+                   P384_RAW_VAR_MULT = 13, P384_RAW_DOUBLE_MULT = 14 };
+constexpr int p384_raw_inputs(int op) {
+  return op == P384_RAW_POINT_ADD ? 6 : op == P384_RAW_DOUBLE_MULT ? 4 : (op == P384_RAW_POINT_DBL || op == P384_RAW_VAR_MULT) ? 3
+       : (op == P384_RAW_FE_MUL || op == P384_RAW_FE_ADD || op == P384_RAW_FE_SUB || op == P384_RAW_SC_MUL || op == P384_RAW_DECODE_ENCODE) ? 2 : 1;
+}
+constexpr int p384_raw_outputs(int op) { return op >= P384_RAW_DECODE_ENCODE ? 3 : 1; }
+inline size_t p384_table_bytes(size_t n) { return n * 8 * 36 * 4; }
+inline size_t p384_nonce_bytes(size_t n) { return n * 13 * 4; }
+void p384_sha384(hipStream_t, const uint8_t* msg, size_t msg_bytes, size_t stride_bytes, const uint32_t* lens, uint8_t* digest, size_t n);
+void p384_pubkey(hipStream_t, const uint8_t* d, uint8_t* pub, uint8_t* ok, size_t n);
+void p384_ecdh(hipStream_t, const uint8_t* d, const uint8_t* peer, uint32_t* table, uint8_t* z, uint8_t* ok, size_t n);
+void p384_sign_nonce(hipStream_t, const uint8_t* d, const uint8_t* digest, uint32_t* kws, size_t n);
+void p384_sign_finish(hipStream_t, const uint8_t* d, const uint8_t* digest, const uint32_t* kws, uint8_t* sig, uint8_t* ok, size_t n);
+void p384_verify(hipStream_t, const uint8_t* pub, const uint8_t* digest, const uint8_t* sig, uint32_t* table, uint8_t* ok, size_t n);
+void p384_raw(hipStream_t, int op, const uint8_t* in, uint8_t* out, uint32_t* table, size_t n);
+
 // k_point_<curve>.hip
 void from_affine(hipStream_t, int curve, const uint64_t* x, const uint64_t* y, uint64_t* jx, uint64_t* jy, uint64_t* jz, size_t n);
 void to_affine(hipStream_t, int curve, const uint64_t* jx, const uint64_t* jy, const uint64_t* jz, uint64_t* x, uint64_t* y, size_t n);

@@ -590,6 +590,77 @@ class Engine:
         self._check(self.lib.ecsimd_x25519_raw(self.ctx, C.c_int(op), ip, C.c_void_p(out.data_ptr()), C.c_size_t(n)), "x25519_raw")
         return out
 
+    # ---- NIST P-384 (include/ecsimd_p384.h): integers are 48 big-endian bytes, public keys X || Y and signatures r || s 96
+    (P384_RAW_FE_MUL, P384_RAW_FE_SQR, P384_RAW_FE_ADD, P384_RAW_FE_SUB, P384_RAW_FE_NEG, P384_RAW_FE_INVERT, P384_RAW_FE_CANON, P384_RAW_SC_MUL, P384_RAW_SC_INVERT,
+     P384_RAW_DECODE_ENCODE, P384_RAW_POINT_ADD, P384_RAW_POINT_DBL, P384_RAW_BASE_MULT, P384_RAW_VAR_MULT, P384_RAW_DOUBLE_MULT) = range(15)
+
+    def _p384_rows(self, what, *pairs):
+        """The pointers of (tensor, width) pairs and their common row count."""
+        ptrs, ns = [], set()
+        for t, width in pairs:
+            p, n = self._rows_u8(t, width, what)
+            ptrs.append(p); ns.add(n)
+        if len(ns) != 1:
+            raise EcsimdHipError(f"{what}: operands disagree on the batch length: {sorted(ns)}")
+        return ptrs, ns.pop()
+
+    def p384_sha384(self, msgs, lens=None):
+        """ecsimd_p384_sha384: the (n, 48) uint8 SHA-384 digests of the rows of `msgs` (as keccak256's: 2-D uint8, rows may be strided; lens: lane i hashes the
+        first lens[i] bytes of its row)."""
+        n = int(msgs.shape[0])
+        keep, mp, length, stride = self._messages(msgs, n)
+        out = self._u8_out(n, 48)
+        lp = self._lens_ptr("p384_sha384", lens if length.value else None, n)
+        self._bind_stream()
+        self._check(self.lib.ecsimd_p384_sha384(self.ctx, mp, length, stride, lp, C.c_void_p(out.data_ptr() if n else 0), C.c_size_t(n)), "p384_sha384")
+        return out
+
+    def p384_pubkey(self, d):
+        """ecsimd_p384_pubkey: (pub, ok), the (n, 96) uint8 public keys X || Y of the SECRET (n, 48) uint8 private keys; ok = 0 and zeros where d is not in [1, n - 1]."""
+        (dp,), n = self._p384_rows("p384_pubkey", (d, 48))
+        pub, ok = self._u8_out(n, 96), self.flags(n)
+        self._bind_stream()
+        self._check(self.lib.ecsimd_p384_pubkey(self.ctx, dp, C.c_void_p(pub.data_ptr() if n else 0), C.c_void_p(ok.data_ptr() if n else 0), C.c_size_t(n)), "p384_pubkey")
+        return pub, ok
+
+    def p384_ecdh(self, d, peer):
+        """ecsimd_p384_ecdh: (z, ok), z = x(d peer) as (n, 48) uint8 for the SECRET (n, 48) private keys and the peers' (n, 96) public keys; ok = 0 and zeros
+        where d is not in [1, n - 1] or the peer does not decode."""
+        (dp, pp), n = self._p384_rows("p384_ecdh", (d, 48), (peer, 96))
+        z, ok = self._u8_out(n, 48), self.flags(n)
+        self._bind_stream()
+        self._check(self.lib.ecsimd_p384_ecdh(self.ctx, dp, pp, C.c_void_p(z.data_ptr() if n else 0), C.c_void_p(ok.data_ptr() if n else 0), C.c_size_t(n)), "p384_ecdh")
+        return z, ok
+
+    def p384_ecdsa_verify(self, pub, digest, sig):
+        """ecsimd_p384_ecdsa_verify: ok, one byte per lane, for the (n, 96) signatures r || s of the (n, 48) digests under the (n, 96) public keys.  Public data."""
+        (pp, gp, sp), n = self._p384_rows("p384_ecdsa_verify", (pub, 96), (digest, 48), (sig, 96))
+        ok = self.flags(n)
+        self._bind_stream()
+        self._check(self.lib.ecsimd_p384_ecdsa_verify(self.ctx, pp, gp, sp, C.c_void_p(ok.data_ptr() if n else 0), C.c_size_t(n)), "p384_ecdsa_verify")
+        return ok
+
+    def p384_ecdsa_sign(self, d, digest, flags=0):
+        """ecsimd_p384_ecdsa_sign: (sig, ok), the deterministic (RFC 6979, HMAC-SHA-384, one candidate) signatures r || s of the (n, 48) digests under the SECRET
+        (n, 48) private keys; ok = 0 and zeros where d is not in [1, n - 1]."""
+        (dp, gp), n = self._p384_rows("p384_ecdsa_sign", (d, 48), (digest, 48))
+        sig, ok = self._u8_out(n, 96), self.flags(n)
+        self._bind_stream()
+        self._check(self.lib.ecsimd_p384_ecdsa_sign(self.ctx, dp, gp, C.c_void_p(sig.data_ptr() if n else 0), C.c_void_p(ok.data_ptr() if n else 0), C.c_size_t(n), C.c_int(flags)),
+                    "p384_ecdsa_sign")
+        return sig, ok
+
+    def p384_raw(self, op, records):
+        """ecsimd_p384_raw: one function of the layers below on (n, 48 * inputs) uint8 records; returns (n, 48 * outputs) uint8 (see the header's table)."""
+        ni, no = int(self.lib.ecsimd_p384_raw_inputs(C.c_int(op))), int(self.lib.ecsimd_p384_raw_outputs(C.c_int(op)))
+        if ni == 0:
+            raise EcsimdHipError(f"p384_raw: unknown function {op}")
+        ip, n = self._rows_u8(records, 48 * ni, "records")
+        out = self._u8_out(n, 48 * no)
+        self._bind_stream()
+        self._check(self.lib.ecsimd_p384_raw(self.ctx, C.c_int(op), ip, C.c_void_p(out.data_ptr() if n else 0), C.c_size_t(n)), "p384_raw")
+        return out
+
     # ---- multi-scalar multiplication (include/ecsimd_msm.h): ONE point out of a batch.  PUBLIC data only.
     MSM_ALG_AUTO, MSM_ALG_BUCKETS, MSM_ALG_LANES = 0, 1, 2
 
