@@ -2539,8 +2539,9 @@ int ecsimd_p384_raw(ecsimd_hip_ctx* ctx, int op, const uint8_t* in, uint8_t* out
   const hipError_t e = hipGetLastError();
   return e == hipSuccess ? ECSIMD_HIP_OK : fail(ctx, e, "p384_raw launch"); }
 
-// ---- Multi-scalar multiplication and the point sum (include/ecsimd_msm.h; k_msm.inc has the stages).  PUBLIC data.  msm_schedule_of is the ONE place that turns
-// (n, bits, flags) into sizes: ecsimd_msm_plan reports it, ecsimd_msm enqueues from it, tools/msm_model.py restates it.  Nothing here looks at the data.
+// ---- Multi-scalar multiplication and the point sum (include/ecsimd_msm.h; msm_stages.cuh has the stages).  PUBLIC data.  msm_schedule_of is the ONE place that turns
+// (n, bits, flags) into sizes: ecsimd_msm_plan reports it, ecsimd_msm enqueues from it, tools/msm_model.py restates it.  Nothing here looks at the data.  The
+// bucket route is ONE driver (bucket_sum_run) and ONE layout (msm_carve) for both curve forms: they differ in the planes of a point and in six launchers.
 namespace {
 int floor_log2(size_t v) { int r = 0; while (v >>= 1) ++r; return r; }
 int ceil_log2(size_t v) { return v <= 1 ? 0 : floor_log2(v - 1) + 1; }
@@ -2549,11 +2550,13 @@ size_t round16(size_t b) { return (b + 15) / 16 * 16; }
 struct msm_schedule {
   ecsimd_msm_plan_t plan;
   size_t T, K, slices, per_window, chunk_lanes, front_lanes;      // BUCKETS: entries, keys, slice lanes, chunks per window, their product with the windows; LANES: the affine tree's lanes
+  size_t planes;                                                  // BUCKETS: field elements per point of the sum: 3 (Jacobian) or 4 (extended Edwards); a decoded term has one fewer
 };
 // The workspace of a call, carved from `base` (nullptr: sizes only).
 struct msm_blocks {
   uint32_t *counter, *hist, *start, *cursor, *sorted;   // counter (invalid points, broken invariants) and hist are ONE block, zeroed by one kernel
-  uint64_t *kk, *px, *py, *buckets, *partial, *tree;    // LANES: kk, px, py = the sanitized scalars and points, buckets / partial = the affine products (ox, oy)
+  uint64_t *kk, *px, *py, *buckets, *partial, *tree;    // BUCKETS: the decoded terms are planes - 1 planes of n from px on (Jacobian: px, py; Edwards: ed_precomp's three)
+                                                        // LANES: kk, px, py = the sanitized scalars and points, buckets / partial = the affine products (ox, oy)
   size_t zero_bytes, reserve;                           // the length of that block; LANES: what run_varwin leaves alone at the start of the workspace
 };
 msm_blocks msm_carve(const msm_schedule& S, size_t n, void* base, size_t* bytes) {
@@ -2565,8 +2568,8 @@ msm_blocks msm_carve(const msm_schedule& S, size_t n, void* base, size_t* bytes)
     B.start = static_cast<uint32_t*>(carve_bytes(c, round16(4 * (S.K + 1))));
     B.cursor = static_cast<uint32_t*>(carve_bytes(c, round16(4 * S.K)));
     B.sorted = static_cast<uint32_t*>(carve_bytes(c, round16(4 * S.T)));
-    B.kk = carve_limbs(c, n); B.px = carve_limbs(c, n); B.py = carve_limbs(c, n);
-    B.buckets = carve_limbs(c, 3 * S.K); B.partial = carve_limbs(c, 3 * 2 * S.slices); B.tree = carve_limbs(c, 3 * S.chunk_lanes);
+    B.kk = carve_limbs(c, n); B.px = carve_limbs(c, n); B.py = carve_limbs(c, (S.planes - 2) * n);
+    B.buckets = carve_limbs(c, S.planes * S.K); B.partial = carve_limbs(c, S.planes * 2 * S.slices); B.tree = carve_limbs(c, S.planes * S.chunk_lanes);
   } else {
     B.zero_bytes = 32;                                  // (32: run_varwin's scratch behind `reserve` stays 32-byte aligned)
     B.counter = static_cast<uint32_t*>(carve_bytes(c, 32));
@@ -2578,10 +2581,11 @@ msm_blocks msm_carve(const msm_schedule& S, size_t n, void* base, size_t* bytes)
   *bytes = c.bytes;
   return B;
 }
-bool msm_schedule_of(size_t n, int bits, int flags, msm_schedule* S) {
+bool msm_schedule_of(size_t n, int bits, int flags, msm_schedule* S, size_t planes = 3) {
   if (bits < 1 || bits > 256 || n > ECSIMD_MSM_MAX_N) return false;
   if (flags != ECSIMD_MSM_ALG_AUTO && flags != ECSIMD_MSM_ALG_BUCKETS && flags != ECSIMD_MSM_ALG_LANES) return false;
   *S = msm_schedule();
+  S->planes = planes;
   ecsimd_msm_plan_t& P = S->plan;
   P.route = flags != ECSIMD_MSM_ALG_AUTO ? flags : n >= ECSIMD_MSM_AUTO_THRESHOLD ? ECSIMD_MSM_ALG_BUCKETS : ECSIMD_MSM_ALG_LANES;
   if (n == 0) { P.launches = 1; P.max_chain = 0; return true; }                  // the last kernel alone writes the empty sum
@@ -2606,44 +2610,70 @@ bool msm_schedule_of(size_t n, int bits, int flags, msm_schedule* S) {
   (void)msm_carve(*S, n, nullptr, &P.workspace_bytes);
   return true;
 }
-extern "C++" template <int CV> int msm_run(ecsimd_hip_ctx* ctx, const msm_schedule& S, const uint64_t* k, const uint64_t* x, const uint64_t* y, uint64_t* rx, uint64_t* ry, uint8_t* finite,
-                              uint32_t* invalid, size_t n, int bits, size_t offset = 0) {
-  // offset: the bytes at the start of the workspace that are the caller's (schnorr_verify_batch keeps its own arrays there); the blocks are carved behind them
-  using ML = launch::msm_launch<CV>;
+// arr[g * stride ..]: `groups` runs of `count` elements summed into their first, fan-in 16 per launch
+extern "C++" template <class ML> void tree_run(hipStream_t s, uint64_t* arr, size_t total, size_t count, size_t stride, size_t groups) {
+  const int fan = launch::MSM_TREE_FAN;
+  while (count > 1) {
+    const size_t lanes = (count + fan - 1) / fan;
+    ML::tree(s, arr, total, count, stride, groups, lanes, fan);
+    count = lanes;
+  }
+}
+// The bucket route for either curve form (the empty sum, on any route, is its last kernel alone).  A sum type names the group's launchers -- ML: combine, chunks,
+// tree; its own digits, slices and finish, which carry the terms as the caller gives them and the result as the group writes it -- and `what` for the error text.
+// offset: the bytes at the start of the workspace that are the caller's (the batch verifications keep their own arrays there); the blocks are carved behind them.
+extern "C++" template <class Sum> int bucket_sum_run(ecsimd_hip_ctx* ctx, const msm_schedule& S, const Sum& sum, uint8_t* finite, uint32_t* invalid, size_t n, int bits, size_t offset) {
+  using ML = typename Sum::ML;
   const ecsimd_msm_plan_t& P = S.plan;
   hipStream_t s = ctx->stream;
-  const int fan = launch::MSM_TREE_FAN;
-  if (n == 0) { ML::finish(s, nullptr, 0, 0, 0, 0, nullptr, rx, ry, finite, invalid); const hipError_t e0 = hipGetLastError(); return e0 == hipSuccess ? ECSIMD_HIP_OK : fail(ctx, e0, "msm launch"); }
-  int rc = ensure_workspace(ctx, offset + P.workspace_bytes);
+  if (n == 0) sum.finish(s, nullptr, 0, 0, 0, 0, nullptr, finite, invalid);
+  else {
+    const int rc = ensure_workspace(ctx, offset + P.workspace_bytes);
+    if (rc != ECSIMD_HIP_OK) return rc;
+    size_t bytes = 0;
+    const msm_blocks B = msm_carve(S, n, reinterpret_cast<uint8_t*>(ctx->workspace) + offset, &bytes);
+    launch::msm_zero(s, B.counter, B.zero_bytes);
+    sum.digits(s, B, n, bits, P.c, P.windows);
+    launch::msm_scan(s, B.hist, B.start, B.cursor, S.K);
+    launch::msm_scatter(s, B.kk, B.cursor, B.sorted, B.counter + 1, n, S.T, P.c, P.windows);
+    sum.slices(s, B, n, S.T, P.L, S.slices, P.c, S.K);
+    ML::combine(s, B.start, B.buckets, B.partial, B.counter + 1, P.L, S.slices, P.c, S.K);
+    ML::chunks(s, B.buckets, B.tree, S.chunk_lanes, S.per_window, P.c, (int)P.m, S.K);
+    tree_run<ML>(s, B.tree, S.chunk_lanes, S.per_window, S.per_window, (size_t)P.windows);
+    sum.finish(s, B.tree, S.chunk_lanes, S.per_window, P.windows, P.c, B.counter, finite, invalid);
+  }
+  const hipError_t e = hipGetLastError();
+  return e == hipSuccess ? ECSIMD_HIP_OK : fail(ctx, e, Sum::what);
+}
+extern "C++" template <int CV> struct jacobian_sum {
+  using ML = launch::msm_launch<CV>;
+  static constexpr const char* what = "msm launch";
+  const uint64_t *k, *x, *y; uint64_t *rx, *ry;
+  void digits(hipStream_t s, const msm_blocks& B, size_t n, int bits, int c, int windows) const { ML::digits(s, k, x, y, B.kk, B.px, B.py, B.hist, B.counter, n, bits, c, windows); }
+  void slices(hipStream_t s, const msm_blocks& B, size_t n, size_t T, size_t L, size_t slices, int c, size_t K) const {
+    ML::slices(s, B.sorted, B.kk, B.px, B.py, B.start, B.buckets, B.partial, B.counter + 1, n, T, L, slices, c, K);
+  }
+  void finish(hipStream_t s, const uint64_t* arr, size_t total, size_t stride, int windows, int c, const uint32_t* counter, uint8_t* finite, uint32_t* invalid) const {
+    ML::finish(s, arr, total, stride, windows, c, counter, rx, ry, finite, invalid);
+  }
+};
+extern "C++" template <int CV> int msm_run(ecsimd_hip_ctx* ctx, const msm_schedule& S, const uint64_t* k, const uint64_t* x, const uint64_t* y, uint64_t* rx, uint64_t* ry, uint8_t* finite,
+                              uint32_t* invalid, size_t n, int bits, size_t offset = 0) {
+  using ML = launch::msm_launch<CV>;
+  if (n == 0 || S.plan.route == ECSIMD_MSM_ALG_BUCKETS) return bucket_sum_run(ctx, S, jacobian_sum<CV>{k, x, y, rx, ry}, finite, invalid, n, bits, offset);
+  hipStream_t s = ctx->stream;
+  int rc = ensure_workspace(ctx, offset + S.plan.workspace_bytes);
   if (rc != ECSIMD_HIP_OK) return rc;
   size_t bytes = 0;
   const msm_blocks B = msm_carve(S, n, reinterpret_cast<uint8_t*>(ctx->workspace) + offset, &bytes);
-  hipError_t e;
-  ML::zero(s, B.counter, B.zero_bytes);
-  size_t count, stride; int windows;
-  if (P.route == ECSIMD_MSM_ALG_BUCKETS) {
-    ML::digits(s, k, x, y, B.kk, B.px, B.py, B.hist, B.counter, n, bits, P.c, P.windows);
-    ML::scan(s, B.hist, B.start, B.cursor, S.K);
-    ML::scatter(s, B.kk, B.cursor, B.sorted, B.counter + 1, n, S.T, P.c, P.windows);
-    ML::slices(s, B.sorted, B.kk, B.px, B.py, B.start, B.buckets, B.partial, B.counter + 1, n, S.T, P.L, S.slices, P.c, S.K);
-    ML::combine(s, B.start, B.buckets, B.partial, B.counter + 1, P.L, S.slices, P.c, S.K);
-    ML::chunks(s, B.buckets, B.tree, S.chunk_lanes, S.per_window, P.c, (int)P.m, S.K);
-    count = S.per_window; stride = S.per_window; windows = P.windows;
-  } else {
-    ML::sanitize(s, k, x, y, B.kk, B.px, B.py, B.counter, n, bits);
-    rc = run_varwin(ctx, CV, B.kk, 4, B.px, B.py, B.buckets, B.partial, n, ECSIMD_HIP_OUT_AFFINE | ECSIMD_HIP_ALG_WINDOWED, offset + B.reserve);   // the workspace is large enough: nothing moves
-    if (rc != ECSIMD_HIP_OK) return rc;
-    ML::tree_affine(s, B.buckets, B.partial, false, B.counter, B.tree, n, S.front_lanes, fan);
-    count = S.front_lanes; stride = 0; windows = 1;
-  }
-  const size_t total = P.route == ECSIMD_MSM_ALG_BUCKETS ? S.chunk_lanes : S.front_lanes;
-  while (count > 1) {
-    const size_t lanes = (count + fan - 1) / fan;
-    ML::tree(s, B.tree, total, count, stride, (size_t)windows, lanes, fan);
-    count = lanes;
-  }
-  ML::finish(s, B.tree, total, stride, windows, P.route == ECSIMD_MSM_ALG_BUCKETS ? P.c : 0, B.counter, rx, ry, finite, invalid);
-  e = hipGetLastError();
+  launch::msm_zero(s, B.counter, B.zero_bytes);
+  ML::sanitize(s, k, x, y, B.kk, B.px, B.py, B.counter, n, bits);
+  rc = run_varwin(ctx, CV, B.kk, 4, B.px, B.py, B.buckets, B.partial, n, ECSIMD_HIP_OUT_AFFINE | ECSIMD_HIP_ALG_WINDOWED, offset + B.reserve);   // the workspace is large enough: nothing moves
+  if (rc != ECSIMD_HIP_OK) return rc;
+  ML::tree_affine(s, B.buckets, B.partial, false, B.counter, B.tree, n, S.front_lanes, launch::MSM_TREE_FAN);
+  tree_run<ML>(s, B.tree, S.front_lanes, S.front_lanes, 0, 1);
+  ML::finish(s, B.tree, S.front_lanes, 0, 1, 0, B.counter, rx, ry, finite, invalid);
+  const hipError_t e = hipGetLastError();
   return e == hipSuccess ? ECSIMD_HIP_OK : fail(ctx, e, "msm launch");
 }
 extern "C++" template <int CV> int point_sum_run(ecsimd_hip_ctx* ctx, const uint64_t* x, const uint64_t* y, uint64_t* rx, uint64_t* ry, uint8_t* finite, uint32_t* invalid, size_t n) {
@@ -2657,16 +2687,11 @@ extern "C++" template <int CV> int point_sum_run(ecsimd_hip_ctx* ctx, const uint
   if (rc != ECSIMD_HIP_OK) return rc;
   c = carve_from(ctx->workspace);
   uint32_t* counter = static_cast<uint32_t*>(carve_bytes(c, 16)); uint64_t* tree = carve_limbs(c, 3 * front);
-  hipError_t e;
-  ML::zero(s, counter, 16);
+  launch::msm_zero(s, counter, 16);
   ML::tree_affine(s, x, y, true, counter, tree, n, front, fan);
-  for (size_t count = front; count > 1;) {
-    const size_t lanes = (count + fan - 1) / fan;
-    ML::tree(s, tree, front, count, 0, 1, lanes, fan);
-    count = lanes;
-  }
+  tree_run<ML>(s, tree, front, front, 0, 1);
   ML::finish(s, tree, front, 0, 1, 0, counter, rx, ry, finite, invalid);
-  e = hipGetLastError();
+  const hipError_t e = hipGetLastError();
   return e == hipSuccess ? ECSIMD_HIP_OK : fail(ctx, e, "point_sum launch");
 }
 int msm_check_common(ecsimd_hip_ctx* ctx, int curve, const uint64_t* x, const uint64_t* y, uint64_t* rx, uint64_t* ry, uint8_t* finite, uint32_t* invalid, size_t n) {
@@ -2712,10 +2737,73 @@ int ecsimd_msm_point_sum(ecsimd_hip_ctx* ctx, int curve, const uint64_t* x, cons
 // ---- BIP-340 batch verification (include/ecsimd_schnorr_batch.h; k_schnorr_batch.hip has the stages, tools/schnorr_batch_model.py the definition).  PUBLIC data.
 // sb_schedule_of is the ONE place that turns (n, msg_bytes, flags) into sizes: ecsimd_schnorr_batch_plan reports it, the calls enqueue from it.  The MSM route's
 // workspace: the call's own arrays first (sb_carve), then the blocks of the two bucket sums, which run one after the other and share their bytes.
+// What this call and Ed25519 batch verification do alike -- the fan-16 trees, the workspace of the MSM route, the shared checks -- is the batch_* functions' here.
 namespace {
-size_t fan_lanes(size_t count) { return (count + launch::SCHNORR_BATCH_FAN - 1) / launch::SCHNORR_BATCH_FAN; }
+size_t fan_lanes(size_t count) { return (count + launch::BATCH_FAN - 1) / launch::BATCH_FAN; }
 int fan_passes(size_t count) { int p = 0; while (count > 1) { count = fan_lanes(count); ++p; } return p; }
 size_t fan_elements(size_t count) { size_t t = 0; while (count > 1) { count = fan_lanes(count); t += count; } return t; }      // every level below the leaves
+// The MSM route of a batch of n >= 1 signatures: a sum of n terms with 128-bit scalars, then one of n + 1 terms with key_bits-bit scalars.
+struct batch_sums { msm_schedule r, key; };
+bool batch_sums_of(size_t n, int key_bits, size_t planes, batch_sums* S) {
+  return msm_schedule_of(n, 128, ECSIMD_MSM_ALG_BUCKETS, &S->r, planes) && msm_schedule_of(n + 1, key_bits, ECSIMD_MSM_ALG_BUCKETS, &S->key, planes);
+}
+// ... its bytes for exactly n: the call's own arrays, then the larger of the two sums' blocks (they run one after the other)
+size_t batch_msm_bytes(size_t own, size_t n, int key_bits, size_t planes) {
+  batch_sums S;
+  if (!batch_sums_of(n, key_bits, planes, &S)) return 0;
+  return own + (S.r.plan.workspace_bytes > S.key.plan.workspace_bytes ? S.r.plan.workspace_bytes : S.key.plan.workspace_bytes);
+}
+// What a batch of n needs, and what every smaller batch would: the bucket sums' blocks are not monotone in the number of terms (a wider window means fewer
+// sorted entries), but between powers of two they are -- the window width, the bucket count and the segment split are fixed there and only the entries
+// grow --, so the largest need below n is met at n itself or next to a power of two.  A context warmed up at n then serves every smaller batch in a capture.
+size_t batch_workspace_bytes(size_t n, size_t (*bytes_for_exactly)(size_t)) {
+  size_t need = bytes_for_exactly(n);
+  for (size_t p = 2; p <= n + 2; p <<= 1)
+    for (size_t m = p - 2; m <= p && m <= n; ++m)
+      if (m >= 1 && bytes_for_exactly(m) > need) need = bytes_for_exactly(m);
+  return need;
+}
+// ... and its kernels: zero, front, seed, scalars, accept; the two trees; the two sums
+int batch_msm_launches(size_t n, const batch_sums& S) {
+  const int levels = fan_passes(n);
+  return 5 + levels + (levels > 1 ? levels : 1) + S.r.plan.launches + S.key.plan.launches;
+}
+// Enqueues the hash tree over the n leaves, a level per launch, the levels one behind the other in `nodes`; returns the root's level (n = 1: the leaf).
+const uint64_t* batch_hash_tree(hipStream_t s, void (*node)(hipStream_t, const uint64_t*, size_t, uint64_t*), const uint64_t* leaf, uint64_t* nodes, size_t n) {
+  const uint64_t* level = leaf;
+  for (size_t count = n; count > 1;) {
+    node(s, level, count, nodes);
+    count = fan_lanes(count); level = nodes; nodes += 4 * count;
+  }
+  return level;
+}
+// Enqueues the tree of additions over the n scalars at `in`, the levels one behind the other in `levels`: sum(in, count, out, last); the last level (one lane,
+// even for n = 1) writes to last_out, where it is term n of the key sum.
+extern "C++" template <class Sum> void batch_scalar_sum(const uint64_t* in, uint64_t* levels, uint64_t* last_out, size_t n, Sum sum) {
+  for (size_t count = n, lanes = 0; lanes != 1; count = lanes) {
+    lanes = fan_lanes(count);
+    const bool last = lanes == 1;
+    sum(in, count, last ? last_out : levels, last);
+    in = levels; levels += 4 * lanes;
+  }
+}
+// Two byte ranges that share a byte (an empty or a null one shares none).
+struct byte_range { const void* p; size_t bytes; };
+bool ranges_overlap(const void* a, size_t abytes, const void* b, size_t bbytes) {
+  if (!a || !b || !abytes || !bbytes) return false;
+  const uintptr_t pa = reinterpret_cast<uintptr_t>(a), pb = reinterpret_cast<uintptr_t>(b);
+  return pa < pb + bbytes && pb < pa + abytes;
+}
+// What the batch calls check alike: the cap on n, the messages by the call's own rule, and that `out` (what the call writes) overlaps no input.
+extern "C++" template <class Messages> int batch_check(ecsimd_hip_ctx* ctx, const char* what, size_t n, Messages messages, byte_range out, std::initializer_list<byte_range> in) {
+  char text[128];
+  snprintf(text, sizeof text, "%s: n is above ECSIMD_MSM_MAX_N - 1: verify chunks and AND their verdicts", what);
+  if (n > ECSIMD_MSM_MAX_N - 1) return bad(ctx, text);
+  const int rc = messages(); if (rc != ECSIMD_HIP_OK) return rc;
+  snprintf(text, sizeof text, "%s: the output must not overlap an input", what);
+  for (const byte_range& r : in) if (ranges_overlap(out.p, out.bytes, r.p, r.bytes)) return bad(ctx, text);
+  return ECSIMD_HIP_OK;
+}
 struct sb_blocks {
   launch::schnorr_batch_head* head;
   uint64_t *E, *leaf, *nodes, *a, *ae, *as, *sums, *Px, *Py, *Rx, *Ry;      // ae, Px, Py: n + 1 elements, the last one the G term; nodes, sums: the trees' levels, one behind the other
@@ -2732,14 +2820,8 @@ sb_blocks sb_carve(size_t n, void* base, size_t* bytes) {
   *bytes = c.bytes;
   return B;
 }
-struct sb_schedule { ecsimd_schnorr_batch_plan_t plan; msm_schedule sum_r, sum_p; };
-// The MSM route's bytes for exactly n >= 1 signatures: its own arrays, then the larger of the two sums' blocks.
-size_t sb_msm_bytes(size_t n) {
-  msm_schedule r, p; size_t own = 0;
-  if (!msm_schedule_of(n, 128, ECSIMD_MSM_ALG_BUCKETS, &r) || !msm_schedule_of(n + 1, 256, ECSIMD_MSM_ALG_BUCKETS, &p)) return 0;
-  (void)sb_carve(n, nullptr, &own);
-  return own + (r.plan.workspace_bytes > p.plan.workspace_bytes ? r.plan.workspace_bytes : p.plan.workspace_bytes);
-}
+struct sb_schedule { ecsimd_schnorr_batch_plan_t plan; batch_sums sums; };
+size_t sb_msm_bytes(size_t n) { size_t own = 0; (void)sb_carve(n, nullptr, &own); return batch_msm_bytes(own, n, 256, 3); }
 bool sb_route_ok(int flags) { return flags == ECSIMD_SCHNORR_BATCH_AUTO || flags == ECSIMD_SCHNORR_BATCH_MSM || flags == ECSIMD_SCHNORR_BATCH_LANES; }
 bool sb_schedule_of(size_t n, size_t msg_bytes, int flags, sb_schedule* S) {
   if (n > ECSIMD_MSM_MAX_N - 1 || msg_bytes > ((size_t)1 << 40) || !sb_route_ok(flags)) return false;
@@ -2748,51 +2830,30 @@ bool sb_schedule_of(size_t n, size_t msg_bytes, int flags, sb_schedule* S) {
   P.route = flags != ECSIMD_SCHNORR_BATCH_AUTO ? flags : n >= ECSIMD_SCHNORR_BATCH_AUTO_THRESHOLD ? ECSIMD_SCHNORR_BATCH_MSM : ECSIMD_SCHNORR_BATCH_LANES;
   if (n == 0) { P.launches = 1; return true; }                                   // the reduction kernel alone writes the empty batch's verdict
   if (P.route == ECSIMD_SCHNORR_BATCH_MSM) {
-    if (!msm_schedule_of(n, 128, ECSIMD_MSM_ALG_BUCKETS, &S->sum_r) || !msm_schedule_of(n + 1, 256, ECSIMD_MSM_ALG_BUCKETS, &S->sum_p)) return false;
-    // What this batch needs, and what every smaller batch would: the bucket sums' blocks are not monotone in the number of terms (a wider window means fewer
-    // sorted entries), but between powers of two they are -- the window width, the bucket count and the segment split are fixed there and only the entries
-    // grow --, so the largest need below n is met at n itself or next to a power of two.  A context warmed up at n then serves every smaller batch in a capture.
-    P.workspace_bytes = sb_msm_bytes(n);
-    for (size_t p = 2; p <= n + 2; p <<= 1)
-      for (size_t m = p - 2; m <= p && m <= n; ++m)
-        if (m >= 1 && sb_msm_bytes(m) > P.workspace_bytes) P.workspace_bytes = sb_msm_bytes(m);
-    const int levels = fan_passes(n);
-    P.launches = 5 + levels + (levels > 1 ? levels : 1) + S->sum_r.plan.launches + S->sum_p.plan.launches;   // zero, front, seed, scalars, accept; the two trees; the two sums
+    if (!batch_sums_of(n, 256, 3, &S->sums)) return false;
+    P.workspace_bytes = batch_workspace_bytes(n, sb_msm_bytes);
+    P.launches = batch_msm_launches(n, S->sums);
   } else {
     P.workspace_bytes = schnorr_verify_bytes(n, true);
     P.launches = 1 + 9 * (int)((n + VARWIN_CHUNK - 1) / VARWIN_CHUNK);
   }
   return true;
 }
-// Two byte ranges that share a byte (an empty or a null one shares none).
-bool ranges_overlap(const void* a, size_t abytes, const void* b, size_t bbytes) {
-  if (!a || !b || !abytes || !bbytes) return false;
-  const uintptr_t pa = reinterpret_cast<uintptr_t>(a), pb = reinterpret_cast<uintptr_t>(b);
-  return pa < pb + bbytes && pb < pa + abytes;
-}
 // What the two calls check alike, `out` being the `out_bytes` bytes either writes; fills O.
 int sb_check(ecsimd_hip_ctx* ctx, const char* what, const uint64_t* px, const uint8_t* msg, size_t msg_bytes, size_t stride_bytes, const uint64_t* r, const uint64_t* s_,
              const void* out, size_t out_bytes, size_t n, group_order* O) {
   REQUIRE_PTR(px); REQUIRE_PTR(r); REQUIRE_PTR(s_);
-  if (n > ECSIMD_MSM_MAX_N - 1) return bad(ctx, "schnorr batch: n is above ECSIMD_MSM_MAX_N - 1: verify chunks and AND their verdicts");
-  int rc = schnorr_common(ctx, what, msg, msg_bytes, stride_bytes, n, O); if (rc != ECSIMD_HIP_OK) return rc;
   const size_t msg_extent = n ? (n - 1) * stride_bytes + msg_bytes : 0;
-  if (ranges_overlap(out, out_bytes, px, 32 * n) || ranges_overlap(out, out_bytes, r, 32 * n) || ranges_overlap(out, out_bytes, s_, 32 * n) ||
-      ranges_overlap(out, out_bytes, msg, msg_extent)) return bad(ctx, "schnorr batch: the output must not overlap an input");
-  return ECSIMD_HIP_OK;
+  return batch_check(ctx, "schnorr batch", n, [&] { return schnorr_common(ctx, what, msg, msg_bytes, stride_bytes, n, O); }, {out, out_bytes},
+                     {{px, 32 * n}, {r, 32 * n}, {s_, 32 * n}, {msg, msg_extent}});
 }
 // Stages 1 to 3 for n >= 1: the front, the hash tree, the seed, the scalars.  `a`: where the randomizers go (B.a, or the caller's array).
 void sb_randomizers(ecsimd_hip_ctx* ctx, const group_order& O, const sb_blocks& B, const uint64_t* px, const uint8_t* msg, size_t msg_bytes, size_t stride_bytes,
                     const uint64_t* r, const uint64_t* s_, uint64_t* a, size_t n) {
   hipStream_t s = ctx->stream;
-  launch::msm_launch<CURVE_SECP256K1>::zero(s, B.head, sizeof(launch::schnorr_batch_head));
+  launch::msm_zero(s, B.head, sizeof(launch::schnorr_batch_head));
   launch::schnorr_batch_front(s, O.words, px, r, s_, msg, msg_bytes, stride_bytes, B.E, B.leaf, B.Px, B.Py, B.Rx, B.Ry, B.valid, B.head, n);
-  const uint64_t* level = B.leaf; uint64_t* out = B.nodes;
-  for (size_t count = n; count > 1;) {
-    launch::schnorr_batch_node(s, level, count, out);
-    count = fan_lanes(count); level = out; out += 4 * count;
-  }
-  launch::schnorr_batch_seed(s, level, n, B.head);
+  launch::schnorr_batch_seed(s, batch_hash_tree(s, launch::schnorr_batch_node, B.leaf, B.nodes, n), n, B.head);
   launch::schnorr_batch_scalars(s, O.N, B.head, B.E, s_, B.valid, a, B.ae, B.as, n);
 }
 }  // namespace
@@ -2814,25 +2875,21 @@ int ecsimd_schnorr_verify_batch(ecsimd_hip_ctx* ctx, const uint64_t* px, const u
   if (!sb_schedule_of(n, msg_bytes, flags, &S)) return bad(ctx, "schnorr_verify_batch: no schedule for these arguments");
   const hipError_t e0 = hipSetDevice(ctx->device); if (e0 != hipSuccess) return fail(ctx, e0, "hipSetDevice");
   hipStream_t s = ctx->stream;
-  if (n == 0) launch::schnorr_batch_all(s, nullptr, 0, ok);
+  if (n == 0) launch::flags_all(s, nullptr, 0, ok);
   else if (S.plan.route == ECSIMD_SCHNORR_BATCH_LANES) {
     uint8_t* verdicts = nullptr;
     rc = schnorr_verify_run(ctx, O, px, msg, msg_bytes, stride_bytes, r, s_, nullptr, n, &verdicts); if (rc != ECSIMD_HIP_OK) return rc;
-    launch::schnorr_batch_all(s, verdicts, n, ok);
+    launch::flags_all(s, verdicts, n, ok);
   } else {
     rc = ensure_workspace(ctx, S.plan.workspace_bytes); if (rc != ECSIMD_HIP_OK) return rc;      // all of it now: the sums below find it large enough, nothing moves
     size_t own = 0;
     const sb_blocks B = sb_carve(n, ctx->workspace, &own);
     sb_randomizers(ctx, O, B, px, msg, msg_bytes, stride_bytes, r, s_, B.a, n);
-    const uint64_t* in = B.as; uint64_t* out = B.sums;
-    for (size_t count = n, lanes = 0; lanes != 1; count = lanes) {                                  // sum a s: the last level writes term n of the key sum
-      lanes = fan_lanes(count);
-      const bool last = lanes == 1;
-      launch::schnorr_batch_sum(s, O.N, in, count, last ? B.ae + 4 * n : out, last ? B.Px + 4 * n : nullptr, last ? B.Py + 4 * n : nullptr);
-      in = out; out += 4 * lanes;
-    }
-    rc = msm_run<CURVE_SECP256K1>(ctx, S.sum_r, B.a, B.Rx, B.Ry, B.head->rx[0], B.head->ry[0], &B.head->finite[0], &B.head->invalid[0], n, 128, own);
-    if (rc == ECSIMD_HIP_OK) rc = msm_run<CURVE_SECP256K1>(ctx, S.sum_p, B.ae, B.Px, B.Py, B.head->rx[1], B.head->ry[1], &B.head->finite[1], &B.head->invalid[1], n + 1, 256, own);
+    batch_scalar_sum(B.as, B.sums, B.ae + 4 * n, n, [&](const uint64_t* in, size_t count, uint64_t* out, bool last) {        // sum a s, and G beside it
+      launch::schnorr_batch_sum(s, O.N, in, count, out, last ? B.Px + 4 * n : nullptr, last ? B.Py + 4 * n : nullptr);
+    });
+    rc = msm_run<CURVE_SECP256K1>(ctx, S.sums.r, B.a, B.Rx, B.Ry, B.head->rx[0], B.head->ry[0], &B.head->finite[0], &B.head->invalid[0], n, 128, own);
+    if (rc == ECSIMD_HIP_OK) rc = msm_run<CURVE_SECP256K1>(ctx, S.sums.key, B.ae, B.Px, B.Py, B.head->rx[1], B.head->ry[1], &B.head->finite[1], &B.head->invalid[1], n + 1, 256, own);
     if (rc != ECSIMD_HIP_OK) return rc;
     launch::schnorr_batch_accept(s, B.head, ok);
   }
@@ -2853,62 +2910,26 @@ int ecsimd_schnorr_batch_randomizers(ecsimd_hip_ctx* ctx, const uint64_t* px, co
   return e == hipSuccess ? ECSIMD_HIP_OK : fail(ctx, e, "schnorr_batch_randomizers launch"); }
 
 // ---- The bucket method on the Edwards curve and Ed25519 batch verification (include/ecsimd_ed25519_batch.h; k_msm_ed25519.hip has the stages,
-// tools/ed25519_batch_model.py the definition).  PUBLIC data.  The sum's schedule is msm_schedule_of's BUCKETS route, field for field; its workspace is its own
-// (edm_carve).  edb_schedule_of is the ONE place that turns (n, msg_bytes, flags) into the batch's sizes.
+// tools/ed25519_batch_model.py the definition).  PUBLIC data.  The sum's schedule is msm_schedule_of's BUCKETS route with four planes a point, its driver
+// bucket_sum_run.  edb_schedule_of is the ONE place that turns (n, msg_bytes, flags) into the batch's sizes.
 namespace {
-struct edm_blocks {
-  uint32_t *counter, *hist, *start, *cursor, *sorted;   // counter (refused encodings, broken invariants) and hist are ONE block, zeroed by one kernel
-  uint64_t *kk, *pre, *buckets, *partial, *tree;        // pre: three planes of n; buckets, partial, tree: four planes
-  size_t zero_bytes;
-};
-edm_blocks edm_carve(const msm_schedule& S, size_t n, void* base, size_t* bytes) {
-  edm_blocks B = {};
-  carve c = carve_from(base);
-  B.zero_bytes = round16(16 + 4 * S.K);
-  B.counter = static_cast<uint32_t*>(carve_bytes(c, B.zero_bytes)); B.hist = B.counter ? B.counter + 4 : nullptr;
-  B.start = static_cast<uint32_t*>(carve_bytes(c, round16(4 * (S.K + 1))));
-  B.cursor = static_cast<uint32_t*>(carve_bytes(c, round16(4 * S.K)));
-  B.sorted = static_cast<uint32_t*>(carve_bytes(c, round16(4 * S.T)));
-  B.kk = carve_limbs(c, n); B.pre = carve_limbs(c, 3 * n);
-  B.buckets = carve_limbs(c, 4 * S.K); B.partial = carve_limbs(c, 4 * 2 * S.slices); B.tree = carve_limbs(c, 4 * S.chunk_lanes);
-  *bytes = c.bytes;
-  return B;
-}
 bool edm_schedule_of(size_t n, int bits, int flags, msm_schedule* S) {
   if (flags != ECSIMD_MSM_ALG_AUTO && flags != ECSIMD_MSM_ALG_BUCKETS) return false;                 // the bucket route only
-  if (!msm_schedule_of(n, bits, ECSIMD_MSM_ALG_BUCKETS, S)) return false;
-  S->plan.workspace_bytes = 0;
-  if (n) (void)edm_carve(*S, n, nullptr, &S->plan.workspace_bytes);
-  return true;
+  return msm_schedule_of(n, bits, ECSIMD_MSM_ALG_BUCKETS, S, 4);
 }
-// out: the encoding (raw == nullptr) or raw: the extended point.  offset: the bytes at the start of the workspace that are the caller's.
-int edm_run(ecsimd_hip_ctx* ctx, const msm_schedule& S, const uint8_t* k, const uint8_t* pts, uint8_t* out, uint64_t* raw, uint8_t* finite, uint32_t* invalid, size_t n, int bits,
-            size_t offset = 0) {
-  using ML = launch::msm_launch<CURVE_SECP256K1>;       // zero, scan and scatter do not depend on the curve
-  const ecsimd_msm_plan_t& P = S.plan;
-  hipStream_t s = ctx->stream;
-  const int fan = launch::MSM_TREE_FAN;
-  if (n == 0) { launch::ed25519_msm_finish(s, nullptr, 0, 0, 0, 0, nullptr, out, raw, finite, invalid); const hipError_t e0 = hipGetLastError(); return e0 == hipSuccess ? ECSIMD_HIP_OK : fail(ctx, e0, "ed25519_msm launch"); }
-  int rc = ensure_workspace(ctx, offset + P.workspace_bytes);
-  if (rc != ECSIMD_HIP_OK) return rc;
-  size_t bytes = 0;
-  const edm_blocks B = edm_carve(S, n, reinterpret_cast<uint8_t*>(ctx->workspace) + offset, &bytes);
-  ML::zero(s, B.counter, B.zero_bytes);
-  launch::ed25519_msm_digits(s, k, pts, B.kk, B.pre, B.hist, B.counter, n, bits, P.c, P.windows);
-  ML::scan(s, B.hist, B.start, B.cursor, S.K);
-  ML::scatter(s, B.kk, B.cursor, B.sorted, B.counter + 1, n, S.T, P.c, P.windows);
-  launch::ed25519_msm_slices(s, B.sorted, B.kk, B.pre, B.start, B.buckets, B.partial, B.counter + 1, n, S.T, P.L, S.slices, P.c, S.K);
-  launch::ed25519_msm_combine(s, B.start, B.buckets, B.partial, B.counter + 1, P.L, S.slices, P.c, S.K);
-  launch::ed25519_msm_chunks(s, B.buckets, B.tree, S.chunk_lanes, S.per_window, P.c, (int)P.m, S.K);
-  for (size_t count = S.per_window; count > 1;) {
-    const size_t lanes = (count + fan - 1) / fan;
-    launch::ed25519_msm_tree(s, B.tree, S.chunk_lanes, count, S.per_window, (size_t)P.windows, lanes, fan);
-    count = lanes;
+// out: the encoding (raw == nullptr) or raw: the extended point.
+struct edwards_sum {
+  using ML = launch::ed25519_msm_launch;
+  static constexpr const char* what = "ed25519_msm launch";
+  const uint8_t *k, *pts; uint8_t* out; uint64_t* raw;
+  void digits(hipStream_t s, const msm_blocks& B, size_t n, int bits, int c, int windows) const { ML::digits(s, k, pts, B.kk, B.px, B.hist, B.counter, n, bits, c, windows); }
+  void slices(hipStream_t s, const msm_blocks& B, size_t n, size_t T, size_t L, size_t slices, int c, size_t K) const {
+    ML::slices(s, B.sorted, B.kk, B.px, B.start, B.buckets, B.partial, B.counter + 1, n, T, L, slices, c, K);
   }
-  launch::ed25519_msm_finish(s, B.tree, S.chunk_lanes, S.per_window, P.windows, P.c, B.counter, out, raw, finite, invalid);
-  const hipError_t e = hipGetLastError();
-  return e == hipSuccess ? ECSIMD_HIP_OK : fail(ctx, e, "ed25519_msm launch");
-}
+  void finish(hipStream_t s, const uint64_t* arr, size_t total, size_t stride, int windows, int c, const uint32_t* counter, uint8_t* finite, uint32_t* invalid) const {
+    ML::finish(s, arr, total, stride, windows, c, counter, out, raw, finite, invalid);
+  }
+};
 
 // The per-lane cofactored rule, a chunk at a time: s, h, R's (x, y), the table of -A, valid.
 struct edc_layout { uint64_t *s, *h, *rxy; void* table; uint8_t* valid; size_t bytes; };
@@ -2938,9 +2959,6 @@ int edc_run(ecsimd_hip_ctx* ctx, const uint8_t* pk, const uint8_t* msg, size_t m
   return ECSIMD_HIP_OK;
 }
 
-size_t edb_fan_lanes(size_t count) { return (count + launch::ED25519_BATCH_FAN - 1) / launch::ED25519_BATCH_FAN; }
-int edb_fan_passes(size_t count) { int p = 0; while (count > 1) { count = edb_fan_lanes(count); ++p; } return p; }
-size_t edb_fan_elements(size_t count) { size_t t = 0; while (count > 1) { count = edb_fan_lanes(count); t += count; } return t; }      // every level below the leaves
 struct edb_blocks {
   launch::ed25519_batch_head* head;
   uint64_t *h, *leaf, *nodes, *z, *zh, *zs, *sums, *Aenc, *Renc;      // zh, Aenc: n + 1 elements, the last one the B term; nodes, sums: the trees' levels, one behind the other
@@ -2949,8 +2967,8 @@ struct edb_blocks {
 edb_blocks edb_carve(size_t n, void* base, size_t* bytes) {
   edb_blocks B; carve c = carve_from(base);
   B.head = static_cast<launch::ed25519_batch_head*>(carve_bytes(c, sizeof(launch::ed25519_batch_head)));
-  B.h = carve_limbs(c, n); B.leaf = carve_limbs(c, n); B.nodes = carve_limbs(c, edb_fan_elements(n));
-  B.z = carve_limbs(c, n); B.zh = carve_limbs(c, n + 1); B.zs = carve_limbs(c, n); B.sums = carve_limbs(c, edb_fan_elements(n));
+  B.h = carve_limbs(c, n); B.leaf = carve_limbs(c, n); B.nodes = carve_limbs(c, fan_elements(n));
+  B.z = carve_limbs(c, n); B.zh = carve_limbs(c, n + 1); B.zs = carve_limbs(c, n); B.sums = carve_limbs(c, fan_elements(n));
   B.Aenc = carve_limbs(c, n + 1); B.Renc = carve_limbs(c, n);
   B.valid = carve_flags(c, n);
   (void)carve_bytes(c, (32 - c.bytes % 32) % 32);      // the sums' blocks start on 32 bytes
@@ -2958,14 +2976,8 @@ edb_blocks edb_carve(size_t n, void* base, size_t* bytes) {
   return B;
 }
 constexpr int EDB_KEY_BITS = 253;                       // z h mod L and L - sum z s are below L < 2^253
-struct edb_schedule { ecsimd_ed25519_batch_plan_t plan; msm_schedule sum_r, sum_a; bool reject_small; };
-// The MSM route's bytes for exactly n >= 1 signatures: its own arrays, then the larger of the two sums' blocks (they run one after the other).
-size_t edb_msm_bytes(size_t n) {
-  msm_schedule r, a; size_t own = 0;
-  if (!edm_schedule_of(n, 128, ECSIMD_MSM_ALG_BUCKETS, &r) || !edm_schedule_of(n + 1, EDB_KEY_BITS, ECSIMD_MSM_ALG_BUCKETS, &a)) return 0;
-  (void)edb_carve(n, nullptr, &own);
-  return own + (r.plan.workspace_bytes > a.plan.workspace_bytes ? r.plan.workspace_bytes : a.plan.workspace_bytes);
-}
+struct edb_schedule { ecsimd_ed25519_batch_plan_t plan; batch_sums sums; bool reject_small; };
+size_t edb_msm_bytes(size_t n) { size_t own = 0; (void)edb_carve(n, nullptr, &own); return batch_msm_bytes(own, n, EDB_KEY_BITS, 4); }
 bool edb_flags_ok(int flags) {
   const int route = flags & ~ECSIMD_ED25519_REJECT_SMALL_ORDER;
   return flags >= 0 && (route == ECSIMD_ED25519_BATCH_AUTO || route == ECSIMD_ED25519_BATCH_MSM || route == ECSIMD_ED25519_BATCH_LANES);
@@ -2979,15 +2991,9 @@ bool edb_schedule_of(size_t n, size_t msg_bytes, int flags, edb_schedule* S) {
   P.route = route != ECSIMD_ED25519_BATCH_AUTO ? route : n >= ECSIMD_ED25519_BATCH_AUTO_THRESHOLD ? ECSIMD_ED25519_BATCH_MSM : ECSIMD_ED25519_BATCH_LANES;
   if (n == 0) { P.launches = 1; return true; }                                   // the reduction kernel alone writes the empty batch's verdict
   if (P.route == ECSIMD_ED25519_BATCH_MSM) {
-    if (!edm_schedule_of(n, 128, ECSIMD_MSM_ALG_BUCKETS, &S->sum_r) || !edm_schedule_of(n + 1, EDB_KEY_BITS, ECSIMD_MSM_ALG_BUCKETS, &S->sum_a)) return false;
-    // What this batch needs, and what every smaller batch would: as in sb_schedule_of, the sums' blocks are monotone in the number of terms between powers of
-    // two only, so the largest need below n is met at n itself or next to a power of two.
-    P.workspace_bytes = edb_msm_bytes(n);
-    for (size_t p = 2; p <= n + 2; p <<= 1)
-      for (size_t m = p - 2; m <= p && m <= n; ++m)
-        if (m >= 1 && edb_msm_bytes(m) > P.workspace_bytes) P.workspace_bytes = edb_msm_bytes(m);
-    const int levels = edb_fan_passes(n);
-    P.launches = 5 + levels + (levels > 1 ? levels : 1) + S->sum_r.plan.launches + S->sum_a.plan.launches;   // zero, front, seed, scalars, accept; the two trees; the two sums
+    if (!batch_sums_of(n, EDB_KEY_BITS, 4, &S->sums)) return false;
+    P.workspace_bytes = batch_workspace_bytes(n, edb_msm_bytes);
+    P.launches = batch_msm_launches(n, S->sums);
   } else {
     P.workspace_bytes = edc_bytes(n, true);
     P.launches = 1 + 2 * (int)((n + ED25519_VERIFY_CHUNK - 1) / ED25519_VERIFY_CHUNK);
@@ -2998,25 +3004,17 @@ bool edb_schedule_of(size_t n, size_t msg_bytes, int flags, edb_schedule* S) {
 int edb_check(ecsimd_hip_ctx* ctx, const uint8_t* pk, const uint8_t* msg, size_t* msg_bytes, size_t stride_bytes, const uint32_t* lens, const uint8_t* sig, const void* out,
               size_t out_bytes, size_t n) {
   if ((!pk || !sig) && n) return bad(ctx, "ed25519 batch: pk or sig is null");
-  if (n > ECSIMD_MSM_MAX_N - 1) return bad(ctx, "ed25519 batch: n is above ECSIMD_MSM_MAX_N - 1: verify chunks and AND their verdicts");
-  const int rc = ed25519_messages(ctx, msg, msg_bytes, stride_bytes, lens, n); if (rc != ECSIMD_HIP_OK) return rc;
   const size_t msg_extent = n ? (n - 1) * stride_bytes + (lens ? stride_bytes : *msg_bytes) : 0;
-  if (ranges_overlap(out, out_bytes, pk, 32 * n) || ranges_overlap(out, out_bytes, sig, 64 * n) || ranges_overlap(out, out_bytes, msg, msg_extent) ||
-      ranges_overlap(out, out_bytes, lens, 4 * n)) return bad(ctx, "ed25519 batch: the output must not overlap an input");
-  return ECSIMD_HIP_OK;
+  return batch_check(ctx, "ed25519 batch", n, [&] { return ed25519_messages(ctx, msg, msg_bytes, stride_bytes, lens, n); }, {out, out_bytes},
+                     {{pk, 32 * n}, {sig, 64 * n}, {msg, msg_extent}, {lens, 4 * n}});
 }
 // The front, the hash tree, the seed, the scalars for n >= 1.  z: where the randomizers go; products: also z h and z s (B.zh, B.zs).
 void edb_randomizers(ecsimd_hip_ctx* ctx, const edb_blocks& B, const uint8_t* pk, const uint8_t* msg, size_t msg_bytes, size_t stride_bytes, const uint32_t* lens,
                      const uint8_t* sig, bool reject_small, uint64_t* z, bool products, size_t n) {
   hipStream_t s = ctx->stream;
-  launch::msm_launch<CURVE_SECP256K1>::zero(s, B.head, sizeof(launch::ed25519_batch_head));
+  launch::msm_zero(s, B.head, sizeof(launch::ed25519_batch_head));
   launch::ed25519_batch_front(s, *ed25519_order(), pk, sig, msg, msg_bytes, stride_bytes, lens, reject_small, B.h, B.leaf, B.Aenc, B.Renc, B.valid, B.head, n);
-  const uint64_t* level = B.leaf; uint64_t* out = B.nodes;
-  for (size_t count = n; count > 1;) {
-    launch::ed25519_batch_node(s, level, count, out);
-    count = edb_fan_lanes(count); level = out; out += 4 * count;
-  }
-  launch::ed25519_batch_seed(s, level, n, B.head);
+  launch::ed25519_batch_seed(s, batch_hash_tree(s, launch::ed25519_batch_node, B.leaf, B.nodes, n), n, B.head);
   launch::ed25519_batch_scalars(s, *ed25519_order(), B.head, B.h, sig, B.valid, z, products ? B.zh : nullptr, products ? B.zs : nullptr, n);
 }
 }  // namespace
@@ -3042,7 +3040,7 @@ int ecsimd_ed25519_msm(ecsimd_hip_ctx* ctx, const uint8_t* k, const uint8_t* pts
     for (int b = a + 1; b < 3; ++b) if (ranges_overlap(outs[a], out_bytes[a], outs[b], out_bytes[b])) return bad(ctx, "ed25519_msm: an output must not overlap an input or another output");
   }
   const hipError_t e0 = hipSetDevice(ctx->device); if (e0 != hipSuccess) return fail(ctx, e0, "hipSetDevice");
-  return edm_run(ctx, S, k, pts, out, nullptr, finite, invalid, n, bits); }
+  return bucket_sum_run(ctx, S, edwards_sum{k, pts, out, nullptr}, finite, invalid, n, bits, 0); }
 
 int ecsimd_ed25519_verify_cofactored(ecsimd_hip_ctx* ctx, const uint8_t* pk, const uint8_t* msg, size_t msg_bytes, size_t stride_bytes, const uint32_t* lens,
                                      const uint8_t* sig, uint8_t* ok, size_t n, int flags) {
@@ -3071,26 +3069,23 @@ int ecsimd_ed25519_verify_batch(ecsimd_hip_ctx* ctx, const uint8_t* pk, const ui
   if (!edb_schedule_of(n, lens ? stride_bytes : msg_bytes, flags, &S)) return bad(ctx, "ed25519_verify_batch: no schedule for these arguments");
   const hipError_t e0 = hipSetDevice(ctx->device); if (e0 != hipSuccess) return fail(ctx, e0, "hipSetDevice");
   hipStream_t s = ctx->stream;
-  if (n == 0) launch::schnorr_batch_all(s, nullptr, 0, ok);
+  if (n == 0) launch::flags_all(s, nullptr, 0, ok);
   else if (S.plan.route == ECSIMD_ED25519_BATCH_LANES) {
     uint8_t* verdicts = nullptr;
     rc = edc_run(ctx, pk, msg, msg_bytes, stride_bytes, lens, sig, nullptr, n, S.reject_small, &verdicts); if (rc != ECSIMD_HIP_OK) return rc;
-    launch::schnorr_batch_all(s, verdicts, n, ok);      // k_schnorr_batch.hip's reduction: the AND of n bytes has no curve
+    launch::flags_all(s, verdicts, n, ok);
   } else {
     rc = ensure_workspace(ctx, S.plan.workspace_bytes); if (rc != ECSIMD_HIP_OK) return rc;      // all of it now: the sums below find it large enough, nothing moves
     size_t own = 0;
     const edb_blocks B = edb_carve(n, ctx->workspace, &own);
     edb_randomizers(ctx, B, pk, msg, msg_bytes, stride_bytes, lens, sig, S.reject_small, B.z, true, n);
-    const uint64_t* in = B.zs; uint64_t* out = B.sums;
-    for (size_t count = n, lanes = 0; lanes != 1; count = lanes) {                                  // sum z s: the last level writes term n of the key sum
-      lanes = edb_fan_lanes(count);
-      const bool last = lanes == 1;
-      launch::ed25519_batch_sum(s, *ed25519_order(), in, count, last ? B.zh + 4 * n : out, last ? B.Aenc + 4 * n : nullptr);
-      in = out; out += 4 * lanes;
-    }
-    rc = edm_run(ctx, S.sum_r, reinterpret_cast<const uint8_t*>(B.z), reinterpret_cast<const uint8_t*>(B.Renc), nullptr, B.head->sum[0], &B.head->finite[0], &B.head->invalid[0], n, 128, own);
-    if (rc == ECSIMD_HIP_OK) rc = edm_run(ctx, S.sum_a, reinterpret_cast<const uint8_t*>(B.zh), reinterpret_cast<const uint8_t*>(B.Aenc), nullptr, B.head->sum[1], &B.head->finite[1],
-                                          &B.head->invalid[1], n + 1, EDB_KEY_BITS, own);
+    batch_scalar_sum(B.zs, B.sums, B.zh + 4 * n, n, [&](const uint64_t* in, size_t count, uint64_t* out, bool last) {        // sum z s, and B's encoding beside it
+      launch::ed25519_batch_sum(s, *ed25519_order(), in, count, out, last ? B.Aenc + 4 * n : nullptr);
+    });
+    rc = bucket_sum_run(ctx, S.sums.r, edwards_sum{reinterpret_cast<const uint8_t*>(B.z), reinterpret_cast<const uint8_t*>(B.Renc), nullptr, B.head->sum[0]}, &B.head->finite[0],
+                        &B.head->invalid[0], n, 128, own);
+    if (rc == ECSIMD_HIP_OK) rc = bucket_sum_run(ctx, S.sums.key, edwards_sum{reinterpret_cast<const uint8_t*>(B.zh), reinterpret_cast<const uint8_t*>(B.Aenc), nullptr, B.head->sum[1]},
+                                                 &B.head->finite[1], &B.head->invalid[1], n + 1, EDB_KEY_BITS, own);
     if (rc != ECSIMD_HIP_OK) return rc;
     launch::ed25519_batch_accept(s, B.head, ok);
   }

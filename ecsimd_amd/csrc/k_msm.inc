@@ -3,21 +3,9 @@
 // is a branch.  The schedule -- which kernels, how many lanes, how long a lane's loop -- is a function of (n, bits, flags) alone (capi.hip msm_schedule_of,
 // tools/msm_model.py); the data decide only which side of a branch a lane takes.
 //
-// The BUCKETS route, T = n * windows entries, K = windows * 2^c keys (key = window * 2^c + digit):
-//   k_msm_zero      the two counters and the histogram, by a kernel (every node of a captured call is a kernel).
-//   k_msm_digits    one lane per term: the point is validated as k_on_curve validates, converted to the fast domain, its scalar masked to `bits` bits (zeroed
-//                   where the point is infinity or invalid) and the histogram of its c-bit digits taken, one vector atomic per window.
-//   k_msm_scan      one workgroup: the exclusive scan of the histogram -> start[K + 1], cursor[K].
-//   k_msm_scatter   one lane per term: sorted[cursor[key]++] = i for every window (the order inside a bucket is whatever the atomics give: the sum commutes).
-//                   Every term has ONE entry per window, digit 0 included, so window w owns sorted[w n, (w + 1) n).
-//   k_msm_slices    one lane per L consecutive entries of `sorted`: complete mixed additions into a Jacobian accumulator, flushed where the key changes.  A run
-//                   that holds its whole bucket goes to the bucket; a run cut by the slice's edge goes to the slice's head slot (it starts at the slice's first
-//                   entry) or tail slot (it does not: then it runs to the slice's end).  At most L additions per lane.
-//   k_msm_combine   one lane per key: an empty bucket becomes infinity, a bucket spread over several slices the sum of their slots: at most
-//                   ceil(n / L) + 1 general additions, whatever the scalars (a bucket has at most n entries).
-//   k_msm_chunks    one lane per m buckets of a window: the running-sum form of sum t B_(j m + t) plus (j m) times the chunk's plain sum.
-//   k_msm_tree      fan-in 16 per launch, lanes owning strided slices; grid.y = the window.  Complete Jacobian addition.
-//   k_msm_final     one lane: Horner over the windows (c doublings each), ONE inversion, the affine classical result, the flag and the invalid count.
+// The BUCKETS route: msm_stages.cuh has the stages and their bodies; this file gives them the Jacobian group (complete additions: every exceptional case of the
+// group law decided by a branch) and keeps what is the curve's: k_msm_digits validates the point as k_on_curve validates and converts it to the fast domain,
+// k_msm_final ends Horner with ONE inversion, the affine classical result, the flag and the invalid count.  k_msm_common.hip has zero, scan and scatter.
 // The LANES route: k_msm_sanitize (the same validation; (0, G) where a term contributes nothing), the per-lane windowed products of k_varwin.inc, then
 // k_msm_tree_affine / k_msm_tree / k_msm_final.  ecsimd_msm_point_sum is k_msm_tree_affine with the validation on, then the same two.
 //
@@ -30,6 +18,7 @@
 // a loop around an addition use (112 - 768).
 #include "kernels.h"
 #include "point.cuh"
+#include "msm_stages.cuh"
 
 namespace ecsimd_hip {
 namespace {
@@ -120,30 +109,19 @@ ECS_DEV int classify(const fe& xv, const fe& yv, fe& xf, fe& yf) {
   else rhs = fe_add<CI>(rhs, FE_CONST(CI, BM));
   return (below_p(xv) && below_p(yv) && fe_eq(fe_sqr<CI>(yf), rhs)) ? 1 : 2;
 }
-// the low `bits` bits of k (1 <= bits <= 256)
-ECS_DEV fe mask_bits(fe k, int bits) {
-#pragma unroll
-  for (int j = 0; j < 8; ++j) {
-    const int lo = 32 * j;
-    if (bits <= lo) k.w[j] = 0u;
-    else if (bits < lo + 32) k.w[j] &= (1u << (bits - lo)) - 1u;
-  }
-  return k;
-}
-// digit w of the masked scalar at kw (8 words in global memory: indexing registers by w would cost scratch), c <= 16 bits: at most two words
-ECS_DEV uint32_t digit_of(const uint32_t* __restrict__ kw, int w, int c) {
-  const int pos = w * c, word = pos >> 5, off = pos & 31;
-  uint32_t v = kw[word] >> off;
-  if (off + c > 32 && word < 7) v |= kw[word + 1] << (32 - off);
-  return v & ((1u << c) - 1u);
-}
+// msm_stages.cuh's group: Jacobian accumulators, three planes, Z = 0; the terms are the affine fast-domain points k_msm_digits left at (px, py)
+struct jacobian_group {
+  using point = jpoint;
+  struct terms { const uint64_t* __restrict__ px; const uint64_t* __restrict__ py; };
+  ECS_DEV static point identity() { return j_infinity(); }
+  ECS_DEV static point add(const point& P, const point& Q) { return j_add(P, Q); }
+  ECS_DEV static point dbl(const point& P) { return j_dbl(P); }
+  ECS_DEV static point add_term(const point& P, const terms& t, size_t, size_t idx) { return j_madd(P, fe_load(t.px, idx), fe_load(t.py, idx)); }
+  ECS_DEV static point load(const uint64_t* __restrict__ a, size_t total, size_t e) { return j_load(a, total, e); }
+  ECS_DEV static void store(uint64_t* __restrict__ a, size_t total, size_t e, const point& P) { j_store(a, total, e, P); }
+};
+using G = jacobian_group;
 
-// The words a call counts into -- counter[0] invalid points, counter[1] broken invariants, the histogram behind them -- zeroed by a kernel, as every other
-// node of a captured call is a kernel: 16 bytes per lane.
-__global__ void __launch_bounds__(BLOCK) k_msm_zero(uint4* __restrict__ words, size_t n16) {
-  const size_t i = (size_t)blockIdx.x * BLOCK + threadIdx.x;
-  if (i < n16) words[i] = make_uint4(0u, 0u, 0u, 0u);
-}
 __global__ void __launch_bounds__(BLOCK) k_msm_digits(const uint64_t* __restrict__ k, const uint64_t* __restrict__ x, const uint64_t* __restrict__ y, uint64_t* __restrict__ kk,
                                                       uint64_t* __restrict__ px, uint64_t* __restrict__ py, uint32_t* __restrict__ hist, uint32_t* __restrict__ counter,
                                                       size_t n, int bits, int c, int windows) {
@@ -154,136 +132,23 @@ __global__ void __launch_bounds__(BLOCK) k_msm_digits(const uint64_t* __restrict
   if (cls == 2) atomicAdd(counter, 1u);
   const fe kv = cls == 1 ? mask_bits(fe_load(k, i), bits) : fe_zero();
   fe_store(kk, i, kv); fe_store(px, i, xf); fe_store(py, i, yf);
-  const uint32_t mask = (1u << c) - 1u;
-  // the digits from the registers: a running 64-bit window over the words, shifted by c per step (no register is indexed by w)
-  uint64_t acc = kv.w[0]; int have = 32, next = 1;
-#pragma unroll 1
-  for (int w = 0; w < windows; ++w) {
-    if (have < c && next < 8) {
-      uint32_t word = 0;
-#pragma unroll
-      for (int j = 1; j < 8; ++j) if (j == next) word = kv.w[j];
-      acc |= (uint64_t)word << have; have += 32; ++next;
-    }
-    atomicAdd(&hist[((size_t)w << c) + ((uint32_t)acc & mask)], 1u);
-    acc >>= c; have -= c;
-  }
+  msm_histogram(kv, hist, c, windows);
 }
 
-// One workgroup of 1024: lane t sums its `per` consecutive counters, the sums are scanned in LDS, the lane walks its counters again.
-__global__ void __launch_bounds__(1024) k_msm_scan(const uint32_t* __restrict__ hist, uint32_t* __restrict__ start, uint32_t* __restrict__ cursor, size_t K) {
-  __shared__ uint32_t part[1024];
-  const size_t per = (K + 1023) / 1024, t = threadIdx.x;
-  const size_t lo = t * per < K ? t * per : K, hi = lo + per < K ? lo + per : K;
-  uint32_t sum = 0;
-  for (size_t e = lo; e < hi; ++e) sum += hist[e];
-  part[t] = sum;
-  __syncthreads();
-  for (int d = 1; d < 1024; d <<= 1) {
-    const uint32_t v = t >= (size_t)d ? part[t - d] : 0u;
-    __syncthreads();
-    part[t] += v;
-    __syncthreads();
-  }
-  uint32_t run = part[t] - sum;                                         // exclusive
-  for (size_t e = lo; e < hi; ++e) { start[e] = run; cursor[e] = run; run += hist[e]; }
-  if (t == 1023) start[K] = part[1023];
-}
-
-__global__ void __launch_bounds__(BLOCK) k_msm_scatter(const uint64_t* __restrict__ kk, uint32_t* __restrict__ cursor, uint32_t* __restrict__ sorted, uint32_t* __restrict__ broken, size_t n, size_t T, int c, int windows) {
-  const size_t i = (size_t)blockIdx.x * BLOCK + threadIdx.x;
-  if (i >= n) return;
-  const uint32_t* kw = reinterpret_cast<const uint32_t*>(kk) + 8 * i;
-#pragma unroll 1
-  for (int w = 0; w < windows; ++w) {
-    const uint32_t pos = atomicAdd(&cursor[((size_t)w << c) + digit_of(kw, w, c)], 1u);
-    if (pos < T) sorted[pos] = (uint32_t)i; else atomicAdd(broken, 1u);  // the histogram counted this very digit: anything else fails the call (k_msm_final)
-  }
-}
-
-// where a finished run goes (see the head of the file); p0, p1 = the slice, first = the run's first entry in it
-ECS_DEV void flush_run(uint32_t key, const jpoint& acc, size_t first, size_t p0, size_t p1, size_t slice, const uint32_t* __restrict__ start, uint32_t dmask,
-                       uint64_t* __restrict__ buckets, size_t K, uint64_t* __restrict__ partial, size_t slots) {
-  if (key == 0xffffffffu || (key & dmask) == 0u) return;                // no run yet, or digit 0: skipped
-  const size_t a = start[key], b = start[key + 1];
-  if (a >= p0 && b <= p1) j_store(buckets, K, key, acc);
-  else j_store(partial, slots, 2 * slice + (first == p0 ? 0 : 1), acc);
-}
 __global__ void __launch_bounds__(BLOCK) k_msm_slices(const uint32_t* __restrict__ sorted, const uint64_t* __restrict__ kk, const uint64_t* __restrict__ px,
                                                       const uint64_t* __restrict__ py, const uint32_t* __restrict__ start, uint64_t* __restrict__ buckets,
                                                       uint64_t* __restrict__ partial, uint32_t* __restrict__ broken, size_t n, size_t T, size_t L, size_t slices, int c, size_t K) {
-  const size_t s = (size_t)blockIdx.x * BLOCK + threadIdx.x;
-  if (s >= slices) return;
-  const size_t p0 = s * L, p1 = p0 + L < T ? p0 + L : T;
-  const uint32_t dmask = (1u << c) - 1u;
-  int w = (int)(p0 / n);
-  size_t wend = ((size_t)w + 1) * n, first = p0;
-  uint32_t cur = 0xffffffffu;
-  jpoint acc = j_infinity();
-#pragma unroll 1
-  for (size_t pos = p0; pos < p1; ++pos) {
-    while (pos >= wend) { ++w; wend += n; }
-    const size_t idx = sorted[pos];
-    if (idx >= n) { atomicAdd(broken, 1u); continue; }                  // every entry was written by the scatter: anything else fails the call
-    const uint32_t d = digit_of(reinterpret_cast<const uint32_t*>(kk) + 8 * idx, w, c);
-    const uint32_t key = ((uint32_t)w << c) + d;
-    if (key != cur) {
-      flush_run(cur, acc, first, p0, p1, s, start, dmask, buckets, K, partial, 2 * slices);
-      cur = key; first = pos; acc = j_infinity();
-    }
-    if (d != 0u) acc = j_madd(acc, fe_load(px, idx), fe_load(py, idx));
-  }
-  flush_run(cur, acc, first, p0, p1, s, start, dmask, buckets, K, partial, 2 * slices);
+  msm_slices<G>(sorted, kk, {px, py}, start, buckets, partial, broken, n, T, L, slices, c, K);
 }
-
 __global__ void __launch_bounds__(BLOCK) k_msm_combine(const uint32_t* __restrict__ start, uint64_t* __restrict__ buckets, const uint64_t* __restrict__ partial,
                                                        uint32_t* __restrict__ broken, size_t L, size_t slices, int c, size_t K) {
-  const size_t key = (size_t)blockIdx.x * BLOCK + threadIdx.x;
-  if (key >= K || (key & ((1u << c) - 1u)) == 0) return;
-  const size_t a = start[key], b = start[key + 1];
-  if (a > b || b > slices * L) atomicAdd(broken, 1u);                  // offsets that are no scan of a histogram fail the call; no load follows them out of `partial`
-  if (a >= b || b > slices * L) { j_store(buckets, K, key, j_infinity()); return; }       // a == b: an empty bucket
-  const size_t s0 = a / L, s1 = (b - 1) / L;
-  if (s0 == s1) return;                                                 // the whole bucket lay in one slice, which wrote it
-  jpoint acc = j_infinity();
-#pragma unroll 1
-  for (size_t s = s0; s <= s1; ++s) acc = j_add(acc, j_load(partial, 2 * slices, 2 * s + (a <= s * L ? 0 : 1)));
-  j_store(buckets, K, key, acc);
+  msm_combine<G>(start, buckets, partial, broken, L, slices, c, K);
 }
-
-// lane (w, j): sum over t < m of (j m + t) B[j m + t] = sum t B + (j m) sum B.  Bucket 0 of a window is never read.
 __global__ void __launch_bounds__(BLOCK) k_msm_chunks(const uint64_t* __restrict__ buckets, uint64_t* __restrict__ out, size_t lanes, size_t per_window, int c, int m, size_t K) {
-  const size_t g = (size_t)blockIdx.x * BLOCK + threadIdx.x;
-  if (g >= lanes) return;
-  const size_t w = g / per_window, j = g % per_window, off = j * (size_t)m, base = (w << c) + off;
-  jpoint run = j_infinity(), tot = j_infinity();
-#pragma unroll 1
-  for (int t = m - 1; t >= 0; --t) {
-    if (off + t != 0) run = j_add(run, j_load(buckets, K, base + t));
-    if (t != 0) tot = j_add(tot, run);
-  }
-  jpoint mult = j_infinity();
-#pragma unroll 1
-  for (int bit = c - 1; bit >= 0; --bit) {
-    mult = j_dbl(mult);
-    if ((off >> bit) & 1u) mult = j_add(mult, run);
-  }
-  j_store(out, lanes, g, j_add(tot, mult));
+  msm_chunks<G>(buckets, out, lanes, per_window, c, m, K);
 }
-
-// arr[group * stride + g] = the sum of arr[group * stride + g + t * lanes], t < fan, for g < lanes: in place (a lane reads its own elements, then writes the first)
 __global__ void __launch_bounds__(BLOCK) k_msm_tree(uint64_t* arr, size_t total, size_t count, size_t stride, size_t lanes, int fan) {
-  const size_t g = (size_t)blockIdx.x * BLOCK + threadIdx.x;
-  if (g >= lanes) return;
-  const size_t base = (size_t)blockIdx.y * stride;
-  jpoint acc = j_load(arr, total, base + g);
-#pragma unroll 1
-  for (int t = 1; t < fan; ++t) {
-    const size_t e = g + (size_t)t * lanes;
-    if (e >= count) break;
-    acc = j_add(acc, j_load(arr, total, base + e));
-  }
-  j_store(arr, total, base + g, acc);
+  msm_tree<G>(arr, total, count, stride, lanes, fan);
 }
 // the same from affine classical points ((0, 0) = infinity) into a Jacobian array; VALIDATE: each point checked as k_msm_digits checks it, invalid ones counted and skipped
 template <bool VALIDATE>
@@ -324,17 +189,11 @@ __global__ void __launch_bounds__(BLOCK) k_msm_sanitize(const uint64_t* __restri
   fe_store(kk, i, kv); fe_store(sx, i, xv); fe_store(sy, i, yv);
 }
 
-// One lane.  windows > 0: arr[w * stride] = the sum of window w; Horner from the top, c doublings per window.  windows == 0: the empty sum.
+// One lane: msm_horner, then the affine classical result.
 __global__ void __launch_bounds__(64) k_msm_final(const uint64_t* __restrict__ arr, size_t total, size_t stride, int windows, int c, const uint32_t* __restrict__ counter,
                                                   uint64_t* __restrict__ rx, uint64_t* __restrict__ ry, uint8_t* __restrict__ finite, uint32_t* __restrict__ invalid) {
   if (blockIdx.x != 0 || threadIdx.x != 0) return;
-  jpoint acc = j_infinity();
-#pragma unroll 1
-  for (int w = windows - 1; w >= 0; --w) {
-#pragma unroll 1
-    for (int d = 0; d < c; ++d) acc = j_dbl(acc);
-    acc = j_add(acc, j_load(arr, total, (size_t)w * stride));
-  }
+  const jpoint acc = msm_horner<G>(arr, total, stride, windows, c);
   fe ax = fe_zero(), ay = fe_zero();
   const bool fin = !fe_is_zero(acc.z);
   if (fin) {
@@ -356,18 +215,9 @@ __global__ void __launch_bounds__(64) k_msm_final(const uint64_t* __restrict__ a
 
 namespace launch {
 static dim3 grid_of(size_t lanes, size_t y = 1) { return dim3((unsigned)((lanes + BLOCK - 1) / BLOCK), (unsigned)y); }
-template <> void msm_launch<C>::zero(hipStream_t s, void* words, size_t bytes) {
-  hipLaunchKernelGGL(k_msm_zero, grid_of(bytes / 16), dim3(BLOCK), 0, s, static_cast<uint4*>(words), bytes / 16);
-}
 template <> void msm_launch<C>::digits(hipStream_t s, const uint64_t* k, const uint64_t* x, const uint64_t* y, uint64_t* kk, uint64_t* px, uint64_t* py, uint32_t* hist,
                                        uint32_t* counter, size_t n, int bits, int c, int windows) {
   hipLaunchKernelGGL(k_msm_digits, grid_of(n), dim3(BLOCK), 0, s, k, x, y, kk, px, py, hist, counter, n, bits, c, windows);
-}
-template <> void msm_launch<C>::scan(hipStream_t s, const uint32_t* hist, uint32_t* start, uint32_t* cursor, size_t K) {
-  hipLaunchKernelGGL(k_msm_scan, dim3(1), dim3(1024), 0, s, hist, start, cursor, K);
-}
-template <> void msm_launch<C>::scatter(hipStream_t s, const uint64_t* kk, uint32_t* cursor, uint32_t* sorted, uint32_t* broken, size_t n, size_t T, int c, int windows) {
-  hipLaunchKernelGGL(k_msm_scatter, grid_of(n), dim3(BLOCK), 0, s, kk, cursor, sorted, broken, n, T, c, windows);
 }
 template <> void msm_launch<C>::slices(hipStream_t s, const uint32_t* sorted, const uint64_t* kk, const uint64_t* px, const uint64_t* py, const uint32_t* start, uint64_t* buckets,
                                        uint64_t* partial, uint32_t* broken, size_t n, size_t T, size_t L, size_t slices, int c, size_t K) {

@@ -2,14 +2,10 @@
 // ecsimd_ed25519_verify_cofactored, ecsimd_ed25519_verify_batch and ecsimd_ed25519_batch_randomizers (include/ecsimd_ed25519_batch.h).  PUBLIC data only: bucket
 // addresses are scalar digits and the verification loop is indexed by them.  tools/ed25519_batch_model.py is the normative statement.
 //
-// THE SUM.  The stages and the schedule are k_msm.inc's (capi.hip msm_schedule_of, tools/msm_model.py): zero, scan and scatter do not depend on the curve and are
-// msm_launch<CURVE_SECP256K1>'s kernels; the others are restated here on ed25519.cuh's arithmetic:
+// THE SUM.  msm_stages.cuh has the stages and their bodies, k_msm_common.hip the kernels without a curve (zero, scan, scatter); this file gives the stages the
+// extended Edwards group on ed25519.cuh's arithmetic (ed_add_precomp 7 M into an ed_point, ed_add 9 M, ed_dbl) and keeps what is the curve's:
 //   k_edm_digits    one lane per term: the encoding decoded ONCE (ed_decode, strict; a refused one is counted and contributes nothing: scalar 0), stored as
 //                   ed_precomp (y + x, y - x, 2 d x y), the scalar masked to `bits` bits, the histogram of its c-bit digits.
-//   k_edm_slices    one lane per L consecutive entries of `sorted`: ed_add_precomp (7 M) into an ed_point, flushed where the key changes (bucket, head or tail slot).
-//   k_edm_combine   one lane per key: an empty bucket becomes the identity, a bucket spread over several slices the sum of their slots (ed_add, 9 M).
-//   k_edm_chunks    one lane per m buckets of a window: the running-sum form, plus (j m) times the chunk's plain sum.
-//   k_edm_tree      fan-in 16 per launch; grid.y = the window.
 //   k_edm_final     one lane: Horner over the windows; then either the encoding (one inversion) or the extended point as it is (the batch's accept kernel adds two
 //                   of them and needs no inversion); the flag and the invalid count.
 // Accumulators, buckets, slots and the tree are ed_point, FOUR planes of `total` elements (X at e, Y at total + e, Z at 2 total + e, T at 3 total + e); the identity
@@ -18,11 +14,11 @@
 // THE BATCH (the order capi.hip enqueues them):
 //   k_edb_front     one lane per signature: D = SHA-512(R || A || M) in full, h = D mod L, leaf = H_leaf(D || s), A and R copied into the sums' term arrays; a lane
 //                   with s >= L (or a small-order A or R, with the flag) counts itself in head->malformed.  Decoding is the sums' (k_edm_digits counts what it refuses).
-//   k_edb_node / k_edb_seed / k_edb_scalars / k_edb_sum   the fan-16 hash tree, the seed, z = (low 128 bits of H_a(seed || i)) | 1 with z h mod L and z s mod L,
-//                   the fan-16 tree of additions modulo L whose last lane writes L - sum and B's encoding: term n of the key sum.
+//   k_edb_node / k_edb_seed / k_edb_scalars / k_edb_sum   batch_tree.cuh's scaffold under this call's tags and modulo L: the fan-16 hash tree, the seed, z and
+//                   z h, z s, the fan-16 tree of additions whose last lane writes L - sum and B's encoding: term n of the key sum.
 //   k_edb_accept    one lane: ok = no lane malformed, nothing refused or broken in either sum, and [8](sum 0 + sum 1) is the identity (X = 0 and Y = Z).
 // THE PER-LANE RULE: k_edc_front (s < L, A and R decode, h, the table of 1 .. 8 times -A, R's coordinates) and k_edc_loop (ed_straus_vartime, - R, three
-// doublings, X = 0 and Y = Z).  The LANES route of the batch is these two into a byte array, then k_schnorr_batch.hip's reduction kernel.
+// doublings, X = 0 and Y = Z).  The LANES route of the batch is these two into a byte array, then k_msm_common.hip's reduction kernel.
 // Every tagged hash starts from the state after its tag block: four compile-time literals (ED25519_BATCH_MID, pinned to hashlib by tests/test_ed25519_batch_cpu.py).
 //
 // Registers and scratch (build/csrc/k_msm_ed25519-hip-amdgcn-amd-amdhsa-gfx950.s; profiles/r17/ed25519_batch_listing.json): 256-thread workgroups, no kernel spills.
@@ -34,12 +30,13 @@
 #include "sha256.cuh"
 #include "sha512.cuh"
 #include "ed25519.cuh"
+#include "msm_stages.cuh"
+#include "batch_tree.cuh"
 
 namespace ecsimd_hip {
 namespace {
 using launch::BLOCK;
 using launch::ed25519_batch_head;
-constexpr int FAN = launch::ED25519_BATCH_FAN;
 #define GID size_t i = (size_t)blockIdx.x * BLOCK + threadIdx.x; if (i >= n) return
 #define MSG_ARGS const uint8_t* __restrict__ msg, size_t msg_bytes, size_t stride, const uint32_t* __restrict__ lens, uint32_t aligned
 #define MSG_PASS msg, msg_bytes, stride, lens, aligned
@@ -55,23 +52,18 @@ ECS_DEV ed_precomp edq_load(const uint64_t* __restrict__ a, size_t total, size_t
 // all ones where p is the identity: X = 0 and Y = Z (Z is never 0 on this curve)
 ECS_DEV uint32_t ed_identity_mask(const ed_point& p) { return fe25519_zero_mask(p.X) & fe25519_eq_mask(p.Y, p.Z); }
 
-// the low `bits` bits of k (1 <= bits <= 256); k_msm.inc's
-ECS_DEV fe mask_bits(fe k, int bits) {
-#pragma unroll
-  for (int j = 0; j < 8; ++j) {
-    const int lo = 32 * j;
-    if (bits <= lo) k.w[j] = 0u;
-    else if (bits < lo + 32) k.w[j] &= (1u << (bits - lo)) - 1u;
-  }
-  return k;
-}
-// digit w of the masked scalar at kw (8 words in global memory), c <= 16 bits: at most two words; k_msm.inc's
-ECS_DEV uint32_t digit_of(const uint32_t* __restrict__ kw, int w, int c) {
-  const int pos = w * c, word = pos >> 5, off = pos & 31;
-  uint32_t v = kw[word] >> off;
-  if (off + c > 32 && word < 7) v |= kw[word + 1] << (32 - off);
-  return v & ((1u << c) - 1u);
-}
+// msm_stages.cuh's group: extended accumulators, FOUR planes, the identity (0, 1, 1, 0); the terms are the three planes of ed_precomp k_edm_digits left at pre
+struct edwards_group {
+  using point = ed_point;
+  struct terms { const uint64_t* __restrict__ pre; };
+  ECS_DEV static point identity() { return ed_identity(); }
+  ECS_DEV static point add(const point& P, const point& Q) { return ed_add(P, Q); }
+  ECS_DEV static point dbl(const point& P) { return ed_dbl(P); }
+  ECS_DEV static point add_term(const point& P, const terms& t, size_t n, size_t idx) { return ed_add_precomp(P, edq_load(t.pre, n, idx)); }
+  ECS_DEV static point load(const uint64_t* __restrict__ a, size_t total, size_t e) { return edp_load(a, total, e); }
+  ECS_DEV static void store(uint64_t* __restrict__ a, size_t total, size_t e, const point& P) { edp_store(a, total, e, P); }
+};
+using G = edwards_group;
 
 // ---- the sum
 __global__ void __launch_bounds__(BLOCK) k_edm_digits(const uint8_t* __restrict__ k, uint32_t k_aligned, const uint8_t* __restrict__ pts, uint32_t p_aligned,
@@ -89,120 +81,31 @@ __global__ void __launch_bounds__(BLOCK) k_edm_digits(const uint8_t* __restrict_
   fe_store(pre, i, fe25519_select(ok, fe25519_add(P.Y, P.X), one));                       // (a refused term: the identity's entry; its scalar is 0 and no lane adds it)
   fe_store(pre, n + i, fe25519_select(ok, fe25519_sub(P.Y, P.X), one));
   fe_store(pre, 2 * n + i, fe25519_select(ok, fe25519_mul(P.T, fe25519_const<ed25519_consts::D2>()), fe25519_small(0u)));
-  const uint32_t mask = (1u << c) - 1u;
-  // the digits from the registers: a running 64-bit window over the words, shifted by c per step (no register is indexed by w)
-  uint64_t acc = kv.w[0]; int have = 32, next = 1;
-#pragma unroll 1
-  for (int w = 0; w < windows; ++w) {
-    if (have < c && next < 8) {
-      uint32_t word = 0;
-#pragma unroll
-      for (int j = 1; j < 8; ++j) if (j == next) word = kv.w[j];
-      acc |= (uint64_t)word << have; have += 32; ++next;
-    }
-    atomicAdd(&hist[((size_t)w << c) + ((uint32_t)acc & mask)], 1u);
-    acc >>= c; have -= c;
-  }
+  msm_histogram(kv, hist, c, windows);
 }
 
-// where a finished run goes (k_msm.inc's rule); p0, p1 = the slice, first = the run's first entry in it
-ECS_DEV void flush_run(uint32_t key, const ed_point& acc, size_t first, size_t p0, size_t p1, size_t slice, const uint32_t* __restrict__ start, uint32_t dmask,
-                       uint64_t* __restrict__ buckets, size_t K, uint64_t* __restrict__ partial, size_t slots) {
-  if (key == 0xffffffffu || (key & dmask) == 0u) return;                // no run yet, or digit 0: skipped
-  const size_t a = start[key], b = start[key + 1];
-  if (a >= p0 && b <= p1) edp_store(buckets, K, key, acc);
-  else edp_store(partial, slots, 2 * slice + (first == p0 ? 0 : 1), acc);
-}
 __global__ void __launch_bounds__(BLOCK) k_edm_slices(const uint32_t* __restrict__ sorted, const uint64_t* __restrict__ kk, const uint64_t* __restrict__ pre,
                                                       const uint32_t* __restrict__ start, uint64_t* __restrict__ buckets, uint64_t* __restrict__ partial,
                                                       uint32_t* __restrict__ broken, size_t n, size_t T, size_t L, size_t slices, int c, size_t K) {
-  const size_t s = (size_t)blockIdx.x * BLOCK + threadIdx.x;
-  if (s >= slices) return;
-  const size_t p0 = s * L, p1 = p0 + L < T ? p0 + L : T;
-  const uint32_t dmask = (1u << c) - 1u;
-  int w = (int)(p0 / n);
-  size_t wend = ((size_t)w + 1) * n, first = p0;
-  uint32_t cur = 0xffffffffu;
-  ed_point acc = ed_identity();
-#pragma unroll 1
-  for (size_t pos = p0; pos < p1; ++pos) {
-    while (pos >= wend) { ++w; wend += n; }
-    const size_t idx = sorted[pos];
-    if (idx >= n) { atomicAdd(broken, 1u); continue; }                  // every entry was written by the scatter: anything else fails the call
-    const uint32_t d = digit_of(reinterpret_cast<const uint32_t*>(kk) + 8 * idx, w, c);
-    const uint32_t key = ((uint32_t)w << c) + d;
-    if (key != cur) {
-      flush_run(cur, acc, first, p0, p1, s, start, dmask, buckets, K, partial, 2 * slices);
-      cur = key; first = pos; acc = ed_identity();
-    }
-    if (d != 0u) acc = ed_add_precomp(acc, edq_load(pre, n, idx));      // (digit 0 goes to no bucket: skipping it is the schedule's, not the group law's)
-  }
-  flush_run(cur, acc, first, p0, p1, s, start, dmask, buckets, K, partial, 2 * slices);
+  msm_slices<G>(sorted, kk, {pre}, start, buckets, partial, broken, n, T, L, slices, c, K);
 }
-
 __global__ void __launch_bounds__(BLOCK) k_edm_combine(const uint32_t* __restrict__ start, uint64_t* __restrict__ buckets, const uint64_t* __restrict__ partial,
                                                        uint32_t* __restrict__ broken, size_t L, size_t slices, int c, size_t K) {
-  const size_t key = (size_t)blockIdx.x * BLOCK + threadIdx.x;
-  if (key >= K || (key & ((1u << c) - 1u)) == 0) return;
-  const size_t a = start[key], b = start[key + 1];
-  if (a > b || b > slices * L) atomicAdd(broken, 1u);                  // offsets that are no scan of a histogram fail the call; no load follows them out of `partial`
-  if (a >= b || b > slices * L) { edp_store(buckets, K, key, ed_identity()); return; }    // a == b: an empty bucket
-  const size_t s0 = a / L, s1 = (b - 1) / L;
-  if (s0 == s1) return;                                                 // the whole bucket lay in one slice, which wrote it
-  ed_point acc = ed_identity();
-#pragma unroll 1
-  for (size_t s = s0; s <= s1; ++s) acc = ed_add(acc, edp_load(partial, 2 * slices, 2 * s + (a <= s * L ? 0 : 1)));
-  edp_store(buckets, K, key, acc);
+  msm_combine<G>(start, buckets, partial, broken, L, slices, c, K);
 }
-
-// lane (w, j): sum over t < m of (j m + t) B[j m + t] = sum t B + (j m) sum B.  Bucket 0 of a window is never read.
 __global__ void __launch_bounds__(BLOCK) k_edm_chunks(const uint64_t* __restrict__ buckets, uint64_t* __restrict__ out, size_t lanes, size_t per_window, int c, int m, size_t K) {
-  const size_t g = (size_t)blockIdx.x * BLOCK + threadIdx.x;
-  if (g >= lanes) return;
-  const size_t w = g / per_window, j = g % per_window, off = j * (size_t)m, base = (w << c) + off;
-  ed_point run = ed_identity(), tot = ed_identity();
-#pragma unroll 1
-  for (int t = m - 1; t >= 0; --t) {
-    if (off + t != 0) run = ed_add(run, edp_load(buckets, K, base + t));
-    if (t != 0) tot = ed_add(tot, run);
-  }
-  ed_point mult = ed_identity();
-#pragma unroll 1
-  for (int bit = c - 1; bit >= 0; --bit) {
-    mult = ed_dbl(mult);
-    if ((off >> bit) & 1u) mult = ed_add(mult, run);
-  }
-  edp_store(out, lanes, g, ed_add(tot, mult));
+  msm_chunks<G>(buckets, out, lanes, per_window, c, m, K);
 }
-
-// arr[group * stride + g] = the sum of arr[group * stride + g + t * lanes], t < fan, for g < lanes: in place (a lane reads its own elements, then writes the first)
 __global__ void __launch_bounds__(BLOCK) k_edm_tree(uint64_t* arr, size_t total, size_t count, size_t stride, size_t lanes, int fan) {
-  const size_t g = (size_t)blockIdx.x * BLOCK + threadIdx.x;
-  if (g >= lanes) return;
-  const size_t base = (size_t)blockIdx.y * stride;
-  ed_point acc = edp_load(arr, total, base + g);
-#pragma unroll 1
-  for (int t = 1; t < fan; ++t) {
-    const size_t e = g + (size_t)t * lanes;
-    if (e >= count) break;
-    acc = ed_add(acc, edp_load(arr, total, base + e));
-  }
-  edp_store(arr, total, base + g, acc);
+  msm_tree<G>(arr, total, count, stride, lanes, fan);
 }
 
-// One lane.  windows > 0: arr[w * stride] = the sum of window w; Horner from the top, c doublings per window.  windows == 0: the empty sum.
-// raw != nullptr: the extended point (X, Y, Z, T: 16 words of 64 bits) goes there and nothing is encoded; else out = the 32-byte encoding.
+// One lane: msm_horner, then the result.  raw != nullptr: the extended point (X, Y, Z, T: 16 words of 64 bits) goes there and nothing is encoded; else out = the 32-byte encoding.
 __global__ void __launch_bounds__(64) k_edm_final(const uint64_t* __restrict__ arr, size_t total, size_t stride, int windows, int c, const uint32_t* __restrict__ counter,
                                                   uint8_t* __restrict__ out, uint32_t out_aligned, uint64_t* __restrict__ raw, uint8_t* __restrict__ finite,
                                                   uint32_t* __restrict__ invalid) {
   if (blockIdx.x != 0 || threadIdx.x != 0) return;
-  ed_point acc = ed_identity();
-#pragma unroll 1
-  for (int w = windows - 1; w >= 0; --w) {
-#pragma unroll 1
-    for (int d = 0; d < c; ++d) acc = ed_dbl(acc);
-    acc = ed_add(acc, edp_load(arr, total, (size_t)w * stride));
-  }
+  ed_point acc = msm_horner<G>(arr, total, stride, windows, c);
   uint32_t bad = counter ? counter[0] : 0u;
   const bool broken = counter && counter[1] != 0u;                      // a broken invariant of the sort: no sum is better than a wrong one (INTERNAL CHECK in the header)
   if (broken) bad = 0xffffffffu;
@@ -307,24 +210,20 @@ ECS_DEV uint32_t ed_small_order_mask(const fe& enc) {
 }
 
 // The SHA-256 state after the block SHA256(tag) || SHA256(tag), tag = "ecsimd/ed25519-batch/leaf", ".../node", ".../seed", ".../a"
-enum { EB_LEAF = 0, EB_NODE = 1, EB_SEED = 2, EB_A = 3 };
+// (batch_tree.cuh's order)
 struct ed25519_batch_consts {
   static constexpr uint32_t ED25519_BATCH_MID[4][8] = {
       {0xee16ee5du, 0xfd4513eeu, 0x03feb5f3u, 0xa8a1dbf5u, 0x42669db8u, 0x6bb7c4f7u, 0xf78e9b7fu, 0x4be5fc49u},
       {0xdfca4714u, 0xd1e432edu, 0xe53f521eu, 0xfd2c0f7du, 0xea07f9bcu, 0xdcdb2e3fu, 0xf58a9513u, 0x143b726bu},
       {0xcfc6f938u, 0x3799d0b8u, 0x5714f5acu, 0xda6cbc6cu, 0x3f88375au, 0x4fff5ebau, 0x8b89d0eau, 0xbf040506u},
       {0xbd9e8bddu, 0xb0ed2b25u, 0x33235b06u, 0xdcf30e0du, 0x5b34f636u, 0x98621840u, 0xe3843d0bu, 0x7c827d3cu}};
+  ECS_DEV static uint32_t mid(int tag, int j) { return ED25519_BATCH_MID[tag][j]; }
 };
-template <int TAG> ECS_DEV sha256_state mid() {
-  sha256_state s;
-#pragma unroll
-  for (int j = 0; j < 8; ++j) s.h[j] = ed25519_batch_consts::ED25519_BATCH_MID[TAG][j];
-  return s;
-}
+using TAGS = ed25519_batch_consts;
 // H_leaf(D || s): D's 64 bytes are one block; s (32 bytes as given, s.w[j] = bytes 4 j .. 4 j + 3) and the padding the second.  Digests are held as
 // sha_digest_fe leaves them: the big-endian integer of the 32 bytes.
 ECS_DEV fe hash_leaf(const sha512_state& D, const fe& s) {
-  sha256_state st = mid<EB_LEAF>();
+  sha256_state st = mid<TAGS, BATCH_LEAF>();
   sha256_block m;
 #pragma unroll
   for (int j = 0; j < 8; ++j) { m.w[2 * j] = (uint32_t)(D.h[j] >> 32); m.w[2 * j + 1] = (uint32_t)D.h[j]; }
@@ -338,44 +237,6 @@ ECS_DEV fe hash_leaf(const sha512_state& D, const fe& s) {
   sha256_compress(st, m);
   return sha_digest_fe(st);
 }
-// H_tag(bytes(a) || v as 8 big-endian bytes): 40 bytes and the padding in one block
-template <int TAG> ECS_DEV fe hash_32_8(const fe& a, uint64_t v) {
-  sha256_state s = mid<TAG>();
-  sha256_block m;
-#pragma unroll
-  for (int j = 0; j < 8; ++j) m.w[j] = a.w[7 - j];
-  m.w[8] = (uint32_t)(v >> 32); m.w[9] = (uint32_t)v; m.w[10] = 0x80000000u;
-#pragma unroll
-  for (int j = 11; j < 15; ++j) m.w[j] = 0u;
-  m.w[15] = (64u + 40u) * 8u;
-  sha256_compress(s, m);
-  return sha_digest_fe(s);
-}
-// H_node(c_0 || ... || c_{k-1}), c_j = in[first + j], 1 <= k <= 16: two children per block; the padding's first byte follows the last child
-ECS_DEV fe hash_children(const uint64_t* __restrict__ in, size_t first, uint32_t k) {
-  sha256_state s = mid<EB_NODE>();
-  const uint32_t blocks = k / 2u + 1u;
-#pragma unroll 1
-  for (uint32_t b = 0; b < blocks; ++b) {
-    sha256_block m;
-#pragma unroll
-    for (int j = 0; j < 16; ++j) m.w[j] = 0u;
-    if (2u * b < k) {
-      const fe c = fe_load(in, first + 2u * b);
-#pragma unroll
-      for (int j = 0; j < 8; ++j) m.w[j] = c.w[7 - j];
-    } else m.w[0] = 0x80000000u;                               // 2 b == k
-    if (2u * b + 1u < k) {
-      const fe c = fe_load(in, first + 2u * b + 1u);
-#pragma unroll
-      for (int j = 0; j < 8; ++j) m.w[8 + j] = c.w[7 - j];
-    } else if (2u * b + 1u == k) m.w[8] = 0x80000000u;
-    if (b + 1u == blocks) m.w[15] = (64u + 32u * k) * 8u;
-    sha256_compress(s, m);
-  }
-  return sha_digest_fe(s);
-}
-
 // ---- the batch
 __global__ void __launch_bounds__(BLOCK) k_edb_front(gmod M, const uint8_t* __restrict__ pk, uint32_t pk_aligned, const uint8_t* __restrict__ sig, uint32_t sig_aligned, MSG_ARGS,
                                                      uint32_t reject_small, uint64_t* __restrict__ hv, uint64_t* __restrict__ leafv, uint64_t* __restrict__ Aenc,
@@ -393,42 +254,31 @@ __global__ void __launch_bounds__(BLOCK) k_edb_front(gmod M, const uint8_t* __re
 }
 __global__ void __launch_bounds__(BLOCK) k_edb_node(const uint64_t* __restrict__ in, size_t count, uint64_t* __restrict__ out, size_t n) {
   GID;
-  const size_t first = i * FAN, left = count - first;
-  fe_store(out, i, hash_children(in, first, left < (size_t)FAN ? (uint32_t)left : (uint32_t)FAN));
+  batch_node<TAGS>(in, count, out, i);
 }
 __global__ void __launch_bounds__(64) k_edb_seed(const uint64_t* __restrict__ root, uint64_t n, ed25519_batch_head* __restrict__ head) {
   if (blockIdx.x != 0 || threadIdx.x != 0) return;
-  fe_store(head->seed, 0, hash_32_8<EB_SEED>(fe_load(root, 0), n));
+  batch_seed<TAGS>(root, n, head->seed);
 }
 __global__ void __launch_bounds__(BLOCK) k_edb_scalars(gmod M, const ed25519_batch_head* __restrict__ head, const uint64_t* __restrict__ hv, const uint8_t* __restrict__ sig,
                                                        uint32_t sig_aligned, const uint8_t* __restrict__ valid, uint64_t* __restrict__ zv, uint64_t* __restrict__ zhv,
                                                        uint64_t* __restrict__ zsv, size_t n) {
   GID;
-  fe z = hash_32_8<EB_A>(fe_load(head->seed, 0), (uint64_t)i);
-#pragma unroll
-  for (int q = 4; q < 8; ++q) z.w[q] = 0u;
-  z.w[0] |= 1u;
+  const fe z = batch_randomizer<TAGS>(head->seed, i);
   fe h = fe_load(hv, i), s = ed_load32(sig + 64 * i + 32, sig_aligned);
   if (!valid[i]) { h = fe25519_small(0u); s = fe25519_small(0u); }    // (a malformed lane's s may be >= L: g_mul's operands stay below L)
-  const fe zR = g_mul(z, g_words(M.rsq), M);                          // z R mod L: its Montgomery product with a plain value is their plain product
+  const fe zR = batch_randomizer_mgry(z, M);
   fe_store(zv, i, z);
   if (zhv) { fe_store(zhv, i, g_mul(zR, h, M)); fe_store(zsv, i, g_mul(zR, s, M)); }
 }
 // out[i] = the sum of in[16 i ..] modulo L.  benc != nullptr: the last level (one lane): out[0] = L - sum, 0 staying 0, and benc[0] = the encoding of B.
 __global__ void __launch_bounds__(BLOCK) k_edb_sum(gmod M, const uint64_t* __restrict__ in, size_t count, uint64_t* __restrict__ out, uint64_t* __restrict__ benc, size_t n) {
   GID;
-  const size_t first = i * FAN, left = count - first;
-  const uint32_t k = left < (size_t)FAN ? (uint32_t)left : (uint32_t)FAN;
-  fe acc = fe_load(in, first);
-#pragma unroll 1
-  for (uint32_t j = 1; j < k; ++j) acc = g_add(acc, fe_load(in, first + j), M);
+  const fe acc = batch_sum(M, in, count, i, benc != nullptr);
   if (benc) {
-    fe neg;
-    (void)sub8_3(neg, g_words(M.p), acc);
-    const uint32_t keep = ~g_zero_mask(acc);
     fe b;
 #pragma unroll
-    for (int q = 0; q < 8; ++q) { acc.w[q] = neg.w[q] & keep; b.w[q] = 0x66666666u; }
+    for (int q = 0; q < 8; ++q) b.w[q] = 0x66666666u;
     b.w[0] = 0x66666658u;                                             // y = 4 / 5, x even
     fe_store(benc, 0, b);
   }
@@ -477,26 +327,26 @@ namespace launch {
 static_assert(sizeof(ed25519_batch_head) == 304 && sizeof(ed25519_batch_head) % 16 == 0, "ed25519_batch_head: zeroed 16 bytes per lane");
 static uint32_t word_aligned(const void* p, size_t stride_bytes = 0) { return ((reinterpret_cast<uintptr_t>(p) | stride_bytes) & 3u) == 0 ? 1u : 0u; }
 static dim3 grid_of(size_t lanes, size_t y = 1) { return dim3((unsigned)((lanes + BLOCK - 1) / BLOCK), (unsigned)y); }
-static size_t fan_lanes(size_t count) { return (count + ED25519_BATCH_FAN - 1) / ED25519_BATCH_FAN; }
+static size_t fan_lanes(size_t count) { return (count + BATCH_FAN - 1) / BATCH_FAN; }
 
-void ed25519_msm_digits(hipStream_t s, const uint8_t* k, const uint8_t* pts, uint64_t* kk, uint64_t* pre, uint32_t* hist, uint32_t* counter, size_t n, int bits, int c, int windows) {
+void ed25519_msm_launch::digits(hipStream_t s, const uint8_t* k, const uint8_t* pts, uint64_t* kk, uint64_t* pre, uint32_t* hist, uint32_t* counter, size_t n, int bits, int c, int windows) {
   hipLaunchKernelGGL(k_edm_digits, grid_of(n), dim3(BLOCK), 0, s, k, word_aligned(k), pts, word_aligned(pts), kk, pre, hist, counter, n, bits, c, windows);
 }
-void ed25519_msm_slices(hipStream_t s, const uint32_t* sorted, const uint64_t* kk, const uint64_t* pre, const uint32_t* start, uint64_t* buckets, uint64_t* partial, uint32_t* broken,
-                        size_t n, size_t T, size_t L, size_t slices, int c, size_t K) {
+void ed25519_msm_launch::slices(hipStream_t s, const uint32_t* sorted, const uint64_t* kk, const uint64_t* pre, const uint32_t* start, uint64_t* buckets, uint64_t* partial,
+                                uint32_t* broken, size_t n, size_t T, size_t L, size_t slices, int c, size_t K) {
   hipLaunchKernelGGL(k_edm_slices, grid_of(slices), dim3(BLOCK), 0, s, sorted, kk, pre, start, buckets, partial, broken, n, T, L, slices, c, K);
 }
-void ed25519_msm_combine(hipStream_t s, const uint32_t* start, uint64_t* buckets, const uint64_t* partial, uint32_t* broken, size_t L, size_t slices, int c, size_t K) {
+void ed25519_msm_launch::combine(hipStream_t s, const uint32_t* start, uint64_t* buckets, const uint64_t* partial, uint32_t* broken, size_t L, size_t slices, int c, size_t K) {
   hipLaunchKernelGGL(k_edm_combine, grid_of(K), dim3(BLOCK), 0, s, start, buckets, partial, broken, L, slices, c, K);
 }
-void ed25519_msm_chunks(hipStream_t s, const uint64_t* buckets, uint64_t* out, size_t lanes, size_t per_window, int c, int m, size_t K) {
+void ed25519_msm_launch::chunks(hipStream_t s, const uint64_t* buckets, uint64_t* out, size_t lanes, size_t per_window, int c, int m, size_t K) {
   hipLaunchKernelGGL(k_edm_chunks, grid_of(lanes), dim3(BLOCK), 0, s, buckets, out, lanes, per_window, c, m, K);
 }
-void ed25519_msm_tree(hipStream_t s, uint64_t* arr, size_t total, size_t count, size_t stride, size_t groups, size_t lanes, int fan) {
+void ed25519_msm_launch::tree(hipStream_t s, uint64_t* arr, size_t total, size_t count, size_t stride, size_t groups, size_t lanes, int fan) {
   hipLaunchKernelGGL(k_edm_tree, grid_of(lanes, groups), dim3(BLOCK), 0, s, arr, total, count, stride, lanes, fan);
 }
-void ed25519_msm_finish(hipStream_t s, const uint64_t* arr, size_t total, size_t stride, int windows, int c, const uint32_t* counter, uint8_t* out, uint64_t* raw, uint8_t* finite,
-                        uint32_t* invalid) {
+void ed25519_msm_launch::finish(hipStream_t s, const uint64_t* arr, size_t total, size_t stride, int windows, int c, const uint32_t* counter, uint8_t* out, uint64_t* raw,
+                                uint8_t* finite, uint32_t* invalid) {
   hipLaunchKernelGGL(k_edm_final, dim3(1), dim3(64), 0, s, arr, total, stride, windows, c, counter, out, word_aligned(out), raw, finite, invalid);
 }
 void ed25519_batch_front(hipStream_t s, const gmod& L, const uint8_t* pk, const uint8_t* sig, const uint8_t* msg, size_t msg_bytes, size_t stride_bytes, const uint32_t* lens,

@@ -9,23 +9,23 @@
 //   * k_sb_scalars   one lane per signature: a = (low 128 bits of H_a(seed || i)) | 1, a e mod n with e = E mod n, a s mod n; both products 0 on a malformed lane.
 //   * k_sb_sum       one level of the fan-16 tree of additions modulo n; the last level's one lane writes n - sum (0 stays 0) and G: term u of the key sum.
 //   * k_sb_accept    one lane: ok = no lane malformed, no invalid point in either sum, and the sums cancel.
-//   * k_sb_all       the per-lane route's reduction, one workgroup: ok = every verdict byte is 1 (and 1 for an empty batch).
+// node, seed, the randomizer and the sum are batch_tree.cuh's bodies under this call's tags; the per-lane route's reduction is k_msm_common.hip's.
 // Every tagged hash starts from the state after its tag block: five compile-time literals (SCHNORR_BATCH_MID, pinned to hashlib by tests/test_schnorr_batch_cpu.py).
 #include "kernels.h"
 #include "sha256.cuh"
 #include "lift.cuh"
+#include "batch_tree.cuh"
 
 namespace ecsimd_hip {
 namespace {
 using launch::BLOCK;
 using launch::words8;
 using launch::schnorr_batch_head;
-constexpr int FAN = launch::SCHNORR_BATCH_FAN;
 #define GID size_t i = (size_t)blockIdx.x * BLOCK + threadIdx.x; if (i >= n) return
 
 // The SHA-256 state after the block SHA256(tag) || SHA256(tag), tag = "ecsimd/schnorr-batch/leaf", "ecsimd/schnorr-batch/node", "ecsimd/schnorr-batch/seed",
 // "ecsimd/schnorr-batch/a", "BIP0340/challenge"
-enum { SB_LEAF = 0, SB_NODE = 1, SB_SEED = 2, SB_A = 3, SB_CHALLENGE = 4 };
+constexpr int SB_CHALLENGE = 4;                                // (the first four: batch_tree.cuh's order)
 struct schnorr_batch_consts {
   static constexpr uint32_t SCHNORR_BATCH_MID[5][8] = {
       {0x7779a7c6u, 0x3456baf4u, 0xf16728a7u, 0x90b4841du, 0x08db76afu, 0x5301c9ffu, 0x2232d730u, 0x1214dca0u},
@@ -33,17 +33,13 @@ struct schnorr_batch_consts {
       {0xdc917d3du, 0xe712b88au, 0xaa50d908u, 0xbad51688u, 0xd8782f0fu, 0x19146953u, 0xf5861bcdu, 0x169b8603u},
       {0x1f4e0feeu, 0x694b940fu, 0x722b29fdu, 0x6586f4b6u, 0x47ac54cau, 0x59a009c6u, 0x2aa70cbcu, 0xedc4debcu},
       {0x9cecba11u, 0x23925381u, 0x11679112u, 0xd1627e0fu, 0x97c87550u, 0x003cc765u, 0x90f61164u, 0x33e9b66au}};
+  ECS_DEV static uint32_t mid(int tag, int j) { return SCHNORR_BATCH_MID[tag][j]; }
 };
-template <int TAG> ECS_DEV sha256_state mid() {
-  sha256_state s;
-#pragma unroll
-  for (int j = 0; j < 8; ++j) s.h[j] = schnorr_batch_consts::SCHNORR_BATCH_MID[TAG][j];
-  return s;
-}
+using TAGS = schnorr_batch_consts;
 // int(H_tag(a || b || m)): the tag block's midstate, the block a || b, then the message with the padding of a hash of 128 + bytes bytes -- k_schnorr.hip's
 // tagged_hash_2x32, word for word (that unit keeps its own: its kernels' listings are held to instruction counts and its rates are measured)
 template <int TAG> ECS_DEV fe tagged_hash_2x32(const fe& a, const fe& b, const uint8_t* __restrict__ m, size_t msg_bytes, uint32_t aligned) {
-  sha256_state s = mid<TAG>();
+  sha256_state s = mid<TAGS, TAG>();
   sha256_block blk;
 #pragma unroll
   for (int j = 0; j < 8; ++j) { blk.w[j] = a.w[7 - j]; blk.w[8 + j] = b.w[7 - j]; }
@@ -59,7 +55,7 @@ ECS_DEV fe reduce_once(const fe& v, const fe& N) {
 }
 // H_tag(bytes(a) || bytes(b)): 64 bytes are one block, the padding a block of its own
 template <int TAG> ECS_DEV fe hash_2x32(const fe& a, const fe& b) {
-  sha256_state s = mid<TAG>();
+  sha256_state s = mid<TAGS, TAG>();
   sha256_block m;
 #pragma unroll
   for (int j = 0; j < 8; ++j) { m.w[j] = a.w[7 - j]; m.w[8 + j] = b.w[7 - j]; }
@@ -70,45 +66,6 @@ template <int TAG> ECS_DEV fe hash_2x32(const fe& a, const fe& b) {
   sha256_compress(s, m);
   return sha_digest_fe(s);
 }
-// H_tag(bytes(a) || v as 8 big-endian bytes): 40 bytes and the padding in one block
-template <int TAG> ECS_DEV fe hash_32_8(const fe& a, uint64_t v) {
-  sha256_state s = mid<TAG>();
-  sha256_block m;
-#pragma unroll
-  for (int j = 0; j < 8; ++j) m.w[j] = a.w[7 - j];
-  m.w[8] = (uint32_t)(v >> 32); m.w[9] = (uint32_t)v; m.w[10] = 0x80000000u;
-#pragma unroll
-  for (int j = 11; j < 15; ++j) m.w[j] = 0u;
-  m.w[15] = (64u + 40u) * 8u;
-  sha256_compress(s, m);
-  return sha_digest_fe(s);
-}
-// H_node(c_0 || ... || c_{k-1}), c_j = in[first + j], 1 <= k <= 16: two children per block; the padding's first byte follows the last child -- in the second
-// half of the last block where k is odd, at the start of a block of its own where it is even -- and the bit length ends that block.
-ECS_DEV fe hash_children(const uint64_t* __restrict__ in, size_t first, uint32_t k) {
-  sha256_state s = mid<SB_NODE>();
-  const uint32_t blocks = k / 2u + 1u;
-#pragma unroll 1
-  for (uint32_t b = 0; b < blocks; ++b) {
-    sha256_block m;
-#pragma unroll
-    for (int j = 0; j < 16; ++j) m.w[j] = 0u;
-    if (2u * b < k) {
-      const fe c = fe_load(in, first + 2u * b);
-#pragma unroll
-      for (int j = 0; j < 8; ++j) m.w[j] = c.w[7 - j];
-    } else m.w[0] = 0x80000000u;                               // 2 b == k
-    if (2u * b + 1u < k) {
-      const fe c = fe_load(in, first + 2u * b + 1u);
-#pragma unroll
-      for (int j = 0; j < 8; ++j) m.w[8 + j] = c.w[7 - j];
-    } else if (2u * b + 1u == k) m.w[8] = 0x80000000u;
-    if (b + 1u == blocks) m.w[15] = (64u + 32u * k) * 8u;
-    sha256_compress(s, m);
-  }
-  return sha_digest_fe(s);
-}
-
 __global__ void __launch_bounds__(BLOCK) k_sb_front(words8 order, const uint64_t* __restrict__ pxv, const uint64_t* __restrict__ rv, const uint64_t* __restrict__ sv,
                                                     const uint8_t* __restrict__ msg, size_t msg_bytes, size_t stride, uint32_t aligned, uint64_t* __restrict__ Ev,
                                                     uint64_t* __restrict__ leafv, uint64_t* __restrict__ Px, uint64_t* __restrict__ Py, uint64_t* __restrict__ Rx,
@@ -120,7 +77,7 @@ __global__ void __launch_bounds__(BLOCK) k_sb_front(words8 order, const uint64_t
   fe px = fe_load(pxv, i), rx = r, py, ry;
   const fe E = tagged_hash_2x32<SB_CHALLENGE>(r, px, msg + i * stride, msg_bytes, aligned);
   fe_store(Ev, i, E);
-  fe_store(leafv, i, hash_2x32<SB_LEAF>(E, s));
+  fe_store(leafv, i, hash_2x32<BATCH_LEAF>(E, s));
   bool ok = lift_y<C>(px, 0u, py);                             // (false where px >= p)
   ok = lift_y<C>(rx, 0u, ry) && ok;                            // (false where r >= p)
   ok = ok && g_less(s, N);
@@ -132,13 +89,12 @@ __global__ void __launch_bounds__(BLOCK) k_sb_front(words8 order, const uint64_t
 
 __global__ void __launch_bounds__(BLOCK) k_sb_node(const uint64_t* __restrict__ in, size_t count, uint64_t* __restrict__ out, size_t n) {
   GID;
-  const size_t first = i * FAN, left = count - first;
-  fe_store(out, i, hash_children(in, first, left < (size_t)FAN ? (uint32_t)left : (uint32_t)FAN));
+  batch_node<TAGS>(in, count, out, i);
 }
 
 __global__ void __launch_bounds__(64) k_sb_seed(const uint64_t* __restrict__ root, uint64_t n, schnorr_batch_head* __restrict__ head) {
   if (blockIdx.x != 0 || threadIdx.x != 0) return;
-  fe_store(head->seed, 0, hash_32_8<SB_SEED>(fe_load(root, 0), n));
+  batch_seed<TAGS>(root, n, head->seed);
 }
 
 __global__ void __launch_bounds__(BLOCK) k_sb_scalars(gmod M, const schnorr_batch_head* __restrict__ head, const uint64_t* __restrict__ Ev, const uint64_t* __restrict__ sv,
@@ -146,13 +102,10 @@ __global__ void __launch_bounds__(BLOCK) k_sb_scalars(gmod M, const schnorr_batc
                                                       uint64_t* __restrict__ asv, size_t n) {
   GID;
   const fe N = g_words(M.p);
-  fe a = hash_32_8<SB_A>(fe_load(head->seed, 0), (uint64_t)i);
-#pragma unroll
-  for (int q = 4; q < 8; ++q) a.w[q] = 0u;
-  a.w[0] |= 1u;
+  const fe a = batch_randomizer<TAGS>(head->seed, i);
   fe e = reduce_once(fe_load(Ev, i), N), s = fe_load(sv, i);
   if (!valid[i]) { e = fe_zero(); s = fe_zero(); }             // (a malformed lane's s may be >= n: g_mul's operands stay below n)
-  const fe aR = g_mul(a, g_words(M.rsq), M);                   // a R mod n: its Montgomery product with a plain value is their plain product
+  const fe aR = batch_randomizer_mgry(a, M);
   fe_store(av, i, a);
   fe_store(aev, i, g_mul(aR, e, M));
   fe_store(asv, i, g_mul(aR, s, M));
@@ -162,19 +115,8 @@ __global__ void __launch_bounds__(BLOCK) k_sb_scalars(gmod M, const schnorr_batc
 __global__ void __launch_bounds__(BLOCK) k_sb_sum(gmod M, const uint64_t* __restrict__ in, size_t count, uint64_t* __restrict__ out, uint64_t* __restrict__ gx,
                                                   uint64_t* __restrict__ gy, size_t n) {
   GID;
-  const size_t first = i * FAN, left = count - first;
-  const uint32_t k = left < (size_t)FAN ? (uint32_t)left : (uint32_t)FAN;
-  fe acc = fe_load(in, first);
-#pragma unroll 1
-  for (uint32_t j = 1; j < k; ++j) acc = g_add(acc, fe_load(in, first + j), M);
-  if (gx) {
-    fe neg;
-    (void)sub8_3(neg, g_words(M.p), acc);
-    const uint32_t keep = ~g_zero_mask(acc);
-#pragma unroll
-    for (int q = 0; q < 8; ++q) acc.w[q] = neg.w[q] & keep;
-    fe_store(gx, 0, FE_CONST(CURVE_SECP256K1, GX)); fe_store(gy, 0, FE_CONST(CURVE_SECP256K1, GY));
-  }
+  const fe acc = batch_sum(M, in, count, i, gx != nullptr);
+  if (gx) { fe_store(gx, 0, FE_CONST(CURVE_SECP256K1, GX)); fe_store(gy, 0, FE_CONST(CURVE_SECP256K1, GY)); }
   fe_store(out, i, acc);
 }
 
@@ -190,26 +132,12 @@ __global__ void __launch_bounds__(64) k_sb_accept(const schnorr_batch_head* __re
   }
   okv[0] = (uint8_t)ok;
 }
-
-// One workgroup.  flags is 16-byte aligned; the bytes behind flags[n - 1] are not read.
-__global__ void __launch_bounds__(1024) k_sb_all(const uint8_t* __restrict__ flags, size_t n, uint8_t* __restrict__ okv) {
-  const size_t t = threadIdx.x, vec = n / 16;
-  const uint4* q = reinterpret_cast<const uint4*>(flags);
-  int bad = 0;
-  for (size_t v = t; v < vec; v += 1024) {
-    const uint4 w = q[v];
-    bad |= (int)((w.x != 0x01010101u) | (w.y != 0x01010101u) | (w.z != 0x01010101u) | (w.w != 0x01010101u));
-  }
-  for (size_t b = vec * 16 + t; b < n; b += 1024) bad |= (int)(flags[b] != 1u);
-  const int any = __syncthreads_or(bad);
-  if (t == 0) okv[0] = (uint8_t)(any ? 0 : 1);
-}
 }  // namespace
 
 namespace launch {
 static_assert(sizeof(schnorr_batch_head) == 192 && sizeof(schnorr_batch_head) % 16 == 0, "schnorr_batch_head: zeroed 16 bytes per lane");
 static uint32_t word_aligned(const uint8_t* msg, size_t stride_bytes) { return ((reinterpret_cast<uintptr_t>(msg) | stride_bytes) & 3u) == 0 ? 1u : 0u; }
-static size_t fan_lanes(size_t count) { return (count + SCHNORR_BATCH_FAN - 1) / SCHNORR_BATCH_FAN; }
+static size_t fan_lanes(size_t count) { return (count + BATCH_FAN - 1) / BATCH_FAN; }
 void schnorr_batch_front(hipStream_t s, const words8& order, const uint64_t* px, const uint64_t* r, const uint64_t* sg, const uint8_t* msg, size_t msg_bytes, size_t stride_bytes,
                          uint64_t* E, uint64_t* leaf, uint64_t* Px, uint64_t* Py, uint64_t* Rx, uint64_t* Ry, uint8_t* valid, schnorr_batch_head* head, size_t n) {
   hipLaunchKernelGGL(k_sb_front, grid_for(n), dim3(BLOCK), 0, s, order, px, r, sg, msg, msg_bytes, stride_bytes, word_aligned(msg, stride_bytes), E, leaf, Px, Py, Rx, Ry, valid,
@@ -230,9 +158,6 @@ void schnorr_batch_sum(hipStream_t s, const gmod& order, const uint64_t* in, siz
 }
 void schnorr_batch_accept(hipStream_t s, const schnorr_batch_head* head, uint8_t* ok) {
   hipLaunchKernelGGL(k_sb_accept, dim3(1), dim3(64), 0, s, head, ok);
-}
-void schnorr_batch_all(hipStream_t s, const uint8_t* flags, size_t n, uint8_t* ok) {
-  hipLaunchKernelGGL(k_sb_all, dim3(1), dim3(1024), 0, s, flags, n, ok);
 }
 }  // namespace launch
 }  // namespace ecsimd_hip

@@ -337,15 +337,18 @@ template <int C> struct point_launch {
   static void add_mixed_complete(hipStream_t, const uint64_t*, const uint64_t*, const uint64_t*, const uint64_t*, const uint64_t*, uint64_t*, uint64_t*, uint64_t*, size_t);
   static void varwin_scalar_mult(hipStream_t, const uint64_t* k, int k_stride, const uint64_t* x, const uint64_t* y, int flags, uint64_t* scratch, uint64_t* ox, uint64_t* oy, size_t n);
 };
-// k_msm_<curve>.hip: R = sum k_i P_i by the bucket method and the point sum over lanes (k_msm.inc has the stages; PUBLIC data).  Jacobian arrays are three planes
-// of `total` elements in the fast domain, Z = 0 at infinity.  Every launcher enqueues ONE kernel; capi.hip's msm_schedule_of decides the sizes from (n, bits, flags).
+// k_msm_common.hip: the kernels of the bucket sums and the batch verifications that know no curve (msm_stages.cuh has the stages; PUBLIC data).  Every launcher
+// enqueues ONE kernel.  zero: bytes, a multiple of 16.  flags_all: ok[0] = every one of the n bytes of flags (16-byte aligned) is 1; n = 0: 1.
+void msm_zero(hipStream_t, void* words, size_t bytes);
+void msm_scan(hipStream_t, const uint32_t* hist, uint32_t* start, uint32_t* cursor, size_t K);
+void msm_scatter(hipStream_t, const uint64_t* kk, uint32_t* cursor, uint32_t* sorted, uint32_t* broken, size_t n, size_t T, int c, int windows);
+void flags_all(hipStream_t, const uint8_t* flags, size_t n, uint8_t* ok);
+// k_msm_<curve>.hip: R = sum k_i P_i by the bucket method and the point sum over lanes (k_msm.inc; PUBLIC data).  Jacobian arrays are three planes of `total`
+// elements in the fast domain, Z = 0 at infinity.  Every launcher enqueues ONE kernel; capi.hip's msm_schedule_of decides the sizes from (n, bits, flags).
 constexpr int MSM_TREE_FAN = 16;                 // elements a lane of the tree sum adds per launch
 template <int C> struct msm_launch {
-  static void zero(hipStream_t, void* words, size_t bytes);          // bytes: a multiple of 16
   static void digits(hipStream_t, const uint64_t* k, const uint64_t* x, const uint64_t* y, uint64_t* kk, uint64_t* px, uint64_t* py, uint32_t* hist, uint32_t* counter, size_t n,
                      int bits, int c, int windows);
-  static void scan(hipStream_t, const uint32_t* hist, uint32_t* start, uint32_t* cursor, size_t K);
-  static void scatter(hipStream_t, const uint64_t* kk, uint32_t* cursor, uint32_t* sorted, uint32_t* broken, size_t n, size_t T, int c, int windows);
   static void slices(hipStream_t, const uint32_t* sorted, const uint64_t* kk, const uint64_t* px, const uint64_t* py, const uint32_t* start, uint64_t* buckets, uint64_t* partial,
                      uint32_t* broken, size_t n, size_t T, size_t L, size_t slices, int c, size_t K);
   static void combine(hipStream_t, const uint32_t* start, uint64_t* buckets, const uint64_t* partial, uint32_t* broken, size_t L, size_t slices, int c, size_t K);
@@ -357,14 +360,12 @@ template <int C> struct msm_launch {
                      uint32_t* invalid);
 };
 // k_schnorr_batch.hip: BIP-340 batch verification (include/ecsimd_schnorr_batch.h; PUBLIC data).  Every launcher enqueues ONE kernel.  The call's header block in
-// the workspace: the seed, the two sums as msm_launch::finish writes them (0: sum a R, 1: the key sum with the G term), the malformed lanes' counter.  192 bytes,
-// zeroed by msm_launch::zero.
-constexpr int SCHNORR_BATCH_FAN = 16;            // children per node of the hash tree, terms per lane of the tree of additions modulo n
+// the workspace: the seed, the two sums as msm_launch::finish writes them (0: sum a R, 1: the key sum with the G term), the malformed lanes' counter.  192 bytes.
+constexpr int BATCH_FAN = 16;                    // batch_tree.cuh, both batch verifications: children per node of the hash tree, terms per lane of the tree of additions
 struct schnorr_batch_head { uint64_t seed[4], rx[2][4], ry[2][4]; uint32_t malformed, invalid[2]; uint8_t finite[2], unused[18]; };
 // front: E = the challenge digest, leaf, (Px, Py) and (Rx, Ry) = the even-y lifts ((0, 0) on a malformed lane, which is counted in head->malformed), valid.
 // node: out[j] = H_node(in[16 j ..]) for j < ceil(count / 16).  seed: head->seed from the root and n.  scalars: a, a e mod n, a s mod n (0 where not valid).
 // sum: out[j] = sum of in[16 j ..] mod n; with gx (count <= 16): out[0] = n - sum (0 stays 0) and (gx, gy)[0] = G.  accept: ok[0] from head.
-// all: ok[0] = every one of the n bytes of flags (16-byte aligned) is 1; n = 0: 1.
 void schnorr_batch_front(hipStream_t, const words8& order, const uint64_t* px, const uint64_t* r, const uint64_t* s, const uint8_t* msg, size_t msg_bytes, size_t stride_bytes,
                          uint64_t* E, uint64_t* leaf, uint64_t* Px, uint64_t* Py, uint64_t* Rx, uint64_t* Ry, uint8_t* valid, schnorr_batch_head* head, size_t n);
 void schnorr_batch_node(hipStream_t, const uint64_t* in, size_t count, uint64_t* out);
@@ -373,24 +374,23 @@ void schnorr_batch_scalars(hipStream_t, const gmod& order, const schnorr_batch_h
                            uint64_t* as, size_t n);
 void schnorr_batch_sum(hipStream_t, const gmod& order, const uint64_t* in, size_t count, uint64_t* out, uint64_t* gx, uint64_t* gy);
 void schnorr_batch_accept(hipStream_t, const schnorr_batch_head* head, uint8_t* ok);
-void schnorr_batch_all(hipStream_t, const uint8_t* flags, size_t n, uint8_t* ok);
 // k_msm_ed25519.hip: the bucket method on the twisted Edwards curve and Ed25519 batch verification (include/ecsimd_ed25519_batch.h; PUBLIC data).  Every launcher
-// enqueues ONE kernel.  The sum's stages are k_msm.inc's on ed25519.cuh's arithmetic; zero, scan and scatter are msm_launch<CURVE_SECP256K1>'s (they do not depend
-// on the curve).  Terms: k = n x 32 little-endian bytes, pts = n x 32-byte encodings, both at any alignment; kk = the masked scalars, pre = the decoded terms as
+// enqueues ONE kernel.  The sum's stages are msm_stages.cuh's on ed25519.cuh's arithmetic.  Terms: k = n x 32 little-endian bytes, pts = n x 32-byte encodings, both at any alignment; kk = the masked scalars, pre = the decoded terms as
 // three planes of n (y + x, y - x, 2 d x y); buckets, partial and the tree are FOUR planes (X, Y, Z, T), the identity (0, 1, 1, 0).  finish: out = the 32-byte
 // encoding, or with raw != nullptr the extended point as 16 words at raw and no encoding.
 // The batch's header block in the workspace: the seed, the two sums as finish writes them raw (0: sum z R, 1: the key sum with the B term), the malformed lanes'
-// counter.  304 bytes, zeroed by msm_launch::zero.
-constexpr int ED25519_BATCH_FAN = 16;            // children per node of the hash tree, terms per lane of the tree of additions modulo L
+// counter.  304 bytes.
 struct ed25519_batch_head { uint64_t seed[4], sum[2][16]; uint32_t malformed, invalid[2]; uint8_t finite[2], unused[2]; };
-void ed25519_msm_digits(hipStream_t, const uint8_t* k, const uint8_t* pts, uint64_t* kk, uint64_t* pre, uint32_t* hist, uint32_t* counter, size_t n, int bits, int c, int windows);
-void ed25519_msm_slices(hipStream_t, const uint32_t* sorted, const uint64_t* kk, const uint64_t* pre, const uint32_t* start, uint64_t* buckets, uint64_t* partial, uint32_t* broken,
-                        size_t n, size_t T, size_t L, size_t slices, int c, size_t K);
-void ed25519_msm_combine(hipStream_t, const uint32_t* start, uint64_t* buckets, const uint64_t* partial, uint32_t* broken, size_t L, size_t slices, int c, size_t K);
-void ed25519_msm_chunks(hipStream_t, const uint64_t* buckets, uint64_t* out, size_t lanes, size_t per_window, int c, int m, size_t K);
-void ed25519_msm_tree(hipStream_t, uint64_t* arr, size_t total, size_t count, size_t stride, size_t groups, size_t lanes, int fan);
-void ed25519_msm_finish(hipStream_t, const uint64_t* arr, size_t total, size_t stride, int windows, int c, const uint32_t* counter, uint8_t* out, uint64_t* raw, uint8_t* finite,
-                        uint32_t* invalid);
+struct ed25519_msm_launch {                      // msm_launch's shape: capi.hip's bucket_sum_run takes either
+  static void digits(hipStream_t, const uint8_t* k, const uint8_t* pts, uint64_t* kk, uint64_t* pre, uint32_t* hist, uint32_t* counter, size_t n, int bits, int c, int windows);
+  static void slices(hipStream_t, const uint32_t* sorted, const uint64_t* kk, const uint64_t* pre, const uint32_t* start, uint64_t* buckets, uint64_t* partial, uint32_t* broken,
+                     size_t n, size_t T, size_t L, size_t slices, int c, size_t K);
+  static void combine(hipStream_t, const uint32_t* start, uint64_t* buckets, const uint64_t* partial, uint32_t* broken, size_t L, size_t slices, int c, size_t K);
+  static void chunks(hipStream_t, const uint64_t* buckets, uint64_t* out, size_t lanes, size_t per_window, int c, int m, size_t K);
+  static void tree(hipStream_t, uint64_t* arr, size_t total, size_t count, size_t stride, size_t groups, size_t lanes, int fan);
+  static void finish(hipStream_t, const uint64_t* arr, size_t total, size_t stride, int windows, int c, const uint32_t* counter, uint8_t* out, uint64_t* raw, uint8_t* finite,
+                     uint32_t* invalid);
+};
 // front: h = SHA-512(R || A || M) mod L, leaf, A and R copied to Aenc / Renc, valid = s < L (&& no small-order A or R); a lane that is not valid counts in
 // head->malformed.  node / seed: schnorr_batch's shapes under this call's tags.  scalars: z, and where zh is given z h mod L and z s mod L (0 where not valid).
 // sum: out[j] = sum of in[16 j ..] mod L; with benc (count <= 16): out[0] = L - sum (0 stays 0) and benc[0] = B's encoding.  accept: ok[0] from head.

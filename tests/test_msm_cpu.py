@@ -21,8 +21,8 @@ from helpers import CURVE_PARAMS, P256, SECP256K1, ec_add, ec_mul   # noqa: E402
 CSRC = os.path.join(ROOT, "ecsimd_amd", "csrc")
 HEADER = os.path.join(ROOT, "include", "ecsimd_msm.h")
 SYMBOLS = {"ecsimd_msm", "ecsimd_msm_point_sum", "ecsimd_msm_plan"}
-KERNELS = ("k_msm_zero", "k_msm_digits", "k_msm_scan", "k_msm_scatter", "k_msm_slices", "k_msm_combine", "k_msm_chunks", "10k_msm_tree", "k_msm_tree_affineILb1", "k_msm_tree_affineILb0",
-           "k_msm_sanitize", "k_msm_final")
+KERNELS = ("k_msm_digits", "k_msm_slices", "k_msm_combine", "k_msm_chunks", "10k_msm_tree", "k_msm_tree_affineILb1", "k_msm_tree_affineILb0", "k_msm_sanitize", "k_msm_final")   # per curve
+COMMON_KERNELS = ("k_msm_zero", "k_msm_scan", "k_msm_scatter")       # no curve in them: k_msm_common.hip, compiled once
 PLAN_N = (0, 1, 2, 63, 64, 65, 2**10, 2**16, 2**20, 2**24)
 PLAN_BITS = (1, 64, 128, 255, 256)
 
@@ -201,22 +201,32 @@ def kernel_blocks(asm):
     return {re.search(r"\.name:\s+(\S+)", b).group(1): b for b in re.split(r"\n  - \.agpr_count:", meta)[1:]}
 
 
+def unit_figures(unit, sources, kernels):
+    listing = os.path.join(ROOT, "build", "csrc", f"{unit}-hip-amdgcn-amd-amdhsa-gfx950.s")
+    assert os.path.exists(listing), "the Makefile no longer leaves the device listings in build/csrc (-save-temps=obj)"
+    for f in sources:
+        assert os.path.getmtime(listing) >= os.path.getmtime(os.path.join(CSRC, f)), f
+    blocks = kernel_blocks(open(listing).read())
+    out = {}
+    for k in kernels:
+        hit = [b for name, b in blocks.items() if k in name]
+        assert len(hit) == 1, k
+        num = lambda field: int(re.search(r"\.%s:\s+(\d+)" % field, hit[0]).group(1))
+        short = re.sub(r"^\d+", "", k).replace("ILb1", "<validate>").replace("ILb0", "<plain>")
+        out[short] = dict(vgprs=num("vgpr_count"), sgprs=num("sgpr_count"), scratch_bytes=num("private_segment_fixed_size"),
+                          spilled_vgprs=num("vgpr_spill_count"), lds_bytes=num("group_segment_fixed_size"))
+    return out, len(blocks)
+
+
 def listing_figures():
     out = {}
+    common, blocks = unit_figures("k_msm_common", ("k_msm_common.hip", "msm_stages.cuh", "field.cuh", "kernels.h"), COMMON_KERNELS)
+    assert blocks == len(COMMON_KERNELS) + 1                                                           # ... and the AND of verdict bytes, which is no stage of the sum
     for curve in ("p256", "secp256k1"):
-        listing = os.path.join(ROOT, "build", "csrc", f"k_msm_{curve}-hip-amdgcn-amd-amdhsa-gfx950.s")
-        assert os.path.exists(listing), "the Makefile no longer leaves the device listings in build/csrc (-save-temps=obj)"
-        for f in (f"k_msm_{curve}.hip", "k_msm.inc", "point.cuh", "field.cuh", "kernels.h"):
-            assert os.path.getmtime(listing) >= os.path.getmtime(os.path.join(CSRC, f)), f
-        blocks = kernel_blocks(open(listing).read())
-        assert len(blocks) == len(KERNELS), sorted(blocks)
-        for k in KERNELS:
-            hit = [b for name, b in blocks.items() if k in name]
-            assert len(hit) == 1, k
-            num = lambda field: int(re.search(r"\.%s:\s+(\d+)" % field, hit[0]).group(1))
-            short = re.sub(r"^\d+", "", k).replace("ILb1", "<validate>").replace("ILb0", "<plain>")
-            out.setdefault(short, {})[curve] = dict(vgprs=num("vgpr_count"), sgprs=num("sgpr_count"), scratch_bytes=num("private_segment_fixed_size"),
-                                                    spilled_vgprs=num("vgpr_spill_count"), lds_bytes=num("group_segment_fixed_size"))
+        own, blocks = unit_figures(f"k_msm_{curve}", (f"k_msm_{curve}.hip", "k_msm.inc", "msm_stages.cuh", "point.cuh", "field.cuh", "kernels.h"), KERNELS)
+        assert blocks == len(KERNELS) == 9
+        for name, f in {**own, **common}.items():                                                      # the common kernels serve both curves: the record has them under each
+            out.setdefault(name, {})[curve] = f
     return out
 
 
@@ -233,5 +243,5 @@ def test_the_new_kernels_are_in_the_listing_with_the_figures_the_documents_state
                                                 per_curve["secp256k1"]["scratch_bytes"])
         assert row in design, row
     makefile = open(os.path.join(CSRC, "Makefile")).read()
-    for f in ("k_msm_p256.hip", "k_msm_secp256k1.hip", "k_msm.inc", "ecsimd_msm.h"):
+    for f in ("k_msm_p256.hip", "k_msm_secp256k1.hip", "k_msm_common.hip", "k_msm.inc", "msm_stages.cuh", "ecsimd_msm.h"):
         assert f in makefile, f

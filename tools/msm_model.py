@@ -1,4 +1,4 @@
-"""The host model of ecsimd_msm (include/ecsimd_msm.h; ecsimd_amd/csrc/k_msm.inc): the schedule of ecsimd_msm_plan restated in Python -- the same c, L, m,
+"""The host model of ecsimd_msm (include/ecsimd_msm.h; ecsimd_amd/csrc/msm_stages.cuh, k_msm.inc): the schedule of ecsimd_msm_plan restated in Python -- the same c, L, m,
 launches and workspace from the same (n, bits, flags) -- and an index-level emulation of the BUCKETS route's stages on Python integers: digits and
 validation, the counting sort by (window, digit), the slices with their head / tail slots, the combination of a bucket's slices, the bucket reduction in
 chunks, the tree sum and the Horner step over the windows.  Every virtual lane counts the point operations (additions and doublings) it performs one after the
