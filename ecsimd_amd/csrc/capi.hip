@@ -19,6 +19,7 @@
 #include "../../include/ecsimd_ed25519.h"
 #include "../../include/ecsimd_x25519.h"
 #include "../../include/ecsimd_p384.h"
+#include "../../include/ecsimd_sm2.h"
 #include "../../include/ecsimd_msm.h"
 #include "../../include/ecsimd_schnorr_batch.h"
 #include "../../include/ecsimd_ed25519_batch.h"
@@ -2538,6 +2539,180 @@ int ecsimd_p384_raw(ecsimd_hip_ctx* ctx, int op, const uint8_t* in, uint8_t* out
   launch::p384_raw(ctx->stream, op, in, out, table, n);
   const hipError_t e = hipGetLastError();
   return e == hipSuccess ? ECSIMD_HIP_OK : fail(ctx, e, "p384_raw launch"); }
+
+// ---- The SM2 signature scheme on a registered curve with the ECDSA capability (include/ecsimd_sm2.h; k_sm2.hip): SM3, Z_A and the scalar-field halves are new
+// kernels, launched once over the whole batch; every point is made by the steps ECDSA uses on such a curve -- gc_double_scalar_mult for the public sum
+// s G + t Q, the constant-time comb of ecdsa_sign_registered for the secret k G and d G -- and signing's workspace goes through wipe_workspace.
+namespace {
+int sm2_require(ecsimd_hip_ctx* ctx, int curve, curve_record* rec) {
+  if (curve == ECSIMD_HIP_P256 || curve == ECSIMD_HIP_SECP256K1)
+    return bad(ctx, "sm2: a curve registered at run time with the ECDSA capability is needed (ecsimd_sm2_curve gives sm2p256v1's id): the built-in curve ids are refused");
+  return gc_require_ecdsa(ctx, curve, rec);
+}
+launch::sm2_curve_words sm2_words(const curve_record& rec) {
+  launch::sm2_curve_words w;
+  w.a = words8_of(rec.a.l); w.b = words8_of(rec.b.l);
+  for (int i = 0; i < 8; ++i) { w.gx.w[i] = rec.G.gx[i]; w.gy.w[i] = rec.G.gy[i]; }
+  return w;
+}
+int sm2_id_args(ecsimd_hip_ctx* ctx, const uint8_t* id, size_t id_bytes, size_t id_stride, size_t n) {
+  if (id_bytes > 8191) return bad(ctx, "sm2: id_bytes is larger than 8191 (ENTL, the identity's bit length, has 16 bits)");
+  if (!id && n && id_bytes) return bad(ctx, "sm2: id is null");
+  if (id_stride != 0 && id_stride < id_bytes) return bad(ctx, "sm2: id_stride is smaller than id_bytes (0: one identity for the whole batch)");
+  return ECSIMD_HIP_OK;
+}
+int sm2_msg_args(ecsimd_hip_ctx* ctx, const uint8_t* msg, size_t* msg_bytes, size_t stride_bytes, const uint32_t* lens, size_t n) {
+  if (lens) *msg_bytes = 0;                                                       // (ignored: every lane has its own length)
+  if (!msg && n && (*msg_bytes || (lens && stride_bytes))) return bad(ctx, "sm2: msg is null");
+  if (lens && (reinterpret_cast<uintptr_t>(lens) & 3u)) return bad(ctx, "sm2: lens is not 4-byte aligned");
+  if (lens && !stride_bytes && n > 1) return bad(ctx, "sm2: stride_bytes is 0 with lens: every lane would read the first row");
+  if (stride_bytes < *msg_bytes) return bad(ctx, "sm2: stride_bytes is smaller than msg_bytes");
+  if (*msg_bytes >= ((size_t)1 << 31)) return bad(ctx, "sm2: message too long (2^31 bytes or more)");
+  return ECSIMD_HIP_OK;
+}
+// verification's own arrays behind the double product's and verify_plan's: u1 = s, u2 = t, the digest where the call makes it, the range flags
+struct sm2_verify_layout { uint64_t *u1, *u2, *e; uint8_t* valid; size_t extra; };
+sm2_verify_layout sm2_verify_plan(void* base, size_t front, size_t n, bool with_e) {
+  sm2_verify_layout S; carve c = carve_from(base);
+  (void)carve_bytes(c, front); S.u1 = carve_limbs(c, n); S.u2 = carve_limbs(c, n); S.e = with_e ? carve_limbs(c, n) : nullptr; S.valid = carve_flags(c, n); S.extra = c.bytes - front;
+  return S;
+}
+// msg_of == nullptr: the caller's digest e.  Else e = SM3(Z_A || M) into the workspace first.  The caller has gone through ENTER.
+struct sm2_message { const uint8_t* id; size_t id_bytes, id_stride; const uint8_t* msg; size_t msg_bytes, stride_bytes; const uint32_t* lens; };
+int sm2_verify_impl(ecsimd_hip_ctx* ctx, int curve, const curve_record& rec, const uint64_t* e, const sm2_message* msg_of, const uint64_t* r, const uint64_t* s_, const uint64_t* qx,
+                    const uint64_t* qy, uint8_t* ok, size_t n) {
+  const size_t front = gc_plan(nullptr, n, gc_window_possible(rec)).bytes, behind = verify_plan(nullptr, front, n).behind, inner = front + behind;
+  int rc = ensure_workspace(ctx, inner + sm2_verify_plan(nullptr, inner, n, msg_of != nullptr).extra);
+  if (rc != ECSIMD_HIP_OK) return rc;
+  const sm2_verify_layout S = sm2_verify_plan(ctx->workspace, inner, n, msg_of != nullptr);
+  const verify_layout V = verify_plan(ctx->workspace, front, n);
+  if (msg_of) {
+    launch::sm2_digest(ctx->stream, sm2_words(rec), qx, qy, msg_of->id, msg_of->id_bytes, msg_of->id_stride, msg_of->msg, msg_of->msg_bytes, msg_of->stride_bytes, msg_of->lens, S.e, n);
+    e = S.e;
+  }
+  launch::sm2_verify_scalars(ctx->stream, order_words(rec), r, s_, S.u1, S.u2, S.valid, n);
+  rc = gc_double_scalar_mult(ctx, curve, rec, S.u1, S.u2, qx, qy, V.rx, nullptr, V.fin, n, behind + S.extra);      // the workspace is already this large: nothing moves
+  if (rc != ECSIMD_HIP_OK) return rc;
+  launch::sm2_accept(ctx->stream, order_words(rec), e, V.rx, V.fin, r, S.valid, ok, n);                            // fin is 0 for the lanes whose Q failed validation
+  const hipError_t err = hipGetLastError();
+  return err == hipSuccess ? ECSIMD_HIP_OK : fail(ctx, err, "sm2_verify launch");
+}
+// k G for SECRET k on the registered curve, x (and y) affine into the caller's arrays: ecdsa_sign_registered's product -- the constant-time 5-bit comb of the
+// generator; where no table exists yet and a capture in progress forbids building it, the reference's ladder, constant-time as it is.  L's arrays are the
+// caller's to wipe.  ensure_sm2_comb comes first: it may synchronise, and runs before any pointer into the workspace is taken.
+int ensure_sm2_comb(ecsimd_hip_ctx* ctx, int curve, const curve_record& rec, const uint32_t** comb) {
+  *comb = nullptr;
+  if (!gc_comb_possible(rec)) return ECSIMD_HIP_OK;
+  const int rc = ensure_gc_comb(ctx, curve, rec, comb, 5);
+  if (rc != ECSIMD_HIP_OK) { if (!capturing(ctx)) return rc; *comb = nullptr; }
+  return ECSIMD_HIP_OK;
+}
+void sm2_secret_product(ecsimd_hip_ctx* ctx, const curve_record& rec, const gc_layout& L, const uint32_t* comb, const uint64_t* k, uint64_t* x, uint64_t* y, size_t n) {
+  if (comb) {
+    launch::gc_base_windowed_s(ctx->stream, rec.G, order_words(rec), 5, k, comb, L.j[0], L.j[1], L.j[2], n);      // k >= n is reduced by the comb; the caller's kernel refuses the lane
+    launch::gc_to_affine_batched(ctx->stream, rec.G, L.j[0], L.j[1], L.j[2], x, y, n);
+  } else gc_safe_mult(ctx->stream, rec, L, L.adj1, L.neg1, k, nullptr, nullptr, x, y, n);
+}
+// signing's workspace: the product's arrays, then (deterministic nonce) the nonce, K, V and the retry bytes
+struct sm2_sign_layout { gc_layout G; nonce_layout K; size_t bytes; };
+sm2_sign_layout sm2_sign_plan(uint64_t* base, size_t n, bool nonce) {
+  sm2_sign_layout L; L.G = gc_plan(base, n);
+  L.K = nonce_plan_ws(base, L.G.bytes, nonce ? n : 0);
+  L.bytes = L.G.bytes + (nonce ? L.K.bytes : 0);
+  return L;
+}
+const uint64_t SM2P256V1[6][4] = {
+    {0xffffffffffffffffull, 0xffffffff00000000ull, 0xffffffffffffffffull, 0xfffffffeffffffffull},      // p
+    {0xfffffffffffffffcull, 0xffffffff00000000ull, 0xffffffffffffffffull, 0xfffffffeffffffffull},      // a = p - 3
+    {0xddbcbd414d940e93ull, 0xf39789f515ab8f92ull, 0x4d5a9e4bcf6509a7ull, 0x28e9fa9e9d9f5e34ull},      // b
+    {0x715a4589334c74c7ull, 0x8fe30bbff2660be1ull, 0x5f9904466a39c994ull, 0x32c4ae2c1f198119ull},      // x_G
+    {0x02df32e52139f0a0ull, 0xd0a9877cc62a4740ull, 0x59bdcee36b692153ull, 0xbc3736a2f4f6779cull},      // y_G
+    {0x53bbf40939d54123ull, 0x7203df6b21c6052bull, 0xffffffffffffffffull, 0xfffffffeffffffffull}};     // n
+}  // namespace
+
+int ecsimd_sm2_curve(int* curve_id) {
+  if (!curve_id) return ECSIMD_HIP_ERR_BAD_ARG;
+  return ecsimd_hip_register_curve(SM2P256V1[0], SM2P256V1[1], SM2P256V1[2], SM2P256V1[3], SM2P256V1[4], SM2P256V1[5], 0, curve_id); }
+
+int ecsimd_sm2_sm3(ecsimd_hip_ctx* ctx, const uint8_t* msg, size_t msg_bytes, size_t stride_bytes, const uint32_t* lens, uint64_t* e, size_t n) {
+  REQUIRE_CTX(); REQUIRE_PTR(e);
+  int rc = sm2_msg_args(ctx, msg, &msg_bytes, stride_bytes, lens, n); if (rc != ECSIMD_HIP_OK) return rc;
+  if (n != 0 && any_alias({e}, {msg, lens})) return bad(ctx, "sm2_sm3: e must not alias an input");
+  RUN(launch::sm3(s, msg, msg_bytes, stride_bytes, lens, e, n)); }
+
+int ecsimd_sm2_za(ecsimd_hip_ctx* ctx, int curve, const uint64_t* qx, const uint64_t* qy, const uint8_t* id, size_t id_bytes, size_t id_stride, uint64_t* za, size_t n) {
+  REQUIRE_CTX(); REQUIRE_PTR(qx); REQUIRE_PTR(qy); REQUIRE_PTR(za);
+  curve_record rec; int rc = sm2_require(ctx, curve, &rec); if (rc != ECSIMD_HIP_OK) return rc;
+  rc = sm2_id_args(ctx, id, id_bytes, id_stride, n); if (rc != ECSIMD_HIP_OK) return rc;
+  if (n != 0 && any_alias({za}, {qx, qy, id})) return bad(ctx, "sm2_za: za must not alias an input");
+  RUN(launch::sm2_za(s, sm2_words(rec), qx, qy, id, id_bytes, id_stride, za, n)); }
+
+int ecsimd_sm2_digest(ecsimd_hip_ctx* ctx, int curve, const uint64_t* qx, const uint64_t* qy, const uint8_t* id, size_t id_bytes, size_t id_stride, const uint8_t* msg,
+                      size_t msg_bytes, size_t stride_bytes, const uint32_t* lens, uint64_t* e, size_t n) {
+  REQUIRE_CTX(); REQUIRE_PTR(qx); REQUIRE_PTR(qy); REQUIRE_PTR(e);
+  curve_record rec; int rc = sm2_require(ctx, curve, &rec); if (rc != ECSIMD_HIP_OK) return rc;
+  rc = sm2_id_args(ctx, id, id_bytes, id_stride, n); if (rc != ECSIMD_HIP_OK) return rc;
+  rc = sm2_msg_args(ctx, msg, &msg_bytes, stride_bytes, lens, n); if (rc != ECSIMD_HIP_OK) return rc;
+  if (n != 0 && any_alias({e}, {qx, qy, id, msg, lens})) return bad(ctx, "sm2_digest: e must not alias an input");
+  RUN(launch::sm2_digest(s, sm2_words(rec), qx, qy, id, id_bytes, id_stride, msg, msg_bytes, stride_bytes, lens, e, n)); }
+
+int ecsimd_sm2_pubkey(ecsimd_hip_ctx* ctx, int curve, const uint64_t* d, uint64_t* qx, uint64_t* qy, uint8_t* ok, size_t n) {
+  REQUIRE_CTX(); REQUIRE_PTR(d); REQUIRE_PTR(qx); REQUIRE_PTR(qy);
+  if (!ok && n) return bad(ctx, "ok is null");
+  curve_record rec; int rc = sm2_require(ctx, curve, &rec); if (rc != ECSIMD_HIP_OK) return rc;
+  if (n != 0 && any_alias({qx, qy, ok}, {d})) return bad(ctx, "sm2_pubkey: qx, qy and ok must not alias an input or each other");
+  ENTER();
+  if (gc_plan(nullptr, n).chunk != n) return bad(ctx, "sm2_pubkey: at most 2^22 keys per call");
+  rc = ensure_workspace(ctx, gc_plan(nullptr, n).bytes);
+  if (rc != ECSIMD_HIP_OK) return rc;
+  const uint32_t* comb; rc = ensure_sm2_comb(ctx, curve, rec, &comb); if (rc != ECSIMD_HIP_OK) return rc;
+  const gc_layout L = gc_plan(ctx->workspace, n);
+  sm2_secret_product(ctx, rec, L, comb, d, qx, qy, n);
+  launch::sm2_key_range(ctx->stream, rec.N, d, qx, qy, ok, n);
+  const hipError_t err = wipe_workspace(ctx, L.bytes, hipGetLastError());                              // the Jacobian d G (and the ladder route's adjusted copy of d)
+  return err == hipSuccess ? ECSIMD_HIP_OK : fail(ctx, err, "sm2_pubkey launch"); }
+
+int ecsimd_sm2_verify_digest(ecsimd_hip_ctx* ctx, int curve, const uint64_t* e, const uint64_t* r, const uint64_t* s_, const uint64_t* qx, const uint64_t* qy, uint8_t* ok,
+                             size_t n) {
+  REQUIRE_CTX(); REQUIRE_PTR(e); REQUIRE_PTR(r); REQUIRE_PTR(s_); REQUIRE_PTR(qx); REQUIRE_PTR(qy);
+  if (!ok && n) return bad(ctx, "ok is null");
+  curve_record rec; int rc = sm2_require(ctx, curve, &rec); if (rc != ECSIMD_HIP_OK) return rc;
+  if (n != 0 && any_alias({ok}, {e, r, s_, qx, qy})) return bad(ctx, "sm2_verify_digest: ok must not alias an input");
+  ENTER();
+  return sm2_verify_impl(ctx, curve, rec, e, nullptr, r, s_, qx, qy, ok, n); }
+
+int ecsimd_sm2_verify(ecsimd_hip_ctx* ctx, int curve, const uint64_t* qx, const uint64_t* qy, const uint8_t* id, size_t id_bytes, size_t id_stride, const uint8_t* msg,
+                      size_t msg_bytes, size_t stride_bytes, const uint32_t* lens, const uint64_t* r, const uint64_t* s_, uint8_t* ok, size_t n) {
+  REQUIRE_CTX(); REQUIRE_PTR(r); REQUIRE_PTR(s_); REQUIRE_PTR(qx); REQUIRE_PTR(qy);
+  if (!ok && n) return bad(ctx, "ok is null");
+  curve_record rec; int rc = sm2_require(ctx, curve, &rec); if (rc != ECSIMD_HIP_OK) return rc;
+  rc = sm2_id_args(ctx, id, id_bytes, id_stride, n); if (rc != ECSIMD_HIP_OK) return rc;
+  rc = sm2_msg_args(ctx, msg, &msg_bytes, stride_bytes, lens, n); if (rc != ECSIMD_HIP_OK) return rc;
+  if (n != 0 && any_alias({ok}, {r, s_, qx, qy, id, msg, lens})) return bad(ctx, "sm2_verify: ok must not alias an input");
+  ENTER();
+  const sm2_message M = {id, id_bytes, id_stride, msg, msg_bytes, stride_bytes, lens};
+  return sm2_verify_impl(ctx, curve, rec, nullptr, &M, r, s_, qx, qy, ok, n); }
+
+int ecsimd_sm2_sign_digest(ecsimd_hip_ctx* ctx, int curve, const uint64_t* e, const uint64_t* d, const uint64_t* k, uint64_t* r, uint64_t* s_, uint8_t* ok, size_t n, int flags) {
+  REQUIRE_CTX(); REQUIRE_PTR(e); REQUIRE_PTR(d); REQUIRE_PTR(r); REQUIRE_PTR(s_);
+  if (k && !aligned16(k)) return bad(ctx, "k is not 16-byte aligned");
+  if (!ok && n) return bad(ctx, "ok is null");
+  if (flags != 0) return bad(ctx, "sm2_sign_digest: flags must be 0");
+  curve_record rec; int rc = sm2_require(ctx, curve, &rec); if (rc != ECSIMD_HIP_OK) return rc;
+  nonce_plan P; if (!k) { rc = nonce_lookup(ctx, curve, &P); if (rc != ECSIMD_HIP_OK) return rc; }
+  if (n != 0 && any_alias({r, s_, ok}, {e, d, k})) return bad(ctx, "sm2_sign_digest: r, s and ok must not alias an input or each other");
+  ENTER();
+  if (gc_plan(nullptr, n).chunk != n) return bad(ctx, "sm2_sign_digest: at most 2^22 signatures per call");
+  rc = ensure_workspace(ctx, sm2_sign_plan(nullptr, n, k == nullptr).bytes);
+  if (rc != ECSIMD_HIP_OK) return rc;
+  const uint32_t* comb; rc = ensure_sm2_comb(ctx, curve, rec, &comb); if (rc != ECSIMD_HIP_OK) return rc;
+  const sm2_sign_layout L = sm2_sign_plan(ctx->workspace, n, k == nullptr);
+  if (!k) launch::rfc6979_nonce(ctx->stream, P.order, e, d, L.K.k, L.K.state, L.K.retry, ok, n, P.cap);              // its verdict is overwritten: a refused lane has k = 0
+  const uint64_t* nonce = k ? k : L.K.k;
+  sm2_secret_product(ctx, rec, L.G, comb, nonce, L.G.gx, nullptr, n);
+  launch::sm2_sign_scalars(ctx->stream, rec.N, e, d, nonce, L.G.gx, r, s_, ok, n);
+  const hipError_t err = wipe_workspace(ctx, L.bytes, hipGetLastError());                              // the nonce and K, V behind it, the Jacobian k G, x(k G)
+  return err == hipSuccess ? ECSIMD_HIP_OK : fail(ctx, err, "sm2_sign_digest launch"); }
 
 // ---- Multi-scalar multiplication and the point sum (include/ecsimd_msm.h; msm_stages.cuh has the stages).  PUBLIC data.  msm_schedule_of is the ONE place that turns
 // (n, bits, flags) into sizes: ecsimd_msm_plan reports it, ecsimd_msm enqueues from it, tools/msm_model.py restates it.  Nothing here looks at the data.  The

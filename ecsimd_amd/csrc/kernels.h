@@ -407,6 +407,18 @@ void ed25519_batch_accept(hipStream_t, const ed25519_batch_head* head, uint8_t* 
 void ed25519_cofactored_front(hipStream_t, const gmod& L, const uint8_t* pk, const uint8_t* sig, const uint8_t* msg, size_t msg_bytes, size_t stride_bytes, const uint32_t* lens,
                               bool reject_small_order, uint64_t* s, uint64_t* h, uint64_t* rxy, void* table, uint8_t* valid, size_t n);
 void ed25519_cofactored_loop(hipStream_t, const uint64_t* s, const uint64_t* h, const uint64_t* rxy, const void* table, const uint8_t* valid, uint8_t* ok, size_t n);
+
+// k_sm2.hip: SM3 and the SM2 signature scheme around the generic curve kernels.  sm2_curve_words: the curve's classical a, b, x_G, y_G as Z_A hashes them.
+// lens may be null (every lane has msg_bytes bytes); id_stride = 0: one ID for the whole batch; id_bytes <= 8191; msg_bytes < 2^31.
+struct sm2_curve_words { words8 a, b, gx, gy; };
+void sm3(hipStream_t, const uint8_t* msg, size_t msg_bytes, size_t stride_bytes, const uint32_t* lens, uint64_t* e, size_t n);
+void sm2_za(hipStream_t, const sm2_curve_words&, const uint64_t* qx, const uint64_t* qy, const uint8_t* id, size_t id_bytes, size_t id_stride, uint64_t* za, size_t n);
+void sm2_digest(hipStream_t, const sm2_curve_words&, const uint64_t* qx, const uint64_t* qy, const uint8_t* id, size_t id_bytes, size_t id_stride, const uint8_t* msg, size_t msg_bytes,
+                size_t stride_bytes, const uint32_t* lens, uint64_t* e, size_t n);
+void sm2_verify_scalars(hipStream_t, const words8& order, const uint64_t* r, const uint64_t* s, uint64_t* u1, uint64_t* u2, uint8_t* valid, size_t n);
+void sm2_accept(hipStream_t, const words8& order, const uint64_t* e, const uint64_t* x, const uint8_t* finite, const uint64_t* r, const uint8_t* valid, uint8_t* ok, size_t n);
+void sm2_sign_scalars(hipStream_t, const gmod& N, const uint64_t* e, const uint64_t* d, const uint64_t* k, const uint64_t* x, uint64_t* r, uint64_t* s, uint8_t* ok, size_t n);   // SECRET d, k
+void sm2_key_range(hipStream_t, const gmod& N, const uint64_t* d, uint64_t* qx, uint64_t* qy, uint8_t* ok, size_t n);                                                             // SECRET d
 inline size_t scalar_mult_x_scratch_bytes(size_t n) { return 4 * n * 32 + ((n + 31) & ~(size_t)31); }   // odd scalars, num, den, 1/den, zero flags
 // The 4-bit fixed-base table in LDS (BASELINE configs[2]): odd digits only (round 3) -- the regular recoding of the odd one of k mod n, n - k, as in
 // the big-window kernel: 64 windows x 8 odd multiples (2d + 1) 16^w G = 32 KiB, 63 mixed additions, no zero digit and therefore no "skip" / "infinity"

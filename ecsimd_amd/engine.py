@@ -661,6 +661,98 @@ class Engine:
         self._check(self.lib.ecsimd_p384_raw(self.ctx, C.c_int(op), ip, C.c_void_p(out.data_ptr() if n else 0), C.c_size_t(n)), "p384_raw")
         return out
 
+    # ---- the SM2 signature scheme (include/ecsimd_sm2.h): integers are (n, 4) limb tensors as the ECDSA methods take them, digests likewise
+    SM2_DEFAULT_ID = b"1234567812345678"
+
+    @staticmethod
+    def sm2_curve():
+        """ecsimd_sm2_curve: the id of sm2p256v1 (registered on the first call; what curves.curve_id("sm2") returns).  Host only: no GPU and no Engine."""
+        cid = C.c_int(-1)
+        rc = load_library().ecsimd_sm2_curve(C.byref(cid))
+        if rc != 0:
+            raise EcsimdHipError(f"sm2_curve failed ({rc})")
+        return cid.value
+
+    def _sm2_call(self, name, *args):
+        rows, self._rows = self._rows, set()
+        if len(rows) > 1:
+            raise EcsimdHipError(f"{name}: operands disagree on the batch length: {sorted(rows)}")
+        self._bind_stream()
+        self._check(getattr(self.lib, "ecsimd_" + name)(self.ctx, *args), name)
+
+    def _sm2_ids(self, ids, n):
+        """(keep-alive, pointer, id_bytes, id_stride) of `ids`: bytes (one identity for the whole batch, copied to the device) or a 2-D uint8 device tensor with
+        one identity per row."""
+        torch = self.torch
+        if isinstance(ids, (bytes, bytearray)):
+            t = torch.tensor(list(ids), dtype=torch.uint8, device=self.tdev) if len(ids) else None
+            return t, C.c_void_p(t.data_ptr() if t is not None else 0), C.c_size_t(len(ids)), C.c_size_t(0)
+        keep, ip, length, stride = self._messages(ids, n)
+        if n == 1 or length.value == 0:
+            stride = C.c_size_t(0)
+        return keep, ip, length, stride
+
+    def sm3(self, msgs, lens=None):
+        """ecsimd_sm2_sm3: the SM3 digests of the rows of `msgs` (as sha256's: 2-D uint8, rows may be strided; lens: lane i hashes the first lens[i] bytes of its
+        row) as (n, 4) integers."""
+        n = int(msgs.shape[0]); e = self.empty(n)
+        keep, mp, length, stride = self._messages(msgs, n)
+        lp = self._lens_ptr("sm2_sm3", lens if length.value else None, n)
+        self._sm2_call("sm2_sm3", mp, length, stride, lp, self._ptr(e), C.c_size_t(n))
+        return e
+
+    def sm2_za(self, curve, qx, qy, ids=SM2_DEFAULT_ID):
+        """ecsimd_sm2_za: Z_A of each public key and identity (bytes: one for the whole batch; a 2-D uint8 tensor: one per row) as (n, 4) integers."""
+        n = int(qx.shape[0]); za = self.empty(n)
+        keep, ip, ilen, istride = self._sm2_ids(ids, n)
+        self._sm2_call("sm2_za", C.c_int(curve), self._ptr(qx), self._ptr(qy), ip, ilen, istride, self._ptr(za), C.c_size_t(n))
+        return za
+
+    def sm2_digest(self, curve, qx, qy, msgs, ids=SM2_DEFAULT_ID, lens=None):
+        """ecsimd_sm2_digest: e = SM3(Z_A || M) of each lane as (n, 4) integers, ready to be the `e` of sm2_verify_digest and sm2_sign_digest."""
+        n = int(qx.shape[0]); e = self.empty(n)
+        keep, ip, ilen, istride = self._sm2_ids(ids, n)
+        keep2, mp, length, stride = self._messages(msgs, n)
+        lp = self._lens_ptr("sm2_digest", lens if length.value else None, n)
+        self._sm2_call("sm2_digest", C.c_int(curve), self._ptr(qx), self._ptr(qy), ip, ilen, istride, mp, length, stride, lp, self._ptr(e), C.c_size_t(n))
+        return e
+
+    def sm2_pubkey(self, curve, d):
+        """ecsimd_sm2_pubkey: (qx, qy, ok) for the SECRET private keys d; ok = 0 and (0, 0) where d is not in [1, n - 2]."""
+        n = int(d.shape[0]); qx, qy, ok = self.empty(n), self.empty(n), self.flags(n)
+        self._sm2_call("sm2_pubkey", C.c_int(curve), self._ptr(d), self._ptr(qx), self._ptr(qy), self._ptr(ok, 0), C.c_size_t(n))
+        return qx, qy, ok
+
+    def sm2_verify_digest(self, curve, e, r, s, qx, qy):
+        """ecsimd_sm2_verify_digest: ok, one byte per lane, for the signatures (r, s) of the digests e under the public keys (qx, qy).  Public data."""
+        n = int(e.shape[0]); ok = self.flags(n)
+        self._sm2_call("sm2_verify_digest", C.c_int(curve), self._ptr(e), self._ptr(r), self._ptr(s), self._ptr(qx), self._ptr(qy), self._ptr(ok, 0), C.c_size_t(n))
+        return ok
+
+    def sm2_verify(self, curve, qx, qy, msgs, r, s, ids=SM2_DEFAULT_ID, lens=None):
+        """ecsimd_sm2_verify: ok, one byte per lane, for the signatures (r, s) of the rows of `msgs` under the public keys and identities.  Public data."""
+        n = int(qx.shape[0]); ok = self.flags(n)
+        keep, ip, ilen, istride = self._sm2_ids(ids, n)
+        keep2, mp, length, stride = self._messages(msgs, n)
+        lp = self._lens_ptr("sm2_verify", lens if length.value else None, n)
+        self._sm2_call("sm2_verify", C.c_int(curve), self._ptr(qx), self._ptr(qy), ip, ilen, istride, mp, length, stride, lp, self._ptr(r), self._ptr(s), self._ptr(ok, 0),
+                       C.c_size_t(n))
+        return ok
+
+    def sm2_sign_digest(self, curve, e, d, k=None, flags=0):
+        """ecsimd_sm2_sign_digest: (r, s, ok) for the digests e under the SECRET keys d and nonces k; k=None: the deterministic nonce (RFC 6979's construction
+        with HMAC-SHA-256 -- SM2 has no standard one; any verifier accepts the signature), made and wiped on the device."""
+        n = int(e.shape[0]); r, s, ok = self.empty(n), self.empty(n), self.flags(n)
+        self._sm2_call("sm2_sign_digest", C.c_int(curve), self._ptr(e), self._ptr(d), self._ptr(k), self._ptr(r), self._ptr(s), self._ptr(ok, 0), C.c_size_t(n), C.c_int(flags))
+        return r, s, ok
+
+    def sm2_sign(self, curve, d, msgs, ids=SM2_DEFAULT_ID, k=None, lens=None):
+        """(r, s, ok, qx, qy): sm2_pubkey, sm2_digest and sm2_sign_digest in a row -- the message-level signature; a lane whose key is refused has ok = 0."""
+        qx, qy, key_ok = self.sm2_pubkey(curve, d)
+        e = self.sm2_digest(curve, qx, qy, msgs, ids=ids, lens=lens)
+        r, s, ok = self.sm2_sign_digest(curve, e, d, k)
+        return r, s, ok, qx, qy
+
     # ---- multi-scalar multiplication (include/ecsimd_msm.h): ONE point out of a batch.  PUBLIC data only.
     MSM_ALG_AUTO, MSM_ALG_BUCKETS, MSM_ALG_LANES = 0, 1, 2
 
