@@ -19,6 +19,7 @@
 #include "../../include/ecsimd_ed25519.h"
 #include "../../include/ecsimd_x25519.h"
 #include "../../include/ecsimd_p384.h"
+#include "../../include/ecsimd_bls12_381.h"
 #include "../../include/ecsimd_sm2.h"
 #include "../../include/ecsimd_msm.h"
 #include "../../include/ecsimd_schnorr_batch.h"
@@ -2726,6 +2727,7 @@ struct msm_schedule {
   ecsimd_msm_plan_t plan;
   size_t T, K, slices, per_window, chunk_lanes, front_lanes;      // BUCKETS: entries, keys, slice lanes, chunks per window, their product with the windows; LANES: the affine tree's lanes
   size_t planes;                                                  // BUCKETS: field elements per point of the sum: 3 (Jacobian) or 4 (extended Edwards); a decoded term has one fewer
+  size_t elem;                                                    // BUCKETS: bytes of a field element in the workspace: 32, or 48 on BLS12-381 (scalars are 32 on every curve)
 };
 // The workspace of a call, carved from `base` (nullptr: sizes only).
 struct msm_blocks {
@@ -2743,8 +2745,9 @@ msm_blocks msm_carve(const msm_schedule& S, size_t n, void* base, size_t* bytes)
     B.start = static_cast<uint32_t*>(carve_bytes(c, round16(4 * (S.K + 1))));
     B.cursor = static_cast<uint32_t*>(carve_bytes(c, round16(4 * S.K)));
     B.sorted = static_cast<uint32_t*>(carve_bytes(c, round16(4 * S.T)));
-    B.kk = carve_limbs(c, n); B.px = carve_limbs(c, n); B.py = carve_limbs(c, (S.planes - 2) * n);
-    B.buckets = carve_limbs(c, S.planes * S.K); B.partial = carve_limbs(c, S.planes * 2 * S.slices); B.tree = carve_limbs(c, S.planes * S.chunk_lanes);
+    const auto elements = [&](size_t m) { return static_cast<uint64_t*>(carve_bytes(c, m * S.elem)); };
+    B.kk = carve_limbs(c, n); B.px = elements(n); B.py = elements((S.planes - 2) * n);
+    B.buckets = elements(S.planes * S.K); B.partial = elements(S.planes * 2 * S.slices); B.tree = elements(S.planes * S.chunk_lanes);
   } else {
     B.zero_bytes = 32;                                  // (32: run_varwin's scratch behind `reserve` stays 32-byte aligned)
     B.counter = static_cast<uint32_t*>(carve_bytes(c, 32));
@@ -2756,11 +2759,11 @@ msm_blocks msm_carve(const msm_schedule& S, size_t n, void* base, size_t* bytes)
   *bytes = c.bytes;
   return B;
 }
-bool msm_schedule_of(size_t n, int bits, int flags, msm_schedule* S, size_t planes = 3) {
+bool msm_schedule_of(size_t n, int bits, int flags, msm_schedule* S, size_t planes = 3, size_t elem = 32) {
   if (bits < 1 || bits > 256 || n > ECSIMD_MSM_MAX_N) return false;
   if (flags != ECSIMD_MSM_ALG_AUTO && flags != ECSIMD_MSM_ALG_BUCKETS && flags != ECSIMD_MSM_ALG_LANES) return false;
   *S = msm_schedule();
-  S->planes = planes;
+  S->planes = planes; S->elem = elem;
   ecsimd_msm_plan_t& P = S->plan;
   P.route = flags != ECSIMD_MSM_ALG_AUTO ? flags : n >= ECSIMD_MSM_AUTO_THRESHOLD ? ECSIMD_MSM_ALG_BUCKETS : ECSIMD_MSM_ALG_LANES;
   if (n == 0) { P.launches = 1; P.max_chain = 0; return true; }                  // the last kernel alone writes the empty sum
@@ -3216,6 +3219,163 @@ int ecsimd_ed25519_msm(ecsimd_hip_ctx* ctx, const uint8_t* k, const uint8_t* pts
   }
   const hipError_t e0 = hipSetDevice(ctx->device); if (e0 != hipSuccess) return fail(ctx, e0, "hipSetDevice");
   return bucket_sum_run(ctx, S, edwards_sum{k, pts, out, nullptr}, finite, invalid, n, bits, 0); }
+
+// ---- BLS12-381 G1 (include/ecsimd_bls12_381.h; k_bls12_381.hip; tools/bls12_381_model.py the definition).  PUBLIC data.  The bucket route is msm_schedule_of's
+// with 48-byte field elements and bucket_sum_run; g1_schedule_of is the ONE place that turns (n, bits, flags) into this group's sizes, the LANES route included
+// (its products need no per-lane table, so its workspace is the counter and one Jacobian array).
+namespace {
+constexpr size_t G1_ELEM = 48;
+bool g1_schedule_of(size_t n, int bits, int flags, msm_schedule* S) {
+  if (flags != ECSIMD_MSM_ALG_AUTO && flags != ECSIMD_MSM_ALG_BUCKETS && flags != ECSIMD_MSM_ALG_LANES) return false;
+  const int route = flags != ECSIMD_MSM_ALG_AUTO ? flags : n >= ECSIMD_BLS12_381_MSM_AUTO_THRESHOLD ? ECSIMD_MSM_ALG_BUCKETS : ECSIMD_MSM_ALG_LANES;
+  if (route == ECSIMD_MSM_ALG_BUCKETS || n == 0) {
+    if (!msm_schedule_of(n, bits, ECSIMD_MSM_ALG_BUCKETS, S, 3, G1_ELEM)) return false;
+    S->plan.route = route;
+    return true;
+  }
+  if (bits < 1 || bits > 256 || n > ECSIMD_MSM_MAX_N) return false;
+  *S = msm_schedule();
+  S->planes = 3; S->elem = G1_ELEM;
+  S->plan.route = ECSIMD_MSM_ALG_LANES;
+  S->plan.max_chain = launch::MSM_TREE_FAN;
+  S->plan.launches = 3 + tree_passes(n);                              // zero, the products, the tree's passes, the last kernel
+  S->plan.workspace_bytes = 16 + 3 * G1_ELEM * n;
+  return true;
+}
+struct g1_sum {
+  using ML = launch::g1_msm_launch;
+  static constexpr const char* what = "bls12_381_g1_msm launch";
+  const uint64_t* k; const uint8_t* pts; uint8_t* out;
+  void digits(hipStream_t s, const msm_blocks& B, size_t n, int bits, int c, int windows) const { ML::digits(s, k, pts, B.kk, B.px, B.py, B.hist, B.counter, n, bits, c, windows); }
+  void slices(hipStream_t s, const msm_blocks& B, size_t n, size_t T, size_t L, size_t slices, int c, size_t K) const {
+    ML::slices(s, B.sorted, B.kk, B.px, B.py, B.start, B.buckets, B.partial, B.counter + 1, n, T, L, slices, c, K);
+  }
+  void finish(hipStream_t s, const uint64_t* arr, size_t total, size_t stride, int windows, int c, const uint32_t* counter, uint8_t* finite, uint32_t* invalid) const {
+    ML::finish(s, arr, total, stride, windows, c, counter, out, finite, invalid);
+  }
+};
+// the counter (16 bytes, zeroed by a kernel) and a Jacobian array of `elements`, from the start of the workspace
+struct g1_tree_layout { uint32_t* counter; uint64_t* tree; size_t bytes; };
+g1_tree_layout g1_tree_plan(void* base, size_t elements) {
+  g1_tree_layout L; carve c = carve_from(base);
+  L.counter = static_cast<uint32_t*>(carve_bytes(c, 16)); L.tree = static_cast<uint64_t*>(carve_bytes(c, 3 * G1_ELEM * elements));
+  L.bytes = c.bytes;
+  return L;
+}
+// the LANES route (k != nullptr: the products of n terms) and the point sum (k == nullptr: the validating affine front over n encodings); n >= 1
+int g1_tree_sum_run(ecsimd_hip_ctx* ctx, const uint64_t* k, const uint8_t* pts, bool compressed, uint8_t* out, uint8_t* finite, uint32_t* invalid, size_t n, int bits) {
+  using ML = launch::g1_msm_launch;
+  hipStream_t s = ctx->stream;
+  const int fan = launch::MSM_TREE_FAN;
+  const size_t elements = k ? n : (n + fan - 1) / fan;
+  const int rc = ensure_workspace(ctx, g1_tree_plan(nullptr, elements).bytes);
+  if (rc != ECSIMD_HIP_OK) return rc;
+  const g1_tree_layout L = g1_tree_plan(ctx->workspace, elements);
+  launch::msm_zero(s, L.counter, 16);
+  if (k) ML::products(s, k, pts, L.counter, L.tree, n, bits);
+  else ML::tree_affine(s, pts, compressed, L.counter, L.tree, n, elements, fan);
+  tree_run<ML>(s, L.tree, elements, elements, 0, 1);
+  ML::finish(s, L.tree, elements, 0, 1, 0, L.counter, out, finite, invalid);
+  const hipError_t e = hipGetLastError();
+  return e == hipSuccess ? ECSIMD_HIP_OK : fail(ctx, e, k ? "bls12_381_g1_msm launch" : "bls12_381_g1_point_sum launch");
+}
+// the single result's outputs against each other and against the inputs (in1 may be null)
+bool g1_result_overlaps(const uint8_t* out, const uint8_t* finite, const uint32_t* invalid, const void* in0, size_t in0_bytes, const void* in1, size_t in1_bytes) {
+  const void* outs[3] = {out, finite, invalid}; const size_t out_bytes[3] = {96, 1, 4};
+  for (int a = 0; a < 3; ++a) {
+    if (ranges_overlap(outs[a], out_bytes[a], in0, in0_bytes) || ranges_overlap(outs[a], out_bytes[a], in1, in1_bytes)) return true;
+    for (int b = a + 1; b < 3; ++b) if (ranges_overlap(outs[a], out_bytes[a], outs[b], out_bytes[b])) return true;
+  }
+  return false;
+}
+// per-lane calls: every output array against every input array and the other outputs, as byte ranges
+struct g1_array { const void* p; size_t bytes; };
+bool g1_arrays_overlap(std::initializer_list<g1_array> outs, std::initializer_list<g1_array> ins) {
+  for (auto a = outs.begin(); a != outs.end(); ++a) {
+    for (const g1_array& b : ins) if (ranges_overlap(a->p, a->bytes, b.p, b.bytes)) return true;
+    for (auto b = a + 1; b != outs.end(); ++b) if (ranges_overlap(a->p, a->bytes, b->p, b->bytes)) return true;
+  }
+  return false;
+}
+}  // namespace
+
+int ecsimd_bls12_381_g1_decompress(ecsimd_hip_ctx* ctx, const uint8_t* in48, uint8_t* out96, uint8_t* ok, size_t n) {
+  REQUIRE_CTX(); if ((!in48 || !out96 || !ok) && n) return bad(ctx, "bls12_381_g1_decompress: in48, out96 or ok is null");
+  if (g1_arrays_overlap({{out96, 96 * n}, {ok, n}}, {{in48, 48 * n}})) return bad(ctx, "bls12_381_g1_decompress: an output must not overlap an input or another output");
+  ENTER();
+  launch::bls381_g1_decompress(ctx->stream, in48, out96, ok, n);
+  const hipError_t e = hipGetLastError();
+  return e == hipSuccess ? ECSIMD_HIP_OK : fail(ctx, e, "bls12_381_g1_decompress launch"); }
+
+int ecsimd_bls12_381_g1_compress(ecsimd_hip_ctx* ctx, const uint8_t* in96, uint8_t* out48, uint8_t* ok, size_t n) {
+  REQUIRE_CTX(); if ((!in96 || !out48 || !ok) && n) return bad(ctx, "bls12_381_g1_compress: in96, out48 or ok is null");
+  if (g1_arrays_overlap({{out48, 48 * n}, {ok, n}}, {{in96, 96 * n}})) return bad(ctx, "bls12_381_g1_compress: an output must not overlap an input or another output");
+  ENTER();
+  launch::bls381_g1_compress(ctx->stream, in96, out48, ok, n);
+  const hipError_t e = hipGetLastError();
+  return e == hipSuccess ? ECSIMD_HIP_OK : fail(ctx, e, "bls12_381_g1_compress launch"); }
+
+int ecsimd_bls12_381_g1_check(ecsimd_hip_ctx* ctx, const uint8_t* in96, uint8_t* on_curve, uint8_t* in_subgroup, size_t n) {
+  REQUIRE_CTX(); if ((!in96 || !on_curve || !in_subgroup) && n) return bad(ctx, "bls12_381_g1_check: in96, on_curve or in_subgroup is null");
+  if (g1_arrays_overlap({{on_curve, n}, {in_subgroup, n}}, {{in96, 96 * n}})) return bad(ctx, "bls12_381_g1_check: an output must not overlap an input or another output");
+  ENTER();
+  launch::bls381_g1_check(ctx->stream, in96, on_curve, in_subgroup, n);
+  const hipError_t e = hipGetLastError();
+  return e == hipSuccess ? ECSIMD_HIP_OK : fail(ctx, e, "bls12_381_g1_check launch"); }
+
+int ecsimd_bls12_381_g1_mul(ecsimd_hip_ctx* ctx, const uint64_t* k, const uint8_t* in96, uint8_t* out96, uint8_t* ok, size_t n) {
+  REQUIRE_CTX(); if ((!k || !in96 || !out96 || !ok) && n) return bad(ctx, "bls12_381_g1_mul: k, in96, out96 or ok is null");
+  if (!aligned16(k)) return bad(ctx, "bls12_381_g1_mul: k is not 16-byte aligned");
+  if (g1_arrays_overlap({{out96, 96 * n}, {ok, n}}, {{k, 32 * n}, {in96, 96 * n}})) return bad(ctx, "bls12_381_g1_mul: an output must not overlap an input or another output");
+  ENTER();
+  launch::bls381_g1_mul(ctx->stream, k, in96, out96, ok, n);
+  const hipError_t e = hipGetLastError();
+  return e == hipSuccess ? ECSIMD_HIP_OK : fail(ctx, e, "bls12_381_g1_mul launch"); }
+
+int ecsimd_bls12_381_g1_msm_plan(size_t n, int bits, int flags, ecsimd_msm_plan_t* out) {
+  msm_schedule S;
+  if (!out || !g1_schedule_of(n, bits, flags, &S)) return ECSIMD_HIP_ERR_BAD_ARG;
+  *out = S.plan;
+  return ECSIMD_HIP_OK; }
+
+int ecsimd_bls12_381_g1_msm(ecsimd_hip_ctx* ctx, const uint64_t* k, const uint8_t* pts96, uint8_t* out96, uint8_t* finite, uint32_t* invalid, size_t n, int bits, int flags) {
+  REQUIRE_CTX();
+  if ((!k || !pts96) && n) return bad(ctx, "bls12_381_g1_msm: k or pts96 is null");
+  if (!out96 || !finite) return bad(ctx, "bls12_381_g1_msm: out96 or finite is null");
+  if (!aligned16(k)) return bad(ctx, "bls12_381_g1_msm: k is not 16-byte aligned");
+  if (invalid && (reinterpret_cast<uintptr_t>(invalid) & 3u)) return bad(ctx, "bls12_381_g1_msm: invalid is not 4-byte aligned");
+  if (bits < 1 || bits > 256) return bad(ctx, "bls12_381_g1_msm: bits must be 1 .. 256");
+  if (n > ECSIMD_MSM_MAX_N) return bad(ctx, "bls12_381_g1_msm: n is above ECSIMD_MSM_MAX_N: chain chunks through ecsimd_bls12_381_g1_point_sum");
+  msm_schedule S;
+  if (!g1_schedule_of(n, bits, flags, &S)) return bad(ctx, "bls12_381_g1_msm: flags must be ECSIMD_MSM_ALG_AUTO, ECSIMD_MSM_ALG_BUCKETS or ECSIMD_MSM_ALG_LANES");
+  if (g1_result_overlaps(out96, finite, invalid, k, 32 * n, pts96, 96 * n)) return bad(ctx, "bls12_381_g1_msm: an output must not overlap an input or another output");
+  const hipError_t e0 = hipSetDevice(ctx->device); if (e0 != hipSuccess) return fail(ctx, e0, "hipSetDevice");
+  if (n == 0 || S.plan.route == ECSIMD_MSM_ALG_BUCKETS) return bucket_sum_run(ctx, S, g1_sum{k, pts96, out96}, finite, invalid, n, bits, 0);
+  return g1_tree_sum_run(ctx, k, pts96, false, out96, finite, invalid, n, bits); }
+
+int ecsimd_bls12_381_g1_point_sum(ecsimd_hip_ctx* ctx, const uint8_t* pts, uint8_t* out96, uint8_t* finite, uint32_t* invalid, size_t n, int flags) {
+  REQUIRE_CTX();
+  if (!pts && n) return bad(ctx, "bls12_381_g1_point_sum: pts is null");
+  if (!out96 || !finite) return bad(ctx, "bls12_381_g1_point_sum: out96 or finite is null");
+  if (invalid && (reinterpret_cast<uintptr_t>(invalid) & 3u)) return bad(ctx, "bls12_381_g1_point_sum: invalid is not 4-byte aligned");
+  if (flags != ECSIMD_BLS12_381_UNCOMPRESSED && flags != ECSIMD_BLS12_381_COMPRESSED) return bad(ctx, "bls12_381_g1_point_sum: flags must be ECSIMD_BLS12_381_UNCOMPRESSED or ECSIMD_BLS12_381_COMPRESSED");
+  const bool compressed = flags == ECSIMD_BLS12_381_COMPRESSED;
+  if ((n + launch::MSM_TREE_FAN - 1) / launch::MSM_TREE_FAN > MAX_LAUNCH) return bad(ctx, "batch too large");
+  if (g1_result_overlaps(out96, finite, invalid, pts, (compressed ? 48 : 96) * n, nullptr, 0)) return bad(ctx, "bls12_381_g1_point_sum: an output must not overlap an input or another output");
+  const hipError_t e0 = hipSetDevice(ctx->device); if (e0 != hipSuccess) return fail(ctx, e0, "hipSetDevice");
+  if (n == 0) return bucket_sum_run(ctx, msm_schedule(), g1_sum{nullptr, nullptr, out96}, finite, invalid, 0, 1, 0);     // the empty sum: the last kernel alone
+  return g1_tree_sum_run(ctx, nullptr, pts, compressed, out96, finite, invalid, n, 0); }
+
+int ecsimd_bls12_381_raw_inputs(int op) { return (op < 0 || op > launch::BLS381_RAW_POINT_MADD) ? 0 : launch::bls381_raw_inputs(op); }
+int ecsimd_bls12_381_raw_outputs(int op) { return (op < 0 || op > launch::BLS381_RAW_POINT_MADD) ? 0 : launch::bls381_raw_outputs(op); }
+int ecsimd_bls12_381_raw(ecsimd_hip_ctx* ctx, int op, const uint8_t* in, uint8_t* out, size_t n) {
+  REQUIRE_CTX(); if ((!in || !out) && n) return bad(ctx, "bls12_381_raw: null pointer");
+  if (op < 0 || op > launch::BLS381_RAW_POINT_MADD) return bad(ctx, "bls12_381_raw: unknown function");
+  if (ranges_overlap(in, 48 * (size_t)launch::bls381_raw_inputs(op) * n, out, 48 * (size_t)launch::bls381_raw_outputs(op) * n)) return bad(ctx, "bls12_381_raw: out must not overlap in");
+  ENTER();
+  launch::bls381_raw(ctx->stream, op, in, out, n);
+  const hipError_t e = hipGetLastError();
+  return e == hipSuccess ? ECSIMD_HIP_OK : fail(ctx, e, "bls12_381_raw launch"); }
 
 int ecsimd_ed25519_verify_cofactored(ecsimd_hip_ctx* ctx, const uint8_t* pk, const uint8_t* msg, size_t msg_bytes, size_t stride_bytes, const uint32_t* lens,
                                      const uint8_t* sig, uint8_t* ok, size_t n, int flags) {
