@@ -20,6 +20,7 @@
 #include "../../include/ecsimd_x25519.h"
 #include "../../include/ecsimd_p384.h"
 #include "../../include/ecsimd_bls12_381.h"
+#include "../../include/ecsimd_bls12_381_g2.h"
 #include "../../include/ecsimd_sm2.h"
 #include "../../include/ecsimd_msm.h"
 #include "../../include/ecsimd_schnorr_batch.h"
@@ -3376,6 +3377,148 @@ int ecsimd_bls12_381_raw(ecsimd_hip_ctx* ctx, int op, const uint8_t* in, uint8_t
   launch::bls381_raw(ctx->stream, op, in, out, n);
   const hipError_t e = hipGetLastError();
   return e == hipSuccess ? ECSIMD_HIP_OK : fail(ctx, e, "bls12_381_raw launch"); }
+
+// ---- BLS12-381 G2 (include/ecsimd_bls12_381_g2.h; k_bls12_381_g2.hip; tools/bls12_381_g2_model.py the definition).  PUBLIC data.  G1's host layer with the
+// widths changed: 96-byte workspace elements (an Fp2 value), 192- and 96-byte encodings.  g2_schedule_of is the ONE place that turns (n, bits, flags) into this
+// group's sizes; g2_sum is the fourth sum type of bucket_sum_run.
+namespace {
+constexpr size_t G2_ELEM = 96;
+bool g2_schedule_of(size_t n, int bits, int flags, msm_schedule* S) {
+  if (flags != ECSIMD_MSM_ALG_AUTO && flags != ECSIMD_MSM_ALG_BUCKETS && flags != ECSIMD_MSM_ALG_LANES) return false;
+  const int route = flags != ECSIMD_MSM_ALG_AUTO ? flags : n >= ECSIMD_BLS381_G2_MSM_AUTO_THRESHOLD ? ECSIMD_MSM_ALG_BUCKETS : ECSIMD_MSM_ALG_LANES;
+  if (route == ECSIMD_MSM_ALG_BUCKETS || n == 0) {
+    if (!msm_schedule_of(n, bits, ECSIMD_MSM_ALG_BUCKETS, S, 3, G2_ELEM)) return false;
+    S->plan.route = route;
+    return true;
+  }
+  if (bits < 1 || bits > 256 || n > ECSIMD_MSM_MAX_N) return false;
+  *S = msm_schedule();
+  S->planes = 3; S->elem = G2_ELEM;
+  S->plan.route = ECSIMD_MSM_ALG_LANES;
+  S->plan.max_chain = launch::MSM_TREE_FAN;
+  S->plan.launches = 3 + tree_passes(n);                              // zero, the products, the tree's passes, the last kernel
+  S->plan.workspace_bytes = 16 + 3 * G2_ELEM * n;
+  return true;
+}
+struct g2_sum {
+  using ML = launch::g2_msm_launch;
+  static constexpr const char* what = "bls381_g2_msm launch";
+  const uint64_t* k; const uint8_t* pts; uint8_t* out;
+  void digits(hipStream_t s, const msm_blocks& B, size_t n, int bits, int c, int windows) const { ML::digits(s, k, pts, B.kk, B.px, B.py, B.hist, B.counter, n, bits, c, windows); }
+  void slices(hipStream_t s, const msm_blocks& B, size_t n, size_t T, size_t L, size_t slices, int c, size_t K) const {
+    ML::slices(s, B.sorted, B.kk, B.px, B.py, B.start, B.buckets, B.partial, B.counter + 1, n, T, L, slices, c, K);
+  }
+  void finish(hipStream_t s, const uint64_t* arr, size_t total, size_t stride, int windows, int c, const uint32_t* counter, uint8_t* finite, uint32_t* invalid) const {
+    ML::finish(s, arr, total, stride, windows, c, counter, out, finite, invalid);
+  }
+};
+// the counter (16 bytes, zeroed by a kernel) and a Jacobian array of `elements`, from the start of the workspace
+g1_tree_layout g2_tree_plan(void* base, size_t elements) {
+  g1_tree_layout L; carve c = carve_from(base);
+  L.counter = static_cast<uint32_t*>(carve_bytes(c, 16)); L.tree = static_cast<uint64_t*>(carve_bytes(c, 3 * G2_ELEM * elements));
+  L.bytes = c.bytes;
+  return L;
+}
+// the LANES route (k != nullptr: the products of n terms) and the point sum (k == nullptr: the validating affine front over n encodings); n >= 1
+int g2_tree_sum_run(ecsimd_hip_ctx* ctx, const uint64_t* k, const uint8_t* pts, bool compressed, uint8_t* out, uint8_t* finite, uint32_t* invalid, size_t n, int bits) {
+  using ML = launch::g2_msm_launch;
+  hipStream_t s = ctx->stream;
+  const int fan = launch::MSM_TREE_FAN;
+  const size_t elements = k ? n : (n + fan - 1) / fan;
+  const int rc = ensure_workspace(ctx, g2_tree_plan(nullptr, elements).bytes);
+  if (rc != ECSIMD_HIP_OK) return rc;
+  const g1_tree_layout L = g2_tree_plan(ctx->workspace, elements);
+  launch::msm_zero(s, L.counter, 16);
+  if (k) ML::products(s, k, pts, L.counter, L.tree, n, bits);
+  else ML::tree_affine(s, pts, compressed, L.counter, L.tree, n, elements, fan);
+  tree_run<ML>(s, L.tree, elements, elements, 0, 1);
+  ML::finish(s, L.tree, elements, 0, 1, 0, L.counter, out, finite, invalid);
+  const hipError_t e = hipGetLastError();
+  return e == hipSuccess ? ECSIMD_HIP_OK : fail(ctx, e, k ? "bls381_g2_msm launch" : "bls381_g2_point_sum launch");
+}
+// the single result's outputs against each other and against the inputs (in1 may be null)
+bool g2_result_overlaps(const uint8_t* out, const uint8_t* finite, const uint32_t* invalid, const void* in0, size_t in0_bytes, const void* in1, size_t in1_bytes) {
+  return g1_arrays_overlap({{out, 192}, {finite, 1}, {invalid, 4}}, {{in0, in0_bytes}, {in1, in1_bytes}});
+}
+}  // namespace
+
+int ecsimd_bls381_g2_decompress(ecsimd_hip_ctx* ctx, const uint8_t* in96, uint8_t* out192, uint8_t* ok, size_t n) {
+  REQUIRE_CTX(); if ((!in96 || !out192 || !ok) && n) return bad(ctx, "bls381_g2_decompress: in96, out192 or ok is null");
+  if (g1_arrays_overlap({{out192, 192 * n}, {ok, n}}, {{in96, 96 * n}})) return bad(ctx, "bls381_g2_decompress: an output must not overlap an input or another output");
+  ENTER();
+  launch::bls381_g2_decompress(ctx->stream, in96, out192, ok, n);
+  const hipError_t e = hipGetLastError();
+  return e == hipSuccess ? ECSIMD_HIP_OK : fail(ctx, e, "bls381_g2_decompress launch"); }
+
+int ecsimd_bls381_g2_compress(ecsimd_hip_ctx* ctx, const uint8_t* in192, uint8_t* out96, uint8_t* ok, size_t n) {
+  REQUIRE_CTX(); if ((!in192 || !out96 || !ok) && n) return bad(ctx, "bls381_g2_compress: in192, out96 or ok is null");
+  if (g1_arrays_overlap({{out96, 96 * n}, {ok, n}}, {{in192, 192 * n}})) return bad(ctx, "bls381_g2_compress: an output must not overlap an input or another output");
+  ENTER();
+  launch::bls381_g2_compress(ctx->stream, in192, out96, ok, n);
+  const hipError_t e = hipGetLastError();
+  return e == hipSuccess ? ECSIMD_HIP_OK : fail(ctx, e, "bls381_g2_compress launch"); }
+
+int ecsimd_bls381_g2_check(ecsimd_hip_ctx* ctx, const uint8_t* in192, uint8_t* on_curve, uint8_t* in_subgroup, size_t n) {
+  REQUIRE_CTX(); if ((!in192 || !on_curve || !in_subgroup) && n) return bad(ctx, "bls381_g2_check: in192, on_curve or in_subgroup is null");
+  if (g1_arrays_overlap({{on_curve, n}, {in_subgroup, n}}, {{in192, 192 * n}})) return bad(ctx, "bls381_g2_check: an output must not overlap an input or another output");
+  ENTER();
+  launch::bls381_g2_check(ctx->stream, in192, on_curve, in_subgroup, n);
+  const hipError_t e = hipGetLastError();
+  return e == hipSuccess ? ECSIMD_HIP_OK : fail(ctx, e, "bls381_g2_check launch"); }
+
+int ecsimd_bls381_g2_mul(ecsimd_hip_ctx* ctx, const uint64_t* k, const uint8_t* in192, uint8_t* out192, uint8_t* ok, size_t n) {
+  REQUIRE_CTX(); if ((!k || !in192 || !out192 || !ok) && n) return bad(ctx, "bls381_g2_mul: k, in192, out192 or ok is null");
+  if (!aligned16(k)) return bad(ctx, "bls381_g2_mul: k is not 16-byte aligned");
+  if (g1_arrays_overlap({{out192, 192 * n}, {ok, n}}, {{k, 32 * n}, {in192, 192 * n}})) return bad(ctx, "bls381_g2_mul: an output must not overlap an input or another output");
+  ENTER();
+  launch::bls381_g2_mul(ctx->stream, k, in192, out192, ok, n);
+  const hipError_t e = hipGetLastError();
+  return e == hipSuccess ? ECSIMD_HIP_OK : fail(ctx, e, "bls381_g2_mul launch"); }
+
+int ecsimd_bls381_g2_msm_plan(size_t n, int bits, int flags, ecsimd_msm_plan_t* out) {
+  msm_schedule S;
+  if (!out || !g2_schedule_of(n, bits, flags, &S)) return ECSIMD_HIP_ERR_BAD_ARG;
+  *out = S.plan;
+  return ECSIMD_HIP_OK; }
+
+int ecsimd_bls381_g2_msm(ecsimd_hip_ctx* ctx, const uint64_t* k, const uint8_t* pts192, uint8_t* out192, uint8_t* finite, uint32_t* invalid, size_t n, int bits, int flags) {
+  REQUIRE_CTX();
+  if ((!k || !pts192) && n) return bad(ctx, "bls381_g2_msm: k or pts192 is null");
+  if (!out192 || !finite) return bad(ctx, "bls381_g2_msm: out192 or finite is null");
+  if (!aligned16(k)) return bad(ctx, "bls381_g2_msm: k is not 16-byte aligned");
+  if (invalid && (reinterpret_cast<uintptr_t>(invalid) & 3u)) return bad(ctx, "bls381_g2_msm: invalid is not 4-byte aligned");
+  if (bits < 1 || bits > 256) return bad(ctx, "bls381_g2_msm: bits must be 1 .. 256");
+  if (n > ECSIMD_MSM_MAX_N) return bad(ctx, "bls381_g2_msm: n is above ECSIMD_MSM_MAX_N: chain chunks through ecsimd_bls381_g2_point_sum");
+  msm_schedule S;
+  if (!g2_schedule_of(n, bits, flags, &S)) return bad(ctx, "bls381_g2_msm: flags must be ECSIMD_MSM_ALG_AUTO, ECSIMD_MSM_ALG_BUCKETS or ECSIMD_MSM_ALG_LANES");
+  if (g2_result_overlaps(out192, finite, invalid, k, 32 * n, pts192, 192 * n)) return bad(ctx, "bls381_g2_msm: an output must not overlap an input or another output");
+  const hipError_t e0 = hipSetDevice(ctx->device); if (e0 != hipSuccess) return fail(ctx, e0, "hipSetDevice");
+  if (n == 0 || S.plan.route == ECSIMD_MSM_ALG_BUCKETS) return bucket_sum_run(ctx, S, g2_sum{k, pts192, out192}, finite, invalid, n, bits, 0);
+  return g2_tree_sum_run(ctx, k, pts192, false, out192, finite, invalid, n, bits); }
+
+int ecsimd_bls381_g2_point_sum(ecsimd_hip_ctx* ctx, const uint8_t* pts, uint8_t* out192, uint8_t* finite, uint32_t* invalid, size_t n, int flags) {
+  REQUIRE_CTX();
+  if (!pts && n) return bad(ctx, "bls381_g2_point_sum: pts is null");
+  if (!out192 || !finite) return bad(ctx, "bls381_g2_point_sum: out192 or finite is null");
+  if (invalid && (reinterpret_cast<uintptr_t>(invalid) & 3u)) return bad(ctx, "bls381_g2_point_sum: invalid is not 4-byte aligned");
+  if (flags != ECSIMD_BLS381_G2_UNCOMPRESSED && flags != ECSIMD_BLS381_G2_COMPRESSED) return bad(ctx, "bls381_g2_point_sum: flags must be ECSIMD_BLS381_G2_UNCOMPRESSED or ECSIMD_BLS381_G2_COMPRESSED");
+  const bool compressed = flags == ECSIMD_BLS381_G2_COMPRESSED;
+  if ((n + launch::MSM_TREE_FAN - 1) / launch::MSM_TREE_FAN > MAX_LAUNCH) return bad(ctx, "batch too large");
+  if (g2_result_overlaps(out192, finite, invalid, pts, (compressed ? 96 : 192) * n, nullptr, 0)) return bad(ctx, "bls381_g2_point_sum: an output must not overlap an input or another output");
+  const hipError_t e0 = hipSetDevice(ctx->device); if (e0 != hipSuccess) return fail(ctx, e0, "hipSetDevice");
+  if (n == 0) return bucket_sum_run(ctx, msm_schedule(), g2_sum{nullptr, nullptr, out192}, finite, invalid, 0, 1, 0);     // the empty sum: the last kernel alone
+  return g2_tree_sum_run(ctx, nullptr, pts, compressed, out192, finite, invalid, n, 0); }
+
+int ecsimd_bls381_g2_raw_inputs(int op) { return (op < 0 || op > launch::BLS381_G2_RAW_POINT_MADD) ? 0 : launch::bls381_g2_raw_inputs(op); }
+int ecsimd_bls381_g2_raw_outputs(int op) { return (op < 0 || op > launch::BLS381_G2_RAW_POINT_MADD) ? 0 : launch::bls381_g2_raw_outputs(op); }
+int ecsimd_bls381_g2_raw(ecsimd_hip_ctx* ctx, int op, const uint8_t* in, uint8_t* out, size_t n) {
+  REQUIRE_CTX(); if ((!in || !out) && n) return bad(ctx, "bls381_g2_raw: null pointer");
+  if (op < 0 || op > launch::BLS381_G2_RAW_POINT_MADD) return bad(ctx, "bls381_g2_raw: unknown function");
+  if (ranges_overlap(in, 48 * (size_t)launch::bls381_g2_raw_inputs(op) * n, out, 48 * (size_t)launch::bls381_g2_raw_outputs(op) * n)) return bad(ctx, "bls381_g2_raw: out must not overlap in");
+  ENTER();
+  launch::bls381_g2_raw(ctx->stream, op, in, out, n);
+  const hipError_t e = hipGetLastError();
+  return e == hipSuccess ? ECSIMD_HIP_OK : fail(ctx, e, "bls381_g2_raw launch"); }
 
 int ecsimd_ed25519_verify_cofactored(ecsimd_hip_ctx* ctx, const uint8_t* pk, const uint8_t* msg, size_t msg_bytes, size_t stride_bytes, const uint32_t* lens,
                                      const uint8_t* sig, uint8_t* ok, size_t n, int flags) {

@@ -421,6 +421,37 @@ struct g1_msm_launch {                           // msm_launch's shape: capi.hip
   static void products(hipStream_t, const uint64_t* k, const uint8_t* pts96, uint32_t* counter, uint64_t* out, size_t n, int bits);
   static void finish(hipStream_t, const uint64_t* arr, size_t total, size_t stride, int windows, int c, const uint32_t* counter, uint8_t* out96, uint8_t* finite, uint32_t* invalid);
 };
+// k_bls12_381_g2.hip: BLS12-381 G2 (include/ecsimd_bls12_381_g2.h; fp2.cuh, g2.cuh; PUBLIC data).  Every launcher enqueues ONE kernel.  Points cross as the standard
+// 192-byte (pts192) or 96-byte encodings at any alignment, scalars as n x 8 words, 16-byte aligned.  An Fp2 element in the workspace is 96 bytes: c0 then c1, each
+// twelve little-endian words in Montgomery form, element e of an array at byte 96 e; a Jacobian array of `total` elements is X, Y, Z one behind the other, Z = 0 the
+// identity; px, py = the decoded terms' x and y (n elements each).  Raw records are 48 bytes; an Fp2 operand is TWO records, c0 then c1.
+enum bls381_g2_raw_op { BLS381_G2_RAW_FE2_MUL = 0, BLS381_G2_RAW_FE2_SQR = 1, BLS381_G2_RAW_FE2_ADD = 2, BLS381_G2_RAW_FE2_SUB = 3, BLS381_G2_RAW_FE2_NEG = 4,
+                        BLS381_G2_RAW_FE2_INVERT = 5, BLS381_G2_RAW_FE2_SQRT = 6, BLS381_G2_RAW_FE2_CANON = 7, BLS381_G2_RAW_POINT_ADD = 8, BLS381_G2_RAW_POINT_DBL = 9,
+                        BLS381_G2_RAW_POINT_MADD = 10 };
+constexpr int bls381_g2_raw_inputs(int op) {
+  return op == BLS381_G2_RAW_POINT_ADD ? 10 : op == BLS381_G2_RAW_POINT_MADD ? 9 : op == BLS381_G2_RAW_POINT_DBL ? 5
+       : (op == BLS381_G2_RAW_FE2_MUL || op == BLS381_G2_RAW_FE2_ADD || op == BLS381_G2_RAW_FE2_SUB) ? 4 : 2;
+}
+constexpr int bls381_g2_raw_outputs(int op) { return op >= BLS381_G2_RAW_POINT_ADD ? 5 : op == BLS381_G2_RAW_FE2_SQRT ? 3 : 2; }
+void bls381_g2_decompress(hipStream_t, const uint8_t* in96, uint8_t* out192, uint8_t* ok, size_t n);
+void bls381_g2_compress(hipStream_t, const uint8_t* in192, uint8_t* out96, uint8_t* ok, size_t n);
+void bls381_g2_check(hipStream_t, const uint8_t* in192, uint8_t* on_curve, uint8_t* in_subgroup, size_t n);
+void bls381_g2_mul(hipStream_t, const uint64_t* k, const uint8_t* in192, uint8_t* out192, uint8_t* ok, size_t n);
+void bls381_g2_raw(hipStream_t, int op, const uint8_t* in, uint8_t* out, size_t n);
+struct g2_msm_launch {                           // g1_msm_launch's shape with the widths changed
+  static void digits(hipStream_t, const uint64_t* k, const uint8_t* pts192, uint64_t* kk, uint64_t* px, uint64_t* py, uint32_t* hist, uint32_t* counter, size_t n, int bits, int c,
+                     int windows);
+  static void slices(hipStream_t, const uint32_t* sorted, const uint64_t* kk, const uint64_t* px, const uint64_t* py, const uint32_t* start, uint64_t* buckets, uint64_t* partial,
+                     uint32_t* broken, size_t n, size_t T, size_t L, size_t slices, int c, size_t K);
+  static void combine(hipStream_t, const uint32_t* start, uint64_t* buckets, const uint64_t* partial, uint32_t* broken, size_t L, size_t slices, int c, size_t K);
+  static void chunks(hipStream_t, const uint64_t* buckets, uint64_t* out, size_t lanes, size_t per_window, int c, int m, size_t K);
+  static void tree(hipStream_t, uint64_t* arr, size_t total, size_t count, size_t stride, size_t groups, size_t lanes, int fan);
+  // out[g] = the sum of the valid points g, g + lanes, ... (fan of them) of n encodings, 96 bytes each where compressed; malformed ones are counted and skipped
+  static void tree_affine(hipStream_t, const uint8_t* pts, bool compressed, uint32_t* counter, uint64_t* out, size_t n, size_t lanes, int fan);
+  // the LANES route's front: out[i] = (k[i] mod 2^bits) P[i] as a Jacobian array of n; a malformed point is counted and gives the identity
+  static void products(hipStream_t, const uint64_t* k, const uint8_t* pts192, uint32_t* counter, uint64_t* out, size_t n, int bits);
+  static void finish(hipStream_t, const uint64_t* arr, size_t total, size_t stride, int windows, int c, const uint32_t* counter, uint8_t* out192, uint8_t* finite, uint32_t* invalid);
+};
 // front: h = SHA-512(R || A || M) mod L, leaf, A and R copied to Aenc / Renc, valid = s < L (&& no small-order A or R); a lane that is not valid counts in
 // head->malformed.  node / seed: schnorr_batch's shapes under this call's tags.  scalars: z, and where zh is given z h mod L and z s mod L (0 where not valid).
 // sum: out[j] = sum of in[16 j ..] mod L; with benc (count <= 16): out[0] = L - sum (0 stays 0) and benc[0] = B's encoding.  accept: ok[0] from head.

@@ -54,6 +54,13 @@ def declared_bls12_381_symbols():
     return sorted(set(re.findall(r"\b(ecsimd_bls12_381_[a-z0-9_]+)\s*\(", open(hdr).read())))
 
 
+def declared_bls12_381_g2_symbols():
+    """Every function name declared in include/ecsimd_bls12_381_g2.h (parsed from the header): the ecsimd_bls381_g2_* set."""
+    import re
+    hdr = os.path.join(os.path.dirname(_HERE), "include", "ecsimd_bls12_381_g2.h")
+    return sorted(set(re.findall(r"\b(ecsimd_bls381_g2_[a-z0-9_]+)\s*\(", open(hdr).read())))
+
+
 def load_library() -> C.CDLL:
     path = lib_path()
     if not os.path.exists(path):
@@ -765,6 +772,88 @@ class Engine:
         out = self._u8_out(n, 48 * no)
         self._bind_stream()
         self._check(self.lib.ecsimd_bls12_381_raw(self.ctx, C.c_int(op), ip, C.c_void_p(out.data_ptr() if n else 0), C.c_size_t(n)), "bls12_381_raw")
+        return out
+
+    # ---- BLS12-381 G2 (include/ecsimd_bls12_381_g2.h): points are the standard 192-byte (uncompressed) or 96-byte (compressed) encodings, c1 before c0.  PUBLIC
+    # data only.  Scalars and the sums' outputs are shaped like the G1 methods'.
+    (BLS12_381_G2_RAW_FE2_MUL, BLS12_381_G2_RAW_FE2_SQR, BLS12_381_G2_RAW_FE2_ADD, BLS12_381_G2_RAW_FE2_SUB, BLS12_381_G2_RAW_FE2_NEG, BLS12_381_G2_RAW_FE2_INVERT,
+     BLS12_381_G2_RAW_FE2_SQRT, BLS12_381_G2_RAW_FE2_CANON, BLS12_381_G2_RAW_POINT_ADD, BLS12_381_G2_RAW_POINT_DBL, BLS12_381_G2_RAW_POINT_MADD) = range(11)
+
+    def bls12_381_g2_decompress(self, in96):
+        """ecsimd_bls381_g2_decompress: (out192, ok) for (n, 96) uint8 compressed points; a malformed lane gets zeros and ok = 0.  On-curve only."""
+        return self._bls12_381_lanes(self.lib.ecsimd_bls381_g2_decompress, "bls381_g2_decompress", in96, 96, (192, 1))
+
+    def bls12_381_g2_compress(self, in192):
+        """ecsimd_bls381_g2_compress: (out96, ok) for (n, 192) uint8 uncompressed points, validated the same way."""
+        return self._bls12_381_lanes(self.lib.ecsimd_bls381_g2_compress, "bls381_g2_compress", in192, 192, (96, 1))
+
+    def bls12_381_g2_check(self, in192):
+        """ecsimd_bls381_g2_check: (on_curve, in_subgroup), one byte per lane each; in_subgroup is [r] Q = infinity."""
+        return self._bls12_381_lanes(self.lib.ecsimd_bls381_g2_check, "bls381_g2_check", in192, 192, (1, 1))
+
+    def bls12_381_g2_mul(self, k, in192):
+        """ecsimd_bls381_g2_mul: (out192, ok), k[i] Q[i] for the 256-bit INTEGERS k ((n, 4) limbs or (n, 32) uint8 little-endian) and the validated points."""
+        keep, kp, n = self._bls12_381_scalars(k, "bls381_g2_mul")
+        ip, n2 = self._rows_u8(in192, 192, "in192")
+        if n2 != n:
+            raise EcsimdHipError(f"bls381_g2_mul: operands disagree on the batch length: {sorted((n, n2))}")
+        out, ok = self._u8_out(n, 192), self.flags(n)
+        self._bind_stream()
+        self._check(self.lib.ecsimd_bls381_g2_mul(self.ctx, kp, ip, C.c_void_p(out.data_ptr() if n else 0), C.c_void_p(ok.data_ptr() if n else 0), C.c_size_t(n)), "bls381_g2_mul")
+        return out, ok
+
+    @staticmethod
+    def bls12_381_g2_msm_plan(n, bits=255, alg=0):
+        """ecsimd_bls381_g2_msm_plan: msm_plan's dict for bls12_381_g2_msm (the same bucket schedule, this group's workspace_bytes and LANES route).  Host only."""
+        plan = MsmPlan()
+        rc = load_library().ecsimd_bls381_g2_msm_plan(C.c_size_t(n), C.c_int(bits), C.c_int(alg), C.byref(plan))
+        if rc != 0:
+            raise EcsimdHipError(f"bls381_g2_msm_plan(n={n}, bits={bits}, alg={alg}) failed ({rc}): bits must be 1 .. 256, n at most 2^24, alg 0, 1 or 2")
+        return {name: int(getattr(plan, name)) for name, _ in MsmPlan._fields_}
+
+    def _bls12_381_g2_sum_out(self, want_invalid):
+        torch = self.torch
+        out = torch.zeros((192,), dtype=torch.uint8, device=self.tdev)
+        finite = torch.zeros((1,), dtype=torch.uint8, device=self.tdev)
+        invalid = torch.zeros((1,), dtype=torch.int32, device=self.tdev) if want_invalid else None
+        return out, finite, invalid
+
+    def bls12_381_g2_msm(self, k, pts192, bits=255, alg=0, want_invalid=False):
+        """ecsimd_bls381_g2_msm: (out192, finite) = the (192,) uint8 encoding of the sum of (k[i] mod 2^bits) Q[i] and a (1,) uint8 flag (0 and the infinity
+        encoding for the identity).  k as bls12_381_g2_mul's; pts192: (n, 192) uint8.  A malformed point contributes nothing; want_invalid: a third tensor, the
+        (1,) int32 number of them.  Points are NOT tested for subgroup membership.  Capturable after one warm-up call at the same (n, bits, alg)."""
+        keep, kp, n = self._bls12_381_scalars(k, "bls381_g2_msm")
+        pp, n2 = self._rows_u8(pts192, 192, "pts192")
+        if n2 != n:
+            raise EcsimdHipError(f"bls381_g2_msm: operands disagree on the batch length: {sorted((n, n2))}")
+        out, finite, invalid = self._bls12_381_g2_sum_out(want_invalid)
+        self._bind_stream()
+        self._check(self.lib.ecsimd_bls381_g2_msm(self.ctx, kp, pp, C.c_void_p(out.data_ptr()), C.c_void_p(finite.data_ptr()), C.c_void_p(invalid.data_ptr() if want_invalid else 0),
+                                                  C.c_size_t(n), C.c_int(bits), C.c_int(alg)), "bls381_g2_msm")
+        return (out, finite, invalid) if want_invalid else (out, finite)
+
+    def bls12_381_g2_point_sum(self, pts, want_invalid=False):
+        """ecsimd_bls381_g2_point_sum: (out192, finite) = the sum of the points; pts is (n, 192) uint8 uncompressed or (n, 96) uint8 compressed (the width
+        decides).  Malformed points are skipped and counted (want_invalid)."""
+        assert pts.dim() == 2 and int(pts.shape[1]) in (96, 192), tuple(pts.shape)
+        width = int(pts.shape[1])
+        pp, n = self._rows_u8(pts, width, "pts")
+        out, finite, invalid = self._bls12_381_g2_sum_out(want_invalid)
+        self._bind_stream()
+        self._check(self.lib.ecsimd_bls381_g2_point_sum(self.ctx, pp, C.c_void_p(out.data_ptr()), C.c_void_p(finite.data_ptr()), C.c_void_p(invalid.data_ptr() if want_invalid else 0),
+                                                        C.c_size_t(n), C.c_int(1 if width == 96 else 0)), "bls381_g2_point_sum")
+        return (out, finite, invalid) if want_invalid else (out, finite)
+
+    def bls12_381_g2_raw(self, op, records):
+        """ecsimd_bls381_g2_raw: one function of the layers below on (n, 48 * inputs) uint8 records (an Fp2 operand is two records, c0 then c1); returns
+        (n, 48 * outputs) uint8 (see the header's table)."""
+        ni, no = int(self.lib.ecsimd_bls381_g2_raw_inputs(C.c_int(op))), int(self.lib.ecsimd_bls381_g2_raw_outputs(C.c_int(op)))
+        if ni == 0:
+            raise EcsimdHipError(f"bls381_g2_raw: unknown function {op}")
+        ip, n = self._rows_u8(records, 48 * ni, "records")
+        out = self._u8_out(n, 48 * no)
+        self._bind_stream()
+        self._check(self.lib.ecsimd_bls381_g2_raw(self.ctx, C.c_int(op), ip, C.c_void_p(out.data_ptr() if n else 0), C.c_size_t(n)), "bls381_g2_raw")
         return out
 
     # ---- the SM2 signature scheme (include/ecsimd_sm2.h): integers are (n, 4) limb tensors as the ECDSA methods take them, digests likewise
