@@ -7,6 +7,7 @@
 // of its bandwidth.
 #include <hip/hip_runtime.h>
 #include <math.h>
+#include <stdarg.h>
 #include <stdint.h>
 #include <stdio.h>
 #include <string.h>
@@ -3221,304 +3222,209 @@ int ecsimd_ed25519_msm(ecsimd_hip_ctx* ctx, const uint8_t* k, const uint8_t* pts
   const hipError_t e0 = hipSetDevice(ctx->device); if (e0 != hipSuccess) return fail(ctx, e0, "hipSetDevice");
   return bucket_sum_run(ctx, S, edwards_sum{k, pts, out, nullptr}, finite, invalid, n, bits, 0); }
 
-// ---- BLS12-381 G1 (include/ecsimd_bls12_381.h; k_bls12_381.hip; tools/bls12_381_model.py the definition).  PUBLIC data.  The bucket route is msm_schedule_of's
-// with 48-byte field elements and bucket_sum_run; g1_schedule_of is the ONE place that turns (n, bits, flags) into this group's sizes, the LANES route included
-// (its products need no per-lane table, so its workspace is the counter and one Jacobian array).
+// ---- BLS12-381 G1 and G2 (include/ecsimd_bls12_381.h, include/ecsimd_bls12_381_g2.h; k_bls12_381.inc as k_bls12_381.hip and k_bls12_381_g2.hip;
+// tools/bls12_381_model.py and tools/bls12_381_g2_model.py the definitions).  PUBLIC data.  ONE host layer over what a group's sizes are: bls381_g1 and bls381_g2
+// below.  A field element is ELEM bytes in the workspace and compressed, a point 2 ELEM bytes uncompressed.  The bucket route is msm_schedule_of's with ELEM-byte
+// field elements and bucket_sum_run; bls381_schedule_of is the ONE place that turns (n, bits, flags) into a group's sizes, the LANES route included (its products
+// need no per-lane table, so its workspace is the counter and one Jacobian array).  The messages spell the widths out: "in48, out96" for G1, "in96, out192" for G2.
+extern "C++" {
 namespace {
-constexpr size_t G1_ELEM = 48;
-bool g1_schedule_of(size_t n, int bits, int flags, msm_schedule* S) {
+struct bls381_g1 {
+  using ML = launch::bls381_launch<g1_curve>;
+  static constexpr size_t ELEM = 48, AUTO_THRESHOLD = ECSIMD_BLS12_381_MSM_AUTO_THRESHOLD;
+  static constexpr const char *name = "bls12_381_g1", *raw_name = "bls12_381_raw", *flag_stem = "ECSIMD_BLS12_381", *msm_launch = "bls12_381_g1_msm launch";
+};
+struct bls381_g2 {
+  using ML = launch::bls381_launch<g2_curve>;
+  static constexpr size_t ELEM = 96, AUTO_THRESHOLD = ECSIMD_BLS381_G2_MSM_AUTO_THRESHOLD;
+  static constexpr const char *name = "bls381_g2", *raw_name = "bls381_g2_raw", *flag_stem = "ECSIMD_BLS381_G2", *msm_launch = "bls381_g2_msm launch";
+};
+// a message put together from a group's names and widths, for bad() and fail()
+struct text { char s[200]; operator const char*() const { return s; } };
+__attribute__((format(printf, 1, 2))) text textf(const char* fmt, ...) {
+  text t; va_list ap;
+  va_start(ap, fmt); vsnprintf(t.s, sizeof t.s, fmt, ap); va_end(ap);
+  return t;
+}
+template <class T> bool bls381_schedule_of(size_t n, int bits, int flags, msm_schedule* S) {
   if (flags != ECSIMD_MSM_ALG_AUTO && flags != ECSIMD_MSM_ALG_BUCKETS && flags != ECSIMD_MSM_ALG_LANES) return false;
-  const int route = flags != ECSIMD_MSM_ALG_AUTO ? flags : n >= ECSIMD_BLS12_381_MSM_AUTO_THRESHOLD ? ECSIMD_MSM_ALG_BUCKETS : ECSIMD_MSM_ALG_LANES;
+  const int route = flags != ECSIMD_MSM_ALG_AUTO ? flags : n >= T::AUTO_THRESHOLD ? ECSIMD_MSM_ALG_BUCKETS : ECSIMD_MSM_ALG_LANES;
   if (route == ECSIMD_MSM_ALG_BUCKETS || n == 0) {
-    if (!msm_schedule_of(n, bits, ECSIMD_MSM_ALG_BUCKETS, S, 3, G1_ELEM)) return false;
+    if (!msm_schedule_of(n, bits, ECSIMD_MSM_ALG_BUCKETS, S, 3, T::ELEM)) return false;
     S->plan.route = route;
     return true;
   }
   if (bits < 1 || bits > 256 || n > ECSIMD_MSM_MAX_N) return false;
   *S = msm_schedule();
-  S->planes = 3; S->elem = G1_ELEM;
+  S->planes = 3; S->elem = T::ELEM;
   S->plan.route = ECSIMD_MSM_ALG_LANES;
   S->plan.max_chain = launch::MSM_TREE_FAN;
   S->plan.launches = 3 + tree_passes(n);                              // zero, the products, the tree's passes, the last kernel
-  S->plan.workspace_bytes = 16 + 3 * G1_ELEM * n;
+  S->plan.workspace_bytes = 16 + 3 * T::ELEM * n;
   return true;
 }
-struct g1_sum {
-  using ML = launch::g1_msm_launch;
-  static constexpr const char* what = "bls12_381_g1_msm launch";
+template <class T> struct bls381_sum {
+  using ML = typename T::ML;
+  static constexpr const char* what = T::msm_launch;
   const uint64_t* k; const uint8_t* pts; uint8_t* out;
   void digits(hipStream_t s, const msm_blocks& B, size_t n, int bits, int c, int windows) const { ML::digits(s, k, pts, B.kk, B.px, B.py, B.hist, B.counter, n, bits, c, windows); }
-  void slices(hipStream_t s, const msm_blocks& B, size_t n, size_t T, size_t L, size_t slices, int c, size_t K) const {
-    ML::slices(s, B.sorted, B.kk, B.px, B.py, B.start, B.buckets, B.partial, B.counter + 1, n, T, L, slices, c, K);
+  void slices(hipStream_t s, const msm_blocks& B, size_t n, size_t T_, size_t L, size_t slices, int c, size_t K) const {
+    ML::slices(s, B.sorted, B.kk, B.px, B.py, B.start, B.buckets, B.partial, B.counter + 1, n, T_, L, slices, c, K);
   }
   void finish(hipStream_t s, const uint64_t* arr, size_t total, size_t stride, int windows, int c, const uint32_t* counter, uint8_t* finite, uint32_t* invalid) const {
     ML::finish(s, arr, total, stride, windows, c, counter, out, finite, invalid);
   }
 };
 // the counter (16 bytes, zeroed by a kernel) and a Jacobian array of `elements`, from the start of the workspace
-struct g1_tree_layout { uint32_t* counter; uint64_t* tree; size_t bytes; };
-g1_tree_layout g1_tree_plan(void* base, size_t elements) {
-  g1_tree_layout L; carve c = carve_from(base);
-  L.counter = static_cast<uint32_t*>(carve_bytes(c, 16)); L.tree = static_cast<uint64_t*>(carve_bytes(c, 3 * G1_ELEM * elements));
+struct bls381_tree_layout { uint32_t* counter; uint64_t* tree; size_t bytes; };
+template <class T> bls381_tree_layout bls381_tree_plan(void* base, size_t elements) {
+  bls381_tree_layout L; carve c = carve_from(base);
+  L.counter = static_cast<uint32_t*>(carve_bytes(c, 16)); L.tree = static_cast<uint64_t*>(carve_bytes(c, 3 * T::ELEM * elements));
   L.bytes = c.bytes;
   return L;
 }
 // the LANES route (k != nullptr: the products of n terms) and the point sum (k == nullptr: the validating affine front over n encodings); n >= 1
-int g1_tree_sum_run(ecsimd_hip_ctx* ctx, const uint64_t* k, const uint8_t* pts, bool compressed, uint8_t* out, uint8_t* finite, uint32_t* invalid, size_t n, int bits) {
-  using ML = launch::g1_msm_launch;
+template <class T>
+int bls381_tree_sum_run(ecsimd_hip_ctx* ctx, const uint64_t* k, const uint8_t* pts, bool compressed, uint8_t* out, uint8_t* finite, uint32_t* invalid, size_t n, int bits) {
+  using ML = typename T::ML;
   hipStream_t s = ctx->stream;
   const int fan = launch::MSM_TREE_FAN;
   const size_t elements = k ? n : (n + fan - 1) / fan;
-  const int rc = ensure_workspace(ctx, g1_tree_plan(nullptr, elements).bytes);
+  const int rc = ensure_workspace(ctx, bls381_tree_plan<T>(nullptr, elements).bytes);
   if (rc != ECSIMD_HIP_OK) return rc;
-  const g1_tree_layout L = g1_tree_plan(ctx->workspace, elements);
+  const bls381_tree_layout L = bls381_tree_plan<T>(ctx->workspace, elements);
   launch::msm_zero(s, L.counter, 16);
   if (k) ML::products(s, k, pts, L.counter, L.tree, n, bits);
   else ML::tree_affine(s, pts, compressed, L.counter, L.tree, n, elements, fan);
   tree_run<ML>(s, L.tree, elements, elements, 0, 1);
   ML::finish(s, L.tree, elements, 0, 1, 0, L.counter, out, finite, invalid);
   const hipError_t e = hipGetLastError();
-  return e == hipSuccess ? ECSIMD_HIP_OK : fail(ctx, e, k ? "bls12_381_g1_msm launch" : "bls12_381_g1_point_sum launch");
+  return e == hipSuccess ? ECSIMD_HIP_OK : fail(ctx, e, k ? T::msm_launch : textf("%s_point_sum launch", T::name));
 }
-// the single result's outputs against each other and against the inputs (in1 may be null)
-bool g1_result_overlaps(const uint8_t* out, const uint8_t* finite, const uint32_t* invalid, const void* in0, size_t in0_bytes, const void* in1, size_t in1_bytes) {
-  const void* outs[3] = {out, finite, invalid}; const size_t out_bytes[3] = {96, 1, 4};
-  for (int a = 0; a < 3; ++a) {
-    if (ranges_overlap(outs[a], out_bytes[a], in0, in0_bytes) || ranges_overlap(outs[a], out_bytes[a], in1, in1_bytes)) return true;
-    for (int b = a + 1; b < 3; ++b) if (ranges_overlap(outs[a], out_bytes[a], outs[b], out_bytes[b])) return true;
-  }
-  return false;
-}
-// per-lane calls: every output array against every input array and the other outputs, as byte ranges
-struct g1_array { const void* p; size_t bytes; };
-bool g1_arrays_overlap(std::initializer_list<g1_array> outs, std::initializer_list<g1_array> ins) {
+// every output array against every input array (a null one is no array) and the other outputs, as byte ranges
+struct byte_array { const void* p; size_t bytes; };
+bool arrays_overlap(std::initializer_list<byte_array> outs, std::initializer_list<byte_array> ins) {
   for (auto a = outs.begin(); a != outs.end(); ++a) {
-    for (const g1_array& b : ins) if (ranges_overlap(a->p, a->bytes, b.p, b.bytes)) return true;
+    for (const byte_array& b : ins) if (ranges_overlap(a->p, a->bytes, b.p, b.bytes)) return true;
     for (auto b = a + 1; b != outs.end(); ++b) if (ranges_overlap(a->p, a->bytes, b->p, b->bytes)) return true;
   }
   return false;
 }
-}  // namespace
-
-int ecsimd_bls12_381_g1_decompress(ecsimd_hip_ctx* ctx, const uint8_t* in48, uint8_t* out96, uint8_t* ok, size_t n) {
-  REQUIRE_CTX(); if ((!in48 || !out96 || !ok) && n) return bad(ctx, "bls12_381_g1_decompress: in48, out96 or ok is null");
-  if (g1_arrays_overlap({{out96, 96 * n}, {ok, n}}, {{in48, 48 * n}})) return bad(ctx, "bls12_381_g1_decompress: an output must not overlap an input or another output");
-  ENTER();
-  launch::bls381_g1_decompress(ctx->stream, in48, out96, ok, n);
-  const hipError_t e = hipGetLastError();
-  return e == hipSuccess ? ECSIMD_HIP_OK : fail(ctx, e, "bls12_381_g1_decompress launch"); }
-
-int ecsimd_bls12_381_g1_compress(ecsimd_hip_ctx* ctx, const uint8_t* in96, uint8_t* out48, uint8_t* ok, size_t n) {
-  REQUIRE_CTX(); if ((!in96 || !out48 || !ok) && n) return bad(ctx, "bls12_381_g1_compress: in96, out48 or ok is null");
-  if (g1_arrays_overlap({{out48, 48 * n}, {ok, n}}, {{in96, 96 * n}})) return bad(ctx, "bls12_381_g1_compress: an output must not overlap an input or another output");
-  ENTER();
-  launch::bls381_g1_compress(ctx->stream, in96, out48, ok, n);
-  const hipError_t e = hipGetLastError();
-  return e == hipSuccess ? ECSIMD_HIP_OK : fail(ctx, e, "bls12_381_g1_compress launch"); }
-
-int ecsimd_bls12_381_g1_check(ecsimd_hip_ctx* ctx, const uint8_t* in96, uint8_t* on_curve, uint8_t* in_subgroup, size_t n) {
-  REQUIRE_CTX(); if ((!in96 || !on_curve || !in_subgroup) && n) return bad(ctx, "bls12_381_g1_check: in96, on_curve or in_subgroup is null");
-  if (g1_arrays_overlap({{on_curve, n}, {in_subgroup, n}}, {{in96, 96 * n}})) return bad(ctx, "bls12_381_g1_check: an output must not overlap an input or another output");
-  ENTER();
-  launch::bls381_g1_check(ctx->stream, in96, on_curve, in_subgroup, n);
-  const hipError_t e = hipGetLastError();
-  return e == hipSuccess ? ECSIMD_HIP_OK : fail(ctx, e, "bls12_381_g1_check launch"); }
-
-int ecsimd_bls12_381_g1_mul(ecsimd_hip_ctx* ctx, const uint64_t* k, const uint8_t* in96, uint8_t* out96, uint8_t* ok, size_t n) {
-  REQUIRE_CTX(); if ((!k || !in96 || !out96 || !ok) && n) return bad(ctx, "bls12_381_g1_mul: k, in96, out96 or ok is null");
-  if (!aligned16(k)) return bad(ctx, "bls12_381_g1_mul: k is not 16-byte aligned");
-  if (g1_arrays_overlap({{out96, 96 * n}, {ok, n}}, {{k, 32 * n}, {in96, 96 * n}})) return bad(ctx, "bls12_381_g1_mul: an output must not overlap an input or another output");
-  ENTER();
-  launch::bls381_g1_mul(ctx->stream, k, in96, out96, ok, n);
-  const hipError_t e = hipGetLastError();
-  return e == hipSuccess ? ECSIMD_HIP_OK : fail(ctx, e, "bls12_381_g1_mul launch"); }
-
-int ecsimd_bls12_381_g1_msm_plan(size_t n, int bits, int flags, ecsimd_msm_plan_t* out) {
-  msm_schedule S;
-  if (!out || !g1_schedule_of(n, bits, flags, &S)) return ECSIMD_HIP_ERR_BAD_ARG;
-  *out = S.plan;
-  return ECSIMD_HIP_OK; }
-
-int ecsimd_bls12_381_g1_msm(ecsimd_hip_ctx* ctx, const uint64_t* k, const uint8_t* pts96, uint8_t* out96, uint8_t* finite, uint32_t* invalid, size_t n, int bits, int flags) {
-  REQUIRE_CTX();
-  if ((!k || !pts96) && n) return bad(ctx, "bls12_381_g1_msm: k or pts96 is null");
-  if (!out96 || !finite) return bad(ctx, "bls12_381_g1_msm: out96 or finite is null");
-  if (!aligned16(k)) return bad(ctx, "bls12_381_g1_msm: k is not 16-byte aligned");
-  if (invalid && (reinterpret_cast<uintptr_t>(invalid) & 3u)) return bad(ctx, "bls12_381_g1_msm: invalid is not 4-byte aligned");
-  if (bits < 1 || bits > 256) return bad(ctx, "bls12_381_g1_msm: bits must be 1 .. 256");
-  if (n > ECSIMD_MSM_MAX_N) return bad(ctx, "bls12_381_g1_msm: n is above ECSIMD_MSM_MAX_N: chain chunks through ecsimd_bls12_381_g1_point_sum");
-  msm_schedule S;
-  if (!g1_schedule_of(n, bits, flags, &S)) return bad(ctx, "bls12_381_g1_msm: flags must be ECSIMD_MSM_ALG_AUTO, ECSIMD_MSM_ALG_BUCKETS or ECSIMD_MSM_ALG_LANES");
-  if (g1_result_overlaps(out96, finite, invalid, k, 32 * n, pts96, 96 * n)) return bad(ctx, "bls12_381_g1_msm: an output must not overlap an input or another output");
-  const hipError_t e0 = hipSetDevice(ctx->device); if (e0 != hipSuccess) return fail(ctx, e0, "hipSetDevice");
-  if (n == 0 || S.plan.route == ECSIMD_MSM_ALG_BUCKETS) return bucket_sum_run(ctx, S, g1_sum{k, pts96, out96}, finite, invalid, n, bits, 0);
-  return g1_tree_sum_run(ctx, k, pts96, false, out96, finite, invalid, n, bits); }
-
-int ecsimd_bls12_381_g1_point_sum(ecsimd_hip_ctx* ctx, const uint8_t* pts, uint8_t* out96, uint8_t* finite, uint32_t* invalid, size_t n, int flags) {
-  REQUIRE_CTX();
-  if (!pts && n) return bad(ctx, "bls12_381_g1_point_sum: pts is null");
-  if (!out96 || !finite) return bad(ctx, "bls12_381_g1_point_sum: out96 or finite is null");
-  if (invalid && (reinterpret_cast<uintptr_t>(invalid) & 3u)) return bad(ctx, "bls12_381_g1_point_sum: invalid is not 4-byte aligned");
-  if (flags != ECSIMD_BLS12_381_UNCOMPRESSED && flags != ECSIMD_BLS12_381_COMPRESSED) return bad(ctx, "bls12_381_g1_point_sum: flags must be ECSIMD_BLS12_381_UNCOMPRESSED or ECSIMD_BLS12_381_COMPRESSED");
-  const bool compressed = flags == ECSIMD_BLS12_381_COMPRESSED;
-  if ((n + launch::MSM_TREE_FAN - 1) / launch::MSM_TREE_FAN > MAX_LAUNCH) return bad(ctx, "batch too large");
-  if (g1_result_overlaps(out96, finite, invalid, pts, (compressed ? 48 : 96) * n, nullptr, 0)) return bad(ctx, "bls12_381_g1_point_sum: an output must not overlap an input or another output");
-  const hipError_t e0 = hipSetDevice(ctx->device); if (e0 != hipSuccess) return fail(ctx, e0, "hipSetDevice");
-  if (n == 0) return bucket_sum_run(ctx, msm_schedule(), g1_sum{nullptr, nullptr, out96}, finite, invalid, 0, 1, 0);     // the empty sum: the last kernel alone
-  return g1_tree_sum_run(ctx, nullptr, pts, compressed, out96, finite, invalid, n, 0); }
-
-int ecsimd_bls12_381_raw_inputs(int op) { return (op < 0 || op > launch::BLS381_RAW_POINT_MADD) ? 0 : launch::bls381_raw_inputs(op); }
-int ecsimd_bls12_381_raw_outputs(int op) { return (op < 0 || op > launch::BLS381_RAW_POINT_MADD) ? 0 : launch::bls381_raw_outputs(op); }
-int ecsimd_bls12_381_raw(ecsimd_hip_ctx* ctx, int op, const uint8_t* in, uint8_t* out, size_t n) {
-  REQUIRE_CTX(); if ((!in || !out) && n) return bad(ctx, "bls12_381_raw: null pointer");
-  if (op < 0 || op > launch::BLS381_RAW_POINT_MADD) return bad(ctx, "bls12_381_raw: unknown function");
-  if (ranges_overlap(in, 48 * (size_t)launch::bls381_raw_inputs(op) * n, out, 48 * (size_t)launch::bls381_raw_outputs(op) * n)) return bad(ctx, "bls12_381_raw: out must not overlap in");
-  ENTER();
-  launch::bls381_raw(ctx->stream, op, in, out, n);
-  const hipError_t e = hipGetLastError();
-  return e == hipSuccess ? ECSIMD_HIP_OK : fail(ctx, e, "bls12_381_raw launch"); }
-
-// ---- BLS12-381 G2 (include/ecsimd_bls12_381_g2.h; k_bls12_381_g2.hip; tools/bls12_381_g2_model.py the definition).  PUBLIC data.  G1's host layer with the
-// widths changed: 96-byte workspace elements (an Fp2 value), 192- and 96-byte encodings.  g2_schedule_of is the ONE place that turns (n, bits, flags) into this
-// group's sizes; g2_sum is the fourth sum type of bucket_sum_run.
-namespace {
-constexpr size_t G2_ELEM = 96;
-bool g2_schedule_of(size_t n, int bits, int flags, msm_schedule* S) {
-  if (flags != ECSIMD_MSM_ALG_AUTO && flags != ECSIMD_MSM_ALG_BUCKETS && flags != ECSIMD_MSM_ALG_LANES) return false;
-  const int route = flags != ECSIMD_MSM_ALG_AUTO ? flags : n >= ECSIMD_BLS381_G2_MSM_AUTO_THRESHOLD ? ECSIMD_MSM_ALG_BUCKETS : ECSIMD_MSM_ALG_LANES;
-  if (route == ECSIMD_MSM_ALG_BUCKETS || n == 0) {
-    if (!msm_schedule_of(n, bits, ECSIMD_MSM_ALG_BUCKETS, S, 3, G2_ELEM)) return false;
-    S->plan.route = route;
-    return true;
-  }
-  if (bits < 1 || bits > 256 || n > ECSIMD_MSM_MAX_N) return false;
-  *S = msm_schedule();
-  S->planes = 3; S->elem = G2_ELEM;
-  S->plan.route = ECSIMD_MSM_ALG_LANES;
-  S->plan.max_chain = launch::MSM_TREE_FAN;
-  S->plan.launches = 3 + tree_passes(n);                              // zero, the products, the tree's passes, the last kernel
-  S->plan.workspace_bytes = 16 + 3 * G2_ELEM * n;
-  return true;
-}
-struct g2_sum {
-  using ML = launch::g2_msm_launch;
-  static constexpr const char* what = "bls381_g2_msm launch";
-  const uint64_t* k; const uint8_t* pts; uint8_t* out;
-  void digits(hipStream_t s, const msm_blocks& B, size_t n, int bits, int c, int windows) const { ML::digits(s, k, pts, B.kk, B.px, B.py, B.hist, B.counter, n, bits, c, windows); }
-  void slices(hipStream_t s, const msm_blocks& B, size_t n, size_t T, size_t L, size_t slices, int c, size_t K) const {
-    ML::slices(s, B.sorted, B.kk, B.px, B.py, B.start, B.buckets, B.partial, B.counter + 1, n, T, L, slices, c, K);
-  }
-  void finish(hipStream_t s, const uint64_t* arr, size_t total, size_t stride, int windows, int c, const uint32_t* counter, uint8_t* finite, uint32_t* invalid) const {
-    ML::finish(s, arr, total, stride, windows, c, counter, out, finite, invalid);
-  }
-};
-// the counter (16 bytes, zeroed by a kernel) and a Jacobian array of `elements`, from the start of the workspace
-g1_tree_layout g2_tree_plan(void* base, size_t elements) {
-  g1_tree_layout L; carve c = carve_from(base);
-  L.counter = static_cast<uint32_t*>(carve_bytes(c, 16)); L.tree = static_cast<uint64_t*>(carve_bytes(c, 3 * G2_ELEM * elements));
-  L.bytes = c.bytes;
-  return L;
-}
-// the LANES route (k != nullptr: the products of n terms) and the point sum (k == nullptr: the validating affine front over n encodings); n >= 1
-int g2_tree_sum_run(ecsimd_hip_ctx* ctx, const uint64_t* k, const uint8_t* pts, bool compressed, uint8_t* out, uint8_t* finite, uint32_t* invalid, size_t n, int bits) {
-  using ML = launch::g2_msm_launch;
-  hipStream_t s = ctx->stream;
-  const int fan = launch::MSM_TREE_FAN;
-  const size_t elements = k ? n : (n + fan - 1) / fan;
-  const int rc = ensure_workspace(ctx, g2_tree_plan(nullptr, elements).bytes);
-  if (rc != ECSIMD_HIP_OK) return rc;
-  const g1_tree_layout L = g2_tree_plan(ctx->workspace, elements);
-  launch::msm_zero(s, L.counter, 16);
-  if (k) ML::products(s, k, pts, L.counter, L.tree, n, bits);
-  else ML::tree_affine(s, pts, compressed, L.counter, L.tree, n, elements, fan);
-  tree_run<ML>(s, L.tree, elements, elements, 0, 1);
-  ML::finish(s, L.tree, elements, 0, 1, 0, L.counter, out, finite, invalid);
-  const hipError_t e = hipGetLastError();
-  return e == hipSuccess ? ECSIMD_HIP_OK : fail(ctx, e, k ? "bls381_g2_msm launch" : "bls381_g2_point_sum launch");
-}
 // the single result's outputs against each other and against the inputs (in1 may be null)
-bool g2_result_overlaps(const uint8_t* out, const uint8_t* finite, const uint32_t* invalid, const void* in0, size_t in0_bytes, const void* in1, size_t in1_bytes) {
-  return g1_arrays_overlap({{out, 192}, {finite, 1}, {invalid, 4}}, {{in0, in0_bytes}, {in1, in1_bytes}});
+template <class T> bool bls381_result_overlaps(const uint8_t* out, const uint8_t* finite, const uint32_t* invalid, const void* in0, size_t in0_bytes, const void* in1, size_t in1_bytes) {
+  return arrays_overlap({{out, 2 * T::ELEM}, {finite, 1}, {invalid, 4}}, {{in0, in0_bytes}, {in1, in1_bytes}});
 }
-}  // namespace
-
-int ecsimd_bls381_g2_decompress(ecsimd_hip_ctx* ctx, const uint8_t* in96, uint8_t* out192, uint8_t* ok, size_t n) {
-  REQUIRE_CTX(); if ((!in96 || !out192 || !ok) && n) return bad(ctx, "bls381_g2_decompress: in96, out192 or ok is null");
-  if (g1_arrays_overlap({{out192, 192 * n}, {ok, n}}, {{in96, 96 * n}})) return bad(ctx, "bls381_g2_decompress: an output must not overlap an input or another output");
+// the entry points' bodies; W, C: the uncompressed and the compressed width in the messages' argument names
+#define BLS381_WIDTHS const size_t W = 2 * T::ELEM, C = T::ELEM
+#define BLS381_NO_OVERLAP(fn, ...) if (arrays_overlap(__VA_ARGS__)) return bad(ctx, textf("%s_" fn ": an output must not overlap an input or another output", T::name))
+#define BLS381_LAUNCHED(fn) const hipError_t e = hipGetLastError(); return e == hipSuccess ? ECSIMD_HIP_OK : fail(ctx, e, textf("%s_" fn " launch", T::name))
+template <class T> int bls381_decompress(ecsimd_hip_ctx* ctx, const uint8_t* in, uint8_t* out, uint8_t* ok, size_t n) {
+  BLS381_WIDTHS;
+  REQUIRE_CTX(); if ((!in || !out || !ok) && n) return bad(ctx, textf("%s_decompress: in%zu, out%zu or ok is null", T::name, C, W));
+  BLS381_NO_OVERLAP("decompress", {{out, W * n}, {ok, n}}, {{in, C * n}});
   ENTER();
-  launch::bls381_g2_decompress(ctx->stream, in96, out192, ok, n);
-  const hipError_t e = hipGetLastError();
-  return e == hipSuccess ? ECSIMD_HIP_OK : fail(ctx, e, "bls381_g2_decompress launch"); }
-
-int ecsimd_bls381_g2_compress(ecsimd_hip_ctx* ctx, const uint8_t* in192, uint8_t* out96, uint8_t* ok, size_t n) {
-  REQUIRE_CTX(); if ((!in192 || !out96 || !ok) && n) return bad(ctx, "bls381_g2_compress: in192, out96 or ok is null");
-  if (g1_arrays_overlap({{out96, 96 * n}, {ok, n}}, {{in192, 192 * n}})) return bad(ctx, "bls381_g2_compress: an output must not overlap an input or another output");
+  T::ML::decompress(ctx->stream, in, out, ok, n);
+  BLS381_LAUNCHED("decompress"); }
+template <class T> int bls381_compress(ecsimd_hip_ctx* ctx, const uint8_t* in, uint8_t* out, uint8_t* ok, size_t n) {
+  BLS381_WIDTHS;
+  REQUIRE_CTX(); if ((!in || !out || !ok) && n) return bad(ctx, textf("%s_compress: in%zu, out%zu or ok is null", T::name, W, C));
+  BLS381_NO_OVERLAP("compress", {{out, C * n}, {ok, n}}, {{in, W * n}});
   ENTER();
-  launch::bls381_g2_compress(ctx->stream, in192, out96, ok, n);
-  const hipError_t e = hipGetLastError();
-  return e == hipSuccess ? ECSIMD_HIP_OK : fail(ctx, e, "bls381_g2_compress launch"); }
-
-int ecsimd_bls381_g2_check(ecsimd_hip_ctx* ctx, const uint8_t* in192, uint8_t* on_curve, uint8_t* in_subgroup, size_t n) {
-  REQUIRE_CTX(); if ((!in192 || !on_curve || !in_subgroup) && n) return bad(ctx, "bls381_g2_check: in192, on_curve or in_subgroup is null");
-  if (g1_arrays_overlap({{on_curve, n}, {in_subgroup, n}}, {{in192, 192 * n}})) return bad(ctx, "bls381_g2_check: an output must not overlap an input or another output");
+  T::ML::compress(ctx->stream, in, out, ok, n);
+  BLS381_LAUNCHED("compress"); }
+template <class T> int bls381_check(ecsimd_hip_ctx* ctx, const uint8_t* in, uint8_t* on_curve, uint8_t* in_subgroup, size_t n) {
+  BLS381_WIDTHS; (void)C;
+  REQUIRE_CTX(); if ((!in || !on_curve || !in_subgroup) && n) return bad(ctx, textf("%s_check: in%zu, on_curve or in_subgroup is null", T::name, W));
+  BLS381_NO_OVERLAP("check", {{on_curve, n}, {in_subgroup, n}}, {{in, W * n}});
   ENTER();
-  launch::bls381_g2_check(ctx->stream, in192, on_curve, in_subgroup, n);
-  const hipError_t e = hipGetLastError();
-  return e == hipSuccess ? ECSIMD_HIP_OK : fail(ctx, e, "bls381_g2_check launch"); }
-
-int ecsimd_bls381_g2_mul(ecsimd_hip_ctx* ctx, const uint64_t* k, const uint8_t* in192, uint8_t* out192, uint8_t* ok, size_t n) {
-  REQUIRE_CTX(); if ((!k || !in192 || !out192 || !ok) && n) return bad(ctx, "bls381_g2_mul: k, in192, out192 or ok is null");
-  if (!aligned16(k)) return bad(ctx, "bls381_g2_mul: k is not 16-byte aligned");
-  if (g1_arrays_overlap({{out192, 192 * n}, {ok, n}}, {{k, 32 * n}, {in192, 192 * n}})) return bad(ctx, "bls381_g2_mul: an output must not overlap an input or another output");
+  T::ML::check(ctx->stream, in, on_curve, in_subgroup, n);
+  BLS381_LAUNCHED("check"); }
+template <class T> int bls381_mul(ecsimd_hip_ctx* ctx, const uint64_t* k, const uint8_t* in, uint8_t* out, uint8_t* ok, size_t n) {
+  BLS381_WIDTHS; (void)C;
+  REQUIRE_CTX(); if ((!k || !in || !out || !ok) && n) return bad(ctx, textf("%s_mul: k, in%zu, out%zu or ok is null", T::name, W, W));
+  if (!aligned16(k)) return bad(ctx, textf("%s_mul: k is not 16-byte aligned", T::name));
+  BLS381_NO_OVERLAP("mul", {{out, W * n}, {ok, n}}, {{k, 32 * n}, {in, W * n}});
   ENTER();
-  launch::bls381_g2_mul(ctx->stream, k, in192, out192, ok, n);
-  const hipError_t e = hipGetLastError();
-  return e == hipSuccess ? ECSIMD_HIP_OK : fail(ctx, e, "bls381_g2_mul launch"); }
-
-int ecsimd_bls381_g2_msm_plan(size_t n, int bits, int flags, ecsimd_msm_plan_t* out) {
+  T::ML::mul(ctx->stream, k, in, out, ok, n);
+  BLS381_LAUNCHED("mul"); }
+template <class T> int bls381_msm_plan(size_t n, int bits, int flags, ecsimd_msm_plan_t* out) {
   msm_schedule S;
-  if (!out || !g2_schedule_of(n, bits, flags, &S)) return ECSIMD_HIP_ERR_BAD_ARG;
+  if (!out || !bls381_schedule_of<T>(n, bits, flags, &S)) return ECSIMD_HIP_ERR_BAD_ARG;
   *out = S.plan;
   return ECSIMD_HIP_OK; }
-
-int ecsimd_bls381_g2_msm(ecsimd_hip_ctx* ctx, const uint64_t* k, const uint8_t* pts192, uint8_t* out192, uint8_t* finite, uint32_t* invalid, size_t n, int bits, int flags) {
+template <class T> int bls381_msm(ecsimd_hip_ctx* ctx, const uint64_t* k, const uint8_t* pts, uint8_t* out, uint8_t* finite, uint32_t* invalid, size_t n, int bits, int flags) {
+  BLS381_WIDTHS; (void)C;
   REQUIRE_CTX();
-  if ((!k || !pts192) && n) return bad(ctx, "bls381_g2_msm: k or pts192 is null");
-  if (!out192 || !finite) return bad(ctx, "bls381_g2_msm: out192 or finite is null");
-  if (!aligned16(k)) return bad(ctx, "bls381_g2_msm: k is not 16-byte aligned");
-  if (invalid && (reinterpret_cast<uintptr_t>(invalid) & 3u)) return bad(ctx, "bls381_g2_msm: invalid is not 4-byte aligned");
-  if (bits < 1 || bits > 256) return bad(ctx, "bls381_g2_msm: bits must be 1 .. 256");
-  if (n > ECSIMD_MSM_MAX_N) return bad(ctx, "bls381_g2_msm: n is above ECSIMD_MSM_MAX_N: chain chunks through ecsimd_bls381_g2_point_sum");
+  if ((!k || !pts) && n) return bad(ctx, textf("%s_msm: k or pts%zu is null", T::name, W));
+  if (!out || !finite) return bad(ctx, textf("%s_msm: out%zu or finite is null", T::name, W));
+  if (!aligned16(k)) return bad(ctx, textf("%s_msm: k is not 16-byte aligned", T::name));
+  if (invalid && (reinterpret_cast<uintptr_t>(invalid) & 3u)) return bad(ctx, textf("%s_msm: invalid is not 4-byte aligned", T::name));
+  if (bits < 1 || bits > 256) return bad(ctx, textf("%s_msm: bits must be 1 .. 256", T::name));
+  if (n > ECSIMD_MSM_MAX_N) return bad(ctx, textf("%s_msm: n is above ECSIMD_MSM_MAX_N: chain chunks through ecsimd_%s_point_sum", T::name, T::name));
   msm_schedule S;
-  if (!g2_schedule_of(n, bits, flags, &S)) return bad(ctx, "bls381_g2_msm: flags must be ECSIMD_MSM_ALG_AUTO, ECSIMD_MSM_ALG_BUCKETS or ECSIMD_MSM_ALG_LANES");
-  if (g2_result_overlaps(out192, finite, invalid, k, 32 * n, pts192, 192 * n)) return bad(ctx, "bls381_g2_msm: an output must not overlap an input or another output");
+  if (!bls381_schedule_of<T>(n, bits, flags, &S)) return bad(ctx, textf("%s_msm: flags must be ECSIMD_MSM_ALG_AUTO, ECSIMD_MSM_ALG_BUCKETS or ECSIMD_MSM_ALG_LANES", T::name));
+  if (bls381_result_overlaps<T>(out, finite, invalid, k, 32 * n, pts, W * n)) return bad(ctx, textf("%s_msm: an output must not overlap an input or another output", T::name));
   const hipError_t e0 = hipSetDevice(ctx->device); if (e0 != hipSuccess) return fail(ctx, e0, "hipSetDevice");
-  if (n == 0 || S.plan.route == ECSIMD_MSM_ALG_BUCKETS) return bucket_sum_run(ctx, S, g2_sum{k, pts192, out192}, finite, invalid, n, bits, 0);
-  return g2_tree_sum_run(ctx, k, pts192, false, out192, finite, invalid, n, bits); }
-
-int ecsimd_bls381_g2_point_sum(ecsimd_hip_ctx* ctx, const uint8_t* pts, uint8_t* out192, uint8_t* finite, uint32_t* invalid, size_t n, int flags) {
+  if (n == 0 || S.plan.route == ECSIMD_MSM_ALG_BUCKETS) return bucket_sum_run(ctx, S, bls381_sum<T>{k, pts, out}, finite, invalid, n, bits, 0);
+  return bls381_tree_sum_run<T>(ctx, k, pts, false, out, finite, invalid, n, bits); }
+// uncompressed_flag, compressed_flag: the group's two encoding flags (the headers give both groups the same values under their own names)
+template <class T> int bls381_point_sum(ecsimd_hip_ctx* ctx, const uint8_t* pts, uint8_t* out, uint8_t* finite, uint32_t* invalid, size_t n, int flags, int uncompressed_flag,
+                                        int compressed_flag) {
+  BLS381_WIDTHS;
   REQUIRE_CTX();
-  if (!pts && n) return bad(ctx, "bls381_g2_point_sum: pts is null");
-  if (!out192 || !finite) return bad(ctx, "bls381_g2_point_sum: out192 or finite is null");
-  if (invalid && (reinterpret_cast<uintptr_t>(invalid) & 3u)) return bad(ctx, "bls381_g2_point_sum: invalid is not 4-byte aligned");
-  if (flags != ECSIMD_BLS381_G2_UNCOMPRESSED && flags != ECSIMD_BLS381_G2_COMPRESSED) return bad(ctx, "bls381_g2_point_sum: flags must be ECSIMD_BLS381_G2_UNCOMPRESSED or ECSIMD_BLS381_G2_COMPRESSED");
-  const bool compressed = flags == ECSIMD_BLS381_G2_COMPRESSED;
+  if (!pts && n) return bad(ctx, textf("%s_point_sum: pts is null", T::name));
+  if (!out || !finite) return bad(ctx, textf("%s_point_sum: out%zu or finite is null", T::name, W));
+  if (invalid && (reinterpret_cast<uintptr_t>(invalid) & 3u)) return bad(ctx, textf("%s_point_sum: invalid is not 4-byte aligned", T::name));
+  if (flags != uncompressed_flag && flags != compressed_flag) return bad(ctx, textf("%s_point_sum: flags must be %s_UNCOMPRESSED or %s_COMPRESSED", T::name, T::flag_stem, T::flag_stem));
+  const bool compressed = flags == compressed_flag;
   if ((n + launch::MSM_TREE_FAN - 1) / launch::MSM_TREE_FAN > MAX_LAUNCH) return bad(ctx, "batch too large");
-  if (g2_result_overlaps(out192, finite, invalid, pts, (compressed ? 96 : 192) * n, nullptr, 0)) return bad(ctx, "bls381_g2_point_sum: an output must not overlap an input or another output");
+  if (bls381_result_overlaps<T>(out, finite, invalid, pts, (compressed ? C : W) * n, nullptr, 0)) return bad(ctx, textf("%s_point_sum: an output must not overlap an input or another output", T::name));
   const hipError_t e0 = hipSetDevice(ctx->device); if (e0 != hipSuccess) return fail(ctx, e0, "hipSetDevice");
-  if (n == 0) return bucket_sum_run(ctx, msm_schedule(), g2_sum{nullptr, nullptr, out192}, finite, invalid, 0, 1, 0);     // the empty sum: the last kernel alone
-  return g2_tree_sum_run(ctx, nullptr, pts, compressed, out192, finite, invalid, n, 0); }
-
-int ecsimd_bls381_g2_raw_inputs(int op) { return (op < 0 || op > launch::BLS381_G2_RAW_POINT_MADD) ? 0 : launch::bls381_g2_raw_inputs(op); }
-int ecsimd_bls381_g2_raw_outputs(int op) { return (op < 0 || op > launch::BLS381_G2_RAW_POINT_MADD) ? 0 : launch::bls381_g2_raw_outputs(op); }
-int ecsimd_bls381_g2_raw(ecsimd_hip_ctx* ctx, int op, const uint8_t* in, uint8_t* out, size_t n) {
-  REQUIRE_CTX(); if ((!in || !out) && n) return bad(ctx, "bls381_g2_raw: null pointer");
-  if (op < 0 || op > launch::BLS381_G2_RAW_POINT_MADD) return bad(ctx, "bls381_g2_raw: unknown function");
-  if (ranges_overlap(in, 48 * (size_t)launch::bls381_g2_raw_inputs(op) * n, out, 48 * (size_t)launch::bls381_g2_raw_outputs(op) * n)) return bad(ctx, "bls381_g2_raw: out must not overlap in");
+  if (n == 0) return bucket_sum_run(ctx, msm_schedule(), bls381_sum<T>{nullptr, nullptr, out}, finite, invalid, 0, 1, 0);     // the empty sum: the last kernel alone
+  return bls381_tree_sum_run<T>(ctx, nullptr, pts, compressed, out, finite, invalid, n, 0); }
+template <class T> int bls381_raw_records(int op, bool outputs) {
+  const int R = (int)(T::ELEM / 48);
+  return (op < 0 || op > launch::BLS381_RAW_POINT_MADD) ? 0 : outputs ? launch::bls381_raw_outputs(op, R) : launch::bls381_raw_inputs(op, R);
+}
+template <class T> int bls381_raw(ecsimd_hip_ctx* ctx, int op, const uint8_t* in, uint8_t* out, size_t n) {
+  REQUIRE_CTX(); if ((!in || !out) && n) return bad(ctx, textf("%s: null pointer", T::raw_name));
+  if (op < 0 || op > launch::BLS381_RAW_POINT_MADD) return bad(ctx, textf("%s: unknown function", T::raw_name));
+  if (ranges_overlap(in, 48 * (size_t)bls381_raw_records<T>(op, false) * n, out, 48 * (size_t)bls381_raw_records<T>(op, true) * n)) return bad(ctx, textf("%s: out must not overlap in", T::raw_name));
   ENTER();
-  launch::bls381_g2_raw(ctx->stream, op, in, out, n);
+  T::ML::raw(ctx->stream, op, in, out, n);
   const hipError_t e = hipGetLastError();
-  return e == hipSuccess ? ECSIMD_HIP_OK : fail(ctx, e, "bls381_g2_raw launch"); }
+  return e == hipSuccess ? ECSIMD_HIP_OK : fail(ctx, e, textf("%s launch", T::raw_name)); }
+#undef BLS381_WIDTHS
+#undef BLS381_NO_OVERLAP
+#undef BLS381_LAUNCHED
+}  // namespace
+}  // extern "C++"
+
+int ecsimd_bls12_381_g1_decompress(ecsimd_hip_ctx* ctx, const uint8_t* in48, uint8_t* out96, uint8_t* ok, size_t n) { return bls381_decompress<bls381_g1>(ctx, in48, out96, ok, n); }
+int ecsimd_bls12_381_g1_compress(ecsimd_hip_ctx* ctx, const uint8_t* in96, uint8_t* out48, uint8_t* ok, size_t n) { return bls381_compress<bls381_g1>(ctx, in96, out48, ok, n); }
+int ecsimd_bls12_381_g1_check(ecsimd_hip_ctx* ctx, const uint8_t* in96, uint8_t* on_curve, uint8_t* in_subgroup, size_t n) { return bls381_check<bls381_g1>(ctx, in96, on_curve, in_subgroup, n); }
+int ecsimd_bls12_381_g1_mul(ecsimd_hip_ctx* ctx, const uint64_t* k, const uint8_t* in96, uint8_t* out96, uint8_t* ok, size_t n) { return bls381_mul<bls381_g1>(ctx, k, in96, out96, ok, n); }
+int ecsimd_bls12_381_g1_msm_plan(size_t n, int bits, int flags, ecsimd_msm_plan_t* out) { return bls381_msm_plan<bls381_g1>(n, bits, flags, out); }
+int ecsimd_bls12_381_g1_msm(ecsimd_hip_ctx* ctx, const uint64_t* k, const uint8_t* pts96, uint8_t* out96, uint8_t* finite, uint32_t* invalid, size_t n, int bits, int flags) {
+  return bls381_msm<bls381_g1>(ctx, k, pts96, out96, finite, invalid, n, bits, flags); }
+int ecsimd_bls12_381_g1_point_sum(ecsimd_hip_ctx* ctx, const uint8_t* pts, uint8_t* out96, uint8_t* finite, uint32_t* invalid, size_t n, int flags) {
+  return bls381_point_sum<bls381_g1>(ctx, pts, out96, finite, invalid, n, flags, ECSIMD_BLS12_381_UNCOMPRESSED, ECSIMD_BLS12_381_COMPRESSED); }
+int ecsimd_bls12_381_raw_inputs(int op) { return bls381_raw_records<bls381_g1>(op, false); }
+int ecsimd_bls12_381_raw_outputs(int op) { return bls381_raw_records<bls381_g1>(op, true); }
+int ecsimd_bls12_381_raw(ecsimd_hip_ctx* ctx, int op, const uint8_t* in, uint8_t* out, size_t n) { return bls381_raw<bls381_g1>(ctx, op, in, out, n); }
+
+int ecsimd_bls381_g2_decompress(ecsimd_hip_ctx* ctx, const uint8_t* in96, uint8_t* out192, uint8_t* ok, size_t n) { return bls381_decompress<bls381_g2>(ctx, in96, out192, ok, n); }
+int ecsimd_bls381_g2_compress(ecsimd_hip_ctx* ctx, const uint8_t* in192, uint8_t* out96, uint8_t* ok, size_t n) { return bls381_compress<bls381_g2>(ctx, in192, out96, ok, n); }
+int ecsimd_bls381_g2_check(ecsimd_hip_ctx* ctx, const uint8_t* in192, uint8_t* on_curve, uint8_t* in_subgroup, size_t n) { return bls381_check<bls381_g2>(ctx, in192, on_curve, in_subgroup, n); }
+int ecsimd_bls381_g2_mul(ecsimd_hip_ctx* ctx, const uint64_t* k, const uint8_t* in192, uint8_t* out192, uint8_t* ok, size_t n) { return bls381_mul<bls381_g2>(ctx, k, in192, out192, ok, n); }
+int ecsimd_bls381_g2_msm_plan(size_t n, int bits, int flags, ecsimd_msm_plan_t* out) { return bls381_msm_plan<bls381_g2>(n, bits, flags, out); }
+int ecsimd_bls381_g2_msm(ecsimd_hip_ctx* ctx, const uint64_t* k, const uint8_t* pts192, uint8_t* out192, uint8_t* finite, uint32_t* invalid, size_t n, int bits, int flags) {
+  return bls381_msm<bls381_g2>(ctx, k, pts192, out192, finite, invalid, n, bits, flags); }
+int ecsimd_bls381_g2_point_sum(ecsimd_hip_ctx* ctx, const uint8_t* pts, uint8_t* out192, uint8_t* finite, uint32_t* invalid, size_t n, int flags) {
+  return bls381_point_sum<bls381_g2>(ctx, pts, out192, finite, invalid, n, flags, ECSIMD_BLS381_G2_UNCOMPRESSED, ECSIMD_BLS381_G2_COMPRESSED); }
+int ecsimd_bls381_g2_raw_inputs(int op) { return bls381_raw_records<bls381_g2>(op, false); }
+int ecsimd_bls381_g2_raw_outputs(int op) { return bls381_raw_records<bls381_g2>(op, true); }
+int ecsimd_bls381_g2_raw(ecsimd_hip_ctx* ctx, int op, const uint8_t* in, uint8_t* out, size_t n) { return bls381_raw<bls381_g2>(ctx, op, in, out, n); }
 
 int ecsimd_ed25519_verify_cofactored(ecsimd_hip_ctx* ctx, const uint8_t* pk, const uint8_t* msg, size_t msg_bytes, size_t stride_bytes, const uint32_t* lens,
                                      const uint8_t* sig, uint8_t* ok, size_t n, int flags) {

@@ -8,6 +8,8 @@
 namespace ecsimd_hip {
 struct gmod;                 // gfield.cuh: a run-time modulus and what the field layer derives from it
 struct gcurve;               // gcurve.cuh: a run-time curve (its field, a R, b R, the generator, the ladder loop's 29-bit constants)
+struct g1_curve;             // tags: the two BLS12-381 groups as bls381_launch's instances (k_bls12_381.hip, k_bls12_381_g2.hip)
+struct g2_curve;
 namespace launch {
 
 constexpr int BLOCK = 256;   // one wave per SIMD of a CU; several workgroups resident per CU
@@ -391,66 +393,37 @@ struct ed25519_msm_launch {                      // msm_launch's shape: capi.hip
   static void finish(hipStream_t, const uint64_t* arr, size_t total, size_t stride, int windows, int c, const uint32_t* counter, uint8_t* out, uint64_t* raw, uint8_t* finite,
                      uint32_t* invalid);
 };
-// k_bls12_381.hip: BLS12-381 G1 (include/ecsimd_bls12_381.h; fe381.cuh, g1.cuh; PUBLIC data).  Every launcher enqueues ONE kernel.  Points cross as the standard
-// 96-byte (pts96) or 48-byte encodings at any alignment, scalars as n x 8 words, 16-byte aligned.  A field element in the workspace is 48 bytes (twelve little-endian
-// words, Montgomery form), element e of an array at byte 48 e; a Jacobian array of `total` elements is X, Y, Z one behind the other (X at e, Y at total + e, Z at
-// 2 total + e), Z = 0 the identity; px, py = the decoded terms' x and y (n elements each).
+// k_bls12_381.hip (G = g1_curve) and k_bls12_381_g2.hip (G = g2_curve): BLS12-381 G1 and G2 (include/ecsimd_bls12_381.h, include/ecsimd_bls12_381_g2.h; g1.cuh,
+// g2.cuh, the kernels' one text k_bls12_381.inc; PUBLIC data).  Every launcher enqueues ONE kernel.  A field element is R = 1 (Fp) or 2 (Fp2) 48-byte components.  Points
+// cross as the standard uncompressed (96 R bytes: pts) or compressed (48 R bytes) encodings at any alignment, scalars as n x 8 words, 16-byte aligned.  A field
+// element in the workspace is 48 R bytes: its components least significant first, each twelve little-endian words in Montgomery form, element e of an array at
+// byte 48 R e; a Jacobian array of `total` elements is X, Y, Z one behind the other (X at e, Y at total + e, Z at 2 total + e), Z = 0 the identity; px, py = the
+// decoded terms' x and y (n elements each).  Raw records are 48 bytes; a field operand is R records, least significant first, a point x, y and one flag record.
 enum bls381_raw_op { BLS381_RAW_FE_MUL = 0, BLS381_RAW_FE_SQR = 1, BLS381_RAW_FE_ADD = 2, BLS381_RAW_FE_SUB = 3, BLS381_RAW_FE_NEG = 4, BLS381_RAW_FE_INVERT = 5,
                      BLS381_RAW_FE_SQRT = 6, BLS381_RAW_FE_CANON = 7, BLS381_RAW_POINT_ADD = 8, BLS381_RAW_POINT_DBL = 9, BLS381_RAW_POINT_MADD = 10 };
-constexpr int bls381_raw_inputs(int op) {
-  return op == BLS381_RAW_POINT_ADD ? 6 : op == BLS381_RAW_POINT_MADD ? 5 : op == BLS381_RAW_POINT_DBL ? 3
-       : (op == BLS381_RAW_FE_MUL || op == BLS381_RAW_FE_ADD || op == BLS381_RAW_FE_SUB) ? 2 : 1;
+constexpr int bls381_raw_inputs(int op, int R) {
+  return op == BLS381_RAW_POINT_ADD ? 4 * R + 2 : op == BLS381_RAW_POINT_MADD ? 4 * R + 1 : op == BLS381_RAW_POINT_DBL ? 2 * R + 1
+       : (op == BLS381_RAW_FE_MUL || op == BLS381_RAW_FE_ADD || op == BLS381_RAW_FE_SUB) ? 2 * R : R;
 }
-constexpr int bls381_raw_outputs(int op) { return op >= BLS381_RAW_POINT_ADD ? 3 : op == BLS381_RAW_FE_SQRT ? 2 : 1; }
-void bls381_g1_decompress(hipStream_t, const uint8_t* in48, uint8_t* out96, uint8_t* ok, size_t n);
-void bls381_g1_compress(hipStream_t, const uint8_t* in96, uint8_t* out48, uint8_t* ok, size_t n);
-void bls381_g1_check(hipStream_t, const uint8_t* in96, uint8_t* on_curve, uint8_t* in_subgroup, size_t n);
-void bls381_g1_mul(hipStream_t, const uint64_t* k, const uint8_t* in96, uint8_t* out96, uint8_t* ok, size_t n);
-void bls381_raw(hipStream_t, int op, const uint8_t* in, uint8_t* out, size_t n);
-struct g1_msm_launch {                           // msm_launch's shape: capi.hip's bucket_sum_run takes it
-  static void digits(hipStream_t, const uint64_t* k, const uint8_t* pts96, uint64_t* kk, uint64_t* px, uint64_t* py, uint32_t* hist, uint32_t* counter, size_t n, int bits, int c,
+constexpr int bls381_raw_outputs(int op, int R) { return op >= BLS381_RAW_POINT_ADD ? 2 * R + 1 : op == BLS381_RAW_FE_SQRT ? R + 1 : R; }
+template <class G> struct bls381_launch {        // from digits on msm_launch's shape: capi.hip's bucket_sum_run takes it
+  static void decompress(hipStream_t, const uint8_t* in, uint8_t* out, uint8_t* ok, size_t n);
+  static void compress(hipStream_t, const uint8_t* in, uint8_t* out, uint8_t* ok, size_t n);
+  static void check(hipStream_t, const uint8_t* in, uint8_t* on_curve, uint8_t* in_subgroup, size_t n);
+  static void mul(hipStream_t, const uint64_t* k, const uint8_t* in, uint8_t* out, uint8_t* ok, size_t n);
+  static void raw(hipStream_t, int op, const uint8_t* in, uint8_t* out, size_t n);
+  static void digits(hipStream_t, const uint64_t* k, const uint8_t* pts, uint64_t* kk, uint64_t* px, uint64_t* py, uint32_t* hist, uint32_t* counter, size_t n, int bits, int c,
                      int windows);
   static void slices(hipStream_t, const uint32_t* sorted, const uint64_t* kk, const uint64_t* px, const uint64_t* py, const uint32_t* start, uint64_t* buckets, uint64_t* partial,
                      uint32_t* broken, size_t n, size_t T, size_t L, size_t slices, int c, size_t K);
   static void combine(hipStream_t, const uint32_t* start, uint64_t* buckets, const uint64_t* partial, uint32_t* broken, size_t L, size_t slices, int c, size_t K);
   static void chunks(hipStream_t, const uint64_t* buckets, uint64_t* out, size_t lanes, size_t per_window, int c, int m, size_t K);
   static void tree(hipStream_t, uint64_t* arr, size_t total, size_t count, size_t stride, size_t groups, size_t lanes, int fan);
-  // out[g] = the sum of the valid points g, g + lanes, ... (fan of them) of n encodings, 48 bytes each where compressed; malformed ones are counted and skipped
+  // out[g] = the sum of the valid points g, g + lanes, ... (fan of them) of n encodings, the compressed ones where `compressed`; malformed ones are counted and skipped
   static void tree_affine(hipStream_t, const uint8_t* pts, bool compressed, uint32_t* counter, uint64_t* out, size_t n, size_t lanes, int fan);
   // the LANES route's front: out[i] = (k[i] mod 2^bits) P[i] as a Jacobian array of n; a malformed point is counted and gives the identity
-  static void products(hipStream_t, const uint64_t* k, const uint8_t* pts96, uint32_t* counter, uint64_t* out, size_t n, int bits);
-  static void finish(hipStream_t, const uint64_t* arr, size_t total, size_t stride, int windows, int c, const uint32_t* counter, uint8_t* out96, uint8_t* finite, uint32_t* invalid);
-};
-// k_bls12_381_g2.hip: BLS12-381 G2 (include/ecsimd_bls12_381_g2.h; fp2.cuh, g2.cuh; PUBLIC data).  Every launcher enqueues ONE kernel.  Points cross as the standard
-// 192-byte (pts192) or 96-byte encodings at any alignment, scalars as n x 8 words, 16-byte aligned.  An Fp2 element in the workspace is 96 bytes: c0 then c1, each
-// twelve little-endian words in Montgomery form, element e of an array at byte 96 e; a Jacobian array of `total` elements is X, Y, Z one behind the other, Z = 0 the
-// identity; px, py = the decoded terms' x and y (n elements each).  Raw records are 48 bytes; an Fp2 operand is TWO records, c0 then c1.
-enum bls381_g2_raw_op { BLS381_G2_RAW_FE2_MUL = 0, BLS381_G2_RAW_FE2_SQR = 1, BLS381_G2_RAW_FE2_ADD = 2, BLS381_G2_RAW_FE2_SUB = 3, BLS381_G2_RAW_FE2_NEG = 4,
-                        BLS381_G2_RAW_FE2_INVERT = 5, BLS381_G2_RAW_FE2_SQRT = 6, BLS381_G2_RAW_FE2_CANON = 7, BLS381_G2_RAW_POINT_ADD = 8, BLS381_G2_RAW_POINT_DBL = 9,
-                        BLS381_G2_RAW_POINT_MADD = 10 };
-constexpr int bls381_g2_raw_inputs(int op) {
-  return op == BLS381_G2_RAW_POINT_ADD ? 10 : op == BLS381_G2_RAW_POINT_MADD ? 9 : op == BLS381_G2_RAW_POINT_DBL ? 5
-       : (op == BLS381_G2_RAW_FE2_MUL || op == BLS381_G2_RAW_FE2_ADD || op == BLS381_G2_RAW_FE2_SUB) ? 4 : 2;
-}
-constexpr int bls381_g2_raw_outputs(int op) { return op >= BLS381_G2_RAW_POINT_ADD ? 5 : op == BLS381_G2_RAW_FE2_SQRT ? 3 : 2; }
-void bls381_g2_decompress(hipStream_t, const uint8_t* in96, uint8_t* out192, uint8_t* ok, size_t n);
-void bls381_g2_compress(hipStream_t, const uint8_t* in192, uint8_t* out96, uint8_t* ok, size_t n);
-void bls381_g2_check(hipStream_t, const uint8_t* in192, uint8_t* on_curve, uint8_t* in_subgroup, size_t n);
-void bls381_g2_mul(hipStream_t, const uint64_t* k, const uint8_t* in192, uint8_t* out192, uint8_t* ok, size_t n);
-void bls381_g2_raw(hipStream_t, int op, const uint8_t* in, uint8_t* out, size_t n);
-struct g2_msm_launch {                           // g1_msm_launch's shape with the widths changed
-  static void digits(hipStream_t, const uint64_t* k, const uint8_t* pts192, uint64_t* kk, uint64_t* px, uint64_t* py, uint32_t* hist, uint32_t* counter, size_t n, int bits, int c,
-                     int windows);
-  static void slices(hipStream_t, const uint32_t* sorted, const uint64_t* kk, const uint64_t* px, const uint64_t* py, const uint32_t* start, uint64_t* buckets, uint64_t* partial,
-                     uint32_t* broken, size_t n, size_t T, size_t L, size_t slices, int c, size_t K);
-  static void combine(hipStream_t, const uint32_t* start, uint64_t* buckets, const uint64_t* partial, uint32_t* broken, size_t L, size_t slices, int c, size_t K);
-  static void chunks(hipStream_t, const uint64_t* buckets, uint64_t* out, size_t lanes, size_t per_window, int c, int m, size_t K);
-  static void tree(hipStream_t, uint64_t* arr, size_t total, size_t count, size_t stride, size_t groups, size_t lanes, int fan);
-  // out[g] = the sum of the valid points g, g + lanes, ... (fan of them) of n encodings, 96 bytes each where compressed; malformed ones are counted and skipped
-  static void tree_affine(hipStream_t, const uint8_t* pts, bool compressed, uint32_t* counter, uint64_t* out, size_t n, size_t lanes, int fan);
-  // the LANES route's front: out[i] = (k[i] mod 2^bits) P[i] as a Jacobian array of n; a malformed point is counted and gives the identity
-  static void products(hipStream_t, const uint64_t* k, const uint8_t* pts192, uint32_t* counter, uint64_t* out, size_t n, int bits);
-  static void finish(hipStream_t, const uint64_t* arr, size_t total, size_t stride, int windows, int c, const uint32_t* counter, uint8_t* out192, uint8_t* finite, uint32_t* invalid);
+  static void products(hipStream_t, const uint64_t* k, const uint8_t* pts, uint32_t* counter, uint64_t* out, size_t n, int bits);
+  static void finish(hipStream_t, const uint64_t* arr, size_t total, size_t stride, int windows, int c, const uint32_t* counter, uint8_t* out, uint8_t* finite, uint32_t* invalid);
 };
 // front: h = SHA-512(R || A || M) mod L, leaf, A and R copied to Aenc / Renc, valid = s < L (&& no small-order A or R); a lane that is not valid counts in
 // head->malformed.  node / seed: schnorr_batch's shapes under this call's tags.  scalars: z, and where zh is given z h mod L and z s mod L (0 where not valid).

@@ -676,9 +676,13 @@ class Engine:
         self._check(self.lib.ecsimd_p384_raw(self.ctx, C.c_int(op), ip, C.c_void_p(out.data_ptr() if n else 0), C.c_size_t(n)), "p384_raw")
         return out
 
-    # ---- BLS12-381 G1 (include/ecsimd_bls12_381.h): points are the standard 96-byte (uncompressed) or 48-byte (compressed) encodings.  PUBLIC data only.
+    # ---- BLS12-381 G1 and G2 (include/ecsimd_bls12_381.h, include/ecsimd_bls12_381_g2.h): points are the standard encodings, 96 bytes (48 compressed) in G1,
+    # 192 (96 compressed, c1 before c0) in G2.  PUBLIC data only.  The two groups' methods go through ONE set of helpers, which take the C functions' stem
+    # ("bls12_381_g1", "bls381_g2": the error texts' too) and the uncompressed width w; the compressed width is w / 2.
     (BLS12_381_RAW_FE_MUL, BLS12_381_RAW_FE_SQR, BLS12_381_RAW_FE_ADD, BLS12_381_RAW_FE_SUB, BLS12_381_RAW_FE_NEG, BLS12_381_RAW_FE_INVERT, BLS12_381_RAW_FE_SQRT,
      BLS12_381_RAW_FE_CANON, BLS12_381_RAW_POINT_ADD, BLS12_381_RAW_POINT_DBL, BLS12_381_RAW_POINT_MADD) = range(11)
+    (BLS12_381_G2_RAW_FE2_MUL, BLS12_381_G2_RAW_FE2_SQR, BLS12_381_G2_RAW_FE2_ADD, BLS12_381_G2_RAW_FE2_SUB, BLS12_381_G2_RAW_FE2_NEG, BLS12_381_G2_RAW_FE2_INVERT,
+     BLS12_381_G2_RAW_FE2_SQRT, BLS12_381_G2_RAW_FE2_CANON, BLS12_381_G2_RAW_POINT_ADD, BLS12_381_G2_RAW_POINT_DBL, BLS12_381_G2_RAW_POINT_MADD) = range(11)
 
     def _bls12_381_scalars(self, k, what):
         """The C ABI's scalars -- (n, 4) 64-bit little-endian limbs, 16-byte aligned -- from such a tensor or from (n, 32) uint8 little-endian bytes (copied:
@@ -691,170 +695,139 @@ class Engine:
         assert k.dtype in (torch.int64, torch.uint64) and k.dim() == 2 and int(k.shape[1]) == 4 and k.is_contiguous(), (what, k.dtype, tuple(k.shape))
         return k, C.c_void_p(k.data_ptr() if k.shape[0] else 0), int(k.shape[0])
 
-    def _bls12_381_lanes(self, fn, what, inp, in_width, out_widths):
+    def _bls12_381_lanes(self, what, inp, in_width, out_widths):
         ip, n = self._rows_u8(inp, in_width, what)
         outs = [self._u8_out(n, w) if w > 1 else self.flags(n) for w in out_widths]
         self._bind_stream()
-        self._check(fn(self.ctx, ip, *[C.c_void_p(o.data_ptr() if n else 0) for o in outs], C.c_size_t(n)), what)
+        self._check(getattr(self.lib, "ecsimd_" + what)(self.ctx, ip, *[C.c_void_p(o.data_ptr() if n else 0) for o in outs], C.c_size_t(n)), what)
         return tuple(outs)
+
+    def _bls12_381_mul(self, stem, w, k, inp):
+        what = stem + "_mul"
+        keep, kp, n = self._bls12_381_scalars(k, what)
+        ip, n2 = self._rows_u8(inp, w, f"in{w}")
+        if n2 != n:
+            raise EcsimdHipError(f"{what}: operands disagree on the batch length: {sorted((n, n2))}")
+        out, ok = self._u8_out(n, w), self.flags(n)
+        self._bind_stream()
+        self._check(getattr(self.lib, "ecsimd_" + what)(self.ctx, kp, ip, C.c_void_p(out.data_ptr() if n else 0), C.c_void_p(ok.data_ptr() if n else 0), C.c_size_t(n)), what)
+        return out, ok
+
+    @staticmethod
+    def _bls12_381_msm_plan(stem, n, bits, alg):
+        plan = MsmPlan()
+        rc = getattr(load_library(), f"ecsimd_{stem}_msm_plan")(C.c_size_t(n), C.c_int(bits), C.c_int(alg), C.byref(plan))
+        if rc != 0:
+            raise EcsimdHipError(f"{stem}_msm_plan(n={n}, bits={bits}, alg={alg}) failed ({rc}): bits must be 1 .. 256, n at most 2^24, alg 0, 1 or 2")
+        return {name: int(getattr(plan, name)) for name, _ in MsmPlan._fields_}
+
+    def _bls12_381_sum(self, what, w, want_invalid, n, *inputs, tail=()):
+        """One of the calls with a single result: (out, finite[, invalid]) with out the (w,) uint8 encoding."""
+        torch = self.torch
+        out = torch.zeros((w,), dtype=torch.uint8, device=self.tdev)
+        finite = torch.zeros((1,), dtype=torch.uint8, device=self.tdev)
+        invalid = torch.zeros((1,), dtype=torch.int32, device=self.tdev) if want_invalid else None
+        self._bind_stream()
+        self._check(getattr(self.lib, "ecsimd_" + what)(self.ctx, *inputs, C.c_void_p(out.data_ptr()), C.c_void_p(finite.data_ptr()), C.c_void_p(invalid.data_ptr() if want_invalid else 0),
+                                                        C.c_size_t(n), *tail), what)
+        return (out, finite, invalid) if want_invalid else (out, finite)
+
+    def _bls12_381_msm(self, stem, w, k, pts, bits, alg, want_invalid):
+        what = stem + "_msm"
+        keep, kp, n = self._bls12_381_scalars(k, what)
+        pp, n2 = self._rows_u8(pts, w, f"pts{w}")
+        if n2 != n:
+            raise EcsimdHipError(f"{what}: operands disagree on the batch length: {sorted((n, n2))}")
+        return self._bls12_381_sum(what, w, want_invalid, n, kp, pp, tail=(C.c_int(bits), C.c_int(alg)))
+
+    def _bls12_381_point_sum(self, stem, w, pts, want_invalid):
+        assert pts.dim() == 2 and int(pts.shape[1]) in (w // 2, w), tuple(pts.shape)
+        width = int(pts.shape[1])
+        pp, n = self._rows_u8(pts, width, "pts")
+        return self._bls12_381_sum(stem + "_point_sum", w, want_invalid, n, pp, tail=(C.c_int(1 if width == w // 2 else 0),))
+
+    def _bls12_381_raw(self, what, op, records):
+        ni, no = int(getattr(self.lib, f"ecsimd_{what}_inputs")(C.c_int(op))), int(getattr(self.lib, f"ecsimd_{what}_outputs")(C.c_int(op)))
+        if ni == 0:
+            raise EcsimdHipError(f"{what}: unknown function {op}")
+        ip, n = self._rows_u8(records, 48 * ni, "records")
+        out = self._u8_out(n, 48 * no)
+        self._bind_stream()
+        self._check(getattr(self.lib, "ecsimd_" + what)(self.ctx, C.c_int(op), ip, C.c_void_p(out.data_ptr() if n else 0), C.c_size_t(n)), what)
+        return out
 
     def bls12_381_g1_decompress(self, in48):
         """ecsimd_bls12_381_g1_decompress: (out96, ok) for (n, 48) uint8 compressed points; a malformed lane gets zeros and ok = 0.  On-curve only."""
-        return self._bls12_381_lanes(self.lib.ecsimd_bls12_381_g1_decompress, "bls12_381_g1_decompress", in48, 48, (96, 1))
+        return self._bls12_381_lanes("bls12_381_g1_decompress", in48, 48, (96, 1))
 
     def bls12_381_g1_compress(self, in96):
         """ecsimd_bls12_381_g1_compress: (out48, ok) for (n, 96) uint8 uncompressed points, validated the same way."""
-        return self._bls12_381_lanes(self.lib.ecsimd_bls12_381_g1_compress, "bls12_381_g1_compress", in96, 96, (48, 1))
+        return self._bls12_381_lanes("bls12_381_g1_compress", in96, 96, (48, 1))
 
     def bls12_381_g1_check(self, in96):
         """ecsimd_bls12_381_g1_check: (on_curve, in_subgroup), one byte per lane each; in_subgroup is [r] P = infinity."""
-        return self._bls12_381_lanes(self.lib.ecsimd_bls12_381_g1_check, "bls12_381_g1_check", in96, 96, (1, 1))
+        return self._bls12_381_lanes("bls12_381_g1_check", in96, 96, (1, 1))
 
     def bls12_381_g1_mul(self, k, in96):
         """ecsimd_bls12_381_g1_mul: (out96, ok), k[i] P[i] for the 256-bit INTEGERS k ((n, 4) limbs or (n, 32) uint8 little-endian) and the validated points."""
-        keep, kp, n = self._bls12_381_scalars(k, "bls12_381_g1_mul")
-        ip, n2 = self._rows_u8(in96, 96, "in96")
-        if n2 != n:
-            raise EcsimdHipError(f"bls12_381_g1_mul: operands disagree on the batch length: {sorted((n, n2))}")
-        out, ok = self._u8_out(n, 96), self.flags(n)
-        self._bind_stream()
-        self._check(self.lib.ecsimd_bls12_381_g1_mul(self.ctx, kp, ip, C.c_void_p(out.data_ptr() if n else 0), C.c_void_p(ok.data_ptr() if n else 0), C.c_size_t(n)), "bls12_381_g1_mul")
-        return out, ok
+        return self._bls12_381_mul("bls12_381_g1", 96, k, in96)
 
     @staticmethod
     def bls12_381_g1_msm_plan(n, bits=255, alg=0):
         """ecsimd_bls12_381_g1_msm_plan: msm_plan's dict for bls12_381_g1_msm (the same bucket schedule, this group's workspace_bytes and LANES route).  Host only."""
-        plan = MsmPlan()
-        rc = load_library().ecsimd_bls12_381_g1_msm_plan(C.c_size_t(n), C.c_int(bits), C.c_int(alg), C.byref(plan))
-        if rc != 0:
-            raise EcsimdHipError(f"bls12_381_g1_msm_plan(n={n}, bits={bits}, alg={alg}) failed ({rc}): bits must be 1 .. 256, n at most 2^24, alg 0, 1 or 2")
-        return {name: int(getattr(plan, name)) for name, _ in MsmPlan._fields_}
-
-    def _bls12_381_sum_out(self, want_invalid):
-        torch = self.torch
-        out = torch.zeros((96,), dtype=torch.uint8, device=self.tdev)
-        finite = torch.zeros((1,), dtype=torch.uint8, device=self.tdev)
-        invalid = torch.zeros((1,), dtype=torch.int32, device=self.tdev) if want_invalid else None
-        return out, finite, invalid
+        return Engine._bls12_381_msm_plan("bls12_381_g1", n, bits, alg)
 
     def bls12_381_g1_msm(self, k, pts96, bits=255, alg=0, want_invalid=False):
         """ecsimd_bls12_381_g1_msm: (out96, finite) = the (96,) uint8 encoding of the sum of (k[i] mod 2^bits) P[i] and a (1,) uint8 flag (0 and the infinity
         encoding for the identity).  k as bls12_381_g1_mul's; pts96: (n, 96) uint8.  A malformed point contributes nothing; want_invalid: a third tensor, the
         (1,) int32 number of them.  Points are NOT tested for subgroup membership.  Capturable after one warm-up call at the same (n, bits, alg)."""
-        keep, kp, n = self._bls12_381_scalars(k, "bls12_381_g1_msm")
-        pp, n2 = self._rows_u8(pts96, 96, "pts96")
-        if n2 != n:
-            raise EcsimdHipError(f"bls12_381_g1_msm: operands disagree on the batch length: {sorted((n, n2))}")
-        out, finite, invalid = self._bls12_381_sum_out(want_invalid)
-        self._bind_stream()
-        self._check(self.lib.ecsimd_bls12_381_g1_msm(self.ctx, kp, pp, C.c_void_p(out.data_ptr()), C.c_void_p(finite.data_ptr()), C.c_void_p(invalid.data_ptr() if want_invalid else 0),
-                                                     C.c_size_t(n), C.c_int(bits), C.c_int(alg)), "bls12_381_g1_msm")
-        return (out, finite, invalid) if want_invalid else (out, finite)
+        return self._bls12_381_msm("bls12_381_g1", 96, k, pts96, bits, alg, want_invalid)
 
     def bls12_381_g1_point_sum(self, pts, want_invalid=False):
         """ecsimd_bls12_381_g1_point_sum: (out96, finite) = the sum of the points; pts is (n, 96) uint8 uncompressed or (n, 48) uint8 compressed (the width
         decides).  Malformed points are skipped and counted (want_invalid)."""
-        assert pts.dim() == 2 and int(pts.shape[1]) in (48, 96), tuple(pts.shape)
-        width = int(pts.shape[1])
-        pp, n = self._rows_u8(pts, width, "pts")
-        out, finite, invalid = self._bls12_381_sum_out(want_invalid)
-        self._bind_stream()
-        self._check(self.lib.ecsimd_bls12_381_g1_point_sum(self.ctx, pp, C.c_void_p(out.data_ptr()), C.c_void_p(finite.data_ptr()), C.c_void_p(invalid.data_ptr() if want_invalid else 0),
-                                                           C.c_size_t(n), C.c_int(1 if width == 48 else 0)), "bls12_381_g1_point_sum")
-        return (out, finite, invalid) if want_invalid else (out, finite)
+        return self._bls12_381_point_sum("bls12_381_g1", 96, pts, want_invalid)
 
     def bls12_381_raw(self, op, records):
         """ecsimd_bls12_381_raw: one function of the layers below on (n, 48 * inputs) uint8 records; returns (n, 48 * outputs) uint8 (see the header's table)."""
-        ni, no = int(self.lib.ecsimd_bls12_381_raw_inputs(C.c_int(op))), int(self.lib.ecsimd_bls12_381_raw_outputs(C.c_int(op)))
-        if ni == 0:
-            raise EcsimdHipError(f"bls12_381_raw: unknown function {op}")
-        ip, n = self._rows_u8(records, 48 * ni, "records")
-        out = self._u8_out(n, 48 * no)
-        self._bind_stream()
-        self._check(self.lib.ecsimd_bls12_381_raw(self.ctx, C.c_int(op), ip, C.c_void_p(out.data_ptr() if n else 0), C.c_size_t(n)), "bls12_381_raw")
-        return out
-
-    # ---- BLS12-381 G2 (include/ecsimd_bls12_381_g2.h): points are the standard 192-byte (uncompressed) or 96-byte (compressed) encodings, c1 before c0.  PUBLIC
-    # data only.  Scalars and the sums' outputs are shaped like the G1 methods'.
-    (BLS12_381_G2_RAW_FE2_MUL, BLS12_381_G2_RAW_FE2_SQR, BLS12_381_G2_RAW_FE2_ADD, BLS12_381_G2_RAW_FE2_SUB, BLS12_381_G2_RAW_FE2_NEG, BLS12_381_G2_RAW_FE2_INVERT,
-     BLS12_381_G2_RAW_FE2_SQRT, BLS12_381_G2_RAW_FE2_CANON, BLS12_381_G2_RAW_POINT_ADD, BLS12_381_G2_RAW_POINT_DBL, BLS12_381_G2_RAW_POINT_MADD) = range(11)
+        return self._bls12_381_raw("bls12_381_raw", op, records)
 
     def bls12_381_g2_decompress(self, in96):
         """ecsimd_bls381_g2_decompress: (out192, ok) for (n, 96) uint8 compressed points; a malformed lane gets zeros and ok = 0.  On-curve only."""
-        return self._bls12_381_lanes(self.lib.ecsimd_bls381_g2_decompress, "bls381_g2_decompress", in96, 96, (192, 1))
+        return self._bls12_381_lanes("bls381_g2_decompress", in96, 96, (192, 1))
 
     def bls12_381_g2_compress(self, in192):
         """ecsimd_bls381_g2_compress: (out96, ok) for (n, 192) uint8 uncompressed points, validated the same way."""
-        return self._bls12_381_lanes(self.lib.ecsimd_bls381_g2_compress, "bls381_g2_compress", in192, 192, (96, 1))
+        return self._bls12_381_lanes("bls381_g2_compress", in192, 192, (96, 1))
 
     def bls12_381_g2_check(self, in192):
         """ecsimd_bls381_g2_check: (on_curve, in_subgroup), one byte per lane each; in_subgroup is [r] Q = infinity."""
-        return self._bls12_381_lanes(self.lib.ecsimd_bls381_g2_check, "bls381_g2_check", in192, 192, (1, 1))
+        return self._bls12_381_lanes("bls381_g2_check", in192, 192, (1, 1))
 
     def bls12_381_g2_mul(self, k, in192):
         """ecsimd_bls381_g2_mul: (out192, ok), k[i] Q[i] for the 256-bit INTEGERS k ((n, 4) limbs or (n, 32) uint8 little-endian) and the validated points."""
-        keep, kp, n = self._bls12_381_scalars(k, "bls381_g2_mul")
-        ip, n2 = self._rows_u8(in192, 192, "in192")
-        if n2 != n:
-            raise EcsimdHipError(f"bls381_g2_mul: operands disagree on the batch length: {sorted((n, n2))}")
-        out, ok = self._u8_out(n, 192), self.flags(n)
-        self._bind_stream()
-        self._check(self.lib.ecsimd_bls381_g2_mul(self.ctx, kp, ip, C.c_void_p(out.data_ptr() if n else 0), C.c_void_p(ok.data_ptr() if n else 0), C.c_size_t(n)), "bls381_g2_mul")
-        return out, ok
+        return self._bls12_381_mul("bls381_g2", 192, k, in192)
 
     @staticmethod
     def bls12_381_g2_msm_plan(n, bits=255, alg=0):
         """ecsimd_bls381_g2_msm_plan: msm_plan's dict for bls12_381_g2_msm (the same bucket schedule, this group's workspace_bytes and LANES route).  Host only."""
-        plan = MsmPlan()
-        rc = load_library().ecsimd_bls381_g2_msm_plan(C.c_size_t(n), C.c_int(bits), C.c_int(alg), C.byref(plan))
-        if rc != 0:
-            raise EcsimdHipError(f"bls381_g2_msm_plan(n={n}, bits={bits}, alg={alg}) failed ({rc}): bits must be 1 .. 256, n at most 2^24, alg 0, 1 or 2")
-        return {name: int(getattr(plan, name)) for name, _ in MsmPlan._fields_}
-
-    def _bls12_381_g2_sum_out(self, want_invalid):
-        torch = self.torch
-        out = torch.zeros((192,), dtype=torch.uint8, device=self.tdev)
-        finite = torch.zeros((1,), dtype=torch.uint8, device=self.tdev)
-        invalid = torch.zeros((1,), dtype=torch.int32, device=self.tdev) if want_invalid else None
-        return out, finite, invalid
+        return Engine._bls12_381_msm_plan("bls381_g2", n, bits, alg)
 
     def bls12_381_g2_msm(self, k, pts192, bits=255, alg=0, want_invalid=False):
         """ecsimd_bls381_g2_msm: (out192, finite) = the (192,) uint8 encoding of the sum of (k[i] mod 2^bits) Q[i] and a (1,) uint8 flag (0 and the infinity
         encoding for the identity).  k as bls12_381_g2_mul's; pts192: (n, 192) uint8.  A malformed point contributes nothing; want_invalid: a third tensor, the
         (1,) int32 number of them.  Points are NOT tested for subgroup membership.  Capturable after one warm-up call at the same (n, bits, alg)."""
-        keep, kp, n = self._bls12_381_scalars(k, "bls381_g2_msm")
-        pp, n2 = self._rows_u8(pts192, 192, "pts192")
-        if n2 != n:
-            raise EcsimdHipError(f"bls381_g2_msm: operands disagree on the batch length: {sorted((n, n2))}")
-        out, finite, invalid = self._bls12_381_g2_sum_out(want_invalid)
-        self._bind_stream()
-        self._check(self.lib.ecsimd_bls381_g2_msm(self.ctx, kp, pp, C.c_void_p(out.data_ptr()), C.c_void_p(finite.data_ptr()), C.c_void_p(invalid.data_ptr() if want_invalid else 0),
-                                                  C.c_size_t(n), C.c_int(bits), C.c_int(alg)), "bls381_g2_msm")
-        return (out, finite, invalid) if want_invalid else (out, finite)
+        return self._bls12_381_msm("bls381_g2", 192, k, pts192, bits, alg, want_invalid)
 
     def bls12_381_g2_point_sum(self, pts, want_invalid=False):
         """ecsimd_bls381_g2_point_sum: (out192, finite) = the sum of the points; pts is (n, 192) uint8 uncompressed or (n, 96) uint8 compressed (the width
         decides).  Malformed points are skipped and counted (want_invalid)."""
-        assert pts.dim() == 2 and int(pts.shape[1]) in (96, 192), tuple(pts.shape)
-        width = int(pts.shape[1])
-        pp, n = self._rows_u8(pts, width, "pts")
-        out, finite, invalid = self._bls12_381_g2_sum_out(want_invalid)
-        self._bind_stream()
-        self._check(self.lib.ecsimd_bls381_g2_point_sum(self.ctx, pp, C.c_void_p(out.data_ptr()), C.c_void_p(finite.data_ptr()), C.c_void_p(invalid.data_ptr() if want_invalid else 0),
-                                                        C.c_size_t(n), C.c_int(1 if width == 96 else 0)), "bls381_g2_point_sum")
-        return (out, finite, invalid) if want_invalid else (out, finite)
+        return self._bls12_381_point_sum("bls381_g2", 192, pts, want_invalid)
 
     def bls12_381_g2_raw(self, op, records):
         """ecsimd_bls381_g2_raw: one function of the layers below on (n, 48 * inputs) uint8 records (an Fp2 operand is two records, c0 then c1); returns
         (n, 48 * outputs) uint8 (see the header's table)."""
-        ni, no = int(self.lib.ecsimd_bls381_g2_raw_inputs(C.c_int(op))), int(self.lib.ecsimd_bls381_g2_raw_outputs(C.c_int(op)))
-        if ni == 0:
-            raise EcsimdHipError(f"bls381_g2_raw: unknown function {op}")
-        ip, n = self._rows_u8(records, 48 * ni, "records")
-        out = self._u8_out(n, 48 * no)
-        self._bind_stream()
-        self._check(self.lib.ecsimd_bls381_g2_raw(self.ctx, C.c_int(op), ip, C.c_void_p(out.data_ptr() if n else 0), C.c_size_t(n)), "bls381_g2_raw")
-        return out
+        return self._bls12_381_raw("bls381_g2_raw", op, records)
 
     # ---- the SM2 signature scheme (include/ecsimd_sm2.h): integers are (n, 4) limb tensors as the ECDSA methods take them, digests likewise
     SM2_DEFAULT_ID = b"1234567812345678"

@@ -238,3 +238,21 @@ def test_the_old_callers_plans_are_what_the_parent_commit_reported(built):
                 assert p["route"] == flags and tuple(p[f] for f in FIELDS[1:]) == table[(n, bits)], (name, n, bits)
             auto = plan_of(built, "ecsimd_msm_plan", n, bits, 0)
             assert auto == plan_of(built, "ecsimd_msm_plan", n, bits, 1 if n >= 2**20 else 2)
+
+
+def test_the_shipped_listing_has_the_figures_the_profile_records(built):
+    """tools/bls12_381_listing.py --unit g1 --check on the listing the build left in build/csrc, and, said per figure, what no change of the unit may move
+    unnoticed: every kernel's instruction counts, registers, scratch and spills.  Kernel names, resource lines and instruction counts only."""
+    import bls12_381_listing as listing
+    path = os.path.join(ROOT, "build", "csrc", listing.UNITS["g1"]["listing"] + "-hip-amdgcn-amd-amdhsa-gfx950.s")
+    assert os.path.exists(path), "the Makefile no longer leaves the device listings in build/csrc (-save-temps=obj)"
+    for f in ("k_bls12_381.hip", "k_bls12_381.inc", "bls381_curve.inc", "g1.cuh", "fe381.cuh", "fe384.cuh", "bls381_bytes.cuh", "msm_stages.cuh", "kernels.h"):
+        assert os.path.getmtime(path) >= os.path.getmtime(os.path.join(CSRC, f)), f
+    got, recorded = listing.report("g1"), json.load(open(os.path.join(ROOT, listing.UNITS["g1"]["out"])))
+    assert len(recorded["kernels"]) == 14
+    for section in ("kernels", "functions"):
+        for name, figures in recorded.get(section, {}).items():
+            for f in ("valu", "mads", "registers", "agprs", "vgprs", "private_segment_fixed_size", "scratch_bytes", "vgpr_spill_count", "text_bytes"):
+                if f in figures:
+                    assert got[section][name][f] == figures[f], (name, f, got[section][name][f], figures[f])
+    assert got == recorded, f"{listing.UNITS['g1']['out']} is stale: python tools/bls12_381_listing.py --unit g1"

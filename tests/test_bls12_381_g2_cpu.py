@@ -250,3 +250,21 @@ def test_g2_msm_plan_is_the_models_restatement_of_the_schedule(built):
     for n, bits, flags in ((1, 0, 0), (1, 257, 0), (2**24 + 1, 255, 0), (1, 255, 3), (1, 255, -1)):
         assert plan_of(built, "ecsimd_bls381_g2_msm_plan", n, bits, flags) is None and model.plan(n, bits, flags, th) is None
     assert built.ecsimd_bls381_g2_msm_plan(C.c_size_t(1), C.c_int(255), C.c_int(0), None) != 0
+
+
+def test_the_shipped_listing_has_the_figures_the_profile_records(built):
+    """tools/bls12_381_listing.py --unit g2 --check on the listing the build left in build/csrc, and, said per figure, what no change of the unit may move
+    unnoticed: every kernel's and out-of-line function's instruction counts, registers, scratch and spills.  Kernel names, resource lines and instruction counts only."""
+    import bls12_381_listing as listing
+    path = os.path.join(ROOT, "build", "csrc", listing.UNITS["g2"]["listing"] + "-hip-amdgcn-amd-amdhsa-gfx950.s")
+    assert os.path.exists(path), "the Makefile no longer leaves the device listings in build/csrc (-save-temps=obj)"
+    for f in ("k_bls12_381_g2.hip", "k_bls12_381.inc", "bls381_curve.inc", "g2.cuh", "fp2.cuh", "fe381.cuh", "fe384.cuh", "bls381_bytes.cuh", "msm_stages.cuh", "kernels.h"):
+        assert os.path.getmtime(path) >= os.path.getmtime(os.path.join(CSRC, f)), f
+    got, recorded = listing.report("g2"), json.load(open(os.path.join(ROOT, listing.UNITS["g2"]["out"])))
+    assert len(recorded["kernels"]) == 14 and sorted(recorded["functions"]) == ["g2_add", "g2_dbl", "g2_madd"]
+    for section in ("kernels", "functions"):
+        for name, figures in recorded.get(section, {}).items():
+            for f in ("valu", "mads", "registers", "agprs", "vgprs", "private_segment_fixed_size", "scratch_bytes", "vgpr_spill_count", "text_bytes"):
+                if f in figures:
+                    assert got[section][name][f] == figures[f], (name, f, got[section][name][f], figures[f])
+    assert got == recorded, f"{listing.UNITS['g2']['out']} is stale: python tools/bls12_381_listing.py --unit g2"
