@@ -26,10 +26,12 @@
 #include "../../include/ecsimd_msm.h"
 #include "../../include/ecsimd_schnorr_batch.h"
 #include "../../include/ecsimd_ed25519_batch.h"
+#include "../../include/ecsimd_ntt.h"
 #include "kernels.h"
 #include "point.cuh"   // curve constants for ecsimd_hip_get_constant (host-side constexpr use only)
 #include "gfield.cuh"  // gmod: a run-time modulus as the generic field kernels take it
 #include "gcurve.cuh"  // gcurve: a run-time curve as the generic point kernels and the ladder take it
+#include "ntt.cuh"     // the transform's schedule, one pass's geometry and the portable field the domain tables are built with
 
 using namespace ecsimd_hip;
 using launch::BLOCK;
@@ -3706,4 +3708,257 @@ int ecsimd_hip_bip39_seed(ecsimd_hip_ctx* ctx, const uint8_t* mnemonic, size_t m
   REQUIRE_CTX();
   return pbkdf2_derive(ctx, {mnemonic, mnemonic_bytes, mnemonic_stride_bytes, mnemonic_lens}, {passphrase, passphrase_bytes, passphrase_stride_bytes, passphrase_lens},
                        0x6d6e656d6f6e6963ull /* "mnemonic" */, 8u, 2048u, seed64, 64, 64, n); }
+}  // extern "C"
+
+// ================================================================== number-theoretic transform (include/ecsimd_ntt.h)
+// ntt.cuh decides the schedule and every index; k_ntt.hip runs one pass per launch.  Here: the host-only questions about a field (two-adicity, roots), a domain's
+// tables -- computed on the host with ntt.cuh's portable Montgomery arithmetic, at most 6 x 2^12 + 4 x 2^12 products, and uploaded once -- and the calls' checks.
+namespace {
+using ntt::pel;
+using ntt::pfield;
+pfield pfield_of(const gmod& M) {
+  pfield F;
+  for (int i = 0; i < 8; ++i) { F.p[i] = M.p[i]; F.r2[i] = M.rsq[i]; }
+  F.mprime = M.mprime;
+  return F;
+}
+pel pel_of(const uint32_t (&w)[8]) { pel r; for (int i = 0; i < 8; ++i) r.w[i] = w[i]; return r; }
+pel pel_of(const u256& v) { pel r; limbs_to_words(v.l, r.w); return r; }
+u256 u_of(const pel& v) { u256 r; words_to_limbs(v.w, r.l); return r; }
+bool pel_eq(const pel& a, const pel& b) { return !memcmp(a.w, b.w, sizeof a.w); }
+pel to_mgry(const pfield& F, const pel& a) { return F.mul(a, F.rsq()); }
+pel from_mgry(const pfield& F, const pel& a) { return F.mul(a, pfield::one()); }
+// base^e, Montgomery form in and out (one = R mod p)
+pel p_pow(const pfield& F, const pel& one, pel base, const u256& e) {
+  pel r = one;
+  for (int i = 0; i < 256; ++i) {
+    if ((e.l[i >> 6] >> (i & 63)) & 1u) r = F.mul(r, base);
+    base = F.mul(base, base);
+  }
+  return r;
+}
+u256 u_shr(u256 a, int bits) {
+  for (; bits > 0; --bits) { for (int i = 0; i < 3; ++i) a.l[i] = (a.l[i] >> 1) | (a.l[i + 1] << 63); a.l[3] >>= 1; }
+  return a;
+}
+// The field of an id, for a transform: a modulus the registry holds as PRIME, a registered curve's prime, or one of the two curve primes.
+bool ntt_field(int field, gmod* M) {
+  if (field == ECSIMD_HIP_P256 || field == ECSIMD_HIP_SECP256K1) {
+    uint64_t c[4];
+    words_to_limbs(field == ECSIMD_HIP_P256 ? curve_consts<CURVE_P256>::P : curve_consts<CURVE_SECP256K1>::P, c);
+    *M = make_gmod(c, GMOD_PRIME);
+    return true;
+  }
+  return lookup_modulus(field, M) && (M->flags & GMOD_PRIME);
+}
+struct field_facts { int s; u256 pm1; pel one, minus_one; };       // p - 1 = 2^s m; 1 and -1 in Montgomery form
+field_facts facts_of(const gmod& M) {
+  field_facts K;
+  K.one = pel_of(M.r); K.minus_one = pel_of(M.negr);
+  u256 p; words_to_limbs(M.p, p.l);
+  const u256 one = {{1, 0, 0, 0}};
+  (void)u_sub(K.pm1, p, one);
+  K.s = 0;
+  while (!((u_shr(K.pm1, K.s).l[0]) & 1u)) ++K.s;                    // p is odd and >= 3: p - 1 is even and not 0
+  return K;
+}
+// g^((p - 1) / 2^s) for the smallest integer g >= 2 with g^((p - 1) / 2) = -1, in Montgomery form
+pel default_root_mgry(const pfield& F, const field_facts& K) {
+  pel g = F.add(K.one, K.one);
+  while (!pel_eq(p_pow(F, K.one, g, u_shr(K.pm1, 1)), K.minus_one)) g = F.add(g, K.one);     // a prime has a non-residue below it
+  return p_pow(F, K.one, g, u_shr(K.pm1, K.s));
+}
+constexpr uint64_t FR_LIMBS[4] = {0xffffffff00000001ull, 0x53bda402fffe5bfeull, 0x3339d80809a1d805ull, 0x73eda753299d7d48ull};
+}  // namespace
+
+struct ecsimd_ntt_domain {
+  ecsimd_hip_ctx* owner;
+  gmod M;
+  int log_n, coset;
+  ntt::u4* block;                // the tables, one allocation
+  ntt::tables tw[2];             // [0] forward, [1] inverse: pointers into block
+};
+
+namespace {
+int ntt_cap(int flags) {         // the log-radix cap of `flags`, 0 if they are no flags
+  if (flags & ~15) return 0;
+  const int cap = flags ? flags : ntt::DEFAULT_RADIX_LOG;
+  return cap <= ntt::DEFAULT_RADIX_LOG ? cap : 0;
+}
+constexpr size_t NTT_MAX_ELEMENTS = (size_t)1 << 38;
+bool ranges_overlap(const void* a, const void* b, size_t bytes) {
+  const uintptr_t x = reinterpret_cast<uintptr_t>(a), y = reinterpret_cast<uintptr_t>(b);
+  return x < y + bytes && y < x + bytes;
+}
+int ntt_transform(ecsimd_hip_ctx* ctx, const ecsimd_ntt_domain* dom, const uint64_t* in, uint64_t* out, size_t batch, int flags, int inverse) {
+  REQUIRE_CTX();
+  if (!dom) return bad(ctx, "dom is null");
+  if (dom->owner != ctx) return bad(ctx, "the domain belongs to another context");
+  ntt::schedule S;
+  const int cap = ntt_cap(flags);
+  if (!cap || !ntt::make_schedule(dom->log_n, cap, &S)) return bad(ctx, "flags: 0 or ECSIMD_NTT_MAX_RADIX_LOG(1 .. 9)");
+  if (batch == 0) return ECSIMD_HIP_OK;
+  if (batch > (NTT_MAX_ELEMENTS >> dom->log_n)) return bad(ctx, "batch too large");
+  if (!in || !out) return bad(ctx, "in or out is null");
+  if (!aligned16(in) || !aligned16(out)) return bad(ctx, "in or out is not 16-byte aligned");
+  const size_t bytes = (batch << dom->log_n) * 32;
+  if (in != out && ranges_overlap(in, out, bytes)) return bad(ctx, "in and out overlap without being equal");
+  hipError_t e = hipSetDevice(ctx->device);
+  if (e != hipSuccess) return fail(ctx, e, "hipSetDevice");
+  if (S.passes > 1) {
+    int rc = ensure_workspace(ctx, bytes);
+    if (rc != ECSIMD_HIP_OK) return rc;
+    if (ranges_overlap(ctx->workspace, in, bytes) || ranges_overlap(ctx->workspace, out, bytes)) return bad(ctx, "in or out lies in the context's workspace");
+  }
+  const ntt::u4* src = reinterpret_cast<const ntt::u4*>(in);
+  for (int i = 0; i < S.passes; ++i) {
+    ntt::pass_args A;
+    A.G = ntt::make_geom(dom->log_n, S, i, batch, inverse, dom->coset);
+    A.tw = dom->tw[inverse];
+    A.src = src;
+    A.dst = reinterpret_cast<ntt::u4*>(ntt::pass_writes_workspace(i, S.passes) ? ctx->workspace : out);
+    launch::ntt_pass(ctx->stream, dom->M, A);
+    src = A.dst;
+  }
+  e = hipGetLastError();
+  return e == hipSuccess ? ECSIMD_HIP_OK : fail(ctx, e, "ntt pass launch");
+}
+}  // namespace
+
+extern "C" {
+int ecsimd_ntt_plan(int log_n, size_t batch, int flags, ecsimd_ntt_plan_t* out) {
+  ntt::schedule S;
+  const int cap = ntt_cap(flags);
+  if (!out || !cap || !ntt::make_schedule(log_n, cap, &S) || batch == 0 || batch > (NTT_MAX_ELEMENTS >> log_n)) return ECSIMD_HIP_ERR_BAD_ARG;
+  static_assert(ECSIMD_NTT_MAX_PASSES == ntt::MAX_PASSES && ECSIMD_NTT_MAX_LOG_N == ntt::MAX_LOG_N && ECSIMD_NTT_DEFAULT_RADIX_LOG == ntt::DEFAULT_RADIX_LOG, "ecsimd_ntt.h restates ntt.cuh");
+  memset(out, 0, sizeof *out);
+  out->passes = out->launches = S.passes;
+  for (int i = 0; i < ntt::MAX_PASSES; ++i) out->log_radix[i] = S.log_radix[i];
+  out->lanes = ntt::LANES;
+  out->lds_bytes = ntt::LDS_BYTES;
+  out->workspace_bytes = S.passes > 1 ? (batch << log_n) * 32 : 0;
+  return ECSIMD_HIP_OK;
+}
+
+int ecsimd_ntt_field_info(int field, int* two_adicity, uint64_t root[4]) {
+  gmod M;
+  if (!ntt_field(field, &M)) return ECSIMD_HIP_ERR_BAD_ARG;
+  const pfield F = pfield_of(M);
+  const field_facts K = facts_of(M);
+  if (two_adicity) *two_adicity = K.s;
+  if (root) { const u256 r = u_of(from_mgry(F, default_root_mgry(F, K))); memcpy(root, r.l, 32); }
+  return ECSIMD_HIP_OK;
+}
+
+int ecsimd_ntt_bls12_381_fr(int* field, uint64_t root[4]) {
+  if (!field) return ECSIMD_HIP_ERR_BAD_ARG;
+  int rc = ecsimd_hip_register_modulus(FR_LIMBS, ECSIMD_HIP_MODULUS_PRIME, field);
+  if (rc != ECSIMD_HIP_OK || !root) return rc;
+  gmod M;
+  if (!ntt_field(*field, &M)) return ECSIMD_HIP_ERR_BAD_ARG;
+  const pfield F = pfield_of(M);
+  const field_facts K = facts_of(M);
+  pel seven = K.one;
+  for (int i = 0; i < 6; ++i) seven = F.add(seven, K.one);
+  const u256 r = u_of(from_mgry(F, p_pow(F, K.one, seven, u_shr(K.pm1, K.s))));
+  memcpy(root, r.l, 32);
+  return ECSIMD_HIP_OK;
+}
+
+int ecsimd_ntt_domain_create(ecsimd_hip_ctx* ctx, int field, int log_n, const uint64_t root[4], const uint64_t shift[4], ecsimd_ntt_domain** dom) {
+  REQUIRE_CTX();
+  if (!dom) return bad(ctx, "dom is null");
+  *dom = nullptr;
+  REFUSE_IN_CAPTURE("ntt_domain_create allocates, uploads its tables and waits for the copy");
+  gmod M;
+  if (!ntt_field(field, &M)) return bad(ctx, "field: not a modulus registered as prime");
+  const pfield F = pfield_of(M);
+  const field_facts K = facts_of(M);
+  if (log_n < 1 || log_n > ntt::MAX_LOG_N || log_n > K.s) return bad(ctx, "log_n: 1 .. min(the field's two-adicity, 24)");
+  u256 p; words_to_limbs(M.p, p.l);
+  pel rt;
+  if (root) {
+    if (u_geq(u_from(root), p)) return bad(ctx, "root is not below p");
+    rt = to_mgry(F, pel_of(u_from(root)));
+    pel t = rt;
+    for (int i = 0; i + 1 < K.s; ++i) t = F.mul(t, t);
+    if (!pel_eq(t, K.minus_one)) return bad(ctx, "root is not a primitive 2^s-th root of unity: root^(2^(s-1)) != -1");
+  } else rt = default_root_mgry(F, K);
+  pel g = K.one;
+  if (shift) {
+    if (u_is_zero(u_from(shift)) || u_geq(u_from(shift), p)) return bad(ctx, "shift: 0 < shift < p");
+    g = to_mgry(F, pel_of(u_from(shift)));
+  }
+  const int coset = !pel_eq(g, K.one);
+  pel w = rt;
+  for (int i = 0; i < K.s - log_n; ++i) w = F.mul(w, w);                    // w = root^(2^(s - log_n))
+  u256 pm2; { const u256 one = {{1, 0, 0, 0}}; (void)u_sub(pm2, K.pm1, one); }
+  pel nm = K.one;
+  for (int i = 0; i < log_n; ++i) nm = F.add(nm, nm);                       // n
+  const pel ninv = p_pow(F, K.one, nm, pm2);
+  const size_t n = (size_t)1 << log_n, lo_n = n < (size_t)ntt::SPLIT ? n : (size_t)ntt::SPLIT, hi_n = n > (size_t)ntt::SPLIT ? n >> ntt::SPLIT_LOG : 1;
+  const int log_rt = log_n < ntt::DEFAULT_RADIX_LOG ? log_n : ntt::DEFAULT_RADIX_LOG;
+  const size_t stage_n = (size_t)1 << (log_rt - 1), per_dir = stage_n + 2 * lo_n + 2 * hi_n;
+  ecsimd_ntt_domain* D = nullptr;
+  std::vector<pel> host;
+  try { host.reserve(2 * per_dir); D = new ecsimd_ntt_domain; }
+  catch (...) { return bad(ctx, "ntt domain: out of host memory"); }
+  auto powers = [&](const pel& base, size_t count, const pel& first) { pel t = first; for (size_t i = 0; i < count; ++i) { host.push_back(t); t = F.mul(t, base); } };
+  auto pow2k = [&](pel v, int k) { for (int i = 0; i < k; ++i) v = F.mul(v, v); return v; };
+  size_t off[2][5];
+  for (int dir = 0; dir < 2; ++dir) {
+    const pel wd = dir ? p_pow(F, K.one, w, pm2) : w, gd = dir ? p_pow(F, K.one, g, pm2) : g;
+    off[dir][0] = host.size(); powers(pow2k(wd, log_n - log_rt), stage_n, K.one);
+    off[dir][1] = host.size(); powers(wd, lo_n, K.one);
+    off[dir][2] = host.size(); powers(pow2k(wd, ntt::SPLIT_LOG), hi_n, K.one);
+    off[dir][3] = host.size(); powers(gd, lo_n, K.one);
+    // forward: g^(SPLIT i) R^2 (Montgomery form twice over); inverse: n^-1 g^(-SPLIT i), classical
+    off[dir][4] = host.size(); powers(pow2k(gd, ntt::SPLIT_LOG), hi_n, dir ? from_mgry(F, ninv) : to_mgry(F, K.one));
+  }
+  D->owner = ctx; D->M = M; D->log_n = log_n; D->coset = coset; D->block = nullptr;
+  (void)hipSetDevice(ctx->device);
+  hipError_t e = hipMalloc(&D->block, host.size() * sizeof(pel));
+  if (e == hipSuccess) e = hipMemcpyAsync(D->block, host.data(), host.size() * sizeof(pel), hipMemcpyHostToDevice, ctx->stream);
+  if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);               // `host` must outlive the copy
+  if (e != hipSuccess) { (void)hipFree(D->block); delete D; return fail(ctx, e, "ntt domain tables"); }
+  for (int dir = 0; dir < 2; ++dir) {
+    const ntt::u4* b = D->block;
+    D->tw[dir] = ntt::tables{b + 2 * off[dir][0], b + 2 * off[dir][1], b + 2 * off[dir][2], b + 2 * off[dir][3], b + 2 * off[dir][4]};
+  }
+  *dom = D;
+  return ECSIMD_HIP_OK;
+}
+
+int ecsimd_ntt_domain_destroy(ecsimd_hip_ctx* ctx, ecsimd_ntt_domain* dom) {
+  REQUIRE_CTX();
+  if (!dom) return ECSIMD_HIP_OK;
+  if (dom->owner != ctx) return bad(ctx, "the domain belongs to another context");
+  REFUSE_IN_CAPTURE("ntt_domain_destroy releases device memory, which waits for the device");
+  (void)hipSetDevice(ctx->device);
+  hipError_t e = hipFree(dom->block);
+  delete dom;
+  return e == hipSuccess ? ECSIMD_HIP_OK : fail(ctx, e, "hipFree");
+}
+
+int ecsimd_ntt_forward(ecsimd_hip_ctx* ctx, const ecsimd_ntt_domain* dom, const uint64_t* in, uint64_t* out, size_t batch, int flags) {
+  return ntt_transform(ctx, dom, in, out, batch, flags, 0);
+}
+int ecsimd_ntt_inverse(ecsimd_hip_ctx* ctx, const ecsimd_ntt_domain* dom, const uint64_t* in, uint64_t* out, size_t batch, int flags) {
+  return ntt_transform(ctx, dom, in, out, batch, flags, 1);
+}
+
+int ecsimd_ntt_bitrev(ecsimd_hip_ctx* ctx, int log_n, const uint64_t* in, uint64_t* out, size_t batch) {
+  REQUIRE_CTX();
+  if (log_n < 1 || log_n > ntt::MAX_LOG_N) return bad(ctx, "log_n: 1 .. 24");
+  if (batch == 0) return ECSIMD_HIP_OK;
+  if (batch > (NTT_MAX_ELEMENTS >> log_n)) return bad(ctx, "batch too large");
+  if (!in || !out) return bad(ctx, "in or out is null");
+  if (!aligned16(in) || !aligned16(out)) return bad(ctx, "in or out is not 16-byte aligned");
+  if (in != out && ranges_overlap(in, out, (batch << log_n) * 32)) return bad(ctx, "in and out overlap without being equal");
+  hipError_t e = hipSetDevice(ctx->device);
+  if (e != hipSuccess) return fail(ctx, e, "hipSetDevice");
+  launch::ntt_bitrev(ctx->stream, in, out, log_n, batch);
+  e = hipGetLastError();
+  return e == hipSuccess ? ECSIMD_HIP_OK : fail(ctx, e, "ntt bitrev launch");
+}
 }  // extern "C"

@@ -10,6 +10,7 @@ struct gmod;                 // gfield.cuh: a run-time modulus and what the fiel
 struct gcurve;               // gcurve.cuh: a run-time curve (its field, a R, b R, the generator, the ladder loop's 29-bit constants)
 struct g1_curve;             // tags: the two BLS12-381 groups as bls381_launch's instances (k_bls12_381.hip, k_bls12_381_g2.hip)
 struct g2_curve;
+namespace ntt { struct pass_args; }   // ntt.cuh: one pass of a number-theoretic transform (buffers, tables, geometry)
 namespace launch {
 
 constexpr int BLOCK = 256;   // one wave per SIMD of a CU; several workgroups resident per CU
@@ -460,6 +461,11 @@ inline size_t scalar_mult_x_scratch_bytes(size_t n) { return 4 * n * 32 + ((n + 
 // (Round 1's unsigned 4-bit digits and carry-recoded signed digits were measured against these and removed.)
 constexpr int FIXED4_ENTRIES = 8;
 constexpr size_t WINDOW_TABLE_BYTES = 64 * FIXED4_ENTRIES * 64;   // 64 windows x entries x (x, y)
+
+// k_ntt.hip: the number-theoretic transform over a registered prime field (include/ecsimd_ntt.h; ntt.cuh has the schedule and the pass body).  Every launcher
+// enqueues ONE kernel.  ntt_pass: ntt::tiles_of(A.G) workgroups of ntt::LANES; ntt_bitrev: out[rev(i)] = in[i] per array of 2^log_n elements, out may be in.
+void ntt_pass(hipStream_t, const gmod& M, const ntt::pass_args& A);
+void ntt_bitrev(hipStream_t, const uint64_t* in, uint64_t* out, int log_n, size_t batch);
 
 }  // namespace launch
 }  // namespace ecsimd_hip

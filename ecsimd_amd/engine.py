@@ -92,6 +92,42 @@ class Ed25519BatchPlan(C.Structure):
     _fields_ = [("route", C.c_int), ("launches", C.c_int), ("workspace_bytes", C.c_size_t)]
 
 
+class NttPlan(C.Structure):
+    """ecsimd_ntt_plan_t (include/ecsimd_ntt.h)."""
+    _fields_ = [("passes", C.c_int), ("log_radix", C.c_int * 24), ("lanes", C.c_int), ("lds_bytes", C.c_int), ("launches", C.c_int), ("workspace_bytes", C.c_size_t)]
+
+
+# the conventional 2^32-th root of unity of BLS12-381's scalar field, 7^((r - 1) / 2^32): what ecsimd_ntt_bls12_381_fr returns
+BLS12_381_FR_ROOT = 0x16a2a19edfe81f20d09b681922c813b4b63683508c2280b93829971f439f0d2b
+
+
+def _limbs(v):
+    return (C.c_uint64 * 4)(*[(int(v) >> (64 * i)) & 0xFFFFFFFFFFFFFFFF for i in range(4)])
+
+
+def _from_limbs(l):
+    return sum(int(l[i]) << (64 * i) for i in range(4))
+
+
+class NttDomain:
+    """An ecsimd_ntt_domain: the device tables of one (field, log_n, root, shift).  It belongs to the Engine that made it and is destroyed with close() or when
+    it is collected -- before its Engine closes."""
+
+    def __init__(self, engine, handle, field, log_n):
+        self.engine, self.handle, self.field, self.log_n, self.n = engine, handle, field, log_n, 1 << log_n
+
+    def close(self):
+        if self.handle and self.engine.ctx:
+            self.engine.lib.ecsimd_ntt_domain_destroy(self.engine.ctx, self.handle)
+        self.handle = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
 class Engine:
     """One context (HIP stream owner) on one GPU."""
 
@@ -969,6 +1005,87 @@ class Engine:
         self._check(self.lib.ecsimd_msm_point_sum(self.ctx, C.c_int(curve), xp, yp, C.c_void_p(rx.data_ptr()), C.c_void_p(ry.data_ptr()), C.c_void_p(finite.data_ptr()),
                                                   C.c_void_p(invalid.data_ptr() if want_invalid else 0), C.c_size_t(n)), "point_sum")
         return (rx, ry, finite, invalid) if want_invalid else (rx, ry, finite)
+
+    # ---- number-theoretic transform (include/ecsimd_ntt.h) over a registered prime field: PUBLIC OR SECRET-INDEPENDENT (a data-independent schedule)
+    @staticmethod
+    def ntt_max_radix_log(r):
+        """ECSIMD_NTT_MAX_RADIX_LOG(r): the `flags` that cap every pass at r butterfly stages (a test hook: same values, more passes)."""
+        return r & 15
+
+    @staticmethod
+    def ntt_field_info(field):
+        """ecsimd_ntt_field_info: (two_adicity, default root as an int) of a prime field id.  Host only."""
+        s, root = C.c_int(0), (C.c_uint64 * 4)()
+        rc = load_library().ecsimd_ntt_field_info(C.c_int(field), C.byref(s), root)
+        if rc != 0:
+            raise EcsimdHipError(f"ntt_field_info(field={field}) failed ({rc}): the field must be a modulus registered as prime")
+        return s.value, _from_limbs(root)
+
+    @staticmethod
+    def ntt_bls12_381_fr():
+        """ecsimd_ntt_bls12_381_fr: (field id of Fr, the conventional root 7^((r - 1) / 2^32) as an int).  Host only."""
+        fid, root = C.c_int(-1), (C.c_uint64 * 4)()
+        rc = load_library().ecsimd_ntt_bls12_381_fr(C.byref(fid), root)
+        if rc != 0:
+            raise EcsimdHipError(f"ntt_bls12_381_fr failed ({rc})")
+        return fid.value, _from_limbs(root)
+
+    @staticmethod
+    def ntt_plan(log_n, batch=1, flags=0):
+        """ecsimd_ntt_plan as a dict (passes, log_radix: 24 entries, lanes, lds_bytes, launches, workspace_bytes).  Host only."""
+        plan = NttPlan()
+        rc = load_library().ecsimd_ntt_plan(C.c_int(log_n), C.c_size_t(batch), C.c_int(flags), C.byref(plan))
+        if rc != 0:
+            raise EcsimdHipError(f"ntt_plan(log_n={log_n}, batch={batch}, flags={flags}) failed ({rc}): log_n must be 1 .. 24, batch at least 1, flags 0 or a radix cap 1 .. 9")
+        return {name: (list(plan.log_radix) if name == "log_radix" else int(getattr(plan, name))) for name, _ in NttPlan._fields_}
+
+    def ntt_domain(self, field, log_n, root=None, shift=None):
+        """ecsimd_ntt_domain_create: the domain {shift * w^k} of size 2^log_n, w = root^(2^(s - log_n)); root None = the field's default root, shift None = 1."""
+        handle = C.c_void_p()
+        self._bind_stream()
+        self._check(self.lib.ecsimd_ntt_domain_create(self.ctx, C.c_int(field), C.c_int(log_n), _limbs(root) if root is not None else None,
+                                                      _limbs(shift) if shift is not None else None, C.byref(handle)), "ntt_domain_create")
+        return NttDomain(self, handle, field, log_n)
+
+    def _ntt(self, name, dom, x, out, flags):
+        rows = int(x.shape[0])
+        if rows % dom.n:
+            raise EcsimdHipError(f"{name}: {rows} rows are no whole number of arrays of {dom.n}")
+        out = self.empty(rows) if out is None else out
+        if int(out.shape[0]) != rows:
+            raise EcsimdHipError(f"{name}: operands disagree on the batch length: {sorted({rows, int(out.shape[0])})}")
+        xp, op = self._ptr(x), self._ptr(out)
+        self._rows.clear()
+        self._bind_stream()
+        self._check(getattr(self.lib, "ecsimd_" + name)(self.ctx, dom.handle, xp, op, C.c_size_t(rows // dom.n), C.c_int(flags)), name)
+        return out
+
+    def ntt_forward(self, dom, x, out=None, flags=0):
+        """ecsimd_ntt_forward: x is (batch * n, 4), batch arrays one after the other; out[k] = sum_i x[i] (g w^k)^i.  out may be x (in place)."""
+        return self._ntt("ntt_forward", dom, x, out, flags)
+
+    def ntt_inverse(self, dom, x, out=None, flags=0):
+        """ecsimd_ntt_inverse: the exact inverse of ntt_forward on the same domain."""
+        return self._ntt("ntt_inverse", dom, x, out, flags)
+
+    def ntt_bitrev(self, log_n, x, out=None):
+        """ecsimd_ntt_bitrev: out[rev(i)] = x[i] in each array of 2^log_n rows; out may be x."""
+        rows = int(x.shape[0])
+        if rows % (1 << log_n):
+            raise EcsimdHipError(f"ntt_bitrev: {rows} rows are no whole number of arrays of {1 << log_n}")
+        out = self.empty(rows) if out is None else out
+        if int(out.shape[0]) != rows:
+            raise EcsimdHipError(f"ntt_bitrev: operands disagree on the batch length: {sorted({rows, int(out.shape[0])})}")
+        xp, op = self._ptr(x), self._ptr(out)
+        self._rows.clear()
+        self._bind_stream()
+        self._check(self.lib.ecsimd_ntt_bitrev(self.ctx, C.c_int(log_n), xp, op, C.c_size_t(rows >> log_n)), "ntt_bitrev")
+        return out
+
+    def ntt_poly_mul(self, dom, a, b):
+        """The product of two polynomials given as dom.n coefficients each (classical): forward both, mod_mul, inverse.  The product's degree must be below dom.n
+        -- the caller pads with zeros --, else it comes out reduced modulo x^n - g^n."""
+        return self.ntt_inverse(dom, self.mod_mul(dom.field, self.ntt_forward(dom, a), self.ntt_forward(dom, b)))
 
     # ---- BIP-340 batch verification (include/ecsimd_schnorr_batch.h): ONE verdict out of a batch.  PUBLIC data only.
     @staticmethod
